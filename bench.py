@@ -15,10 +15,21 @@ HBM before the timed region starts.  Two ways through the C-ABI are timed:
 own GPU; the only collectives are the barrier and the max-reduction of the elapsed time
 (RCCL, a few bytes): weak scaling, no data-path exchange.
 
-One JSON line is printed by rank 0 (see the contract in the task description) with two extra
-objects: "roofline" (dominant kernel: algorithmic bytes per launch / HIP-event duration on the
-library's own stream, vs 8 TB/s) and "cpu_baseline" (the reference -- oracle/_ref, built from the
-reference's own sources -- or, if that build is absent, the scalar oracle port, on one host core).
+One JSON line is printed by rank 0.  A plain run sets up, warms up, times the K steps and prints
+the headline ("value", "ms_per_step" = milliseconds of one timed step, ...).  With --full the line
+also carries every other leg: the per-frame API, the live VO loop, the multi-sequence and mono legs,
+the parity check against the reference's hashes, the host-fed call, the secondary configurations,
+"roofline" (dominant kernel: algorithmic bytes per launch / HIP-event duration on the library's own
+stream, vs 8 TB/s) and "cpu_baseline" (the reference -- oracle/_ref, built from the reference's own
+sources -- or, if that build is absent, the scalar oracle port, on one host core).  The --no-*
+switches drop legs of a --full run.
+
+--dump-outputs DIR (rank 0) writes what the last timed step computed, after the timed steps:
+  DIR/matches.npy  float32 [M, 12]: every frame's final list (vsm_sequence_get_matches) in frame order,
+                   the columns are the p_match fields u1p v1p i1p u2p v2p i2p u1c v1c i1c u2c v2c i2c
+                   (the indices are exact in float32); at most 64 MB - beyond that a fixed, seeded
+                   sample of rows, whose positions are then in DIR/matches_rows.npy (float64)
+  DIR/counts.npy   float64 [F]: the number of matches of every frame
 """
 import argparse
 import gc
@@ -100,6 +111,24 @@ def sha(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, lists):
+    """the final lists of one step as float32 columns (see the top of the file); a seeded sample of rows beyond 64 MB"""
+    os.makedirs(out_dir, exist_ok=True)
+    counts = np.array([len(l) for l in lists], dtype=np.float64)
+    recs = np.concatenate(lists)
+    cols = np.stack([recs[k].astype(np.float32) for k in recs.dtype.names], axis=1)
+    limit_rows = (DUMP_LIMIT_BYTES - 4096 - counts.nbytes) // (cols.shape[1] * 4 + 8)   # (4096: the three files' headers)
+    if len(cols) > limit_rows:
+        rows = np.sort(np.random.default_rng(0).choice(len(cols), size=limit_rows, replace=False))
+        cols = cols[rows]
+        np.save(os.path.join(out_dir, "matches_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "matches.npy"), np.ascontiguousarray(cols))
+    np.save(os.path.join(out_dir, "counts.npy"), counts)
+
+
 def algorithmic_bytes(kernel, counts):
     """SURVEY.md section 8(d) per-unit figures, split per kernel.  counts: per-launch work."""
     P, Ph, Hh = counts["P"], counts["Ph"], counts["Hh"]
@@ -138,10 +167,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--frames", type=int, default=N_FRAMES)
     ap.add_argument("--startup", type=int, default=0, help="untimed calls in front of the warm-up steps (reported as startup_calls; none by default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-verify", action="store_true")
-    ap.add_argument("--no-per-frame", action="store_true", help="skip the per-frame API leg (profiling runs)")
-    ap.add_argument("--no-alone", action="store_true", help="skip the non-overlapped profiling pass (runs under rocprofv3: its launches would mix into the averages)")
+    ap.add_argument("--full", action="store_true", help="run every leg beyond the headline (see the top of the file); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's final lists to DIR as .npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-verify", action="store_true", help="(--full) skip the parity checks")
+    ap.add_argument("--no-per-frame", action="store_true", help="(--full) skip the per-frame API leg and the legs beside it (profiling runs)")
+    ap.add_argument("--no-alone", action="store_true", help="(--full) skip the non-overlapped profiling pass (runs under rocprofv3: its launches would mix into the averages)")
     args = ap.parse_args()
 
     import torch
@@ -278,6 +309,38 @@ def main():
                                                 sorted(step_ms)[len(step_ms) // 2], max(step_ms), lookahead_form], comm_dev)
     ranks_info = [{"rank": int(r[0]), "host_threads": int(r[1]), "cpus_allowed": int(r[2]), "chunk_frames": int(r[3]), "median_step_ms": round(r[4], 3),
                    "slowest_step_ms": round(r[5], 3), "lookahead_form": int(r[6])} for r in rank_rows]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [m.sequence_matches(f) for f in range(nf)])
+
+    def config_of(chunk):
+        return {"workload": f"KITTI-shaped synthetic stereo sequence 1242x375, {nf} frames per GPU, quad matching, "
+                            "default parameters, replayed Tr_delta feedback, look-ahead C-ABI entry point "
+                            f"vsm_sequence_run (chunks of {chunk} frames)",
+                "frames_per_step": nf, "sequences": world, "inputs": "resident in HBM",
+                "results": "when the timed call returns every frame's final list is in host memory as 48-byte p_match records "
+                           "(viso/matcher.h:86-100), as Matcher::matchFeatures leaves p_matched_2: the refined lists cross PCIe by DMA as they "
+                           "are, the device sends one survivor bit per match behind them, the host pool closes the gaps in "
+                           "place - all inside the timed call; vsm_sequence_get_matches copies from there"}
+
+    head = {
+        "metric": "stereo frame-pairs/sec (1242x375) through pushBack+matchFeatures(2), p_matched bit-exact",
+        "value": round(value, 3), "unit": "frame-pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "u8", "data": "synthetic",
+        # untimed calls in front of the W warm-up steps (process start-up; DESIGN.md section 6) and the slowest call among start-up + warm-up
+        "python_gc": "off inside the timed legs (as timeit does), collections between them: a full collection is a 55-65 ms pause of the harness",
+        "startup_calls": args.startup, "startup_worst_ms": max(startup_ms) if startup_ms else None,
+        "config": config_of(seq_t.get("chunk", 0)),
+    }
+    if not args.full:
+        # the headline alone: the legs below (checks, other entry points and configurations, roofline, CPU baseline) need --full
+        if rank == 0:
+            head.update({"sequence_timings_us": seq_t, "host_threads": int(os.environ["VSM_HOST_THREADS"]), "ranks": ranks_info,
+                         "step_ms_rank0": step_ms})
+            print(json.dumps(head))
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     gc.collect()
     # ---- the same sequence through the per-frame (drop-in) entry points ---------------------
@@ -560,22 +623,8 @@ def main():
                                   "frac_gpu_kernels_only": round(Bp * gpu_only_fps / (HBM_PEAK_GBS * 1e9), 6),
                                   "what": "B * frame-pairs/s / 8 TB/s per GPU; gpu_kernels_only = with the summed kernel durations of all "
                                           "streams (PCIe export excluded) instead of the wall clock"}
-    out = {
-        "metric": "stereo frame-pairs/sec (1242x375) through pushBack+matchFeatures(2), p_matched bit-exact",
-        "value": round(value, 3), "unit": "frame-pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "u8", "data": "synthetic",
-        # untimed calls in front of the W warm-up steps (process start-up; DESIGN.md section 6) and the slowest call among start-up + warm-up
-        "python_gc": "off inside the timed legs (as timeit does), collections between them: a full collection is a 55-65 ms pause of the harness",
-        "startup_calls": args.startup, "startup_worst_ms": max(startup_ms) if startup_ms else None,
-        "config": {"workload": f"KITTI-shaped synthetic stereo sequence 1242x375, {nf} frames per GPU, quad matching, "
-                               "default parameters, replayed Tr_delta feedback, look-ahead C-ABI entry point "
-                               f"vsm_sequence_run (chunks of {chunk} frames)",
-                   "frames_per_step": nf, "sequences": world, "inputs": "resident in HBM",
-                   "results": "when the timed call returns every frame's final list is in host memory as 48-byte p_match records "
-                              "(viso/matcher.h:86-100), as Matcher::matchFeatures leaves p_matched_2: the refined lists cross PCIe by DMA as they "
-                              "are, the device sends one survivor bit per match behind them, the host pool closes the gaps in "
-                              "place - all inside the timed call; vsm_sequence_get_matches copies from there"},
+    out = dict(head, config=config_of(chunk))
+    out.update({
         "per_frame_api": {"value": round(per_frame_value, 3) if per_frame_value else None, "unit": "frame-pairs/s", "caller_thread_on_cpus": caller_cpus,
                           "what": "same sequence through vsm_push_back_device + vsm_match per frame (drop-in "
                                   "Matcher::pushBack/matchFeatures path)"},
@@ -619,7 +668,7 @@ def main():
         "verified_ranks": n_verified,
         "step_ms_rank0": step_ms,
         "match_timings_us_last_frame": m.timings(),
-    }
+    })
     print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()

@@ -293,10 +293,13 @@ struct Seq2Chunk {
   bool warm = false;
   std::unique_ptr<std::atomic<signed char>[]> warm_domain;  // [n] L3 domain that has list i (-1: none)
   std::unique_ptr<std::atomic<unsigned char>[]> warm_claim; // [n] 1: a gap-closing task has taken list i
+  // warm-up tasks not yet finished: they read the chunk and the arena, so the call does not return (and the next call does not
+  // free the chunk) before they are through - they are queued behind everything else and may outlast the gap closing
+  std::atomic<int> warm_left{0};
   // the second part (votes, survivors) needs the vertex sorts AND the refinement's event, which the caller's thread records:
   // whoever comes last enqueues it
   std::atomic<int> gate{2};
-  std::atomic<int> unpack_left{0};  // frames whose survivors the pool is still moving together in the arena
+  std::atomic<int> unpack_left{0};  // gap-closing tasks of the chunk not yet finished (a frame each; the warm form: seq2_chunk_done)
   std::atomic<int> state{0};  // 0 idle, 1 triangulation enqueued, 2 second part enqueued, 3 done (views in vsm_handle::seq_view)
   std::atomic<int> hip_error{0};
   double t_keys = 0, t_sorted = 0, t_done = 0, t_ready = 0;
@@ -480,17 +483,17 @@ static void seq2_chunk_done(void *arg) {  // (the poller thread has seen the cha
   ch->unpack_left.store(n, std::memory_order_relaxed);
   if (ch->warm && ch->n > 0) {  // (lists by L3 domain: a task takes what its own domain has read, then whatever is left)
     const int T = std::min(std::max(h->pool->size() - 1, 1), ch->n);
+    // (counted in tasks: a task that finds every list taken still reads the chunk, so the chunk is done when the last task is)
+    ch->unpack_left.store(T, std::memory_order_relaxed);
     h->pool->submit(T, [ch, h](int) {
       const int dom = vsm_thread_domain();
-      int done = 0;
       for (int pass = 0; pass < 2; pass++)
         for (int i = 0; i < ch->n; i++) {
           if (pass == 0 && (int)ch->warm_domain[i].load(std::memory_order_relaxed) != dom) continue;
           if (ch->warm_claim[i].exchange(1, std::memory_order_acq_rel)) continue;
           seq2_close_gaps(ch, h, i);
-          done++;
         }
-      if (done && ch->unpack_left.fetch_sub(done, std::memory_order_acq_rel) == done) {
+      if (ch->unpack_left.fetch_sub(1, std::memory_order_acq_rel) == 1) {
         ch->t_ready = vsm_now_us();
         ch->state.store(3, std::memory_order_release);
       }
@@ -573,18 +576,24 @@ static void seq2_keys_ready(Seq2Chunk *ch, int first, int last) {
     ch->sort_ns.fetch_add((long long)((vsm_now_us() - t0) * 1e3), std::memory_order_relaxed);
     if (ch->sort_tasks_left.fetch_sub(1, std::memory_order_acq_rel) == 1) {
       ch->sorts_left.fetch_sub(1, std::memory_order_acq_rel);
+      const bool warm = ch->warm;
+      const int nw_tasks = ch->n;
+      if (warm) ch->warm_left.store(nw_tasks, std::memory_order_release);  // (before the gate opens: the chunk cannot end first)
       seq2_open_gate(ch);
-      if (ch->warm) {  // (the pool is idle until this chunk's survivor bits arrive: see Seq2Chunk::warm)
+      if (warm) {  // (the pool is idle until this chunk's survivor bits arrive: see Seq2Chunk::warm)
         vsm_handle *h2 = ch->h;
-        h2->pool->submit(ch->n, [ch, h2](int j) {
-          Seq2 &S = *h2->seq2;
-          const int32_t f = ch->f0 + j;
-          const int32_t n_all = std::max(0, std::min(ch->B->h_n[j], ch->B->cap));
-          const volatile uint64_t *p = (const volatile uint64_t *)(S.res + S.res_off[f]);
-          uint64_t acc = 0;
-          for (size_t w = 0, nw = (size_t)n_all * sizeof(vsm_p_match) / 8; w < nw; w += 8) acc += p[w];  // (one word per 64-byte line)
-          (void)acc;
-          ch->warm_domain[j].store((signed char)vsm_thread_domain(), std::memory_order_release);
+        h2->pool->submit(nw_tasks, [ch, h2](int j) {
+          if (!ch->warm_claim[j].load(std::memory_order_acquire)) {  // (a list whose gaps are being closed already needs no warming)
+            Seq2 &S = *h2->seq2;
+            const int32_t f = ch->f0 + j;
+            const int32_t n_all = std::max(0, std::min(ch->B->h_n[j], ch->B->cap));
+            const volatile uint64_t *p = (const volatile uint64_t *)(S.res + S.res_off[f]);
+            uint64_t acc = 0;
+            for (size_t w = 0, nw = (size_t)n_all * sizeof(vsm_p_match) / 8; w < nw; w += 8) acc += p[w];  // (one word per 64-byte line)
+            (void)acc;
+            ch->warm_domain[j].store((signed char)vsm_thread_domain(), std::memory_order_release);
+          }
+          ch->warm_left.fetch_sub(1, std::memory_order_acq_rel);  // (the last access to the chunk)
         });
       }
     }
@@ -595,7 +604,8 @@ static void seq2_keys_ready(Seq2Chunk *ch, int first, int last) {
 // is host work: the last chunk's vertex sorts and the closing of the gaps in its lists)
 static bool seq2_wait_chunk(Seq2Chunk *ch, double timeout_us, VsmPool *helper = nullptr) {
   const double t0 = vsm_now_us();
-  while (ch->state.load(std::memory_order_acquire) != 3 && ch->state.load(std::memory_order_acquire) != 0) {
+  while ((ch->state.load(std::memory_order_acquire) != 3 && ch->state.load(std::memory_order_acquire) != 0) ||
+         ch->warm_left.load(std::memory_order_acquire) > 0) {
     if (helper) {
       if (!helper->help()) std::this_thread::yield();
     } else {
@@ -778,17 +788,20 @@ static int sequence_run_v2(vsm_handle *h, const uint8_t *left, const uint8_t *ri
           (void)hipStreamSynchronize(ch->stream);
           const double t0 = vsm_now_us();
           while (ch->gate.load() > 1 && vsm_now_us() - t0 < 5e6) std::this_thread::sleep_for(std::chrono::microseconds(50));
+          while (ch->warm_left.load() > 0 && vsm_now_us() - t0 < 10e6)  // (the last sort queued warm-up tasks behind the gate)
+            if (!h->pool->help()) std::this_thread::yield();
           ch->state.store(0);
           continue;
         }
         if (!seq2_wait_chunk(ch.get(), 30e6)) {
           fprintf(stderr, "visomatch: the final stage of a look-ahead chunk did not complete: %s\n", hipGetErrorString(hipStreamQuery(ch->stream)));
-          fprintf(stderr, "  chunk %d: state %d gate %d sorts_left %d unpack_left %d hip_error %d; events: keys %s, mesh %s, exp %s, ref %s\n", ch->k, ch->state.load(),
-                  ch->gate.load(), ch->sorts_left.load(), ch->unpack_left.load(), ch->hip_error.load(),
+          fprintf(stderr, "  chunk %d: state %d gate %d sorts_left %d unpack_left %d warm_left %d hip_error %d; events: keys %s, mesh %s, exp %s, ref %s\n", ch->k,
+                  ch->state.load(), ch->gate.load(), ch->sorts_left.load(), ch->unpack_left.load(), ch->warm_left.load(), ch->hip_error.load(),
                   ch->ev_keys ? hipGetErrorString(hipEventQuery(ch->ev_keys)) : "-", ch->ev_mesh ? hipGetErrorString(hipEventQuery(ch->ev_mesh)) : "-",
                   ch->ev_exp ? hipGetErrorString(hipEventQuery(ch->ev_exp)) : "-", ch->ev_ref ? hipGetErrorString(hipEventQuery(ch->ev_ref)) : "-");
           (void)hipStreamSynchronize(ch->stream);
-          while (ch->sorts_left.load() > 0 || ch->unpack_left.load() > 0) std::this_thread::sleep_for(std::chrono::microseconds(50));
+          while (ch->sorts_left.load() > 0 || ch->unpack_left.load() > 0 || ch->warm_left.load() > 0)
+            std::this_thread::sleep_for(std::chrono::microseconds(50));
         }
       }
       for (int i = 0; i < S.dc_streams; i++) (void)hipStreamSynchronize(S.dc2[i]);

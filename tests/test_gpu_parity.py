@@ -207,7 +207,7 @@ def test_full_size_properties(vm, synth):
 
 @pytest.mark.parametrize("binary", ["vo_dropin", "vo_native"])
 def test_reference_vo_runs_on_dropin_matcher(synth, tmp_path, binary):
-    """tools/dropin/_build/vo_dropin = the reference's unmodified VisualOdometryStereo sources
+    """oracle/_ref/dropin/vo_dropin = the reference's unmodified VisualOdometryStereo sources
     compiled against include/matcher.h + libvisomatch.so (built where /root/reference exists);
     vo_native = the same driver compiled against include/viso_stereo.h (the C-ABI's own
     VisualOdometryStereo; only the reference's Matrix class is compiled in).
@@ -215,7 +215,7 @@ def test_reference_vo_runs_on_dropin_matcher(synth, tmp_path, binary):
     import os
     import subprocess
     from conftest import ROOT
-    exe = os.path.join(ROOT, "tools", "dropin", "_build", binary)
+    exe = os.path.join(ROOT, "oracle", "_ref", "dropin", binary)
     if not os.path.exists(exe):
         pytest.skip("drop-in binary not built (needs the reference sources at build time)")
     g = G.load("cfg2_seq200_tr")
@@ -982,13 +982,13 @@ def test_vo_mono_large_vs_oracle(vm, B):
 
 
 def test_vo_mono_dropin_header(vm, tmp_path):
-    """tools/dropin/_build/mono_native = a C++ caller of include/viso_mono.h (VisualOdometryMono over
+    """oracle/_ref/dropin/mono_native = a C++ caller of include/viso_mono.h (VisualOdometryMono over
     the C-ABI): same result as the Python mirror on the same match list, both from a fresh sampler"""
     import os
     import subprocess
     import sys
     from conftest import ROOT
-    exe = os.path.join(ROOT, "tools", "dropin", "_build", "mono_native")
+    exe = os.path.join(ROOT, "oracle", "_ref", "dropin", "mono_native")
     if not os.path.exists(exe):
         pytest.skip("drop-in binary not built (needs the reference's matrix.cpp at build time)")
     sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))

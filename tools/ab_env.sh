@@ -2,7 +2,7 @@
 # interleaved bench runs under environment settings: tools/ab_env.sh "A=1 B=2" "A=0" ... (each argument one setting; "-" = none)
 for r in 1 2; do
 for v in "$@"; do
-  ( [ "$v" != "-" ] && export $v; python bench.py --steps 8 --warmup 3 --no-cpu-baseline --no-per-frame --no-alone 2>/dev/null | python -c "
+  ( [ "$v" != "-" ] && export $v; python bench.py --full --steps 8 --warmup 3 --no-cpu-baseline --no-per-frame --no-alone 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 k=d['kernel_avg_launch_us']

@@ -3,7 +3,7 @@
 ROUNDS=${ROUNDS:-2}
 for r in $(seq $ROUNDS); do
 for v in "$@"; do
-  ( [ "$v" != "-" ] && export $v; python bench.py --steps 8 --warmup 3 --no-cpu-baseline --no-per-frame --no-alone 2>/dev/null | python -c "
+  ( [ "$v" != "-" ] && export $v; python bench.py --full --steps 8 --warmup 3 --no-cpu-baseline --no-per-frame --no-alone 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 k=d['kernel_avg_launch_us']

@@ -1,10 +1,11 @@
 #!/bin/bash
 # per-kernel times of the look-ahead call under rocprofv3 --stats, image-side kernels first: tools/feat_stats.sh TAG [extra bench args]
+ROOT_DIR=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 TAG=$1; shift
 O=$GRAFT_REPO_ROOT/gpurun_out/r5/stats_$TAG
 rm -rf $O && mkdir -p $O
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O -o run -- python3 $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 1 --startup 0 --no-cpu-baseline --no-verify --no-per-frame --no-alone "$@" > $O.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O -o run -- python3 $ROOT_DIR/bench.py --full --steps 3 --warmup 1 --startup 0 --no-cpu-baseline --no-verify --no-per-frame --no-alone "$@" > $O.log 2>&1
 python3 - <<P
 import csv,glob
 f=glob.glob("$O/**/*kernel_stats.csv", recursive=True)[0]

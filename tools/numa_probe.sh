@@ -19,7 +19,7 @@ if [ "$1" = "run" ]; then
   for r in 1 2; do
     for set in none "$NEAR" "$FAR"; do
       if [ "$set" = none ]; then P=""; else P="taskset -c $set"; fi
-      $P python bench.py --steps 40 --warmup 3 --no-cpu-baseline --no-per-frame --no-alone --no-verify 2>/dev/null | python -c "
+      $P python bench.py --full --steps 40 --warmup 3 --no-cpu-baseline --no-per-frame --no-alone --no-verify 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); s=sorted(d['step_ms_rank0'])
 print('cpus %-22s value %6.0f  min %.2f p50 %.2f p90 %.2f max %.2f' % ('$set', d['value'], s[0], s[len(s)//2], s[int(len(s)*.9)], s[-1]))"

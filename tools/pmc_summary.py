@@ -5,7 +5,7 @@
 
 The two inputs come from SEPARATE runs (`rocprofv3 --pmc FETCH_SIZE --kernel-trace ...` and
 `--pmc WRITE_SIZE ...`; FETCH_SIZE and WRITE_SIZE do not fit one pass on gfx950) of
-`bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-verify --no-per-frame`.
+`bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-verify --no-per-frame`.
 traffic = (2 x FETCH_SIZE + WRITE_SIZE) x 1024 bytes per launch: on gfx950 FETCH_SIZE reports half
 of the bytes of wide streaming reads (MI355X_MICROARCH.md, HBM section); WRITE_SIZE is exact.
 `bench_name` is the kernel's name in bench.py's kernel tables.
