@@ -278,6 +278,11 @@ int32_t vsm_debug_dc2(const vsm_params *p, const vsm_p_match *list, int32_t n, i
  * LDS lines; a node that needs more is redone by one lane in global memory.  f < 0 restores the default (12); a small f
  * forces that second path, which no list of the benchmark takes.  Process-wide. */
 void vsm_debug_dc2_band_factor(int32_t f);
+/* Test hook of the exact Delaunay's device predicates (vsm_dc_lds.h, the edge-word mesh of the device chain): for n
+ * quadruples of packed points x | y << 16 (coordinates < 2^14) out[i*3..i*3+2] = orientation determinant of a, b, c,
+ * sign of the in-circle determinant of a, b, c, d, and 1 if d lies strictly inside the circle through a, b, c, as the
+ * GPU computes them.  0, or -1 on a HIP error. */
+int32_t vsm_debug_predicates(const uint32_t *quads, int32_t n, int32_t *out);
 
 /* ---- stereo visual odometry on top of the matcher ----
  * class VisualOdometryStereo, viso/viso_stereo.h:28-88 + viso/viso.h:28-131: process() =

@@ -1061,7 +1061,7 @@ int vsm_match(vsm_handle *h, int32_t method, const double *Tr) {
   // sub-pixel refinement: the fits' least-squares tail and the removal of failed matches on the device too (as in the look-ahead
   // path; 7 k matches x 3 fits were 3 ms of one host thread) - unless the stage views are wanted, which show the list in between
   const bool fits_on_device = p.refinement == 2 && !h->capture_stage2 && nq2 <= VSM_PARA_MAX_LIST;
-  if (fits_on_device) vsm_launch_parabolic_apply(h->stream, c.d_pairs, 1);
+  if (fits_on_device) vsm_launch_parabolic_apply(h->stream, h->prof, c.d_pairs, 1);
   vsm_launch_export(h->stream, h->prof, c.d_pairs, 1, 1, nq2);
   if (early_xy) {
     // (an event behind the export: waiting for it when it has long fired costs 2 us, hipStreamSynchronize on the idle stream 18)
@@ -2269,7 +2269,7 @@ static const char *kKernelNames[VSM_K_COUNT] = {
     "k_bin_scatter", "k_bin_rank", "k_match<16>:pass1", "k_compact_matches:pass1", "k_match<16>:pass2",
     "k_compact_matches:pass2", "k_refine", "k_export_list", "k_front",
     "k_dc_keys", "k_dc_vertex_sort", "k_dc_prepare_kd_order", "k_dc_block", "k_dc_merge", "k_dc_support", "k_dc_compact", "k_dc_prior",
-    "k_feat_dense", "k_feat_sparse", "k_feat_scan", "k_feat_order"};
+    "k_feat_dense", "k_feat_sparse", "k_feat_scan", "k_feat_order", "k_parabolic_apply"};
 
 void vsm_set_profiling(vsm_handle *h, int on) {
   h->prof.on = on != 0;

@@ -2251,6 +2251,32 @@ static std::atomic<int> g_dc2_band_factor{DC2_BAND_F};
 // test hook: bands of 256 + f * sqrt(points) LDS lines (f < 0: the default) - with a small f the large merge nodes overflow
 // their band and are redone by one lane in global memory, the path that no list of the benchmark takes
 extern "C" void vsm_debug_dc2_band_factor(int32_t f) { g_dc2_band_factor.store(f < 0 ? DC2_BAND_F : f); }
+// test hook: the edge-word mesh's predicates as the device evaluates them, for quadruples of packed points x | y << 16
+// (coordinates < 2^14): out[i*3] = ccw_p(a, b, c), out[i*3+1] = incircle_s(a, b, c, d), out[i*3+2] = incircle_in(a, b, c, d)
+__global__ void __launch_bounds__(256) k_debug_predicates(const uint32_t *__restrict__ q, int32_t n, int32_t *__restrict__ out) {
+  const int32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t a = q[i * 4], b = q[i * 4 + 1], c = q[i * 4 + 2], d = q[i * 4 + 3];
+  out[i * 3] = DcBandMesh::ccw_p(a, b, c);
+  out[i * 3 + 1] = DcBandMesh::incircle_s(a, b, c, d);
+  out[i * 3 + 2] = DcBandMesh::incircle_in(a, b, c, d) ? 1 : 0;
+}
+extern "C" int32_t vsm_debug_predicates(const uint32_t *quads, int32_t n, int32_t *out) {
+  if (n <= 0) return 0;
+  uint32_t *dq = nullptr;
+  int32_t *dout = nullptr;
+  int32_t rc = -1;
+  if (hipMalloc((void **)&dq, (size_t)n * 16) == hipSuccess && hipMalloc((void **)&dout, (size_t)n * 12) == hipSuccess &&
+      hipMemcpy(dq, quads, (size_t)n * 16, hipMemcpyHostToDevice) == hipSuccess) {
+    hipLaunchKernelGGL(k_debug_predicates, dim3((n + 255) / 256), dim3(256), 0, nullptr, dq, n, dout);
+    if (hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
+        hipMemcpy(out, dout, (size_t)n * 12, hipMemcpyDeviceToHost) == hipSuccess)
+      rc = 0;
+  }
+  if (dq) (void)hipFree(dq);
+  if (dout) (void)hipFree(dout);
+  return rc;
+}
 void vsm_dc2_launch_merges(hipStream_t s, const VsmDc2Job *d_jobs, int njobs, int depth, int max_list) {
   if (njobs <= 0) return;
   const double band_f = (double)g_dc2_band_factor.load(std::memory_order_relaxed);

@@ -118,35 +118,18 @@ struct DcEdgeMesh {
     const int32_t cx = (int32_t)(pc & 0xffffu), cy = (int32_t)(pc >> 16);
     return mul24((int32_t)(pa & 0xffffu) - cx, (int32_t)(pb >> 16) - cy) - mul24((int32_t)(pa >> 16) - cy, (int32_t)(pb & 0xffffu) - cx);
   }
-  // sign of the in-circle determinant.  Every lifted length and every cross product is an integer below 2^31 and their
-  // products sum to less than 2^53 in magnitude (coordinates < 2^14): exact in double, three fused multiply-adds
-  // instead of three 64-bit integer multiply-adds of five instructions each
-  DC2_DEV static inline int32_t incircle_s(uint32_t pa, uint32_t pb, uint32_t pc, uint32_t pd) {
+  // the in-circle determinant, exact for coordinates < 2^14: every lifted length and every cross product is an integer
+  // below 2 * 16383^2 < 2^29 in magnitude (the 24-bit multiplies and their sums are exact in int32), but their products
+  // reach 2^58 and the sum of three stays below 2^60 - beyond double's 53 bits (in double, exactly cocircular points on a
+  // 16383 x 16383 frame come out with either sign), inside int64: the three products as v_mad_i64_i32, one instruction
+  // each (the compiler's own 64-bit multiply of a known-non-negative by a signed 32-bit value comes out as two
+  // v_mad_u64_u32 plus moves)
+  DC2_DEV static inline int64_t incircle_det(uint32_t pa, uint32_t pb, uint32_t pc, uint32_t pd) {
     const int32_t dx = (int32_t)(pd & 0xffffu), dy = (int32_t)(pd >> 16);
     const int32_t adx = (int32_t)(pa & 0xffffu) - dx, ady = (int32_t)(pa >> 16) - dy;
     const int32_t bdx = (int32_t)(pb & 0xffffu) - dx, bdy = (int32_t)(pb >> 16) - dy;
     const int32_t cdx = (int32_t)(pc & 0xffffu) - dx, cdy = (int32_t)(pc >> 16) - dy;
 #ifdef __HIP_DEVICE_COMPILE__
-    const double l1 = (double)(mul24(adx, adx) + mul24(ady, ady)), l2 = (double)(mul24(bdx, bdx) + mul24(bdy, bdy)), l3 = (double)(mul24(cdx, cdx) + mul24(cdy, cdy));
-    const double c1 = (double)(mul24(bdx, cdy) - mul24(cdx, bdy)), c2 = (double)(mul24(cdx, ady) - mul24(adx, cdy)), c3 = (double)(mul24(adx, bdy) - mul24(bdx, ady));
-    const double det = __builtin_fma(l1, c1, __builtin_fma(l2, c2, l3 * c3));
-    return det > 0 ? 1 : (det < 0 ? -1 : 0);
-#else
-    const int64_t det = (int64_t)(adx * adx + ady * ady) * (bdx * cdy - cdx * bdy) + (int64_t)(bdx * bdx + bdy * bdy) * (cdx * ady - adx * cdy) +
-                        (int64_t)(cdx * cdx + cdy * cdy) * (adx * bdy - bdx * ady);
-    return det > 0 ? 1 : (det < 0 ? -1 : 0);
-#endif
-  }
-  DC2_DEV static inline int64_t incircle_p(uint32_t pa, uint32_t pb, uint32_t pc, uint32_t pd) { return incircle_s(pa, pb, pc, pd); }
-  // ... and only "is d strictly inside the circle through a, b, c" (what the seam walk asks): the three products as
-  // v_mad_i64_i32, one instruction each (the compiler's own 64-bit multiply of a known-non-negative by a signed 32-bit value
-  // comes out as two v_mad_u64_u32 plus moves; DC2_INCIRCLE_F64 selects the same sum in double, exact as well and 7 % slower).
-  DC2_DEV static inline bool incircle_in(uint32_t pa, uint32_t pb, uint32_t pc, uint32_t pd) {
-    const int32_t dx = (int32_t)(pd & 0xffffu), dy = (int32_t)(pd >> 16);
-    const int32_t adx = (int32_t)(pa & 0xffffu) - dx, ady = (int32_t)(pa >> 16) - dy;
-    const int32_t bdx = (int32_t)(pb & 0xffffu) - dx, bdy = (int32_t)(pb >> 16) - dy;
-    const int32_t cdx = (int32_t)(pc & 0xffffu) - dx, cdy = (int32_t)(pc >> 16) - dy;
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(DC2_INCIRCLE_F64)
     const int32_t l1 = mul24(adx, adx) + mul24(ady, ady), l2 = mul24(bdx, bdx) + mul24(bdy, bdy), l3 = mul24(cdx, cdx) + mul24(cdy, cdy);
     const int32_t c1 = mul24(bdx, cdy) - mul24(cdx, bdy), c2 = mul24(cdx, ady) - mul24(adx, cdy), c3 = mul24(adx, bdy) - mul24(bdx, ady);
     int64_t det;
@@ -154,17 +137,21 @@ struct DcEdgeMesh {
     asm("v_mad_i64_i32 %0, %1, %2, %3, 0" : "=v"(det), "=s"(carry) : "v"(l1), "v"(c1));
     asm("v_mad_i64_i32 %0, %1, %2, %3, %4" : "=v"(det), "=s"(carry) : "v"(l2), "v"(c2), "v"(det));
     asm("v_mad_i64_i32 %0, %1, %2, %3, %4" : "=v"(det), "=s"(carry) : "v"(l3), "v"(c3), "v"(det));
-    return det > 0;
-#elif defined(__HIP_DEVICE_COMPILE__)
-    const double l1 = (double)(mul24(adx, adx) + mul24(ady, ady)), l2 = (double)(mul24(bdx, bdx) + mul24(bdy, bdy)), l3 = (double)(mul24(cdx, cdx) + mul24(cdy, cdy));
-    const double c1 = (double)(mul24(bdx, cdy) - mul24(cdx, bdy)), c2 = (double)(mul24(cdx, ady) - mul24(adx, cdy)), c3 = (double)(mul24(adx, bdy) - mul24(bdx, ady));
-    return __builtin_fma(l1, c1, __builtin_fma(l2, c2, l3 * c3)) > 0;
+    return det;
 #else
     return (int64_t)(adx * adx + ady * ady) * (bdx * cdy - cdx * bdy) + (int64_t)(bdx * bdx + bdy * bdy) * (cdx * ady - adx * cdy) +
-               (int64_t)(cdx * cdx + cdy * cdy) * (adx * bdy - bdx * ady) >
-           0;
+           (int64_t)(cdx * cdx + cdy * cdy) * (adx * bdy - bdx * ady);
 #endif
   }
+  // sign of the in-circle determinant (the merge levels' dc2_zip asks incircle_in; this one serves dc_merge_hulls'
+  // accessors and the device check vsm_debug_predicates)
+  DC2_DEV static inline int32_t incircle_s(uint32_t pa, uint32_t pb, uint32_t pc, uint32_t pd) {
+    const int64_t det = incircle_det(pa, pb, pc, pd);
+    return det > 0 ? 1 : (det < 0 ? -1 : 0);
+  }
+  DC2_DEV static inline int64_t incircle_p(uint32_t pa, uint32_t pb, uint32_t pc, uint32_t pd) { return incircle_s(pa, pb, pc, pd); }
+  // ... and only "is d strictly inside the circle through a, b, c" (what the seam walk asks)
+  DC2_DEV static inline bool incircle_in(uint32_t pa, uint32_t pb, uint32_t pc, uint32_t pd) { return incircle_det(pa, pb, pc, pd) > 0; }
   // rotation of a handle inside its triangle: dir = true -> lnext, false -> lprev (one code path for both)
   DC2_DEV static inline int32_t hrot(int32_t h, bool next) {
     const uint32_t lut = next ? 0x09u : 0x12u;  // o -> o + 1 mod 3 / o - 1 mod 3, two bits per o

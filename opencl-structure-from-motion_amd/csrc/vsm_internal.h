@@ -101,6 +101,8 @@ enum VsmKernelId {
   VSM_K_FEAT_DENSE, VSM_K_FEAT_SPARSE,
   // feature records + bin-sorted copy in two kernels (k_feat_scan, k_feat_order)
   VSM_K_FEAT_SCAN, VSM_K_FEAT_ORDER,
+  // refinement = 2 on the device: the sub-pixel fits' least-squares tail and the removal of failed matches
+  VSM_K_PARA_APPLY,
   VSM_K_COUNT
 };
 struct VsmProf {
@@ -183,7 +185,7 @@ bool vsm_launch_match(hipStream_t s, VsmProf &pf, const VsmImage *d_imgs, const 
 void vsm_launch_export(hipStream_t s, VsmProf &pf, const VsmPair *d_pairs, int npairs, int pass, int n_upper);
 void vsm_launch_export_xy(hipStream_t s, const VsmPair *d_pairs, uint32_t *dst_host_mapped, int n_upper);  // pair 0's pass-2 pixels, x | y << 16
 #define VSM_PARA_MAX_LIST 16384  // matches per pair the batched tail of refinement==2 takes
-void vsm_launch_parabolic_apply(hipStream_t s, const VsmPair *d_pairs, int npairs);
+void vsm_launch_parabolic_apply(hipStream_t s, VsmProf &pf, const VsmPair *d_pairs, int npairs);
 void vsm_launch_refine(hipStream_t s, VsmProf &pf, const VsmImage *d_imgs, const VsmPair *d_pairs, const VsmJob *d_jobs,
                        const VsmJob &job0, int npairs, const VsmDims &dp, const VsmDims &dc, int method, int refinement,
                        int n_upper);

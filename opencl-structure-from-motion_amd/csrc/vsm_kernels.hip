@@ -3024,10 +3024,12 @@ void vsm_launch_export_xy(hipStream_t s, const VsmPair *d_pairs, uint32_t *dst_h
 }
 
 // the batched tail of refinement==2 (behind vsm_launch_refine): fits, dropped matches, the lists closed up again
-void vsm_launch_parabolic_apply(hipStream_t s, const VsmPair *d_pairs, int npairs) {
+void vsm_launch_parabolic_apply(hipStream_t s, VsmProf &pf, const VsmPair *d_pairs, int npairs) {
   if (npairs <= 0) return;
   static const VsmParaPlan plan = make_para_plan();
+  pf.begin(VSM_K_PARA_APPLY, s);
   hipLaunchKernelGGL(k_parabolic_apply, dim3(npairs), dim3(1024), 0, s, d_pairs, plan);
+  pf.end(s);
 }
 
 void vsm_launch_refine(hipStream_t s, VsmProf &pf, const VsmImage *d_imgs, const VsmPair *d_pairs, const VsmJob *d_jobs,

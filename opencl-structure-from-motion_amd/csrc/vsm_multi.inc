@@ -263,7 +263,7 @@ int vsm_multi_process(vsm_multi *m, const uint8_t *left, const uint8_t *right, i
     MULTI_CHK(vsm_upload(h->stream, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * K));
     if (p.refinement == 2) {  // sub-pixel fits drop matches: they come before the keys of what is left (section 6b of DESIGN.md)
       vsm_launch_refine(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, K, c.dims, c.dims, method, p.refinement, max_nq[1]);
-      vsm_launch_parabolic_apply(h->stream, d_pairs, K);
+      vsm_launch_parabolic_apply(h->stream, h->prof, d_pairs, K);
     }
     vsm_dc2_launch_keys(h->stream, B.d_jobs, K, max_nq[1]);  // (also into host-mapped memory: the pool sorts them)
     MULTI_CHK(hipEventRecord(m->ev_keys, h->stream));

@@ -1178,7 +1178,7 @@ static int sequence_run_v2(vsm_handle *h, const uint8_t *left, const uint8_t *ri
                         p.refinement, q.max_nq[1]);
     // sub-pixel refinement: the fits' least-squares tail and the removal of the matches whose fit fails - the list gets shorter,
     // so this chunk's chain starts behind it (ev_ref), not behind the second pass
-    if (p.refinement == 2) vsm_launch_parabolic_apply(h->stream, c.d_pairs + q.first_pair, q.n);
+    if (p.refinement == 2) vsm_launch_parabolic_apply(h->stream, h->prof, c.d_pairs + q.first_pair, q.n);
     ch->ev_ref = S.get_event();
     if (!ch->ev_ref) return VSM_EHIP;
     HIPCHK(hipEventRecord(ch->ev_ref, h->stream));

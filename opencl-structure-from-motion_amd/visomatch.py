@@ -34,7 +34,7 @@ EXPORTS = ["vsm_default_params", "vsm_create", "vsm_destroy", "vsm_set_intrinsic
            "vsm_num_features", "vsm_get_features", "vsm_set_stage_capture", "vsm_stage_size", "vsm_stage_get",
            "vsm_num_ranges", "vsm_get_ranges", "vsm_get_gradients", "vsm_get_filter_responses", "vsm_get_counters",
            "vsm_get_timings", "vsm_set_profiling", "vsm_num_kernels", "vsm_kernel_name", "vsm_get_kernel_stats",
-           "vsm_host_delaunay", "vsm_host_delaunay_split", "vsm_debug_delaunay_gpu", "vsm_debug_dc_bench", "vsm_host_ties", "vsm_debug_ties_gpu", "vsm_host_outliers_and_prior", "vsm_host_outliers_and_prior_threads", "vsm_debug_dc2", "vsm_debug_dc2_band_factor", "vsm_local_cpus", "vsm_forkjoin_cpus", "vsm_device_pool_stats", "vsm_device_pool_trim", "vsm_sequence_run", "vsm_sequence_num_matches", "vsm_sequence_get_matches",
+           "vsm_host_delaunay", "vsm_host_delaunay_split", "vsm_debug_delaunay_gpu", "vsm_debug_dc_bench", "vsm_host_ties", "vsm_debug_ties_gpu", "vsm_host_outliers_and_prior", "vsm_host_outliers_and_prior_threads", "vsm_debug_dc2", "vsm_debug_dc2_band_factor", "vsm_debug_predicates", "vsm_local_cpus", "vsm_forkjoin_cpus", "vsm_device_pool_stats", "vsm_device_pool_trim", "vsm_sequence_run", "vsm_sequence_num_matches", "vsm_sequence_get_matches",
            "vsm_sequence_get_timings", "vsm_sequence_path", "vsm_set_option", "vsm_version", "vsm_host_register", "vsm_host_unregister",
            "vsm_multi_create", "vsm_multi_destroy", "vsm_multi_process", "vsm_multi_num_sequences", "vsm_multi_get_motion",
            "vsm_multi_motion_valid", "vsm_multi_num_matches", "vsm_multi_get_matches", "vsm_multi_num_inliers", "vsm_multi_get_inliers",
@@ -156,6 +156,7 @@ def lib():
         L.vsm_host_outliers_and_prior_threads.argtypes = [C.POINTER(VsmParams), vp, i32, i32, vp, i32, vp, i32, i32, i32]
         L.vsm_debug_dc2.argtypes = [C.POINTER(VsmParams), vp, i32, i32, i32, i32, vp, i32, vp, i32, i32, vp]
         L.vsm_debug_dc2_band_factor.argtypes = [i32]
+        L.vsm_debug_predicates.argtypes = [vp, i32, vp]
         L.vsm_local_cpus.argtypes = [vp, i32]
         L.vsm_forkjoin_cpus.argtypes = [vp, i32]
         L.vsm_debug_dc2_band_factor.restype = None
@@ -339,7 +340,8 @@ def delaunay_gpu_split(pts, max_task_points, device_top_points=0, device_kd=Fals
 
 def ties(pts, gpu=False):
     """which matches at shared pixels stand for their points: sorted (carried index, right index) pairs where they
-    differ, from the host emulation of Triangle's vertex sort or from the GPU's; (pairs, kernel microseconds)"""
+    differ, from the host emulation of Triangle's vertex sort or from the GPU's; (pairs, kernel microseconds).  pairs is
+    None where the GPU's sort declines the list (too long, or more shared pixels than it reports)"""
     pts = np.asarray(pts).reshape(-1, 2)
     x = np.ascontiguousarray(pts[:, 0], dtype=np.int32)
     y = np.ascontiguousarray(pts[:, 1], dtype=np.int32)
@@ -351,10 +353,25 @@ def ties(pts, gpu=False):
                                      C.byref(us))
     else:
         k = lib().vsm_host_ties(x.ctypes.data_as(C.c_void_p), y.ctypes.data_as(C.c_void_p), len(x), out.ctypes.data_as(C.c_void_p), cap)
+    if k == -2:
+        raise VisoMatchError("vsm_debug_ties_gpu: HIP error")
     if k < 0:
         return None, us.value
     o = out[:k]
     return o[np.lexsort(o.T[::-1])], us.value
+
+
+def device_predicates(quads):
+    """test hook: the exact Delaunay's predicates as the GPU evaluates them on [n, 4, 2] integer points (coordinates < 2^14):
+    an [n, 3] array of (orientation determinant of a, b, c; sign of the in-circle determinant of a, b, c, d; 1 if d lies
+    strictly inside the circle through a, b, c)"""
+    q = np.asarray(quads, dtype=np.int64).reshape(-1, 4, 2)
+    assert q.min(initial=0) >= 0 and q.max(initial=0) < 1 << 14
+    packed = np.ascontiguousarray(q[:, :, 0] | (q[:, :, 1] << 16), dtype=np.uint32)
+    out = np.zeros((len(q), 3), dtype=np.int32)
+    if lib().vsm_debug_predicates(packed.ctypes.data_as(C.c_void_p), len(q), out.ctypes.data_as(C.c_void_p)) != 0:
+        raise VisoMatchError("vsm_debug_predicates: HIP error")
+    return out
 
 
 def remove_outliers(matches, method, w, h, gpu=False, gpu_ties=False, copies=1, threads=1, **params):
