@@ -124,7 +124,8 @@ float vsm_gain(vsm_handle *h, const int32_t *inliers, int32_t n);
 int vsm_sequence_run(vsm_handle *h, const uint8_t *left, const uint8_t *right, int64_t frame_stride, int on_device,
                      int32_t n_frames, int32_t width, int32_t height, int32_t bpl, int32_t method,
                      const double *Tr_delta, const uint8_t *Tr_valid);
-/* getMatches() as it would read after frame `frame` */
+/* getMatches() as it would read after frame `frame`: where matchFeatures returned early on a frame (an image without
+ * features), the list of the last frame before it on which it ran */
 int32_t vsm_sequence_num_matches(vsm_handle *h, int32_t frame);
 int32_t vsm_sequence_get_matches(vsm_handle *h, int32_t frame, vsm_p_match *out, int32_t cap);
 /* wall-clock split of the last vsm_sequence_run() on the caller's thread, microseconds: {launching and waiting

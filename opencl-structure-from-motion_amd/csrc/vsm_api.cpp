@@ -643,6 +643,10 @@ struct vsm_handle {
     int32_t n = 0;
   };
   std::vector<SeqView> seq_view;
+  // per frame of the last look-ahead call: the frame whose list getMatches() shows after it - the frame itself where
+  // matchFeatures ran, else the last one before it where it did (the reference returns early without touching p_matched,
+  // viso/matcher.cpp:184-203), -1: none yet.  The batched forms fill it; the frame-by-frame form copies the lists themselves.
+  std::vector<int32_t> seq_src;
   double seq_timings[4] = {0, 0, 0, 0};
   bool dc_gpu_broken = false;    // a Delaunay stream reported a HIP error once: the host-shared form keeps off the GPU share from then on
   std::atomic<int> seq_hip_error{0};  // set by a chunk whose GPU share failed during the current vsm_sequence_run
@@ -1644,6 +1648,7 @@ static int sequence_fallback(vsm_handle *h, const uint8_t *left, const uint8_t *
   ctx_destroy(h->ring);
   reset_ring_state(h);
   h->matched.clear();
+  for (int32_t f = 0; f < n_frames; f++) h->seq_src[f] = f;
   for (int32_t f = 0; f < n_frames; f++) {
     const uint8_t *l = left + (size_t)f * frame_stride, *r = right ? right + (size_t)f * frame_stride : nullptr;
     int rc = push_common(h, l, r, w, hh, bpl, 0, on_device != 0);
@@ -1670,6 +1675,8 @@ int vsm_sequence_run(vsm_handle *h, const uint8_t *left, const uint8_t *right, i
   h->seq_matches.resize(n_frames);  // keeps the capacity of earlier runs: no page-fault storm
   for (auto &v : h->seq_matches) v.clear();
   h->seq_view.assign(n_frames, vsm_handle::SeqView());
+  h->seq_src.resize(n_frames);
+  for (int32_t f = 0; f < n_frames; f++) h->seq_src[f] = f;
   // (mono input can only be flow-matched; the host-shared form below has no sub-pixel refinement - its fits and dropped matches
   // are the GPU-resident form's, or the per-frame code's)
   if ((!right && (method != 0 || !h->sw.seq_v2)) || (p.refinement == 2 && !h->sw.seq_v2))
@@ -1898,6 +1905,7 @@ int vsm_sequence_run(vsm_handle *h, const uint8_t *left, const uint8_t *right, i
           memcpy(jb.t, Tr + (size_t)f * 12, 12 * sizeof(double));
         }
       }
+      h->seq_src[f] = valid[i] ? f : (f > 0 ? h->seq_src[f - 1] : -1);
       max_nq[0] = std::max(max_nq[0], jb.nq[0]);
       max_nq[1] = std::max(max_nq[1], jb.nq[1]);
     }
@@ -2133,15 +2141,23 @@ int vsm_sequence_run(vsm_handle *h, const uint8_t *left, const uint8_t *right, i
   return h->seq_hip_error.load() ? VSM_EHIP : VSM_OK;
 }
 
+// the frame whose list stands after `frame` (vsm_handle::seq_src), -1: no list yet
+static int32_t seq_source_frame(const vsm_handle *h, int32_t frame) {
+  if (frame < 0 || frame >= (int32_t)h->seq_matches.size()) return -1;
+  return frame < (int32_t)h->seq_src.size() ? h->seq_src[frame] : frame;
+}
+
 int32_t vsm_sequence_num_matches(vsm_handle *h, int32_t frame) {
-  if (frame < 0 || frame >= (int32_t)h->seq_matches.size()) return 0;
+  frame = seq_source_frame(h, frame);
+  if (frame < 0) return 0;
   if (frame < (int32_t)h->seq_view.size() && h->seq_view[frame].p) return h->seq_view[frame].n;
   return (int32_t)h->seq_matches[frame].size();
 }
 
 // (both look-ahead forms end with every frame's list in the reference's 48-byte p_match form in host memory)
 int32_t vsm_sequence_get_matches(vsm_handle *h, int32_t frame, vsm_p_match *out, int32_t cap) {
-  if (frame < 0 || frame >= (int32_t)h->seq_matches.size()) return 0;
+  frame = seq_source_frame(h, frame);
+  if (frame < 0) return 0;
   const bool view = frame < (int32_t)h->seq_view.size() && h->seq_view[frame].p;
   int32_t n = view ? h->seq_view[frame].n : (int32_t)h->seq_matches[frame].size();
   if (n > cap) n = cap;

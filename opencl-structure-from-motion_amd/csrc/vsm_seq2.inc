@@ -1051,6 +1051,7 @@ static int sequence_run_v2(vsm_handle *h, const uint8_t *left, const uint8_t *ri
           memcpy(jb.t, Tr + (size_t)f * 12, 12 * sizeof(double));
         }
       }
+      h->seq_src[f] = (*q.valid)[i] ? f : (f > 0 ? h->seq_src[f - 1] : -1);
       q.max_nq[0] = std::max(q.max_nq[0], jb.nq[0]);
       q.max_nq[1] = std::max(q.max_nq[1], jb.nq[1]);
     }
