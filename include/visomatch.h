@@ -284,6 +284,13 @@ void vsm_debug_dc2_band_factor(int32_t f);
  * sign of the in-circle determinant of a, b, c, d, and 1 if d lies strictly inside the circle through a, b, c, as the
  * GPU computes them.  0, or -1 on a HIP error. */
 int32_t vsm_debug_predicates(const uint32_t *quads, int32_t n, int32_t *out);
+/* Test hook of the look-ahead call's chunk plan (pure arithmetic, no GPU): how vsm_sequence_run's GPU-resident form cuts
+ * n_frames frames into chunks for a host pool of pool_threads threads, frames in HBM (host_in = 0) or in host memory
+ * (1), options seq_chunk / seq_first_chunk (0: default) and the plan string of VSM_SEQ_PLAN (NULL: none).  *chunk = the
+ * banks' stride, starts[0 .. n] = first frame of each chunk and n_frames; returns the number of chunks n, or -1 (a bad
+ * argument, or cap < n + 1). */
+int32_t vsm_debug_seq_plan(int32_t n_frames, int32_t pool_threads, int32_t host_in, int32_t seq_chunk, int32_t seq_first_chunk,
+                           const char *plan, int32_t *chunk, int32_t *starts, int32_t cap);
 
 /* ---- stereo visual odometry on top of the matcher ----
  * class VisualOdometryStereo, viso/viso_stereo.h:28-88 + viso/viso.h:28-131: process() =

@@ -521,7 +521,7 @@ struct VsmSwitches {
   int seq_last_first = 1;    // ... a chain's sort + kd order kernel goes in with its head, and the block kernel of the last chunk but one waits for the last chunk's
   int seq_first_chunk = 0;   // ... frames of the call's first chunk (0: like the others)
   int seq_p2_first = -1;     // ... a chunk's second pass in front of the features of chunk k + 2 (the order host-resident inputs get): -1 = by pool size
-  int seq_export_budget = 2; // ... pieces of the early export submitted behind a chunk's keys where the next chunk's keys follow at once (sequence_run_v2: export_some)
+  int seq_export_budget = 2; // ... pieces of the early export submitted behind a chunk's keys where the next chunk's keys follow at once (Seq2Call::export_some)
   int seq_null_stream = 1;   // ... its fifth stream (early exports, the device's vertex sorts) is the process's null stream (1) or a non-blocking stream of
                              // the library's own (0: for applications that keep work of their own on the null stream - INTEGRATION.md)
   int seq_host_inorder = 1;  // ... host-resident inputs: chunk by chunk in the order of arrival - the caller's thread waits for a chunk's feature counts only when everything of the chunk in front is enqueued (0: the run-ahead order of HBM-resident inputs)

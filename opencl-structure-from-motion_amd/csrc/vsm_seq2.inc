@@ -320,7 +320,7 @@ struct Seq2 {
   //   pass-1 vertex sort of chunk j (one wave per list, 0.4 ms, beside the pass-1 mesh)                 null stream
   //   final chain of chunk j (head: jobs, keys, the keys' DMA copy to the pool; mesh; second part)   cs[j % 3]
   //   early export of chunk j's refined lists (28 MB per 80 pairs, in DMA copies of 20 pairs)           null stream, submitted in the order the copy engine
-  //                                                                                                      should work in (sequence_run_v2: export_some)
+  //                                                                                                      should work in (Seq2Call::export_some)
   hipStream_t dc2[4] = {nullptr, nullptr, nullptr, nullptr};  // cs[]: dc_streams (1..3) of them
   // the device's share of the final chains' vertex sorts (ranks with few host threads): ONE launch for the lists of all the
   // chunks that are waiting for it - a wave per list takes 3.2 ms whatever the number of lists - on the null stream; its job
@@ -377,12 +377,8 @@ struct Seq2 {
   int dc_streams = 3;                  // streams the final chains of successive chunks rotate over
   bool expect_long = false;            // a list of more than 8192 points has been seen (vsm_dc2_launch_prepare)
   std::mutex ev_mu;  // (events are also taken by pool threads: the second parts)
-  hipEvent_t get_event_locked() {
+  hipEvent_t get_event() {
     std::lock_guard<std::mutex> lk(ev_mu);
-    return get_event_unlocked();
-  }
-  hipEvent_t get_event() { return get_event_locked(); }
-  hipEvent_t get_event_unlocked() {
     if (ev_used == events.size()) {
       hipEvent_t e = nullptr;
       if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return nullptr;
@@ -530,7 +526,7 @@ static void seq2_enqueue_second_part(Seq2Chunk *ch) {
       ok = hipMemcpy2DAsync(S.res + S.res_off[ch->f0], S.res_slot, S.res_stage + S.res_off[ch->f0], S.res_slot, row, (size_t)ch->n, hipMemcpyDeviceToHost,
                             s) == hipSuccess;
     // (who sees the chain's end: Seq2Poller)
-    hipEvent_t ev_done = ok ? h->seq2->get_event_locked() : nullptr;
+    hipEvent_t ev_done = ok ? h->seq2->get_event() : nullptr;
     ok = ok && ev_done && hipGetLastError() == hipSuccess && hipEventRecord(ev_done, s) == hipSuccess;
     if (ok) {
       // (before the task can run: it ends in state 3, and a store of 2 behind it would undo that)
@@ -616,16 +612,14 @@ static bool seq2_wait_chunk(Seq2Chunk *ch, double timeout_us, VsmPool *helper = 
   return true;
 }
 
-// returns VSM_OK, an error, or VSM_SEQ2_DECLINED when this path does not take the run (the caller uses the first form)
-#define VSM_SEQ2_DECLINED 1000
-static int sequence_run_v2(vsm_handle *h, const uint8_t *left, const uint8_t *right, int64_t frame_stride, int on_device, int32_t n_frames,
-                           int32_t w, int32_t hh, int32_t bpl, int32_t method, const double *Tr, const uint8_t *Tr_valid) {
-  const vsm_params &p = h->param;
-  const VsmSwitches &sw = h->sw;
-  // Mono input (right == NULL, flow matching: Matcher::pushBack(I1, dims, replace) + matchFeatures(0), viso/matcher.h:118,
-  // viso/matcher.cpp:1006-1041) runs the same pipeline over one image per frame: image ids are then consecutive per frame
-  // instead of (left, right) pairs.
-  const int sides = right ? 2 : 1;
+// The chunk plan of a look-ahead call: the chunk size C (the frame and pair banks' stride) and the frame every chunk starts
+// at (start[nchunks] = n_frames).  Pure arithmetic - no HIP call, nothing of a handle - so the CPU suite pins it through
+// vsm_debug_seq_plan (tests/test_seq_plan.py).  `plan`: the call passes getenv("VSM_SEQ_PLAN").
+struct Seq2Plan {
+  int C = 0;
+  std::vector<int32_t> start;
+};
+static Seq2Plan seq2_plan(int32_t n_frames, int pool_threads, bool host_in, int seq_chunk, int seq_first_chunk, const char *plan) {
   // Chunk size.  A final chain is a row of latency-bound kernels and takes about as long for 50 lists as for 80, so fewer,
   // larger chunks pay as long as the host keeps up with their vertex sorts.  Measured (200 frames 1242x375, ms per sequence,
   // 14 pool threads, round 4's five-queue layout): 6.0 / 5.15 / 4.65 / 4.55 / 4.56 / 4.61 / 4.97 with chunks of 40 / 50 / 67 /
@@ -635,62 +629,22 @@ static int sequence_run_v2(vsm_handle *h, const uint8_t *left, const uint8_t *ri
   // / 134 (110: 110 + 90) -; with eight threads the pool's vertex sorts bound the call either way (5.3 ms), with four 50 wins.
   // Host-resident inputs: the first chunk's upload is the one transfer nothing hides, so the first chunk is HALF a chunk
   // (and the chunks a little larger, so that 200 frames still make three): 40 + 80 + 80.
-  const bool host_in = !on_device;
-  const int keys_dma = sw.seq_keys_dma >= 0 ? sw.seq_keys_dma : (h->pool->size() >= 10 ? 2 : 1);  // (vsm_api.cpp: VsmSwitches)
   // (three host threads or fewer: the device sorts a share of the final lists in one launch behind the call's last keys, and
   // every chunk's survivors cross PCIe behind that - two chunks of 100: 7.6 ms against 8.3 with four of 50)
-  int C = sw.seq_chunk > 0 ? sw.seq_chunk : (h->pool->size() >= 10 && !host_in ? 110 : (h->pool->size() >= 6 ? 80 : (h->pool->size() <= 4 && !host_in ? 100 : 50)));
+  int C = seq_chunk > 0 ? seq_chunk : (pool_threads >= 10 && !host_in ? 110 : (pool_threads >= 6 ? 80 : (pool_threads <= 4 && !host_in ? 100 : 50)));
   if (C > n_frames) C = n_frames;
-  if (sw.seq_chunk <= 0 && n_frames > C && n_frames % C != 0 && n_frames % C < C / 2) {
+  if (seq_chunk <= 0 && n_frames > C && n_frames % C != 0 && n_frames % C < C / 2) {
     // (a short last chunk costs a whole chain's latency at the end of the call: 1000 frames are ten chunks of 100, not nine
     // of 110 and one of 10; 200 stay 110 + 90)
     const int nch = (n_frames + C - 1) / C;
     C = (n_frames + nch - 1) / nch;
   }
-  if (!h->seq2) h->seq2 = new Seq2();
-  Seq2 &S = *h->seq2;
-  VsmCtx &c = h->seq;
-  // Frame banks: the features run two chunks ahead of the second matching pass, and a chunk's first pair reads the previous
-  // chunk's last frame: chunks k-1 .. k+2 are alive at once, and the bank of chunk k+3 must not be the one chunk k-1's chain
-  // still reads.  Pair banks: a chunk's lists are read until its final chain is done (the wait below).
-  const int kPairBanks = 4, kFrameBanks = 5;
-  if (!c.ready || c.dims.w != w || c.dims.h != hh || h->seq_chunk != C || c.npairs != kPairBanks * C || c.nframes != kFrameBanks * C) {
-    (void)hipStreamSynchronize(h->stream);
-    int rc = ctx_create(c, p, w, hh, kFrameBanks * C, kPairBanks * C, h->stream, h->sw.match_heads != 0);
-    if (rc != VSM_OK) return rc;
-    h->seq_chunk = C;
-  }
-  if ((size_t)c.dims.ub * c.dims.vb > 1024) return VSM_SEQ2_DECLINED;  // (k_dc2_prior keeps the bins' minima and maxima in LDS)
-  auto make_stream = [&](hipStream_t &st) { return st || hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess; };  // (priorities - main stream high, side streams low - change nothing: measured again in round 4)
-
-  // (only the streams this run uses: the runtime deals its hardware queues out per stream, idle ones included, and a stream
-  // that shares a hardware queue with another one runs in turns with it)
-  S.poller.start(h->device, h->aff, h->pool->size() >= 10);
-  // (host-resident inputs: the copy stream is one of the five, so the chains rotate over two streams - with a sixth stream in
-  // the process two of them share a hardware queue and run in turns: 8.5-9.4 ms per 200 frames against 7.5-7.9; an idle
-  // stream keeps its queue, so the third one is given back)
-  S.dc_streams = host_in ? std::min(2, sw.seq_dc_streams) : sw.seq_dc_streams;
-  for (int i = S.dc_streams; i < 4; i++)
-    if (S.dc2[i]) {
-      (void)hipStreamSynchronize(S.dc2[i]);
-      (void)hipStreamDestroy(S.dc2[i]);
-      S.dc2[i] = nullptr;
-    }
-  for (int i = 0; i < S.dc_streams; i++)
-    if (!make_stream(S.dc2[i])) return VSM_SEQ2_DECLINED;
-  if (sw.seq_null_stream) {
-    S.ns = nullptr;
-  } else {
-    if (!make_stream(S.aux)) return VSM_SEQ2_DECLINED;
-    S.ns = S.aux;
-  }
-
-  S.ev_used = 0;
-  S.bank1_copied[0] = S.bank1_copied[1] = nullptr;
-  std::vector<int32_t> chunk_start;
-  if (host_in && getenv("VSM_SEQ_PLAN")) {  // (experiments: the chunks' sizes, "40,80,60,20")
+  Seq2Plan P;
+  P.C = C;
+  std::vector<int32_t> &chunk_start = P.start;
+  if (host_in && plan) {  // (experiments: the chunks' sizes, "40,80,60,20")
     chunk_start.push_back(0);
-    for (const char *q = getenv("VSM_SEQ_PLAN"); *q && chunk_start.back() < n_frames;) {
+    for (const char *q = plan; *q && chunk_start.back() < n_frames;) {
       const int v = std::min(std::max(atoi(q), 2), C);
       chunk_start.push_back(std::min(n_frames, chunk_start.back() + v));
       while (*q && *q != ',') q++;
@@ -704,121 +658,256 @@ static int sequence_run_v2(vsm_handle *h, const uint8_t *left, const uint8_t *ri
     // (the frames arrive at the link's rate and the GPU keeps up with them: what the call waits for at its end is everything
     // that follows the LAST frames' arrival - features, both passes, two chain latencies - so the last chunk is a short one)
     if (n_frames - chunk_start.back() > 30) chunk_start.push_back(n_frames - 20);
-  } else if (sw.seq_first_chunk > 0 && sw.seq_first_chunk < C && n_frames > C) {
+  } else if (seq_first_chunk > 0 && seq_first_chunk < C && n_frames > C) {
     chunk_start.push_back(0);
-    for (int32_t f = sw.seq_first_chunk; f < n_frames; f += C) chunk_start.push_back(f);
+    for (int32_t f = seq_first_chunk; f < n_frames; f += C) chunk_start.push_back(f);
   } else {
     for (int32_t f = 0; f < n_frames; f += C) chunk_start.push_back(f);
   }
   chunk_start.push_back(n_frames);
-  const int nchunks = (int)chunk_start.size() - 1;
-  // result arena: one slot of `slot` matches per frame (no list is longer than its query count, which the host only
-  // learns chunk by chunk: the dense feature capacity bounds it)
-  const size_t slot = ((size_t)c.cap_set[1] * sizeof(vsm_p_match) + 255) & ~(size_t)255;
-  if (S.res_bytes < slot * n_frames || S.res_frames < n_frames) {
-    if (S.res) (void)hipHostFree(S.res);
-    if (S.res_cnt) (void)hipHostFree(S.res_cnt);
-    S.res = nullptr;
-    S.res_cnt = nullptr;
-    S.res_bytes = 0;
-    if (hipHostMalloc((void **)&S.res, slot * n_frames, hipHostMallocMapped) != hipSuccess ||
-        hipHostGetDevicePointer((void **)&S.res_dev, S.res, 0) != hipSuccess ||
-        hipHostMalloc((void **)&S.res_cnt, (size_t)n_frames * 4, hipHostMallocMapped) != hipSuccess ||
-        hipHostGetDevicePointer((void **)&S.res_cnt_dev, S.res_cnt, 0) != hipSuccess) {
-      (void)hipGetLastError();
-      return VSM_SEQ2_DECLINED;
+  return P;
+}
+// (debug entry, include/visomatch.h)
+extern "C" int32_t vsm_debug_seq_plan(int32_t n_frames, int32_t pool_threads, int32_t host_in, int32_t seq_chunk, int32_t seq_first_chunk,
+                                      const char *plan, int32_t *chunk, int32_t *starts, int32_t cap) {
+  if (n_frames <= 0 || pool_threads <= 0 || !chunk || !starts) return -1;
+  const Seq2Plan P = seq2_plan(n_frames, pool_threads, host_in != 0, seq_chunk, seq_first_chunk, plan);
+  if ((int32_t)P.start.size() > cap) return -1;
+  *chunk = P.C;
+  std::copy(P.start.begin(), P.start.end(), starts);
+  return (int32_t)P.start.size() - 1;
+}
+// Whatever way a look-ahead call is left, nothing of it may still be running: the last data member of Seq2Call, so that it
+// waits - for the pool's tasks, the poller's, the streams - BEFORE anything else of the call is destroyed.
+struct Seq2Drain {
+  vsm_handle *h = nullptr;  // set = armed (sequence_run_v2: when the buffers exist, before the first upload task); until then the set-up's returns wait for nothing
+  ~Seq2Drain() {
+    if (!h) return;
+    Seq2 &S = *h->seq2;
+    for (auto &pc : S.up_pieces)  // (the gathers read the caller's images; the task that takes `left` to zero enqueues the piece's
+                                  // DMA copy AFTERWARDS and says so in `recorded`: only then is everything of the piece on the stream)
+      while (pc->left.load(std::memory_order_acquire) > 0 || pc->recorded.load(std::memory_order_acquire) == 0)
+        if (!h->pool->help()) std::this_thread::yield();
+    if (S.up) {  // (the upload stream lives for the host-fed call only: idle streams keep a share of a hardware queue)
+      (void)hipStreamSynchronize(S.up);
+      (void)hipStreamDestroy(S.up);
+      S.up = nullptr;
     }
-    S.res_bytes = slot * n_frames;
-    S.res_frames = n_frames;
-  }
-  memset(S.res_cnt, 0, (size_t)n_frames * 4);
-  // Result form.  Either the device compacts the survivors as 48-byte p_match records in HBM (res_stage) and one strided DMA
-  // copy per chain takes them into the host-mapped arena - no host-side work at all -, or (res_early) the refined lists cross
-  // PCIe as they are while the chain still triangulates, the chain ends with one survivor bit per match, and the pool closes
-  // the gaps in the arena.  The getters read the arena either way.  (Round 2's 24-byte packed records, expanded by the pool
-  // inside the call: 5.9 / 12.4 ms per 200 frames with 14 / 4 pool threads against 5.4 / 8.8 - removed.)
-  // closing the gaps costs the pool ~30 us per list: worth it where the pool has threads to spare (measured: 5.4 against 5.6 ms per
-  // 200 frames with 14 threads, 9.1 against 8.8 with 4, 11.4 against 9.0 with 1)
-  S.res_early = sw.seq_early_export < 0 ? h->pool->size() >= 6 : sw.seq_early_export != 0;
-  if (S.res_early) {
-    const size_t kw = ((size_t)c.cap_set[1] + 31) / 32 + 1;
-    if (S.keep_words < kw || S.keep_frames < (size_t)n_frames) {
-      if (S.keep) (void)hipHostFree(S.keep);
-      S.keep = nullptr;
-      S.keep_words = S.keep_frames = 0;
-      if (hipHostMalloc((void **)&S.keep, kw * n_frames * 4, hipHostMallocMapped) != hipSuccess ||
-          hipHostGetDevicePointer((void **)&S.keep_dev, S.keep, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        return VSM_SEQ2_DECLINED;
-      }
-      S.keep_words = kw;
-      S.keep_frames = (size_t)n_frames;
-    }
-  }
-  if (S.res_stage_bytes < slot * n_frames) {  // survivors are written in HBM and cross PCIe by DMA copies
-    if (S.res_stage) vsm_dev_free(S.res_stage);
-    S.res_stage = nullptr;
-    S.res_stage_bytes = 0;
-    if (vsm_dev_alloc((void **)&S.res_stage, slot * n_frames) != hipSuccess) {
-      (void)hipGetLastError();
-      return VSM_SEQ2_DECLINED;
-    }
-    S.res_stage_bytes = slot * n_frames;
-  }
-  S.res_slot = slot;
-  S.res_off.assign(n_frames, 0);
-  for (int32_t f = 0; f < n_frames; f++) S.res_off[f] = slot * f;
-  S.chunks.clear();
-  h->seq_hip_error.store(0);
-  struct Drain {  // whatever way this function is left, nothing of it may still be running
-    vsm_handle *h;
-    ~Drain() {
-      Seq2 &S = *h->seq2;
-      for (auto &pc : S.up_pieces)  // (the gathers read the caller's images; the task that takes `left` to zero enqueues the piece's
-                                    // DMA copy AFTERWARDS and says so in `recorded`: only then is everything of the piece on the stream)
-        while (pc->left.load(std::memory_order_acquire) > 0 || pc->recorded.load(std::memory_order_acquire) == 0)
+    for (auto &ch : S.chunks) {
+      if (ch->state.load() == 1 && !ch->caller_gate) {  // left before the caller's half of the gate was opened: only the sorts are on their way
+        (void)hipStreamSynchronize(ch->stream);
+        const double t0 = vsm_now_us();
+        while (ch->gate.load() > 1 && vsm_now_us() - t0 < 5e6) std::this_thread::sleep_for(std::chrono::microseconds(50));
+        while (ch->warm_left.load() > 0 && vsm_now_us() - t0 < 10e6)  // (the last sort queued warm-up tasks behind the gate)
           if (!h->pool->help()) std::this_thread::yield();
-      if (S.up) {  // (the upload stream lives for the host-fed call only: idle streams keep a share of a hardware queue)
-        (void)hipStreamSynchronize(S.up);
-        (void)hipStreamDestroy(S.up);
-        S.up = nullptr;
+        ch->state.store(0);
+        continue;
       }
-      for (auto &ch : S.chunks) {
-        if (ch->state.load() == 1 && !ch->caller_gate) {  // left before the caller's half of the gate was opened: only the sorts are on their way
-          (void)hipStreamSynchronize(ch->stream);
-          const double t0 = vsm_now_us();
-          while (ch->gate.load() > 1 && vsm_now_us() - t0 < 5e6) std::this_thread::sleep_for(std::chrono::microseconds(50));
-          while (ch->warm_left.load() > 0 && vsm_now_us() - t0 < 10e6)  // (the last sort queued warm-up tasks behind the gate)
-            if (!h->pool->help()) std::this_thread::yield();
-          ch->state.store(0);
-          continue;
-        }
-        if (!seq2_wait_chunk(ch.get(), 30e6)) {
-          fprintf(stderr, "visomatch: the final stage of a look-ahead chunk did not complete: %s\n", hipGetErrorString(hipStreamQuery(ch->stream)));
-          fprintf(stderr, "  chunk %d: state %d gate %d sorts_left %d unpack_left %d warm_left %d hip_error %d; events: keys %s, mesh %s, exp %s, ref %s\n", ch->k,
-                  ch->state.load(), ch->gate.load(), ch->sorts_left.load(), ch->unpack_left.load(), ch->warm_left.load(), ch->hip_error.load(),
-                  ch->ev_keys ? hipGetErrorString(hipEventQuery(ch->ev_keys)) : "-", ch->ev_mesh ? hipGetErrorString(hipEventQuery(ch->ev_mesh)) : "-",
-                  ch->ev_exp ? hipGetErrorString(hipEventQuery(ch->ev_exp)) : "-", ch->ev_ref ? hipGetErrorString(hipEventQuery(ch->ev_ref)) : "-");
-          (void)hipStreamSynchronize(ch->stream);
-          while (ch->sorts_left.load() > 0 || ch->unpack_left.load() > 0 || ch->warm_left.load() > 0)
-            std::this_thread::sleep_for(std::chrono::microseconds(50));
-        }
+      if (!seq2_wait_chunk(ch.get(), 30e6)) {
+        fprintf(stderr, "visomatch: the final stage of a look-ahead chunk did not complete: %s\n", hipGetErrorString(hipStreamQuery(ch->stream)));
+        fprintf(stderr, "  chunk %d: state %d gate %d sorts_left %d unpack_left %d warm_left %d hip_error %d; events: keys %s, mesh %s, exp %s, ref %s\n", ch->k,
+                ch->state.load(), ch->gate.load(), ch->sorts_left.load(), ch->unpack_left.load(), ch->warm_left.load(), ch->hip_error.load(),
+                ch->ev_keys ? hipGetErrorString(hipEventQuery(ch->ev_keys)) : "-", ch->ev_mesh ? hipGetErrorString(hipEventQuery(ch->ev_mesh)) : "-",
+                ch->ev_exp ? hipGetErrorString(hipEventQuery(ch->ev_exp)) : "-", ch->ev_ref ? hipGetErrorString(hipEventQuery(ch->ev_ref)) : "-");
+        (void)hipStreamSynchronize(ch->stream);
+        while (ch->sorts_left.load() > 0 || ch->unpack_left.load() > 0 || ch->warm_left.load() > 0)
+          std::this_thread::sleep_for(std::chrono::microseconds(50));
       }
-      for (int i = 0; i < S.dc_streams; i++) (void)hipStreamSynchronize(S.dc2[i]);
-      (void)hipStreamSynchronize(S.ns);
-      (void)hipStreamSynchronize(h->stream);
     }
-  } drain{h};
+    for (int i = 0; i < S.dc_streams; i++) (void)hipStreamSynchronize(S.dc2[i]);
+    (void)hipStreamSynchronize(S.ns);
+    (void)hipStreamSynchronize(h->stream);
+  }
+};
 
-  const double tstart = now_us();
-  double tg = 0;
-  const size_t img_bytes = (size_t)w * hh;
-  S.up_pieces.clear();
+static bool seq2_make_stream(hipStream_t &st) { return st || hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess; }  // (priorities - main stream high, side streams low - change nothing: measured again in round 4)
+// returns VSM_OK, an error, or VSM_SEQ2_DECLINED when this path does not take the run (the caller uses the first form)
+#define VSM_SEQ2_DECLINED 1000
+// One call of the GPU-resident form: what its steps share, by role, and the steps; sequence_run_v2 below is their order.
+// The object lives on the caller's stack for the duration of the call, and only the caller's thread touches it.
+//
+// LIFETIME RULE.  A task handed to the pool (submit), to the poller or to a stream callback may outlive the step that made
+// it - and, on an error return, everything but the drain's wait - so it holds only what outlives the call: vsm_handle*,
+// Seq2*, Seq2Chunk*, Seq2::UpPiece*, and plain values (the caller's image pointers among them, which the caller keeps
+// until the call returns).  It never holds this object, a reference into it or a [&] capture.  The one exception is a
+// blocking pool->run, whose closure is dead when it returns (finish_chain1).  `drain` is the LAST data member and so the
+// first to be destroyed: while it waits, every other member is still there - and by the rule nobody needs them.
+struct Seq2Call {
+  // Frame banks: the features run two chunks ahead of the second matching pass, and a chunk's first pair reads the previous
+  // chunk's last frame: chunks k-1 .. k+2 are alive at once, and the bank of chunk k+3 must not be the one chunk k-1's chain
+  // still reads.  Pair banks: a chunk's lists are read until its final chain is done (wait_for_chunk).
+  static constexpr int kPairBanks = 4, kFrameBanks = 5;
+  struct Ck {  // a chunk as the caller's thread sees it (no task holds one - the rule above - so nothing in it is shared: plain members)
+    int32_t f0 = 0;
+    int n = 0, first_img = 0, first_pair = 0;
+    int max_nq[2] = {0, 0};
+    hipEvent_t ev_prior = nullptr, ev_p1 = nullptr;
+    hipEvent_t ev_k1 = nullptr;   // pass-1 chain with the vertex sorts on the pool: its keys are in host memory (chain stream)
+    bool chain1_open = false;     // ... and its second part (tie patches, votes, boxes) is not enqueued yet (finish_chain1)
+  };
+  // --- inputs and references
+  vsm_handle *const h;
+  Seq2 &S;
+  VsmCtx &c;
+  const vsm_params &p;
+  const VsmSwitches &sw;
+  const uint8_t *const left, *const right;
+  const int64_t frame_stride;
+  const int on_device;
+  const int32_t n_frames, w, hh, bpl, method;
+  const double *const Tr;
+  const uint8_t *const Tr_valid;
+  // Mono input (right == NULL, flow matching: Matcher::pushBack(I1, dims, replace) + matchFeatures(0), viso/matcher.h:118,
+  // viso/matcher.cpp:1006-1041) runs the same pipeline over one image per frame: image ids are then consecutive per frame
+  // instead of (left, right) pairs.
+  const int sides = right ? 2 : 1;
+  // --- the plan: const once the set-up is through
+  const bool host_in = !on_device;
+  const int keys_dma = sw.seq_keys_dma >= 0 ? sw.seq_keys_dma : (h->pool->size() >= 10 ? 2 : 1);  // (vsm_api.cpp: VsmSwitches)
+  const Seq2Plan plan = seq2_plan(n_frames, h->pool->size(), host_in, sw.seq_chunk, sw.seq_first_chunk, getenv("VSM_SEQ_PLAN"));
+  const int C = plan.C;
+  const std::vector<int32_t> &chunk_start = plan.start;
+  const int nchunks = (int)chunk_start.size() - 1;
   // option "seq_host_pinned": the caller vouches that its images lie in page-locked memory (hipHostMalloc, or registered once
   // with vsm_host_register / hipHostRegister): the pieces then cross by DMA straight out of them - no gather pass of the pool
   // (2.2 ms of its time per 200 frames), no pinned twin - enqueued here, all at once, in frame order
   const bool host_pinned = host_in && sw.seq_host_pinned;
-  if (host_in) {
+  const bool inorder = host_in && !sw.seq_serial && sw.seq_host_inorder;
+  // (pass-1 vertex sorts on the pool: ranks with ten pool threads and more, frames in HBM; option seq_ties1_host 0 / 1)
+  const bool ties1_host = p.multi_stage && !sw.seq_serial && (sw.seq_ties1_host >= 0 ? sw.seq_ties1_host != 0 : (h->pool->size() >= 10 && !host_in));
+  // seq_serial (VSM_SEQ_SERIAL=1, measurements): nothing overlaps - every group of launches drains before the next one is
+  // enqueued, so each kernel's HIP-event time is its time with the GPU to itself (bench.py's "alone" figures).  Same
+  // kernels, same data, same results.
+  const bool serial = sw.seq_serial;
+  const int gpu_sorts_default = h->pool->size() <= 2 ? 67 : (h->pool->size() == 3 ? 50 : (h->pool->size() == 4 ? 33 : 0));  // (four threads: 7.0 ms without a share, 8.3 with one)
+  const bool split_sorts = nchunks == 2 && sw.seq_gpu_sorts < 0 && gpu_sorts_default > 0 && !serial;
+  const bool p2_first = sw.seq_p2_first >= 0 ? sw.seq_p2_first != 0 : (h->pool->size() >= 5 && h->pool->size() < 10 && (sw.seq_gpu_sorts >= 0 ? sw.seq_gpu_sorts : gpu_sorts_default) == 0);
+  const size_t img_bytes = (size_t)w * hh;
+  size_t slot = 0;  // bytes per frame in the result arena (setup_results)
+  // --- cursors: the caller's thread only
+  std::vector<Ck> ck = std::vector<Ck>(nchunks);
+  int32_t nprev[2][2] = {{0, 0}, {0, 0}};
+  int chain1_next = 0;  // first chunk whose pass-1 chain has not been enqueued yet
+  int chain_next = 0;  // first chunk whose final chain has not been enqueued yet
+  int refine_pending = -1;  // chunk whose refinement waits for the next chunk's matching (seq_defer_refine)
+  int exp_k = 0;  // first chunk with rows left to submit
+  std::vector<int> ties_pending;   // chunks whose device share has not been launched yet
+  // A sorting wave wants 139 KB of LDS, i.e. a compute unit to itself, and finds none while a block-kernel launch has five
+  // workgroups on every unit: the triangulations that are enqueued behind the launch wait for this event - recorded right
+  // in front of the sort kernel on its stream - so that the sorts are placed first and the meshes share what is left.
+  hipEvent_t ev_ties_go = nullptr;
+  int tie_jobs_at = 0;  // rows of the job table this call's launches have used (every launch its own rows: no launch waits for another's copy)
+  double tstart = 0, tg = 0;  // the call's start; what the caller's thread has spent waiting (seq_timings[0])
+  std::vector<double> dbg_counts, dbg_main;  // (VSM_DEBUG_TIMING: when the caller's thread had a chunk's counts / had enqueued its second pass)
+  Seq2Drain drain;  // LAST: see the rule above
+
+  Seq2Call(vsm_handle *h_, const uint8_t *left_, const uint8_t *right_, int64_t frame_stride_, int on_device_, int32_t n_frames_, int32_t w_, int32_t hh_,
+           int32_t bpl_, int32_t method_, const double *Tr_, const uint8_t *Tr_valid_)
+      : h(h_), S(*h_->seq2), c(h_->seq), p(h_->param), sw(h_->sw), left(left_), right(right_), frame_stride(frame_stride_), on_device(on_device_),
+        n_frames(n_frames_), w(w_), hh(hh_), bpl(bpl_), method(method_), Tr(Tr_), Tr_valid(Tr_valid_) {}
+
+  // set-up, in three steps that return VSM_OK, an error or VSM_SEQ2_DECLINED: the context and the streams ...
+  int setup_streams() {
+    if (!c.ready || c.dims.w != w || c.dims.h != hh || h->seq_chunk != C || c.npairs != kPairBanks * C || c.nframes != kFrameBanks * C) {
+      (void)hipStreamSynchronize(h->stream);
+      int rc = ctx_create(c, p, w, hh, kFrameBanks * C, kPairBanks * C, h->stream, h->sw.match_heads != 0);
+      if (rc != VSM_OK) return rc;
+      h->seq_chunk = C;
+    }
+    if ((size_t)c.dims.ub * c.dims.vb > 1024) return VSM_SEQ2_DECLINED;  // (k_dc2_prior keeps the bins' minima and maxima in LDS)
+
+    // (only the streams this run uses: the runtime deals its hardware queues out per stream, idle ones included, and a stream
+    // that shares a hardware queue with another one runs in turns with it)
+    S.poller.start(h->device, h->aff, h->pool->size() >= 10);
+    // (host-resident inputs: the copy stream is one of the five, so the chains rotate over two streams - with a sixth stream in
+    // the process two of them share a hardware queue and run in turns: 8.5-9.4 ms per 200 frames against 7.5-7.9; an idle
+    // stream keeps its queue, so the third one is given back)
+    S.dc_streams = host_in ? std::min(2, sw.seq_dc_streams) : sw.seq_dc_streams;
+    for (int i = S.dc_streams; i < 4; i++)
+      if (S.dc2[i]) {
+        (void)hipStreamSynchronize(S.dc2[i]);
+        (void)hipStreamDestroy(S.dc2[i]);
+        S.dc2[i] = nullptr;
+      }
+    for (int i = 0; i < S.dc_streams; i++)
+      if (!seq2_make_stream(S.dc2[i])) return VSM_SEQ2_DECLINED;
+    if (sw.seq_null_stream) {
+      S.ns = nullptr;
+    } else {
+      if (!seq2_make_stream(S.aux)) return VSM_SEQ2_DECLINED;
+      S.ns = S.aux;
+    }
+
+    S.ev_used = 0;
+    S.bank1_copied[0] = S.bank1_copied[1] = nullptr;
+    return VSM_OK;
+  }
+  // ... the result arena, `keep` and `res_stage` ...
+  int setup_results() {
+    // result arena: one slot of `slot` matches per frame (no list is longer than its query count, which the host only
+    // learns chunk by chunk: the dense feature capacity bounds it)
+    slot = ((size_t)c.cap_set[1] * sizeof(vsm_p_match) + 255) & ~(size_t)255;
+    if (S.res_bytes < slot * n_frames || S.res_frames < n_frames) {
+      if (S.res) (void)hipHostFree(S.res);
+      if (S.res_cnt) (void)hipHostFree(S.res_cnt);
+      S.res = nullptr;
+      S.res_cnt = nullptr;
+      S.res_bytes = 0;
+      if (hipHostMalloc((void **)&S.res, slot * n_frames, hipHostMallocMapped) != hipSuccess ||
+          hipHostGetDevicePointer((void **)&S.res_dev, S.res, 0) != hipSuccess ||
+          hipHostMalloc((void **)&S.res_cnt, (size_t)n_frames * 4, hipHostMallocMapped) != hipSuccess ||
+          hipHostGetDevicePointer((void **)&S.res_cnt_dev, S.res_cnt, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        return VSM_SEQ2_DECLINED;
+      }
+      S.res_bytes = slot * n_frames;
+      S.res_frames = n_frames;
+    }
+    memset(S.res_cnt, 0, (size_t)n_frames * 4);
+    // Result form.  Either the device compacts the survivors as 48-byte p_match records in HBM (res_stage) and one strided DMA
+    // copy per chain takes them into the host-mapped arena - no host-side work at all -, or (res_early) the refined lists cross
+    // PCIe as they are while the chain still triangulates, the chain ends with one survivor bit per match, and the pool closes
+    // the gaps in the arena.  The getters read the arena either way.  (Round 2's 24-byte packed records, expanded by the pool
+    // inside the call: 5.9 / 12.4 ms per 200 frames with 14 / 4 pool threads against 5.4 / 8.8 - removed.)
+    // closing the gaps costs the pool ~30 us per list: worth it where the pool has threads to spare (measured: 5.4 against 5.6 ms per
+    // 200 frames with 14 threads, 9.1 against 8.8 with 4, 11.4 against 9.0 with 1)
+    S.res_early = sw.seq_early_export < 0 ? h->pool->size() >= 6 : sw.seq_early_export != 0;
+    if (S.res_early) {
+      const size_t kw = ((size_t)c.cap_set[1] + 31) / 32 + 1;
+      if (S.keep_words < kw || S.keep_frames < (size_t)n_frames) {
+        if (S.keep) (void)hipHostFree(S.keep);
+        S.keep = nullptr;
+        S.keep_words = S.keep_frames = 0;
+        if (hipHostMalloc((void **)&S.keep, kw * n_frames * 4, hipHostMallocMapped) != hipSuccess ||
+            hipHostGetDevicePointer((void **)&S.keep_dev, S.keep, 0) != hipSuccess) {
+          (void)hipGetLastError();
+          return VSM_SEQ2_DECLINED;
+        }
+        S.keep_words = kw;
+        S.keep_frames = (size_t)n_frames;
+      }
+    }
+    if (S.res_stage_bytes < slot * n_frames) {  // survivors are written in HBM and cross PCIe by DMA copies
+      if (S.res_stage) vsm_dev_free(S.res_stage);
+      S.res_stage = nullptr;
+      S.res_stage_bytes = 0;
+      if (vsm_dev_alloc((void **)&S.res_stage, slot * n_frames) != hipSuccess) {
+        (void)hipGetLastError();
+        return VSM_SEQ2_DECLINED;
+      }
+      S.res_stage_bytes = slot * n_frames;
+    }
+    S.res_slot = slot;
+    S.res_off.assign(n_frames, 0);
+    for (int32_t f = 0; f < n_frames; f++) S.res_off[f] = slot * f;
+    S.chunks.clear();
+    h->seq_hip_error.store(0);
+    return VSM_OK;
+  }
+  // ... and, for host-resident inputs, the upload buffers and the pieces the frames cross in
+  int setup_uploads() {
+    S.up_pieces.clear();
+    if (!host_in) return VSM_OK;
     const size_t need = (size_t)sides * n_frames * img_bytes;
     if (S.up_bytes < need || (!host_pinned && !S.up_h)) {
       if (S.up) HIPCHK(hipStreamSynchronize(S.up));
@@ -832,7 +921,7 @@ static int sequence_run_v2(vsm_handle *h, const uint8_t *left, const uint8_t *ri
       }
       S.up_bytes = need;
     }
-    if (!make_stream(S.up)) return VSM_SEQ2_DECLINED;
+    if (!seq2_make_stream(S.up)) return VSM_SEQ2_DECLINED;
     // pieces of at most `per` frames, none across a chunk boundary (a chunk's features wait for its pieces only)
     // (a copy + its event cost ~50 us of the copy stream on top of the transfer: 20 frames = 18.6 MB = 0.33 ms at the link's 57 GB/s)
     constexpr int32_t per = 20;
@@ -852,44 +941,48 @@ static int sequence_run_v2(vsm_handle *h, const uint8_t *left, const uint8_t *ri
         }
       S.up_pieces = std::move(pieces);
     }
-    if (host_pinned) {
-      for (auto &pcu : S.up_pieces) {
-        Seq2::UpPiece *pc = pcu.get();
-        bool ok = true;
-        for (int side = 0; side < sides && ok; side++) {
-          // (device layout of this form: PLANAR - all left images, then all right images - so that a piece of contiguous
-          // frames is ONE linear copy per side: the DMA engine runs linear copies at the link's rate, pitched ones at a
-          // fraction of it)
-          const uint8_t *src = (side ? right : left) + (size_t)pc->f0 * frame_stride;
-          uint8_t *dst = S.up_d + ((size_t)side * n_frames + pc->f0) * img_bytes;
-          if (bpl == w && (size_t)frame_stride == img_bytes) {
-            ok = hipMemcpyAsync(dst, src, img_bytes * (size_t)pc->n, hipMemcpyHostToDevice, S.up) == hipSuccess;
-          } else if (bpl == w) {  // an image is one row of the copy
-            ok = hipMemcpy2DAsync(dst, img_bytes, src, (size_t)frame_stride, img_bytes, (size_t)pc->n, hipMemcpyHostToDevice, S.up) == hipSuccess;
-          } else {
-            for (int32_t i = 0; i < pc->n && ok; i++)
-              ok = hipMemcpy2DAsync(dst + (size_t)i * img_bytes, (size_t)w, src + (size_t)i * frame_stride, (size_t)bpl, (size_t)w, (size_t)hh,
-                                    hipMemcpyHostToDevice, S.up) == hipSuccess;
-          }
-        }
-        ok = ok && hipEventRecord(pc->ev, S.up) == hipSuccess;
-        pc->t_recorded = vsm_now_us();
-        pc->left.store(0, std::memory_order_release);
-        pc->recorded.store(ok ? 1 : -1, std::memory_order_release);
-        if (ok && vsm_debug_timing()) S.poller.add(pc->ev, [pc](bool) { pc->t_arrived = vsm_now_us(); });
-        if (!ok) {  // (nothing will ever count the other pieces down: Drain must not wait for them)
-          for (auto &rest : S.up_pieces)
-            if (rest->recorded.load() == 0) {
-              rest->left.store(0, std::memory_order_release);
-              rest->recorded.store(-1, std::memory_order_release);
-            }
-          return VSM_EHIP;
-        }
-      }
-    } else
+    return host_pinned ? enqueue_pinned_pieces() : submit_gathers();
+  }
+  int enqueue_pinned_pieces() {
     for (auto &pcu : S.up_pieces) {
       Seq2::UpPiece *pc = pcu.get();
-      h->pool->submit(sides * pc->n, [h, pc, left, right, frame_stride, bpl, w, hh, sides, img_bytes](int t) {
+      bool ok = true;
+      for (int side = 0; side < sides && ok; side++) {
+        // (device layout of this form: PLANAR - all left images, then all right images - so that a piece of contiguous
+        // frames is ONE linear copy per side: the DMA engine runs linear copies at the link's rate, pitched ones at a
+        // fraction of it)
+        const uint8_t *src = (side ? right : left) + (size_t)pc->f0 * frame_stride;
+        uint8_t *dst = S.up_d + ((size_t)side * n_frames + pc->f0) * img_bytes;
+        if (bpl == w && (size_t)frame_stride == img_bytes) {
+          ok = hipMemcpyAsync(dst, src, img_bytes * (size_t)pc->n, hipMemcpyHostToDevice, S.up) == hipSuccess;
+        } else if (bpl == w) {  // an image is one row of the copy
+          ok = hipMemcpy2DAsync(dst, img_bytes, src, (size_t)frame_stride, img_bytes, (size_t)pc->n, hipMemcpyHostToDevice, S.up) == hipSuccess;
+        } else {
+          for (int32_t i = 0; i < pc->n && ok; i++)
+            ok = hipMemcpy2DAsync(dst + (size_t)i * img_bytes, (size_t)w, src + (size_t)i * frame_stride, (size_t)bpl, (size_t)w, (size_t)hh,
+                                  hipMemcpyHostToDevice, S.up) == hipSuccess;
+        }
+      }
+      ok = ok && hipEventRecord(pc->ev, S.up) == hipSuccess;
+      pc->t_recorded = vsm_now_us();
+      pc->left.store(0, std::memory_order_release);
+      pc->recorded.store(ok ? 1 : -1, std::memory_order_release);
+      if (ok && vsm_debug_timing()) S.poller.add(pc->ev, [pc](bool) { pc->t_arrived = vsm_now_us(); });
+      if (!ok) {  // (nothing will ever count the other pieces down: Drain must not wait for them)
+        for (auto &rest : S.up_pieces)
+          if (rest->recorded.load() == 0) {
+            rest->left.store(0, std::memory_order_release);
+            rest->recorded.store(-1, std::memory_order_release);
+          }
+        return VSM_EHIP;
+      }
+    }
+    return VSM_OK;
+  }
+  int submit_gathers() {
+    for (auto &pcu : S.up_pieces) {
+      Seq2::UpPiece *pc = pcu.get();
+      h->pool->submit(sides * pc->n, [h = h, pc, left = left, right = right, frame_stride = frame_stride, bpl = bpl, w = w, hh = hh, sides = sides, img_bytes = img_bytes](int t) {  // (by value: the rule)
         Seq2 &S2 = *h->seq2;
         const int32_t f = pc->f0 + t / sides;
         const int side = t % sides;
@@ -911,41 +1004,32 @@ static int sequence_run_v2(vsm_handle *h, const uint8_t *left, const uint8_t *ri
         }
       });
     }
+    return VSM_OK;
   }
-  int32_t nprev[2][2] = {{0, 0}, {0, 0}};
-  struct Ck {
-    int32_t f0 = 0;
-    int n = 0, first_img = 0, first_pair = 0;
-    int max_nq[2] = {0, 0};
-    hipEvent_t ev_prior = nullptr, ev_p1 = nullptr;
-    hipEvent_t ev_k1 = nullptr;   // pass-1 chain with the vertex sorts on the pool: its keys are in host memory (chain stream)
-    bool chain1_open = false;     // ... and its second part (tie patches, votes, boxes) is not enqueued yet (finish_chain1)
-    std::shared_ptr<std::vector<char>> valid;
-  };
-  std::vector<Ck> ck(nchunks);
-  std::vector<double> dbg_counts, dbg_main;  // (VSM_DEBUG_TIMING: when the caller's thread had a chunk's counts / had enqueued its second pass)
-  auto launch_features_of = [&](int k) -> hipError_t {
+  // the front kernels number their images first + 2 * frame + side: consecutive mono frames go through as (even, odd) pairs
+  void front(int first, const uint8_t *s0, const uint8_t *s1, size_t stride, int pitch, int frames) {
+    if (frames <= 0) return;
+    if (p.half_resolution && sw.front)
+      vsm_launch_front(h->stream, h->prof, c.d_imgs, first, s0, s1, stride, pitch, frames, c.dims, 0);
+    else
+      vsm_launch_ingest(h->stream, h->prof, c.d_imgs, first, s0, s1, stride, pitch, frames, c.dims);
+  }
+  // n frames from s0, a frame every `step` bytes (pitch: bytes per source row); stereo: their right images from s1, every `stride2` bytes
+  void front_frames(int first_img, const uint8_t *s0, size_t step, const uint8_t *s1, size_t stride2, int pitch, int n) {
+    if (right) {
+      front(first_img, s0, s1, stride2, pitch, n);
+    } else {
+      front(first_img, s0, s0 + step, 2 * step, pitch, n / 2);
+      if (n & 1) front(first_img + n - 1, s0 + step * (size_t)(n - 1), nullptr, step, pitch, 1);
+    }
+  }
+  hipError_t launch_features_of(int k) {
     const int32_t f0 = chunk_start[k];
     const int n = chunk_start[k + 1] - f0;
     const int first_img = sides * (k % kFrameBanks) * C;
     const bool fused_front = p.half_resolution && sw.front;
-    // the front kernels number their images first + 2 * frame + side: consecutive mono frames go through as (even, odd) pairs
-    int pitch = bpl;  // bytes per source row
-    auto front = [&](int first, const uint8_t *s0, const uint8_t *s1, size_t stride, int frames) {
-      if (frames <= 0) return;
-      if (fused_front)
-        vsm_launch_front(h->stream, h->prof, c.d_imgs, first, s0, s1, stride, pitch, frames, c.dims, 0);
-      else
-        vsm_launch_ingest(h->stream, h->prof, c.d_imgs, first, s0, s1, stride, pitch, frames, c.dims);
-    };
     if (on_device) {
-      const uint8_t *l0 = left + (size_t)f0 * frame_stride;
-      if (right) {
-        front(first_img, l0, right + (size_t)f0 * frame_stride, (size_t)frame_stride, n);
-      } else {
-        front(first_img, l0, l0 + frame_stride, 2 * (size_t)frame_stride, n / 2);
-        if (n & 1) front(first_img + n - 1, l0 + (size_t)(n - 1) * frame_stride, nullptr, (size_t)frame_stride, 1);
-      }
+      front_frames(first_img, left + (size_t)f0 * frame_stride, (size_t)frame_stride, right ? right + (size_t)f0 * frame_stride : nullptr, (size_t)frame_stride, bpl, n);
     } else {
       for (auto &pc : S.up_pieces) {  // the chunk's pieces: their copies are (being) enqueued by the pool
         if (pc->f0 < f0 || pc->f0 >= f0 + n) continue;
@@ -956,40 +1040,18 @@ static int sequence_run_v2(vsm_handle *h, const uint8_t *left, const uint8_t *ri
         const hipError_t e = hipStreamWaitEvent(h->stream, pc->ev, 0);
         if (e != hipSuccess) return e;
       }
-      pitch = w;  // (the pieces arrive row-tight)
-      if (host_pinned) {  // planar: left images, then right images
-        const uint8_t *l0 = S.up_d + (size_t)f0 * img_bytes;
-        if (right) {
-          front(first_img, l0, l0 + (size_t)n_frames * img_bytes, img_bytes, n);
-        } else {
-          front(first_img, l0, l0 + img_bytes, 2 * img_bytes, n / 2);
-          if (n & 1) front(first_img + n - 1, l0 + img_bytes * (size_t)(n - 1), nullptr, img_bytes, 1);
-        }
-      } else {
-        const uint8_t *d0 = S.up_d + (size_t)sides * f0 * img_bytes;
-        if (right) {
-          front(first_img, d0, d0 + img_bytes, 2 * img_bytes, n);
-        } else {
-          front(first_img, d0, d0 + img_bytes, 2 * img_bytes, n / 2);
-          if (n & 1) front(first_img + n - 1, d0 + img_bytes * (size_t)(n - 1), nullptr, img_bytes, 1);
-        }
-      }
+      // (the pieces arrive row-tight; page-locked input is planar - left images, then right images -, gathered input frame by frame)
+      if (host_pinned)
+        front_frames(first_img, S.up_d + (size_t)f0 * img_bytes, img_bytes, S.up_d + ((size_t)n_frames + f0) * img_bytes, img_bytes, w, n);
+      else
+        front_frames(first_img, S.up_d + (size_t)sides * f0 * img_bytes, img_bytes, S.up_d + ((size_t)sides * f0 + 1) * img_bytes, 2 * img_bytes, w, n);
     }
     vsm_launch_features(h->stream, h->prof, c.d_imgs, first_img, sides * n, c.dims, c.f1, c.f2, c.f_stride, p.nms_tau, p.multi_stage,
                         p.half_resolution, p.match_binsize, c.h_imgs.data(), fused_front ? 1 : 0, (h->sw.fused_features ? 1 : 0) | (h->sw.feat_order ? 0 : 4));
     return hipEventRecord(h->seq_ev[0], h->stream);
-  };
-  bool declined = false;
-  const bool inorder = host_in && !sw.seq_serial && sw.seq_host_inorder;
-  // (pass-1 vertex sorts on the pool: ranks with ten pool threads and more, frames in HBM; option seq_ties1_host 0 / 1)
-  const bool ties1_host = p.multi_stage && !sw.seq_serial && (sw.seq_ties1_host >= 0 ? sw.seq_ties1_host != 0 : (h->pool->size() >= 10 && !host_in));
-  // seq_serial (VSM_SEQ_SERIAL=1, measurements): nothing overlaps - every group of launches drains before the next one is
-  // enqueued, so each kernel's HIP-event time is its time with the GPU to itself (bench.py's "alone" figures).  Same
-  // kernels, same data, same results.
-  const bool serial = sw.seq_serial;
+  }
   // jobs of chunk k from its feature counts, pass 1 and the pass-1 chain
-  std::function<int(int)> finish_chain1_of;  // (defined below: the pool's share of a pass-1 chain)
-  auto start_chunk = [&](int k) -> int {
+  int start_chunk(int k) {  // (VSM_SEQ2_DECLINED: a list of this chunk is longer than this form takes)
     Ck &q = ck[k];
     q.f0 = chunk_start[k];
     q.n = chunk_start[k + 1] - q.f0;
@@ -1000,18 +1062,16 @@ static int sequence_run_v2(vsm_handle *h, const uint8_t *left, const uint8_t *ri
     VsmJob *h_jobs = c.h_jobs + first_pair, *d_jobs = c.d_jobs + first_pair;
     // (the caller's thread is about to wait for this chunk's features: the pass-1 chains of the chunks in front that wait for
     // their vertex sorts get them now - their keys are long there - instead of when their second pass is enqueued, 0.2 ms later)
-    if (finish_chain1_of)
-      for (int j = 0; j < k; j++) {
-        const int rc = finish_chain1_of(j);
-        if (rc != VSM_OK) return rc;
-      }
+    for (int j = 0; j < k; j++) {
+      const int rc = finish_chain1(j);
+      if (rc != VSM_OK) return rc;
+    }
     const double t0 = now_us();
     HIPCHK(hipEventSynchronize(h->seq_ev[0]));  // the chunk's feature counts are in host-mapped memory
     HIPCHK(hipGetLastError());
     tg += now_us() - t0;
     dbg_counts.push_back(now_us());
     q.max_nq[0] = q.max_nq[1] = 0;
-    q.valid = std::make_shared<std::vector<char>>(n, 0);
     for (int i = 0; i < n; i++) {
       const int32_t f = q.f0 + i;
       VsmJob &jb = h_jobs[i];
@@ -1041,8 +1101,8 @@ static int sequence_run_v2(vsm_handle *h, const uint8_t *left, const uint8_t *ri
       }
       jb.img_prev = img_p;
       jb.img_curr = img_c;
-      if (match_ready(p, method, cnt)) {
-        (*q.valid)[i] = 1;
+      const bool valid = match_ready(p, method, cnt);
+      if (valid) {
         const int qimg = method == 2 ? 0 : 2;
         jb.nq[0] = p.multi_stage ? cnt[qimg][0] : 0;
         jb.nq[1] = cnt[qimg][1];
@@ -1051,7 +1111,7 @@ static int sequence_run_v2(vsm_handle *h, const uint8_t *left, const uint8_t *ri
           memcpy(jb.t, Tr + (size_t)f * 12, 12 * sizeof(double));
         }
       }
-      h->seq_src[f] = (*q.valid)[i] ? f : (f > 0 ? h->seq_src[f - 1] : -1);
+      h->seq_src[f] = valid ? f : (f > 0 ? h->seq_src[f - 1] : -1);
       q.max_nq[0] = std::max(q.max_nq[0], jb.nq[0]);
       q.max_nq[1] = std::max(q.max_nq[1], jb.nq[1]);
     }
@@ -1061,8 +1121,7 @@ static int sequence_run_v2(vsm_handle *h, const uint8_t *left, const uint8_t *ri
     }
     if (q.max_nq[0] > VSM_DC_TIE_POINTS || q.max_nq[1] > VSM_DC_KD_MAX_POINTS || (p.refinement == 2 && q.max_nq[1] > VSM_PARA_MAX_LIST) ||
         vsm_dc2_depth(std::max(q.max_nq[0], q.max_nq[1])) > VSM_DC2_MAX_DEPTH) {
-      declined = true;  // (a pass-1 list longer than the device's vertex sort takes: the first form does this run)
-      return VSM_OK;
+      return VSM_SEQ2_DECLINED;  // (a pass-1 list longer than the device's vertex sort takes: the first form does this run)
     }
     HIPCHK(vsm_upload(h->stream, d_jobs, h_jobs, sizeof(VsmJob) * n));
     if (p.multi_stage) {
@@ -1078,10 +1137,10 @@ static int sequence_run_v2(vsm_handle *h, const uint8_t *left, const uint8_t *ri
       HIPCHK(hipEventRecord(q.ev_p1, h->stream));
     }
     return VSM_OK;
-  };
+  }
   // ... and the chain of its pass-1 lists (outlier removal + prior boxes) on a stream of its own: a dozen and a half enqueue
   // calls that the caller makes AFTER it has given the main stream its next kernels - the boxes are wanted two chunks later
-  auto start_chain1 = [&](int k) -> int {
+  int start_chain1(int k) {
     Ck &q = ck[k];
     if (!p.multi_stage) return VSM_OK;
     const int n = q.n, first_pair = q.first_pair;
@@ -1141,8 +1200,8 @@ static int sequence_run_v2(vsm_handle *h, const uint8_t *left, const uint8_t *ri
       HIPCHK(hipEventRecord(q.ev_prior, c1));
     }
     return VSM_OK;
-  };
-  auto finish_chain1 = [&](int k) -> int {
+  }
+  int finish_chain1(int k) {  // (the pool's share of a pass-1 chain)
     Ck &q = ck[k];
     if (!q.chain1_open) return VSM_OK;
     q.chain1_open = false;
@@ -1166,11 +1225,10 @@ static int sequence_run_v2(vsm_handle *h, const uint8_t *left, const uint8_t *ri
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(q.ev_prior, c1));
     return VSM_OK;
-  };
-  finish_chain1_of = finish_chain1;
+  }
   // the refinement of a chunk on the main stream, enqueued right behind the chunk's second pass and in front of the chain's
   // two dozen enqueue calls, so that the main stream never waits for the caller's thread
-  auto launch_refine = [&](Seq2Chunk *ch, int k) -> int {
+  int launch_refine(Seq2Chunk *ch, int k) {
     const Ck &q = ck[k];
     VsmJob dummy;
     memset(&dummy, 0, sizeof(dummy));
@@ -1184,7 +1242,7 @@ static int sequence_run_v2(vsm_handle *h, const uint8_t *left, const uint8_t *ri
     if (!ch->ev_ref) return VSM_EHIP;
     HIPCHK(hipEventRecord(ch->ev_ref, h->stream));
     return VSM_OK;
-  };
+  }
   // The refined lists leave for the host beside the triangulation, as they are (48-byte p_match records), straight out of the
   // pair buffers by strided DMA copies (28 MB per 80 pairs, 0.58 ms at the link's 49 GB/s); the chain's end only adds a bit per
   // match.  The device has ONE engine for copies to the host and it takes them in the order they were SUBMITTED, waiting for
@@ -1195,8 +1253,7 @@ static int sequence_run_v2(vsm_handle *h, const uint8_t *left, const uint8_t *ri
   // during the call; all streams of this path are non-blocking - and are submitted in the order the engine should work in:
   // behind a chunk's keys as many pieces as fit in front of the next chunk's keys (two where the next second pass follows at
   // once: the end of every call; otherwise all that are pending), the rest when the call's last keys are in.
-  int exp_k = 0;  // first chunk with rows left to submit
-  auto export_some = [&](int upto, int budget) -> int {  // budget: pieces (< 0: all)
+  int export_some(int upto, int budget) {  // budget: pieces (< 0: all)
     if (!S.res_early) return VSM_OK;
     std::lock_guard<std::mutex> lk(S.enq_mu);
     hipStream_t xs = S.ns;
@@ -1223,13 +1280,13 @@ static int sequence_run_v2(vsm_handle *h, const uint8_t *left, const uint8_t *ri
         ch->exp_row += rows;
         if (budget > 0) budget--;
       }
-      ch->ev_exp = S.get_event_locked();
+      ch->ev_exp = S.get_event();
       if (!ch->ev_exp) return VSM_EHIP;
       HIPCHK(hipEventRecord(ch->ev_exp, xs));
       exp_k++;
     }
     return VSM_OK;
-  };
+  }
   // The device's share of the final vertex sorts.  A wave sorts one list in 3.2 ms and a launch takes that long whatever the
   // number of lists, so the lists of ALL chunks that wait for the device go into one launch - on the null stream (a launch
   // per chunk needs a stream per chunk: a sixth, seventh, eighth hardware queue, and with those every kernel's dispatch is
@@ -1239,16 +1296,7 @@ static int sequence_run_v2(vsm_handle *h, const uint8_t *left, const uint8_t *ri
   // its gate stays shut until the launch is enqueued.
   // Share by pool size: the host has from the first keys (2 ms) to the end of that launch (last keys at 3 ms + 3.2) for its
   // part - 4.2 ms x threads / 125 us per list.
-  const int gpu_sorts_default = h->pool->size() <= 2 ? 67 : (h->pool->size() == 3 ? 50 : (h->pool->size() == 4 ? 33 : 0));  // (four threads: 7.0 ms without a share, 8.3 with one)
-  const bool split_sorts = nchunks == 2 && sw.seq_gpu_sorts < 0 && gpu_sorts_default > 0 && !serial;
-  std::vector<int> ties_pending;   // chunks whose device share has not been launched yet
-  int ties_launches = 0;
-  // A sorting wave wants 139 KB of LDS, i.e. a compute unit to itself, and finds none while a block-kernel launch has five
-  // workgroups on every unit: the triangulations that are enqueued behind the launch wait for this event - recorded right
-  // in front of the sort kernel on its stream - so that the sorts are placed first and the meshes share what is left.
-  hipEvent_t ev_ties_go = nullptr;
-  int tie_jobs_at = 0;  // rows of the job table this call's launches have used (every launch its own rows: no launch waits for another's copy)
-  auto launch_pending_ties = [&](hipStream_t ts) -> int {
+  int launch_pending_ties(hipStream_t ts) {
     if (ties_pending.empty()) return VSM_OK;
     std::vector<Seq2Chunk *> open;
     int total = 0, max_list = 0;
@@ -1282,17 +1330,16 @@ static int sequence_run_v2(vsm_handle *h, const uint8_t *left, const uint8_t *ri
       HIPCHK(hipStreamWaitEvent(ts, ch->ev_jobs, 0));  // (its keys are written)
     }
     HIPCHK(vsm_upload(ts, rows_d, rows_h, sizeof(VsmDc2Job) * total));
-    ev_ties_go = S.get_event_locked();
+    ev_ties_go = S.get_event();
     if (!ev_ties_go) return VSM_EHIP;
     HIPCHK(hipEventRecord(ev_ties_go, ts));
     h->prof.begin(VSM_K_DC_TIES, ts);
     vsm_dc2_launch_ties(ts, rows_d, total, nullptr, 0, max_list);
     h->prof.end(ts);
     HIPCHK(hipGetLastError());
-    hipEvent_t ev = S.get_event_locked();
+    hipEvent_t ev = S.get_event();
     if (!ev) return VSM_EHIP;
     HIPCHK(hipEventRecord(ev, ts));
-    ties_launches++;
     for (int k : ties_pending) {
       Seq2Chunk *ch = S.chunks[k].get();
       ch->ev_ties = ev;
@@ -1306,25 +1353,34 @@ static int sequence_run_v2(vsm_handle *h, const uint8_t *left, const uint8_t *ri
       seq2_open_gate(ch);
     }
     return VSM_OK;
-  };
+  }
   // the caller's half of the gate of the chain's second part (the export's event has to exist before it opens)
-  auto after_refine = [&](Seq2Chunk *ch, int k, hipEvent_t) -> int {
+  int after_refine(Seq2Chunk *ch, int k) {
     int rc = export_some(k, -1);
     if (rc != VSM_OK) return rc;
     if (ch->gpu_sorts > 0 && !ch->ev_ties) {  // (its second part waits for an event that does not exist yet)
-      if (serial) {
-        rc = launch_pending_ties(S.ns);
-        if (rc != VSM_OK) return rc;
-      } else {
+      if (!serial) {
         ch->gate_deferred = true;
         return VSM_OK;
       }
+      rc = launch_pending_ties(S.ns);
+      if (rc != VSM_OK) return rc;
     }
     ch->caller_gate = true;
     seq2_open_gate(ch);
     if (serial && !seq2_wait_chunk(ch, 60e6)) return VSM_EHIP;
     return VSM_OK;
-  };
+  }
+  // a slab or a pair bank comes round: the chunk that used it last must be through - which it cannot be while its share of the
+  // vertex sorts has not been launched, so that goes in first; the wait is the caller's (tg)
+  int wait_for_chunk(int j) {
+    const int rc = launch_pending_ties(S.ns);
+    if (rc != VSM_OK) return rc;
+    const double t0 = now_us();
+    if (!seq2_wait_chunk(S.chunks[j].get(), 30e6)) return VSM_EHIP;
+    tg += now_us() - t0;
+    return VSM_OK;
+  }
   // Main stream, two chunks ahead with the features and the first pass:
   //   feat 0 | pass 1 (0) | feat 1 | pass 1 (1) | then per k: feat k+2 | pass 1 (k+2) | pass 2 (k) | refinement (k)
   // Between a chunk's first pass and its second the stream has two other chunks' work to do - more than the pass-1 chain
@@ -1332,70 +1388,36 @@ static int sequence_run_v2(vsm_handle *h, const uint8_t *left, const uint8_t *ri
   // the refinement leaves alone: it starts behind pass 2, beside the refinement.
   // (the caller's order of enqueue calls: whatever the main stream runs next first, the side streams' rows of launches while
   // it is busy with that)
-  int chain1_next = 0;  // first chunk whose pass-1 chain has not been enqueued yet
-  auto catch_up_chain1 = [&](int upto) -> int {
+  int catch_up_chain1(int upto) {
     for (; chain1_next <= upto && chain1_next < nchunks; chain1_next++) {
       const int rc = start_chain1(chain1_next);
       if (rc != VSM_OK) return rc;
       if (serial) HIPCHK(hipDeviceSynchronize());
     }
     return VSM_OK;
-  };
-  // Host-resident inputs arrive at the link's rate, which is what bounds the call: chunk by chunk in the order of arrival,
-  // no run-ahead - the caller's thread blocks on a chunk's feature counts (i.e. on its frames' arrival) only when everything
-  // of the chunk in front, final chain included, is enqueued.  (In the run-ahead order it waited for chunk k + 2's frames
-  // before it enqueued chunk k + 1's second pass: the last two chunks' second passes and chains all started behind the last
-  // frame's arrival - 7.4 ms per 200 frames against 3.3 ms of transfer.)
-  for (int k0 = 0; k0 < std::min(2, nchunks) && !inorder; k0++) {
-    HIPCHK(launch_features_of(k0));
-    if (k0 > 0) {  // (the previous chunk's chain behind this chunk's feature kernels)
-      const int rc = catch_up_chain1(k0 - 1);
-      if (rc != VSM_OK) return rc;
-    }
-    if (serial) HIPCHK(hipDeviceSynchronize());
-    const int rc = start_chunk(k0);
-    if (rc != VSM_OK) return rc;
-    if (declined) return VSM_SEQ2_DECLINED;
-    if (serial) HIPCHK(hipDeviceSynchronize());
   }
   // features + first pass of chunk k + 2 (the run-ahead of the main stream)
-  auto run_ahead = [&](int k) -> int {
+  int run_ahead(int k) {
     if (k + 2 >= nchunks) return VSM_OK;
     // the pair bank of chunk k + 2 was last used by chunk k + 2 - kPairBanks: that chunk's chain must be through
-    const int old = k + 2 - kPairBanks;
-    if (old >= 0) {
-      {  // (that chunk cannot be through while its share of the vertex sorts has not been launched)
-        const int rc = launch_pending_ties(S.ns);
-        if (rc != VSM_OK) return rc;
-      }
-      const double t0 = now_us();
-      if (!seq2_wait_chunk(S.chunks[old].get(), 30e6)) return VSM_EHIP;
-      tg += now_us() - t0;
-    }
-    HIPCHK(launch_features_of(k + 2));
-    {
-      const int rc = catch_up_chain1(k + 1);
-      if (rc != VSM_OK) return rc;
-    }
-    if (serial) HIPCHK(hipDeviceSynchronize());
-    const int rc = start_chunk(k + 2);
+    int rc = k + 2 >= kPairBanks ? wait_for_chunk(k + 2 - kPairBanks) : VSM_OK;
     if (rc != VSM_OK) return rc;
-    if (declined) return VSM_SEQ2_DECLINED;
+    HIPCHK(launch_features_of(k + 2));
+    rc = catch_up_chain1(k + 1);
+    if (rc != VSM_OK) return rc;
+    if (serial) HIPCHK(hipDeviceSynchronize());
+    rc = start_chunk(k + 2);
+    if (rc != VSM_OK) return rc;
     if (serial) HIPCHK(hipDeviceSynchronize());
     return VSM_OK;
-  };
+  }
   // A chunk's second pass + refinement (main stream) and its final chain (side streams) are enqueued by two steps of the
   // caller's thread: the chain's thirty-odd HIP calls take the caller a few hundred microseconds, and while it makes them
   // the main stream must not run dry - where the next chunk's main-stream work needs nothing the caller would have to wait
   // for (no run-ahead block left: the end of every call), that work is enqueued FIRST and the chains follow.
-  int chain_next = 0;  // first chunk whose final chain has not been enqueued yet
-  int refine_pending = -1;  // chunk whose refinement waits for the next chunk's matching (seq_defer_refine)
-  const bool p2_first = sw.seq_p2_first >= 0 ? sw.seq_p2_first != 0 : (h->pool->size() >= 5 && h->pool->size() < 10 && (sw.seq_gpu_sorts >= 0 ? sw.seq_gpu_sorts : gpu_sorts_default) == 0);
-  auto enqueue_main = [&](int k) -> int {
-    {
-      const int rc = catch_up_chain1(k);  // (this chunk's second pass waits for its boxes: that event has to exist)
-      if (rc != VSM_OK) return rc;
-    }
+  int enqueue_main(int k) {
+    int rc = catch_up_chain1(k);  // (this chunk's second pass waits for its boxes: that event has to exist)
+    if (rc != VSM_OK) return rc;
     const Ck &q = ck[k];
     const int n = q.n, first_pair = q.first_pair;
     const VsmPair *d_pairs = c.d_pairs + first_pair;
@@ -1403,15 +1425,8 @@ static int sequence_run_v2(vsm_handle *h, const uint8_t *left, const uint8_t *ri
     VsmMatchCfg cfg = make_cfg(p, method, h->sw.match_heads && c.has_heads);
     VsmJob dummy;
     memset(&dummy, 0, sizeof(dummy));
-    if (k >= Seq2::kBanks) {  // this chunk's final-stage slab was last used by chunk k - kBanks
-      {
-        const int rc = launch_pending_ties(S.ns);
-        if (rc != VSM_OK) return rc;
-      }
-      const double t0 = now_us();
-      if (!seq2_wait_chunk(S.chunks[k - Seq2::kBanks].get(), 30e6)) return VSM_EHIP;
-      tg += now_us() - t0;
-    }
+    if (k >= Seq2::kBanks) rc = wait_for_chunk(k - Seq2::kBanks);  // this chunk's final-stage slab was last used by chunk k - kBanks
+    if (rc != VSM_OK) return rc;
     Dc2Bank &B = S.bank2[k % Seq2::kBanks];
     if (!B.reserve(n, std::max(64, q.max_nq[1]), true)) return VSM_EHIP;
     S.chunks.emplace_back(new Seq2Chunk());
@@ -1438,7 +1453,7 @@ static int sequence_run_v2(vsm_handle *h, const uint8_t *left, const uint8_t *ri
     ch->dtol = (float)p.outlier_disp_tolerance;
     ch->sorts_left.store(1, std::memory_order_relaxed);
     if (p.multi_stage) {
-      const int rc = finish_chain1(k);  // (the pool's share of the pass-1 chain, where it has one: the event below is recorded there)
+      rc = finish_chain1(k);  // (the pool's share of the pass-1 chain, where it has one: the event below is recorded there)
       if (rc != VSM_OK) return rc;
       HIPCHK(hipStreamWaitEvent(h->stream, q.ev_prior, 0));
     }
@@ -1453,7 +1468,7 @@ static int sequence_run_v2(vsm_handle *h, const uint8_t *left, const uint8_t *ri
     // the next chunk's second pass follows at once on the main stream, this chunk's refinement goes BEHIND that pass's
     // matching - the call's last keys, and the last mesh with them, start a refinement earlier (option seq_defer_refine)
     if (refine_pending >= 0) {
-      const int rc = launch_refine(S.chunks[refine_pending].get(), refine_pending);
+      rc = launch_refine(S.chunks[refine_pending].get(), refine_pending);
       if (rc != VSM_OK) return rc;
       refine_pending = -1;
     }
@@ -1461,15 +1476,15 @@ static int sequence_run_v2(vsm_handle *h, const uint8_t *left, const uint8_t *ri
     if (sw.seq_defer_refine && next_follows && p.refinement == 1) {
       refine_pending = k;
     } else {
-      const int rc = launch_refine(ch, k);
+      rc = launch_refine(ch, k);
       if (rc != VSM_OK) return rc;
     }
     if (serial) HIPCHK(hipStreamSynchronize(h->stream));
     return VSM_OK;
-  };
+  }
   // The chain comes in two steps as well.  Its HEAD - jobs, keys, the keys' DMA copy and the pool task that waits for it - goes in
   // right behind the chunk's main-stream work: the vertex sorts are 25 ms of pool work per call and want their keys early.
-  auto enqueue_chain_head = [&](int k) -> int {
+  int enqueue_chain_head(int k) {
     const Ck &q = ck[k];
     const int n = q.n, first_pair = q.first_pair;
     Seq2Chunk *ch = S.chunks[k].get();
@@ -1521,7 +1536,7 @@ static int sequence_run_v2(vsm_handle *h, const uint8_t *left, const uint8_t *ri
       hipStream_t ks = s2;
       if (n > ch->gpu_sorts && keys_dma) {
         if (keys_dma == 2 && !host_in) {
-          hipEvent_t ev_k = S.get_event_locked();
+          hipEvent_t ev_k = S.get_event();
           if (!ev_k) {
             ch->state.store(0, std::memory_order_release);
             return VSM_EHIP;
@@ -1546,7 +1561,7 @@ static int sequence_run_v2(vsm_handle *h, const uint8_t *left, const uint8_t *ri
           if (r1 > r0 && keys_dma)
             HIPCHK(hipMemcpy2DAsync(B.host_keys(r0), Dc2Bank::al((size_t)B.cap * 8), B.pp[r0].keys_in, B.pair_stride,
                                     (size_t)std::min(std::max(q.max_nq[1], 1), B.cap) * 8, (size_t)(r1 - r0), hipMemcpyDeviceToHost, ks));
-          hipEvent_t ev = S.get_event_locked();
+          hipEvent_t ev = S.get_event();
           if (!ev) {
             ch->state.store(0, std::memory_order_release);
             return VSM_EHIP;
@@ -1582,20 +1597,18 @@ static int sequence_run_v2(vsm_handle *h, const uint8_t *left, const uint8_t *ri
     }
     if (!serial) {  // (the engine's order: these keys, then export pieces - see export_some)
       const bool tail = k + 1 < nchunks && k + 3 >= nchunks;   // the next chunk's second pass follows at once
-      const int rc = export_some(k, k + 1 == nchunks ? -1 : (tail ? sw.seq_export_budget : -1));
-      if (rc != VSM_OK) return rc;
+      return export_some(k, k + 1 == nchunks ? -1 : (tail ? sw.seq_export_budget : -1));
     }
     return VSM_OK;
-  };
+  }
   // ... and its mesh (sort + kd order, block sub-trees, merge levels, per-match flows), the early export and the caller's half of
   // the gate: a dozen and a half more calls, which may wait until the main stream has been given its next kernels
-  auto enqueue_chain_mesh = [&](int k) -> int {
+  int enqueue_chain_mesh(int k) {
     const Ck &q = ck[k];
     const int n = q.n;
     Seq2Chunk *ch = S.chunks[k].get();
     Dc2Bank &B = *ch->B;
     hipStream_t s2 = ch->stream;
-    hipEvent_t ev_jobs = ch->ev_jobs;
     {
       std::lock_guard<std::mutex> lk(S.enq_mu);
       hipEvent_t last_prep = nullptr;
@@ -1615,17 +1628,112 @@ static int sequence_run_v2(vsm_handle *h, const uint8_t *left, const uint8_t *ri
       HIPCHK(hipEventRecord(ch->ev_mesh, s2));
     }
     if (serial) HIPCHK(hipStreamSynchronize(s2));
-    const int rc = after_refine(ch, k, ev_jobs);
-    if (rc != VSM_OK) return rc;
-    return VSM_OK;
-  };
-  auto flush_chains = [&](int upto) -> int {
+    return after_refine(ch, k);
+  }
+  int flush_chains(int upto) {
     for (; chain_next <= upto; chain_next++) {
       const int rc = enqueue_chain_mesh(chain_next);
       if (rc != VSM_OK) return rc;
     }
     return VSM_OK;
-  };
+  }
+  // the bank's error word read and cleared (a list this form declines), and whether it met a list beyond the LDS forms
+  int take_bank_errors(Dc2Bank &b) {
+    if (!b.h_error) return 0;
+    const int code = b.h_error[0];
+    S.expect_long |= b.h_error[1] != 0;  // (a list beyond the LDS forms went through the narrow one: the long lists' kernel comes along from now on)
+    b.h_error[0] = b.h_error[1] = 0;
+    return code;
+  }
+  // the end of the call: the chunks' results, the banks' error codes, the VSM_DEBUG_TIMING report, seq_timings
+  int finish() {
+    const double t0 = now_us();
+    for (auto &ch : S.chunks)
+      if (!seq2_wait_chunk(ch.get(), 60e6, h->pool)) return VSM_EHIP;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (h->prof.on) {  // (every stream that carries spans has drained: the chunks are done)
+      for (int i = 0; i < S.dc_streams; i++) HIPCHK(hipStreamSynchronize(S.dc2[i]));
+      HIPCHK(hipStreamSynchronize(S.ns));
+      h->prof.resolve();
+    }
+    tg += now_us() - t0;
+    int declined_code = 0;
+    for (Dc2Bank &b : S.bank1) declined_code |= take_bank_errors(b);
+    for (Dc2Bank &b : S.bank2) declined_code |= take_bank_errors(b);
+    int hip_failed = 0;
+    for (auto &ch : S.chunks) hip_failed |= ch->hip_error.load();
+    if (hip_failed) {  // a HIP call of a second part failed: that is an error, not a list this form declines
+      fprintf(stderr, "visomatch: a final chain of the GPU-resident look-ahead path failed: %s\n", hipGetErrorString(hipGetLastError()));
+      h->seq_hip_error.store(1);
+      return VSM_EHIP;
+    }
+    if (declined_code) {
+      fprintf(stderr, "visomatch: the GPU-resident look-ahead path declined a list (code %d), running the host-shared form\n", declined_code);
+      return VSM_SEQ2_DECLINED;
+    }
+    if (vsm_debug_timing()) {
+      if (!S.up_pieces.empty()) {
+        fprintf(stderr, "  upload pieces enqueued at (us):");
+        for (auto &pc : S.up_pieces) fprintf(stderr, " %d:%.0f", pc->f0, pc->t_recorded - tstart);
+        fprintf(stderr, "\n  ... arrived at (us):");
+        for (auto &pc : S.up_pieces) fprintf(stderr, " %d:%.0f", pc->f0, pc->t_arrived > 0 ? pc->t_arrived - tstart : -1.0);
+        fprintf(stderr, "\n  chunks' feature counts known / second pass enqueued at (us):");
+        for (size_t k = 0; k < dbg_counts.size(); k++) fprintf(stderr, " %zu:%.0f/%.0f", k, dbg_counts[k] - tstart, k < dbg_main.size() ? dbg_main[k] - tstart : -1.0);
+        fprintf(stderr, "\n");
+      }
+      for (auto &ch : S.chunks)
+        fprintf(stderr, "  chunk %d (%d pairs): keys on the host at %.0f us, sorted at %.0f (tasks %.0f us), chain done at %.0f, results in place at %.0f\n", ch->k, ch->n,
+                ch->t_keys - tstart, ch->t_sorted - tstart, ch->sort_ns.load() * 1e-3, ch->t_done - tstart, (ch->t_ready > 0 ? ch->t_ready : ch->t_done) - tstart);
+      fprintf(stderr, "  call returns at %.0f us\n", now_us() - tstart);
+    }
+    h->seq_v2_frames = n_frames;
+    h->seq_timings[0] = tg;
+    h->seq_timings[1] = 0;
+    for (auto &ch : S.chunks) h->seq_timings[1] += ch->sort_ns.load() * 1e-3;
+    h->seq_timings[2] = now_us() - tstart;
+    h->seq_timings[3] = (double)C;
+    return VSM_OK;
+  }
+};
+
+// The order of it all, on the caller's thread.
+static int sequence_run_v2(vsm_handle *h, const uint8_t *left, const uint8_t *right, int64_t frame_stride, int on_device, int32_t n_frames,
+                           int32_t w, int32_t hh, int32_t bpl, int32_t method, const double *Tr, const uint8_t *Tr_valid) {
+  if (!h->seq2) h->seq2 = new Seq2();
+  Seq2Call q(h, left, right, frame_stride, on_device, n_frames, w, hh, bpl, method, Tr, Tr_valid);
+  int rc = q.setup_streams();
+  if (rc == VSM_OK) rc = q.setup_results();
+  if (rc != VSM_OK) return rc;  // (nothing asynchronous has been started yet: no wait)
+  q.drain.h = h;                // from here on every way out waits for what the call has started
+  q.tstart = now_us();
+  rc = q.setup_uploads();
+  if (rc != VSM_OK) return rc;
+  // Host-resident inputs arrive at the link's rate, which is what bounds the call: chunk by chunk in the order of arrival,
+  // no run-ahead - the caller's thread blocks on a chunk's feature counts (i.e. on its frames' arrival) only when everything
+  // of the chunk in front, final chain included, is enqueued.  (In the run-ahead order it waited for chunk k + 2's frames
+  // before it enqueued chunk k + 1's second pass: the last two chunks' second passes and chains all started behind the last
+  // frame's arrival - 7.4 ms per 200 frames against 3.3 ms of transfer.)
+  if (q.inorder) {
+    for (int k = 0; k < q.nchunks; k++) {
+      if (k >= Seq2Call::kPairBanks) {  // the pair bank of chunk k was last used by chunk k - kPairBanks: that chunk's chain must be through
+        rc = q.wait_for_chunk(k - Seq2Call::kPairBanks);
+        if (rc != VSM_OK) return rc;
+      }
+      HIPCHK(q.launch_features_of(k));
+      rc = q.start_chunk(k);
+      if (rc == VSM_OK) rc = q.enqueue_main(k);  // (with the chunk's pass-1 chain in front)
+      if (rc == VSM_OK) rc = q.enqueue_chain_head(k);
+      if (rc == VSM_OK) rc = q.flush_chains(k);
+      if (rc != VSM_OK) return rc;
+    }
+    return q.finish();
+  }
+  // features + first pass of chunks 0 and 1: the run-ahead of "chunks -2 and -1" (no bank to wait for; chunk 0's pass-1 chain
+  // goes in behind chunk 1's feature kernels)
+  for (int k = -2; k < 0; k++) {
+    rc = q.run_ahead(k);
+    if (rc != VSM_OK) return rc;
+  }
   // Host-resident inputs arrive at the link's rate (0.94 MB per frame pair, ~20 us each at 50 GB/s: the 200 frames of the
   // benchmark sequence need 3.7 ms, three quarters of what the whole call takes from HBM), so the GPU works on what has
   // arrived: a chunk's second pass and its final chain go in FRONT of the features of chunk k + 2, whose frames are the last
@@ -1639,112 +1747,28 @@ static int sequence_run_v2(vsm_handle *h, const uint8_t *left, const uint8_t *ri
   // there - 7.3-7.4 ms with calls of 13-18 ms in between.  What is left after the last frame's arrival at 3.9 ms is the chunk's
   // own row of latencies - features, first pass, pass-1 chain, second pass, keys, vertex sorts, final chain - beside the
   // chains of the chunks in front: 3.4 ms, 1.7 on an idle GPU.)
-  if (inorder) {
-    for (int k = 0; k < nchunks; k++) {
-      if (k >= kPairBanks) {  // the pair bank of chunk k was last used by chunk k - kPairBanks: that chunk's chain must be through
-        int rc = launch_pending_ties(S.ns);
-        if (rc != VSM_OK) return rc;
-        const double t0 = now_us();
-        if (!seq2_wait_chunk(S.chunks[k - kPairBanks].get(), 30e6)) return VSM_EHIP;
-        tg += now_us() - t0;
-      }
-      HIPCHK(launch_features_of(k));
-      int rc = start_chunk(k);
-      if (rc != VSM_OK) return rc;
-      if (declined) return VSM_SEQ2_DECLINED;
-      rc = enqueue_main(k);  // (with the chunk's pass-1 chain in front)
-      if (rc == VSM_OK) rc = enqueue_chain_head(k);
-      if (rc == VSM_OK) rc = flush_chains(k);
+  if ((q.host_in || q.p2_first) && !q.serial) {
+    for (int k = 0; k < q.nchunks; k++) {
+      rc = q.catch_up_chain1(k + 1);  // (in front of this chunk's final chain: its vertex sort shares that chain's stream)
+      if (rc == VSM_OK) rc = q.enqueue_main(k);
+      if (rc == VSM_OK) rc = q.enqueue_chain_head(k);
+      if (rc == VSM_OK) rc = q.flush_chains(k);
+      if (rc == VSM_OK) rc = q.run_ahead(k);
+      if (rc == VSM_OK) rc = q.catch_up_chain1(k + 2);
       if (rc != VSM_OK) return rc;
     }
-  } else if ((host_in || p2_first) && !serial) {
-    for (int k = 0; k < nchunks; k++) {
-      int rc = catch_up_chain1(k + 1);  // (in front of this chunk's final chain: its vertex sort shares that chain's stream)
-      if (rc == VSM_OK) rc = enqueue_main(k);
-      if (rc == VSM_OK) rc = enqueue_chain_head(k);
-      if (rc == VSM_OK) rc = flush_chains(k);
-      if (rc == VSM_OK) rc = run_ahead(k);
-      if (rc == VSM_OK) rc = catch_up_chain1(k + 2);
-      if (rc != VSM_OK) return rc;
-    }
-  } else
-  for (int k = 0; k < nchunks; k++) {
-    {
-      const int rc = run_ahead(k);
-      if (rc != VSM_OK) return rc;
-    }
-    {
-      int rc = enqueue_main(k);
-      if (rc == VSM_OK) rc = catch_up_chain1(k + 2);  // the pass-1 chain of the chunk whose first pass went in above (in front of the export on its stream)
-      if (rc == VSM_OK) rc = enqueue_chain_head(k);
-      if (rc != VSM_OK) return rc;
-    }
+    return q.finish();
+  }
+  for (int k = 0; k < q.nchunks; k++) {
+    rc = q.run_ahead(k);
+    if (rc == VSM_OK) rc = q.enqueue_main(k);
+    if (rc == VSM_OK) rc = q.catch_up_chain1(k + 2);  // the pass-1 chain of the chunk whose first pass went in above (in front of the export on its stream)
+    if (rc == VSM_OK) rc = q.enqueue_chain_head(k);
     // the next chunk's second pass can follow at once when no run-ahead block (and so no wait for feature counts) and no wait
     // for a slab lies between: the chains then go in behind it
-    const bool next_main_free = !serial && k + 1 < nchunks && k + 3 >= nchunks && k + 1 < Seq2::kBanks + chain_next;
-    if (!next_main_free) {
-      const int rc = flush_chains(k);
-      if (rc != VSM_OK) return rc;
-    }
+    const bool next_main_free = !q.serial && k + 1 < q.nchunks && k + 3 >= q.nchunks && k + 1 < Seq2::kBanks + q.chain_next;
+    if (rc == VSM_OK && !next_main_free) rc = q.flush_chains(k);
+    if (rc != VSM_OK) return rc;
   }
-  {
-    const double t0 = now_us();
-    for (auto &ch : S.chunks)
-      if (!seq2_wait_chunk(ch.get(), 60e6, h->pool)) return VSM_EHIP;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->prof.on) {  // (every stream that carries spans has drained: the chunks are done)
-      for (int i = 0; i < S.dc_streams; i++) HIPCHK(hipStreamSynchronize(S.dc2[i]));
-      HIPCHK(hipStreamSynchronize(S.ns));
-      h->prof.resolve();
-    }
-    tg += now_us() - t0;
-  }
-  int declined_code = 0;
-  for (Dc2Bank &b : S.bank1)
-    if (b.h_error) declined_code |= *b.h_error;
-  for (Dc2Bank &b : S.bank2)
-    if (b.h_error) declined_code |= *b.h_error;
-  int hip_failed = 0;
-  for (auto &ch : S.chunks) hip_failed |= ch->hip_error.load();
-  for (Dc2Bank &b : S.bank1)
-    if (b.h_error) {
-      S.expect_long |= b.h_error[1] != 0;  // (a list beyond the LDS forms went through the narrow one: the long lists' kernel comes along from now on)
-      b.h_error[0] = b.h_error[1] = 0;
-    }
-  for (Dc2Bank &b : S.bank2)
-    if (b.h_error) {
-      S.expect_long |= b.h_error[1] != 0;
-      b.h_error[0] = b.h_error[1] = 0;
-    }
-  if (hip_failed) {  // a HIP call of a second part failed: that is an error, not a list this form declines
-    fprintf(stderr, "visomatch: a final chain of the GPU-resident look-ahead path failed: %s\n", hipGetErrorString(hipGetLastError()));
-    h->seq_hip_error.store(1);
-    return VSM_EHIP;
-  }
-  if (declined_code) {
-    fprintf(stderr, "visomatch: the GPU-resident look-ahead path declined a list (code %d), running the host-shared form\n", declined_code);
-    return VSM_SEQ2_DECLINED;
-  }
-  if (vsm_debug_timing()) {
-    if (!S.up_pieces.empty()) {
-      fprintf(stderr, "  upload pieces enqueued at (us):");
-      for (auto &pc : S.up_pieces) fprintf(stderr, " %d:%.0f", pc->f0, pc->t_recorded - tstart);
-      fprintf(stderr, "\n  ... arrived at (us):");
-      for (auto &pc : S.up_pieces) fprintf(stderr, " %d:%.0f", pc->f0, pc->t_arrived > 0 ? pc->t_arrived - tstart : -1.0);
-      fprintf(stderr, "\n  chunks' feature counts known / second pass enqueued at (us):");
-      for (size_t k = 0; k < dbg_counts.size(); k++) fprintf(stderr, " %zu:%.0f/%.0f", k, dbg_counts[k] - tstart, k < dbg_main.size() ? dbg_main[k] - tstart : -1.0);
-      fprintf(stderr, "\n");
-    }
-    for (auto &ch : S.chunks)
-      fprintf(stderr, "  chunk %d (%d pairs): keys on the host at %.0f us, sorted at %.0f (tasks %.0f us), chain done at %.0f, results in place at %.0f\n", ch->k, ch->n,
-              ch->t_keys - tstart, ch->t_sorted - tstart, ch->sort_ns.load() * 1e-3, ch->t_done - tstart, (ch->t_ready > 0 ? ch->t_ready : ch->t_done) - tstart);
-    fprintf(stderr, "  call returns at %.0f us\n", now_us() - tstart);
-  }
-  h->seq_v2_frames = n_frames;
-  h->seq_timings[0] = tg;
-  h->seq_timings[1] = 0;
-  for (auto &ch : S.chunks) h->seq_timings[1] += ch->sort_ns.load() * 1e-3;
-  h->seq_timings[2] = now_us() - tstart;
-  h->seq_timings[3] = (double)C;
-  return VSM_OK;
+  return q.finish();
 }

@@ -34,7 +34,7 @@ EXPORTS = ["vsm_default_params", "vsm_create", "vsm_destroy", "vsm_set_intrinsic
            "vsm_num_features", "vsm_get_features", "vsm_set_stage_capture", "vsm_stage_size", "vsm_stage_get",
            "vsm_num_ranges", "vsm_get_ranges", "vsm_get_gradients", "vsm_get_filter_responses", "vsm_get_counters",
            "vsm_get_timings", "vsm_set_profiling", "vsm_num_kernels", "vsm_kernel_name", "vsm_get_kernel_stats",
-           "vsm_host_delaunay", "vsm_host_delaunay_split", "vsm_debug_delaunay_gpu", "vsm_debug_dc_bench", "vsm_host_ties", "vsm_debug_ties_gpu", "vsm_host_outliers_and_prior", "vsm_host_outliers_and_prior_threads", "vsm_debug_dc2", "vsm_debug_dc2_band_factor", "vsm_debug_predicates", "vsm_local_cpus", "vsm_forkjoin_cpus", "vsm_device_pool_stats", "vsm_device_pool_trim", "vsm_sequence_run", "vsm_sequence_num_matches", "vsm_sequence_get_matches",
+           "vsm_host_delaunay", "vsm_host_delaunay_split", "vsm_debug_delaunay_gpu", "vsm_debug_dc_bench", "vsm_host_ties", "vsm_debug_ties_gpu", "vsm_host_outliers_and_prior", "vsm_host_outliers_and_prior_threads", "vsm_debug_dc2", "vsm_debug_dc2_band_factor", "vsm_debug_predicates", "vsm_debug_seq_plan", "vsm_local_cpus", "vsm_forkjoin_cpus", "vsm_device_pool_stats", "vsm_device_pool_trim", "vsm_sequence_run", "vsm_sequence_num_matches", "vsm_sequence_get_matches",
            "vsm_sequence_get_timings", "vsm_sequence_path", "vsm_set_option", "vsm_version", "vsm_host_register", "vsm_host_unregister",
            "vsm_multi_create", "vsm_multi_destroy", "vsm_multi_process", "vsm_multi_num_sequences", "vsm_multi_get_motion",
            "vsm_multi_motion_valid", "vsm_multi_num_matches", "vsm_multi_get_matches", "vsm_multi_num_inliers", "vsm_multi_get_inliers",
@@ -157,6 +157,7 @@ def lib():
         L.vsm_debug_dc2.argtypes = [C.POINTER(VsmParams), vp, i32, i32, i32, i32, vp, i32, vp, i32, i32, vp]
         L.vsm_debug_dc2_band_factor.argtypes = [i32]
         L.vsm_debug_predicates.argtypes = [vp, i32, vp]
+        L.vsm_debug_seq_plan.argtypes = [i32, i32, i32, i32, i32, C.c_char_p, vp, vp, i32]
         L.vsm_local_cpus.argtypes = [vp, i32]
         L.vsm_forkjoin_cpus.argtypes = [vp, i32]
         L.vsm_debug_dc2_band_factor.restype = None
@@ -372,6 +373,18 @@ def device_predicates(quads):
     if lib().vsm_debug_predicates(packed.ctypes.data_as(C.c_void_p), len(q), out.ctypes.data_as(C.c_void_p)) != 0:
         raise VisoMatchError("vsm_debug_predicates: HIP error")
     return out
+
+
+def seq_plan(n_frames, pool_threads, host_in=False, seq_chunk=0, seq_first_chunk=0, plan=None):
+    """test hook (no GPU): the chunk plan of the look-ahead call's GPU-resident form - (chunk size the banks are laid out
+    for, [first frame of each chunk ..., n_frames]); plan: what VSM_SEQ_PLAN would hold"""
+    chunk = C.c_int32(0)
+    starts = np.zeros(n_frames + 2, dtype=np.int32)
+    n = lib().vsm_debug_seq_plan(n_frames, pool_threads, int(bool(host_in)), seq_chunk, seq_first_chunk,
+                                 None if plan is None else plan.encode(), C.addressof(chunk), starts.ctypes.data_as(C.c_void_p), len(starts))
+    if n < 0:
+        raise VisoMatchError("vsm_debug_seq_plan: bad arguments")
+    return chunk.value, starts[:n + 1].tolist()
 
 
 def remove_outliers(matches, method, w, h, gpu=False, gpu_ties=False, copies=1, threads=1, **params):
