@@ -291,6 +291,16 @@ int32_t vsm_debug_predicates(const uint32_t *quads, int32_t n, int32_t *out);
  * argument, or cap < n + 1). */
 int32_t vsm_debug_seq_plan(int32_t n_frames, int32_t pool_threads, int32_t host_in, int32_t seq_chunk, int32_t seq_first_chunk,
                            const char *plan, int32_t *chunk, int32_t *starts, int32_t cap);
+/* Test hook of the batched forms' per-chunk job table (pure arithmetic, no GPU): a look-ahead call of matching method
+ * `method` (0 flow, 1 stereo, 2 quad) over frames of `sides` images (1 or 2), cut into n_chunks chunks that start at
+ * starts[0 .. n_chunks - 1] and end at starts[n_chunks] = the number of frames, with `banks` frame banks of `chunk` frames
+ * each.  counts[frame][side][set]: the feature counts the device would report (set 0 sparse, 1 dense; side 1 is not read
+ * with sides = 1); tr_valid: a byte per frame, or NULL (every frame brings a Tr).  The chunks are walked in order, a
+ * chunk's counts overwriting its bank's as on the device.  frames_out[frame][7] = image slot of the previous frame, of
+ * the frame, queries of the first and the second pass, use_tr, valid, and the frame whose list stands after the frame
+ * (-1: none); max_nq_out[chunk][2] = the chunk's longest query lists.  0, or -1 on a bad argument. */
+int32_t vsm_debug_chunk_jobs(int32_t method, int32_t multi_stage, int32_t sides, int32_t banks, int32_t chunk, const int32_t *starts,
+                             int32_t n_chunks, const int32_t *counts, const uint8_t *tr_valid, int32_t *frames_out, int32_t *max_nq_out);
 
 /* ---- stereo visual odometry on top of the matcher ----
  * class VisualOdometryStereo, viso/viso_stereo.h:28-88 + viso/viso.h:28-131: process() =

@@ -412,89 +412,6 @@ static int ctx_create(VsmCtx &c, const vsm_params &p, int32_t w, int32_t hh, int
   return VSM_OK;
 }
 
-// Look-ahead final stage, shared between host and GPU (vsm_dc.hip): per pair bank the pinned / device
-// slabs that carry the prepared keys and task lists to the GPU and the triangle records back.
-struct DcBank {
-  int npairs = 0, stride_pts = 0, stride_tasks = 0;
-  uint64_t *d_key = nullptr, *h_key = nullptr, *d_key_sorted = nullptr;  // h_key: (x,y) order if the GPU orders them, else kd order
-  uint32_t *d_kd = nullptr;  // scratch of k_dc_kd_order
-  uint64_t *d_tie_keys = nullptr;  // per pair [stride_pts]: keys of the pass-2 list in list order (k_dc_tie_keys)
-  int32_t *d_tie_n = nullptr;      // per pair: list length
-  float *d_flow = nullptr, *h_flow = nullptr;          // per pair [3][stride_pts]: flow u, flow v, disparity of every match
-  int32_t *d_support = nullptr, *h_support = nullptr;  // per pair [stride_pts]: support count of every match
-  uint32_t *d_pt = nullptr, *h_pt = nullptr;
-  int32_t *d_id = nullptr, *h_id = nullptr, *d_tri = nullptr, *h_tri = nullptr;
-  uint32_t *d_trip = nullptr, *h_trip = nullptr;  // packed triangle records, [2 * stride_pts][3] per pair (VsmDcJob::tri_packed)
-  VsmDcTask *d_tasks = nullptr, *h_tasks = nullptr;
-  VsmDcMerge *d_merges = nullptr, *h_merges = nullptr;  // stride_tasks per pair (a binary tree has fewer internal nodes than leaves)
-  VsmDcHull *d_hulls = nullptr, *h_hulls = nullptr;    // by node number: 2 * stride_tasks per pair
-  VsmDcJob *d_jobs = nullptr, *h_jobs = nullptr;
-  std::vector<int32_t> m, nt, nn;  // per pair: distinct points, tasks (nt < 0: the host solves the sub-trees), tree nodes
-  void release() {
-    vsm_dev_free(d_key);
-    vsm_dev_free(d_key_sorted);
-    vsm_dev_free(d_kd);
-    vsm_dev_free(d_tie_keys);
-    vsm_dev_free(d_tie_n);
-    vsm_dev_free(d_flow);
-    vsm_dev_free(d_support);
-    (void)hipHostFree(h_flow);
-    (void)hipHostFree(h_support);
-    vsm_dev_free(d_pt);
-    vsm_dev_free(d_id);
-    vsm_dev_free(d_tri);
-    vsm_dev_free(d_trip);
-    (void)hipHostFree(h_trip);
-    vsm_dev_free(d_tasks);
-    vsm_dev_free(d_merges);
-    vsm_dev_free(d_hulls);
-    vsm_dev_free(d_jobs);
-    (void)hipHostFree(h_key);
-    (void)hipHostFree(h_pt);
-    (void)hipHostFree(h_id);
-    (void)hipHostFree(h_tri);
-    (void)hipHostFree(h_tasks);
-    (void)hipHostFree(h_merges);
-    (void)hipHostFree(h_hulls);
-    (void)hipHostFree(h_jobs);
-    *this = DcBank();
-  }
-  bool reserve(int pairs, int pts, int tasks) {
-    pts = (pts + 1) & ~1;  // (the long-list y order views two adjacent scratch arrays as 64-bit items)
-    if (pairs <= npairs && pts <= stride_pts && tasks <= stride_tasks) return true;
-    release();
-    npairs = pairs;
-    stride_pts = pts;
-    stride_tasks = tasks;
-    const size_t P = (size_t)pairs * pts, T = (size_t)pairs * tasks;
-    bool ok = vsm_dev_alloc((void **)&d_key, P * 8) == hipSuccess && vsm_dev_alloc((void **)&d_key_sorted, P * 8) == hipSuccess &&
-              vsm_dev_alloc((void **)&d_kd, P * 4 * VSM_DC_KD_SCRATCH) == hipSuccess && vsm_dev_alloc((void **)&d_pt, P * 4) == hipSuccess &&
-              vsm_dev_alloc((void **)&d_flow, P * 12) == hipSuccess && vsm_dev_alloc((void **)&d_support, P * 4) == hipSuccess &&
-              vsm_dev_alloc((void **)&d_tie_keys, P * 8) == hipSuccess && vsm_dev_alloc((void **)&d_tie_n, (size_t)pairs * 4) == hipSuccess &&
-              hipHostMalloc((void **)&h_flow, P * 12, hipHostMallocDefault) == hipSuccess &&
-              hipHostMalloc((void **)&h_support, P * 4, hipHostMallocDefault) == hipSuccess &&
-              vsm_dev_alloc((void **)&d_id, P * 4) == hipSuccess && vsm_dev_alloc((void **)&d_tri, P * 64) == hipSuccess &&
-              vsm_dev_alloc((void **)&d_trip, P * 24) == hipSuccess && hipHostMalloc((void **)&h_trip, P * 24, hipHostMallocDefault) == hipSuccess &&
-              vsm_dev_alloc((void **)&d_tasks, T * sizeof(VsmDcTask)) == hipSuccess &&
-              vsm_dev_alloc((void **)&d_merges, T * sizeof(VsmDcMerge)) == hipSuccess &&
-              vsm_dev_alloc((void **)&d_hulls, 2 * T * sizeof(VsmDcHull)) == hipSuccess &&
-              vsm_dev_alloc((void **)&d_jobs, pairs * sizeof(VsmDcJob)) == hipSuccess &&
-              hipHostMalloc((void **)&h_key, P * 8, hipHostMallocDefault) == hipSuccess &&
-              hipHostMalloc((void **)&h_pt, P * 4, hipHostMallocDefault) == hipSuccess &&
-              hipHostMalloc((void **)&h_id, P * 4, hipHostMallocDefault) == hipSuccess &&
-              hipHostMalloc((void **)&h_tri, P * 64, hipHostMallocDefault) == hipSuccess &&
-              hipHostMalloc((void **)&h_tasks, T * sizeof(VsmDcTask), hipHostMallocDefault) == hipSuccess &&
-              hipHostMalloc((void **)&h_merges, T * sizeof(VsmDcMerge), hipHostMallocDefault) == hipSuccess &&
-              hipHostMalloc((void **)&h_hulls, 2 * T * sizeof(VsmDcHull), hipHostMallocDefault) == hipSuccess &&
-              hipHostMalloc((void **)&h_jobs, pairs * sizeof(VsmDcJob), hipHostMallocDefault) == hipSuccess;
-    m.assign(pairs, 0);
-    nt.assign(pairs, 0);
-    nn.assign(pairs, 0);
-    if (!ok) release();
-    return ok;
-  }
-};
-
 // ---------------------------------------------------------------------------------------
 // Measurement / test switches of a handle: read from the environment ONCE, at vsm_create (the calls themselves never
 // look at the environment), and settable afterwards through vsm_set_option (bench.py's "alone" pass, tools/).
@@ -597,12 +514,6 @@ struct vsm_handle {
   hipEvent_t seq_ev[2] = {nullptr, nullptr};  // look-ahead markers: features done / pass 1 done (blocking sync too)
   static constexpr int kDcBanks = 4;  // chunks whose final stage may be in flight at once
   struct DcBank *dc_bank[kDcBanks] = {nullptr, nullptr, nullptr, nullptr};  // look-ahead: GPU share of the exact Delaunay
-  hipStream_t tie_stream[2] = {nullptr, nullptr};  // the emulated vertex sorts of a chunk's pairs (k_dc_ties_of_lists), alternating
-  hipEvent_t tie_ev = nullptr;                     // pass-2 lists compacted
-  hipEvent_t tie_copied[2] = {nullptr, nullptr};   // per pair bank: its lists' keys have been copied out
-  bool tie_copied_set[2] = {false, false};
-  int32_t *hm_ties = nullptr, *d_ties = nullptr;   // host-mapped verdicts [kDcBanks][chunk][VSM_DC_TIE_OUT_INTS]
-  int ties_chunk = 0;
   hipStream_t dc_stream[2] = {nullptr, nullptr};  // alternate per chunk: one chunk's records travel while the next one's kernels run
   std::vector<VsmHostWork> seq_work;               // per pair of every Delaunay bank: state between the two host halves
   VsmCtx ring;  // streaming ring buffer: 2 frame slots, 1 pair
@@ -678,6 +589,7 @@ static void ranges_to_device_layout(float *dst, const float *src, size_t n_float
 VsmPool *vsm_pool_of(vsm_handle *h) { return h->pool; }
 VsmForkJoin *vsm_forkjoin_of(vsm_handle *h) { return h->fj; }
 double vsm_now_us() { return now_us(); }
+static void seq1_destroy(vsm_handle *h);  // vsm_seq1.inc
 static void seq2_destroy(vsm_handle *h);  // vsm_seq2.inc
 
 extern "C" {
@@ -767,8 +679,6 @@ void vsm_destroy(vsm_handle *h) {
   (void)hipStreamSynchronize(h->stream);
   for (hipStream_t st : h->dc_stream)
     if (st) (void)hipStreamSynchronize(st);
-  for (hipStream_t st : h->tie_stream)
-    if (st) (void)hipStreamSynchronize(st);
   seq2_destroy(h);
   ctx_destroy(h->ring);
   ctx_destroy(h->seq);
@@ -782,19 +692,9 @@ void vsm_destroy(vsm_handle *h) {
     if (h->seq_stage_d[k]) vsm_dev_free(h->seq_stage_d[k]);
     if (h->seq_stage_ev[k]) (void)hipEventDestroy(h->seq_stage_ev[k]);
   }
-  for (int b = 0; b < vsm_handle::kDcBanks; b++)
-    if (h->dc_bank[b]) {
-      h->dc_bank[b]->release();
-      delete h->dc_bank[b];
-    }
+  seq1_destroy(h);
   for (hipStream_t st : h->dc_stream)
     if (st) (void)hipStreamDestroy(st);
-  for (hipStream_t st : h->tie_stream)
-    if (st) (void)hipStreamDestroy(st);
-  if (h->tie_ev) (void)hipEventDestroy(h->tie_ev);
-  for (hipEvent_t e : h->tie_copied)
-    if (e) (void)hipEventDestroy(e);
-  if (h->hm_ties) (void)hipHostFree(h->hm_ties);
   if (h->idle_wait) (void)hipEventDestroy(h->idle_wait);
   if (h->input_ev) (void)hipEventDestroy(h->input_ev);
   for (hipEvent_t e : h->seq_ev)
@@ -831,6 +731,44 @@ static int settle(vsm_handle *h) {
   return VSM_OK;
 }
 
+// ---------------------------------------------------------------------------------------
+// Steps that the per-frame path and the batched forms (vsm_seq1.inc, vsm_seq2.inc, vsm_multi.inc) share
+// ---------------------------------------------------------------------------------------
+// the fused front end (k_front) instead of the three separate passes - ingest, halving, full-resolution Sobel (option "front" = 0)
+static bool fused_front(const vsm_handle *h) { return h->param.half_resolution && h->sw.front; }
+
+// One front-end step on the handle's stream: `frames` frames from s0 - and their right images from s1, if there are any -,
+// a frame every `stride` bytes in rows of `pitch` bytes, into images first, first + 1, ... of the context.  write_img: the
+// fused front end also writes the padded copy of the source (the separate ingest pass always does).
+static void enqueue_front(vsm_handle *h, VsmCtx &c, int first, const uint8_t *s0, const uint8_t *s1, size_t stride, int pitch, int frames,
+                          int write_img) {
+  if (frames <= 0) return;
+  if (fused_front(h))
+    vsm_launch_front(h->stream, h->prof, c.d_imgs, first, s0, s1, stride, pitch, frames, c.dims, write_img);
+  else
+    vsm_launch_ingest(h->stream, h->prof, c.d_imgs, first, s0, s1, stride, pitch, frames, c.dims);
+}
+// n frames of a batched form from s0, a frame every `step` bytes; sides == 2: their right images from s1, every `stride2` bytes.
+// The front kernels number their images first + 2 * frame + side: consecutive mono frames go through as (even, odd) pairs,
+// an odd last one alone.
+static void enqueue_front_frames(vsm_handle *h, VsmCtx &c, int first_img, int sides, const uint8_t *s0, size_t step, const uint8_t *s1,
+                                 size_t stride2, int pitch, int n) {
+  if (sides == 2) {
+    enqueue_front(h, c, first_img, s0, s1, stride2, pitch, n, 0);
+  } else {
+    enqueue_front(h, c, first_img, s0, s0 + step, 2 * step, pitch, n / 2, 0);
+    if (n & 1) enqueue_front(h, c, first_img + n - 1, s0 + step * (size_t)(n - 1), nullptr, step, pitch, 1, 0);
+  }
+}
+// every feature kernel over images first .. first + n_img - 1 (behind their front-end step); `extra`: further bits of the
+// launcher's option mask (vsm_internal.h).  Returns what vsm_launch_features returns.
+static int enqueue_features(vsm_handle *h, VsmCtx &c, int first, int n_img, int extra = 0) {
+  const vsm_params &p = h->param;
+  return vsm_launch_features(h->stream, h->prof, c.d_imgs, first, n_img, c.dims, c.f1, c.f2, c.f_stride, p.nms_tau, p.multi_stage,
+                             p.half_resolution, p.match_binsize, c.h_imgs.data(), fused_front(h) ? 1 : 0,
+                             (h->sw.fused_features ? 1 : 0) | (h->sw.feat_order ? 0 : 4) | extra);
+}
+
 static int push_common(vsm_handle *h, const uint8_t *I1, const uint8_t *I2, int32_t w, int32_t hh, int32_t bpl,
                        int replace, bool on_device) {
   if (w <= 0 || hh <= 0 || bpl < w || I1 == nullptr) {
@@ -859,13 +797,8 @@ static int push_common(vsm_handle *h, const uint8_t *I1, const uint8_t *I2, int3
   h->dims_c[1] = hh;
   h->dims_c[2] = c.dims.bpl;
   const int n_img = I2 ? 2 : 1;
-  // (VSM_FRONT=0: the three separate passes - ingest, halving, full-resolution Sobel - instead of the fused front end)
-  const bool fused_front = h->param.half_resolution && h->sw.front;
   if (on_device) {
-    if (fused_front)
-      vsm_launch_front(h->stream, h->prof, c.d_imgs, slot * 2, I1, I2, 0, bpl, 1, c.dims, 1);
-    else
-      vsm_launch_ingest(h->stream, h->prof, c.d_imgs, slot * 2, I1, I2, 0, bpl, 1, c.dims);
+    enqueue_front(h, c, slot * 2, I1, I2, 0, bpl, 1, 1);
   } else {
     // Host images: rows go through our own pinned, pre-padded staging buffer (a pageable 2-D copy
     // is staged row by row by the runtime and costs milliseconds).  The caller's buffer is free as
@@ -885,13 +818,9 @@ static int push_common(vsm_handle *h, const uint8_t *I1, const uint8_t *I2, int3
       HIPCHK(hipMemcpyAsync(c.h_imgs[slot * 2 + k].img, st, plane, hipMemcpyHostToDevice, h->stream));
     }
     // (the padded copies are in place: they are the fused front end's source)
-    if (fused_front)
-      vsm_launch_front(h->stream, h->prof, c.d_imgs, slot * 2, c.h_imgs[slot * 2].img, I2 ? c.h_imgs[slot * 2 + 1].img : nullptr, 0,
-                       c.dims.bpl, 1, c.dims, 0);
+    if (fused_front(h)) enqueue_front(h, c, slot * 2, c.h_imgs[slot * 2].img, I2 ? c.h_imgs[slot * 2 + 1].img : nullptr, 0, c.dims.bpl, 1, 0);
   }
-  const int f_planes = vsm_launch_features(h->stream, h->prof, c.d_imgs, slot * 2, n_img, c.dims, c.f1, c.f2, c.f_stride, h->param.nms_tau,
-                                           h->param.multi_stage, h->param.half_resolution, h->param.match_binsize, c.h_imgs.data(),
-                                           fused_front ? 1 : 0, (h->sw.fused_features ? 1 : 0) | (h->sw.filter_planes ? 2 : 0) | (h->sw.feat_order ? 0 : 4));
+  const int f_planes = enqueue_features(h, c, slot * 2, n_img, h->sw.filter_planes ? 2 : 0);
   HIPCHK(hipGetLastError());
   if (!h->push_ev) HIPCHK(hipEventCreateWithFlags(&h->push_ev, hipEventDisableTiming));
   HIPCHK(hipEventRecord(h->push_ev, h->stream));
@@ -957,6 +886,143 @@ static VsmMatchCfg make_cfg(const vsm_params &p, int method, int heads) {
   cfg.cv = p.cv;
   cfg.base = p.base;
   return cfg;
+}
+
+// The job table of one chunk of a batched form: frames f0 .. f0 + n - 1, whose images stand in slots first_img, first_img +
+// sides, ... (sides: images per frame) and whose feature counts the device has written into `counts` ([image][set], the
+// layout of VsmCtx::hm_counts); img_before: the slot of frame f0 - 1, the last one of the previous chunk's bank.  That
+// bank's counts may be gone by now: nprev[side][set] carries the counts of frame f0 - 1 in, and those of the chunk's last
+// frame out.  Per frame: the job (image slots; query counts and Tr only where matchFeatures would run, match_ready),
+// valid (may be NULL), and seq_src (vsm_handle::seq_src: a frame that is not matched keeps the list of the one before).
+// Pure arithmetic - no HIP call, nothing of a handle - so the CPU suite pins it through vsm_debug_chunk_jobs
+// (tests/test_chunk_jobs.py).
+static void seq_chunk_jobs(const vsm_params &p, int method, int sides, int32_t f0, int n, int first_img, int img_before, const int32_t *counts,
+                           int32_t nprev[2][2], const double *Tr, const uint8_t *Tr_valid, VsmJob *jobs, char *valid, int max_nq[2],
+                           int32_t *seq_src) {
+  max_nq[0] = max_nq[1] = 0;
+  for (int i = 0; i < n; i++) {
+    const int32_t f = f0 + i;
+    VsmJob &jb = jobs[i];
+    memset(&jb, 0, sizeof(jb));
+    const int img_c = first_img + sides * i;
+    int img_p;
+    int32_t cnt[4][2];
+    for (int s = 0; s < 2; s++) {
+      cnt[2][s] = counts[img_c * 2 + s];
+      cnt[3][s] = sides == 2 ? counts[(img_c + 1) * 2 + s] : 0;
+    }
+    if (method == 1) {
+      img_p = img_c;
+      for (int s = 0; s < 2; s++) cnt[0][s] = cnt[1][s] = 0;
+    } else if (i > 0) {
+      img_p = img_c - sides;
+      for (int s = 0; s < 2; s++) {
+        cnt[0][s] = counts[img_p * 2 + s];
+        cnt[1][s] = sides == 2 ? counts[(img_p + 1) * 2 + s] : 0;
+      }
+    } else {  // the previous frame is the last one of the previous chunk's bank
+      img_p = img_before;
+      for (int s = 0; s < 2; s++) {
+        cnt[0][s] = f > 0 ? nprev[0][s] : 0;
+        cnt[1][s] = f > 0 ? nprev[1][s] : 0;
+      }
+    }
+    jb.img_prev = img_p;
+    jb.img_curr = img_c;
+    const bool ready = match_ready(p, method, cnt);
+    if (ready) {
+      const int qimg = method == 2 ? 0 : 2;
+      jb.nq[0] = p.multi_stage ? cnt[qimg][0] : 0;
+      jb.nq[1] = cnt[qimg][1];
+      if (Tr && (!Tr_valid || Tr_valid[f])) {
+        jb.use_tr = 1;
+        memcpy(jb.t, Tr + (size_t)f * 12, 12 * sizeof(double));
+      }
+    }
+    if (valid) valid[i] = ready ? 1 : 0;
+    seq_src[f] = ready ? f : (f > 0 ? seq_src[f - 1] : -1);
+    max_nq[0] = std::max(max_nq[0], jb.nq[0]);
+    max_nq[1] = std::max(max_nq[1], jb.nq[1]);
+  }
+  for (int s = 0; s < 2; s++) {  // remember the last frame's counts for the next chunk
+    nprev[0][s] = counts[(first_img + sides * (n - 1)) * 2 + s];
+    nprev[1][s] = sides == 2 ? counts[(first_img + sides * (n - 1) + 1) * 2 + s] : 0;
+  }
+}
+// the slot of the frame in front of chunk k's first one: the last frame of chunk k - 1, in the bank before chunk k's
+static int seq_slot_before(const std::vector<int32_t> &chunk_start, int k, int sides, int banks, int C) {
+  return sides * ((k + banks - 1) % banks) * C + sides * ((k > 0 ? chunk_start[k] - chunk_start[k - 1] : 1) - 1);
+}
+
+// (debug entry, include/visomatch.h)
+int32_t vsm_debug_chunk_jobs(int32_t method, int32_t multi_stage, int32_t sides, int32_t banks, int32_t chunk, const int32_t *starts,
+                             int32_t n_chunks, const int32_t *counts, const uint8_t *tr_valid, int32_t *frames_out, int32_t *max_nq_out) {
+  if (method < 0 || method > 2 || sides < 1 || sides > 2 || banks < 2 || chunk < 1 || n_chunks < 1 || !starts || !counts || !frames_out ||
+      !max_nq_out || starts[0] != 0)
+    return -1;
+  for (int k = 0; k < n_chunks; k++)
+    if (starts[k + 1] <= starts[k] || starts[k + 1] - starts[k] > chunk) return -1;
+  const std::vector<int32_t> chunk_start(starts, starts + n_chunks + 1);
+  const int32_t n_frames = chunk_start[n_chunks];
+  vsm_params p;
+  vsm_default_params(&p);
+  p.multi_stage = multi_stage;
+  std::vector<int32_t> hm_counts((size_t)banks * chunk * sides * 2, 0), seq_src(n_frames, 0);
+  const std::vector<double> Tr((size_t)n_frames * 12, 0.0);
+  std::vector<VsmJob> jobs(chunk);
+  std::vector<char> valid(chunk);
+  int32_t nprev[2][2] = {{0, 0}, {0, 0}};
+  for (int k = 0; k < n_chunks; k++) {
+    const int32_t f0 = chunk_start[k];
+    const int n = chunk_start[k + 1] - f0, first_img = sides * (k % banks) * chunk;
+    for (int i = 0; i < n; i++)  // what the feature kernels of the chunk leave in its bank (an older chunk's counts are gone)
+      for (int side = 0; side < sides; side++)
+        for (int s = 0; s < 2; s++) hm_counts[(size_t)(first_img + sides * i + side) * 2 + s] = counts[((size_t)(f0 + i) * 2 + side) * 2 + s];
+    int max_nq[2];
+    seq_chunk_jobs(p, method, sides, f0, n, first_img, seq_slot_before(chunk_start, k, sides, banks, chunk), hm_counts.data(), nprev, Tr.data(), tr_valid,
+                   jobs.data(), valid.data(), max_nq, seq_src.data());
+    for (int i = 0; i < n; i++) {
+      int32_t *o = frames_out + (size_t)(f0 + i) * 7;
+      o[0] = jobs[i].img_prev;
+      o[1] = jobs[i].img_curr;
+      o[2] = jobs[i].nq[0];
+      o[3] = jobs[i].nq[1];
+      o[4] = jobs[i].use_tr;
+      o[5] = valid[i];
+      o[6] = seq_src[f0 + i];
+    }
+    max_nq_out[2 * k] = max_nq[0];
+    max_nq_out[2 * k + 1] = max_nq[1];
+  }
+  return 0;
+}
+
+// The pass-1 host stage of n pairs, first_pair onwards, on the pool (viso/matcher.cpp:222-226): a pair's pass-1 list out of
+// host-mapped memory (none for a pair that is not valid), removeOutliers, computePriorStatistics, the boxes in the device's
+// layout; then the boxes' upload on the handle's stream.  task_ns (may be NULL): the two steps' task time is added to
+// task_ns[0] and task_ns[1].
+static hipError_t host_pass1_boxes(vsm_handle *h, VsmCtx &c, int first_pair, int n, const char *valid, int method, const int32_t dims_c[3],
+                                   std::atomic<long long> *task_ns = nullptr) {
+  const vsm_params &p = h->param;
+  h->pool->run(n, [&](int i) {
+    static thread_local VsmHostWork tw;
+    static thread_local std::vector<float> rg;
+    static thread_local std::vector<vsm_p_match> m1;
+    const int pj = first_pair + i;
+    const double t0 = now_us();
+    m1.clear();
+    if (valid[i]) m1.assign(c.hm_list1[pj], c.hm_list1[pj] + std::max(c.hm_lcount[2 * pj], 0));
+    vsm_host_remove_outliers(tw, p, m1, method);
+    const double t1 = now_us();
+    vsm_host_prior_statistics(p, dims_c, m1, method, rg);
+    ranges_to_device_layout(c.h_ranges + (size_t)pj * c.ranges_stride, rg.data(), rg.size());
+    if (task_ns) {
+      task_ns[0].fetch_add((long long)((t1 - t0) * 1e3), std::memory_order_relaxed);
+      task_ns[1].fetch_add((long long)((now_us() - t1) * 1e3), std::memory_order_relaxed);
+    }
+  });
+  return vsm_upload(h->stream, c.d_ranges + (size_t)first_pair * c.ranges_stride, c.h_ranges + (size_t)first_pair * c.ranges_stride,
+                    c.ranges_stride * 4 * n);
 }
 
 int vsm_match(vsm_handle *h, int32_t method, const double *Tr) {
@@ -1195,380 +1261,6 @@ float vsm_gain(vsm_handle *h, const int32_t *inliers, int32_t n) {
   return vsm_host_gain(h->gainI[0].data(), h->gainI[1].data(), h->dims_p, h->dims_c, h->matched, inliers, n);
 }
 
-// ---------------------------------------------------------------------------------------
-// Final stage of a look-ahead chunk (exact Delaunay support test), shared between host and GPU:
-//   A  host pool, per pair: copy the exported list, per-match arrays, ExactDelaunay::prepare (emulated
-//      sort, kd order, tree); keys and sub-tree tasks go to the bank's pinned slab
-//   G  GPU, second stream: all sub-trees of all pairs in one launch (vsm_dc.hip), records back
-//   B  host pool, per pair: adopt the records, the merges above the sub-trees, support, survivors
-// The stages hand over to each other without the caller's thread: the last A task to finish enqueues
-// G, a host function at the end of G submits B.  VSM_DC_GPU=0 keeps everything on the host.
-// ---------------------------------------------------------------------------------------
-struct DcChunk {
-  vsm_handle *h = nullptr;
-  VsmCtx *ctx = nullptr;
-  vsm_params p;
-  int method = 0, leaf = 16, top = 240;
-  bool device_kd = true;  // the GPU orders the keys (k_dc_kd_order); else ExactDelaunay::prepare does
-  bool block = true;      // sub-trees of <= VSM_DC_BLOCK_POINTS points, one wave each inside LDS (k_dc_block); else leaf / top
-  bool full = true;       // (with block) all merge levels and the support test on the GPU too: only the counts come back
-  bool packed = false;    // (with block, not full) the triangle records come back as 12-byte packed words (set when G is enqueued)
-  bool ties_gpu = false;  // Triangle's randomised vertex sort runs on the GPU (k_dc_ties_of_lists), beside everything else
-  const int32_t *ties = nullptr;   // its verdicts, [n][VSM_DC_TIE_OUT_INTS] (host-mapped)
-  std::atomic<int> ties_done{1};
-  int bank = 0, n = 0, f0 = 0, first_pair = 0, work0 = 0;
-  std::shared_ptr<std::vector<char>> valid;
-  std::atomic<int> a_left{0};
-  DcBank *B = nullptr;         // its slabs
-  VsmHostWork *work = nullptr; // its per-pair host state [n]
-  int pass = 1;            // 1: the final stage (pass-2 lists -> seq_matches); 0: pass-1 lists, survivors stay in work[i].tmp_list
-  hipStream_t stream = nullptr;
-  int chunk = 0;           // the look-ahead chunk it belongs to
-  bool submitted = false;  // dc_submit_a() has run (caller's thread only)
-  bool a_waited = false;   // (caller's thread only)
-  std::atomic<int> stage{0};  // 0: A running, 1: G enqueued, 2: B submitted
-  std::atomic<bool> b_once{false};  // B is submitted by whoever comes first: the end of G, or dc_wait() giving up on it
-  VsmPool::Ticket a, b;
-  // VSM_DEBUG_TIMING: when the stages changed hands, and the task time summed over the pool
-  double t_a0 = 0, t_g0 = 0, t_g1 = 0, t_b0 = 0, t_b1 = 0;
-  std::atomic<long long> a_ns{0}, b_ns{0}, part_ns[8] = {};  // A: copy, arrays, prepare, slab; B: records, merges, support
-  std::atomic<int> b_left{0};
-};
-
-// B for pair i of the chunk: the GPU's records adopted, the merges above them, support test, survivors
-static void dc_task_b(DcChunk *ch, int i) {
-  {
-    const double t0 = vsm_now_us();
-    if (!(*ch->valid)[i]) return;
-    vsm_handle *h = ch->h;
-    VsmHostWork &wk = ch->work[i];
-    std::vector<vsm_p_match> dummy_out;
-    std::vector<vsm_p_match> &out = ch->pass == 1 ? h->seq_matches[ch->f0 + i] : dummy_out;
-    const int32_t nl = (int32_t)wk.tmp_list.size();
-    if (nl <= 3) {  // the reference leaves short lists alone (:1210)
-      if (ch->pass == 1) out.assign(wk.tmp_list.begin(), wk.tmp_list.end());
-      return;
-    }
-    const DcBank &B = *ch->B;
-    const int32_t m = B.m[i], nt = B.nt[i];
-    if (ch->block && ch->full && nt > 0) {  // the GPU went all the way: keep the matches with support >= 4 (:1369)
-      const double t1 = vsm_now_us();
-      const int32_t *support = B.h_support + (size_t)i * B.stride_pts;
-      vsm_host_keep_supported(wk.tmp_list, support);  // in place, then the buffers change hands
-      if (ch->pass == 1) out.swap(wk.tmp_list);
-      ch->part_ns[6].fetch_add((long long)((vsm_now_us() - t1) * 1e3), std::memory_order_relaxed);
-      return;
-    }
-    if (m >= 2) {
-      if (nt > 0) {  // adopt what the GPU built
-        // (copied, not used in place: the merges and the support test chase pointers through these arrays, and
-        // on the pinned slab - small pages, no prefetch-friendly order - that cost 25 % of the whole run)
-        const DcMesh mesh = wk.del.mesh();
-        if (ch->packed) {
-          const uint32_t *src = B.h_trip + (size_t)i * B.stride_pts * 6;
-          int32_t *dst = mesh.tri;
-          for (int32_t t = 0; t < 2 * m; t++, src += 3, dst += 8) {
-            for (int o = 0; o < 3; o++) {
-              const uint32_t wv = src[o], nb = wv & 0x1ffffu, vx = wv >> 17;
-              dst[o] = nb == 0x1ffffu ? -1 : (int32_t)nb;
-              dst[4 + o] = vx == 0x7fffu ? -1 : (int32_t)vx;
-            }
-          }
-        } else {
-          memcpy(mesh.tri, B.h_tri + (size_t)i * B.stride_pts * 16, (size_t)m * 16 * sizeof(int32_t));
-        }
-        memcpy(mesh.pt, B.h_pt + (size_t)i * B.stride_pts, (size_t)m * 4);
-        memcpy(mesh.id, B.h_id + (size_t)i * B.stride_pts, (size_t)m * 4);
-        const VsmDcHull *hu = B.h_hulls + (size_t)i * 2 * B.stride_tasks;
-        auto take = [&](int32_t q) { wk.del.set_node_hull(q, ExactDelaunay::OTri{hu[q].fl_t, hu[q].fl_o}, ExactDelaunay::OTri{hu[q].fr_t, hu[q].fr_o}); };
-        for (const ExactDelaunay::Task &tk : wk.del.tasks()) take(tk.node);
-        for (const ExactDelaunay::Merge &mg : wk.del.device_merges()) take(mg.node);
-      } else {
-        wk.del.order_keys();
-        wk.del.solve_tasks();
-        wk.del.solve_merges();
-      }
-      if (ch->ties_gpu) {  // which match stands for a shared pixel: the GPU's verdict (or, where it declined, the host's)
-        while (!ch->ties_done.load(std::memory_order_acquire)) std::this_thread::yield();
-        const int32_t *row = ch->ties + (size_t)i * VSM_DC_TIE_OUT_INTS;
-        if (row[0] >= 0 && row[0] <= VSM_DC_TIE_PATCHES) wk.del.set_ties(row + 1, row[0]);
-        wk.del.apply_ties();
-      }
-      const double t1 = vsm_now_us();
-      ch->part_ns[4].fetch_add((long long)((t1 - t0) * 1e3), std::memory_order_relaxed);
-      wk.del.finish();
-      ch->part_ns[5].fetch_add((long long)((vsm_now_us() - t1) * 1e3), std::memory_order_relaxed);
-    }
-    const double t2 = vsm_now_us();
-    vsm_host_count_support(wk, ch->p, nl, ch->method);
-    vsm_host_keep_supported(wk.tmp_list, wk.support.data());  // in place, then the buffers change hands
-    if (ch->pass == 1) out.swap(wk.tmp_list);
-    ch->part_ns[6].fetch_add((long long)((vsm_now_us() - t2) * 1e3), std::memory_order_relaxed);
-  }
-}
-
-static void dc_submit_b(DcChunk *ch) {
-  vsm_handle *h = ch->h;
-  ch->t_b0 = vsm_now_us();
-  ch->b_left.store(ch->n, std::memory_order_relaxed);
-  ch->b = h->pool->submit(ch->n, [ch](int i) {
-    const double t0 = vsm_now_us();
-    dc_task_b(ch, i);
-    ch->b_ns.fetch_add((long long)((vsm_now_us() - t0) * 1e3), std::memory_order_relaxed);
-    if (ch->b_left.fetch_sub(1, std::memory_order_acq_rel) == 1) ch->t_b1 = vsm_now_us();
-  });
-  ch->stage.store(2, std::memory_order_release);
-}
-
-static void dc_after_gpu(void *arg) {  // runs on a HIP runtime thread: no HIP calls
-  DcChunk *ch = (DcChunk *)arg;
-  ch->t_g1 = vsm_now_us();
-  if (!ch->b_once.exchange(true)) dc_submit_b(ch);
-}
-
-// from the pool thread that finished the chunk's last A task; wait_here: from the caller's thread, which waits for the
-// GPU's part itself and submits nothing (pass 0)
-static void dc_enqueue_gpu(DcChunk *ch, bool wait_here = false) {
-  vsm_handle *h = ch->h;
-  (void)hipSetDevice(h->device);
-  ch->t_g0 = vsm_now_us();
-  DcBank &B = *ch->B;
-  int maxt = 0, maxm = 0, maxin = 0, maxn = 0, maxlev = 0, maxg = 0, lev_nodes[VSM_DC_MAX_LEVELS] = {0};
-  for (int i = 0; i < ch->n; i++) {
-    VsmDcJob &jb = B.h_jobs[i];  // (the A task left the level table in it)
-    jb.key = B.d_key + (size_t)i * B.stride_pts;
-    jb.key_sorted = ch->device_kd && B.nt[i] > 0 ? B.d_key_sorted + (size_t)i * B.stride_pts : nullptr;
-    jb.kd_scratch = B.d_kd + (size_t)i * B.stride_pts * VSM_DC_KD_SCRATCH;
-    jb.kd_stride = B.stride_pts;
-    jb.pt = B.d_pt + (size_t)i * B.stride_pts;
-    jb.id = B.d_id + (size_t)i * B.stride_pts;
-    jb.tri = B.d_tri + (size_t)i * B.stride_pts * 16;
-    jb.tasks = B.d_tasks + (size_t)i * B.stride_tasks;
-    jb.merges = B.d_merges + (size_t)i * B.stride_tasks;
-    jb.hulls = B.d_hulls + (size_t)i * 2 * B.stride_tasks;
-    jb.flow_u = B.d_flow + (size_t)i * 3 * B.stride_pts;
-    jb.flow_v = jb.flow_u + B.stride_pts;
-    jb.disp = jb.flow_v + B.stride_pts;
-    jb.support = ch->full ? B.d_support + (size_t)i * B.stride_pts : nullptr;
-    jb.ntasks = std::max(B.nt[i], 0);
-    jb.m = B.m[i];
-    maxt = std::max(maxt, jb.ntasks);
-    if (B.nt[i] > 0) {
-      maxm = std::max(maxm, B.m[i]);
-      maxin = std::max(maxin, jb.n_in);
-      maxn = std::max(maxn, B.nn[i]);
-      maxlev = std::max(maxlev, jb.nlevels);
-      maxg = std::max(maxg, jb.level_off[jb.nlevels]);
-      for (int l = 0; l < jb.nlevels; l++) lev_nodes[l] = std::max(lev_nodes[l], jb.level_off[l + 1] - jb.level_off[l]);
-    } else {
-      jb.nlevels = 0;
-    }
-  }
-  ch->packed = ch->block && !ch->full && maxm > 0 && maxm <= VSM_DC_PACKED_MAX_POINTS;
-  for (int i = 0; i < ch->n; i++) B.h_jobs[i].tri_packed = ch->packed ? B.d_trip + (size_t)i * B.stride_pts * 6 : nullptr;
-  // only the used part of every pair's slab row travels: rows of maxm points / maxt tasks
-  const size_t sp = (size_t)B.stride_pts, st = (size_t)B.stride_tasks, rows = (size_t)ch->n;
-  hipStream_t s2 = ch->stream;
-  bool ok = true;
-  if (maxt > 0) {
-    ok = hipMemcpy2DAsync(ch->device_kd ? B.d_key_sorted : B.d_key, sp * 8, B.h_key, sp * 8, (size_t)maxm * 8, rows, hipMemcpyHostToDevice,
-                          s2) == hipSuccess &&
-         hipMemcpy2DAsync(B.d_tasks, st * sizeof(VsmDcTask), B.h_tasks, st * sizeof(VsmDcTask), (size_t)maxt * sizeof(VsmDcTask), rows,
-                          hipMemcpyHostToDevice, s2) == hipSuccess &&
-         (maxg == 0 || hipMemcpy2DAsync(B.d_merges, st * sizeof(VsmDcMerge), B.h_merges, st * sizeof(VsmDcMerge),
-                                        (size_t)maxg * sizeof(VsmDcMerge), rows, hipMemcpyHostToDevice, s2) == hipSuccess) &&
-         hipMemcpyAsync(B.d_jobs, B.h_jobs, ch->n * sizeof(VsmDcJob), hipMemcpyHostToDevice, s2) == hipSuccess &&
-         // (k_dc_block writes every slot of every sub-tree; the per-lane kernels rely on empty slots reading -1)
-         (ch->block || hipMemset2DAsync(B.d_tri, sp * 64, 0xff, (size_t)maxm * 64, rows, s2) == hipSuccess);
-    if (ok) {
-      VsmProf &pf = h->prof;
-      if (ch->device_kd) {
-        pf.begin(VSM_K_DC_KD, s2);
-        vsm_dc_launch_kd_order(s2, B.d_jobs, ch->n);
-        pf.end(s2);
-      }
-      pf.begin(VSM_K_DC_BLOCK, s2);
-      if (ch->block) {
-        vsm_dc_launch_blocks(s2, B.d_jobs, ch->n, maxt);
-      } else {
-        vsm_dc_launch_subtrees(s2, B.d_jobs, ch->n, maxt);
-      }
-      pf.end(s2);
-      if (maxlev > 0) {
-        pf.begin(VSM_K_DC_MERGE, s2);
-        for (int l = 0; l < maxlev; l++) vsm_dc_launch_merge_level(s2, B.d_jobs, ch->n, l, lev_nodes[l]);
-        pf.end(s2);
-      }
-      if (ch->block && ch->full) {
-        // the triangulations are complete on the device: count the support there, only the counts travel
-        ok = hipMemcpy2DAsync(B.d_flow, sp * 12, B.h_flow, sp * 12, sp * 12, rows, hipMemcpyHostToDevice, s2) == hipSuccess &&
-             hipMemset2DAsync(B.d_support, sp * 4, 0, (size_t)maxin * 4, rows, s2) == hipSuccess;
-        if (ok) {
-          pf.begin(VSM_K_DC_SUPPORT, s2);
-          vsm_dc_launch_support(s2, B.d_jobs, ch->n, maxm, ch->method, (float)ch->p.outlier_flow_tolerance, (float)ch->p.outlier_disp_tolerance);
-          pf.end(s2);
-          ok = hipMemcpy2DAsync(B.h_support, sp * 4, B.d_support, sp * 4, (size_t)maxin * 4, rows, hipMemcpyDeviceToHost, s2) == hipSuccess;
-        }
-      } else {
-        ok = (ch->packed ? hipMemcpy2DAsync(B.h_trip, sp * 24, B.d_trip, sp * 24, (size_t)maxm * 24, rows, hipMemcpyDeviceToHost, s2)
-                         : hipMemcpy2DAsync(B.h_tri, sp * 64, B.d_tri, sp * 64, (size_t)maxm * 64, rows, hipMemcpyDeviceToHost, s2)) == hipSuccess &&
-             hipMemcpy2DAsync(B.h_pt, sp * 4, B.d_pt, sp * 4, (size_t)maxm * 4, rows, hipMemcpyDeviceToHost, s2) == hipSuccess &&
-             hipMemcpy2DAsync(B.h_id, sp * 4, B.d_id, sp * 4, (size_t)maxm * 4, rows, hipMemcpyDeviceToHost, s2) == hipSuccess &&
-             hipMemcpy2DAsync(B.h_hulls, 2 * st * sizeof(VsmDcHull), B.d_hulls, 2 * st * sizeof(VsmDcHull), (size_t)maxn * sizeof(VsmDcHull),
-                              rows, hipMemcpyDeviceToHost, s2) == hipSuccess;
-      }
-    }
-  }
-  ch->stage.store(1, std::memory_order_release);
-  if (wait_here) {
-    if (maxt > 0 && !(ok && hipStreamSynchronize(s2) == hipSuccess)) {
-      (void)hipStreamSynchronize(s2);
-      for (int i = 0; i < ch->n; i++)
-        if (B.nt[i] > 0) B.nt[i] = -1;
-    }
-    return;
-  }
-  // (option dc_fault_inject = 1, tests only: the completion callback is "lost" - dc_wait()'s watchdog has to notice)
-  const bool lose_callback = ch->h->sw.dc_fault_inject == 1;
-  if (ok && maxt > 0 && lose_callback) return;
-  if (ok && maxt > 0 && hipLaunchHostFunc(s2, dc_after_gpu, ch) == hipSuccess) return;
-  // nothing for the GPU, or it could not be used: the host solves the sub-trees too
-  if (maxt > 0) {
-    (void)hipStreamSynchronize(s2);
-    for (int i = 0; i < ch->n; i++)
-      if (B.nt[i] > 0) B.nt[i] = -1;
-  }
-  if (!ch->b_once.exchange(true)) dc_submit_b(ch);
-}
-
-// A for pair i of the chunk: the list out of host-mapped memory, the per-match arrays, the host's part of the triangulation
-static void dc_task_a(DcChunk *ch, int i) {
-  {
-    const double t0 = vsm_now_us();
-    VsmHostWork &wk = ch->work[i];
-    DcBank &B = *ch->B;
-    B.m[i] = 0;
-    B.nt[i] = 0;
-    wk.tmp_list.clear();
-    if ((*ch->valid)[i]) {
-      const int pj = ch->first_pair + i;
-      // one wide copy out of the host-mapped export, then cache-resident work
-      if (ch->pass == 1)
-        wk.tmp_list.assign(ch->ctx->hm_list2[pj], ch->ctx->hm_list2[pj] + ch->ctx->hm_lcount[2 * pj + 1]);
-      else
-        wk.tmp_list.assign(ch->ctx->hm_list1[pj], ch->ctx->hm_list1[pj] + ch->ctx->hm_lcount[2 * pj]);
-      const int32_t nl = (int32_t)wk.tmp_list.size();
-      const double t1 = vsm_now_us();
-      ch->part_ns[0].fetch_add((long long)((t1 - t0) * 1e3), std::memory_order_relaxed);
-      if (nl > 3) {
-        vsm_host_outliers_begin(wk, wk.tmp_list.data(), nl, ch->method);
-        const double t2 = vsm_now_us();
-        ch->part_ns[1].fetch_add((long long)((t2 - t1) * 1e3), std::memory_order_relaxed);
-        // (ties_gpu: the emulated vertex sort is the GPU's, ExactDelaunay::prepare's defer_ties; on the host it would only
-        // move 150 us per pair from in front of the GPU's part to beside it, and cost a radix sort on top)
-        const bool prepared = ch->block ? wk.del.prepare(wk.x.data(), wk.y.data(), nl, VSM_DC_BLOCK_POINTS, nullptr, ch->full ? INT32_MAX : 0,
-                                                         ch->device_kd, ch->ties_gpu)
-                                        : wk.del.prepare(wk.x.data(), wk.y.data(), nl, ch->leaf, nullptr, ch->top, ch->device_kd, ch->ties_gpu);
-        ch->part_ns[2].fetch_add((long long)((vsm_now_us() - t2) * 1e3), std::memory_order_relaxed);
-        if (prepared) {
-          const int32_t m = wk.del.points(), nt = (int32_t)wk.del.tasks().size(), ng = (int32_t)wk.del.device_merges().size();
-          const std::vector<int32_t> &lv = wk.del.device_levels();
-          B.m[i] = m;
-          B.nn[i] = wk.del.num_nodes();
-          if (m < nl) ch->part_ns[7].fetch_add(1, std::memory_order_relaxed);  // pairs with duplicate points
-          if (m > B.stride_pts || nl > B.stride_pts || nt > B.stride_tasks || ng > B.stride_tasks || B.nn[i] > 2 * B.stride_tasks ||
-              (int)lv.size() > VSM_DC_MAX_LEVELS || (ch->device_kd && m > VSM_DC_KD_MAX_POINTS)) {
-            B.nt[i] = -1;  // does not fit the slab: this pair stays on the host
-          } else {
-            memcpy(B.h_key + (size_t)i * B.stride_pts, wk.del.mesh().key, (size_t)m * 8);
-            memcpy(B.h_tasks + (size_t)i * B.stride_tasks, wk.del.tasks().data(), (size_t)nt * sizeof(VsmDcTask));
-            memcpy(B.h_merges + (size_t)i * B.stride_tasks, wk.del.device_merges().data(), (size_t)ng * sizeof(VsmDcMerge));
-            if (ch->full) {
-              float *fl = B.h_flow + (size_t)i * 3 * B.stride_pts;
-              memcpy(fl, wk.fu.data(), (size_t)nl * 4);
-              memcpy(fl + B.stride_pts, wk.fv.data(), (size_t)nl * 4);
-              memcpy(fl + 2 * (size_t)B.stride_pts, wk.dp.data(), (size_t)nl * 4);
-            }
-            VsmDcJob &jb = B.h_jobs[i];
-            jb.n_in = nl;
-            jb.nlevels = (int32_t)lv.size();
-            jb.level_off[0] = 0;
-            for (int l = 0; l < jb.nlevels; l++) jb.level_off[l + 1] = jb.level_off[l] + lv[l];
-            B.nt[i] = nt;
-          }
-        }
-      }
-    }
-    ch->a_ns.fetch_add((long long)((vsm_now_us() - t0) * 1e3), std::memory_order_relaxed);
-  }
-}
-
-static void dc_submit_a(DcChunk *ch) {
-  ch->submitted = true;
-  ch->a_left.store(ch->n, std::memory_order_relaxed);
-  ch->t_a0 = vsm_now_us();
-  ch->a = ch->h->pool->submit(ch->n, [ch](int i) {
-    dc_task_a(ch, i);
-    if (ch->a_left.fetch_sub(1, std::memory_order_acq_rel) == 1) dc_enqueue_gpu(ch);  // the last one hands over
-  });
-}
-
-// Until the chunk's final lists are in seq_matches.  The GPU's part normally takes a millisecond or two and reports back
-// through a host function on its stream.  If nothing has been heard after the watchdog time (option dc_watchdog_ms, default
-// 20 s) the stream itself is asked: hipStreamSynchronize() either returns an error - the device faulted; that is logged
-// with HIP's own message, remembered in the handle (no GPU share from then on) and reported by vsm_sequence_run as
-// VSM_EHIP - or it returns success, in which case the device's results are complete and only the callback went missing.
-// Either way nothing on the device can touch the chunk's slabs any more when the host takes over, and the chunk and
-// its bank stay alive until then (they are owned by vsm_sequence_run, which calls this for every chunk before it returns).
-static void dc_wait(DcChunk *ch) {
-  vsm_handle *h = ch->h;
-  const double watchdog_us = (double)h->sw.dc_watchdog_ms * 1e3;
-  if (!ch->submitted) {  // (left early, between setting it up and submitting it: only its vertex sorts may be in flight)
-    const double t0 = vsm_now_us();
-    while (!ch->ties_done.load(std::memory_order_acquire)) {
-      std::this_thread::sleep_for(std::chrono::microseconds(50));
-      if (vsm_now_us() - t0 > watchdog_us) {
-        const hipError_t e = hipStreamSynchronize(h->tie_stream[ch->bank & 1]);
-        if (e != hipSuccess) {
-          fprintf(stderr, "visomatch: the vertex-sort stream of the Delaunay stage failed: %s\n", hipGetErrorString(e));
-          h->dc_gpu_broken = true;
-          h->seq_hip_error.store(1);
-        }
-        ch->ties_done.store(1, std::memory_order_release);
-      }
-    }
-    return;
-  }
-  const double t0 = vsm_now_us();
-  while (ch->stage.load(std::memory_order_acquire) < 2) {
-    std::this_thread::sleep_for(std::chrono::microseconds(50));
-    if (ch->stage.load(std::memory_order_acquire) == 1 && vsm_now_us() - t0 > watchdog_us && !ch->b_once.exchange(true)) {
-      const hipError_t e = hipStreamSynchronize(ch->stream);  // (blocks until the stream has drained or failed)
-      hipError_t et = hipSuccess;
-      if (ch->ties_gpu) et = hipStreamSynchronize(h->tie_stream[ch->bank & 1]);
-      if (e != hipSuccess || et != hipSuccess) {
-        fprintf(stderr, "visomatch: the GPU share of the Delaunay stage failed (%s); finishing the chunk on the host, no GPU share from now on\n",
-                hipGetErrorString(e != hipSuccess ? e : et));
-        h->dc_gpu_broken = true;
-        h->seq_hip_error.store(1);
-        DcBank &B = *ch->B;
-        for (int i = 0; i < ch->n; i++)
-          if (B.nt[i] > 0) B.nt[i] = -1;
-        ch->full = false;
-        if (ch->ties_gpu) {  // (its vertex sorts will not report either: the host's verdicts)
-          for (int i = 0; i < ch->n; i++) const_cast<int32_t *>(ch->ties)[(size_t)i * VSM_DC_TIE_OUT_INTS] = -1;
-          ch->ties_done.store(1, std::memory_order_release);
-        }
-      } else {
-        fprintf(stderr, "visomatch: the GPU share of the Delaunay stage finished without reporting back; continuing with its results\n");
-        if (ch->ties_gpu) ch->ties_done.store(1, std::memory_order_release);
-      }
-      dc_submit_b(ch);
-    }
-  }
-  h->pool->wait(ch->b);
-}
-
 // Host images of a look-ahead chunk: a pageable 2-D copy is staged row by row by the runtime (milliseconds per image), so
 // the pool gathers the chunk's 2 n images into a pinned slot (w bytes per row), one upload follows, and k_ingest reads the
 // device twin like any device-resident input.  Two slots alternate; a slot is reused once its ingest has run.
@@ -1605,27 +1297,14 @@ static int seq_ingest_host_frames(vsm_handle *h, VsmCtx &c, int first_img, const
   });
   HIPCHK(hipMemcpyAsync(h->seq_stage_d[slot], dst, (size_t)sides * img * n, hipMemcpyHostToDevice, h->stream));
   const uint8_t *d0 = h->seq_stage_d[slot];
-  const bool fused = h->param.half_resolution && h->sw.front;
-  // (the front kernels number their images first + 2 * frame + side: consecutive mono frames go through as (even, odd) pairs)
-  auto front = [&](int first, const uint8_t *s0, const uint8_t *s1, size_t stride, int frames) {
-    if (frames <= 0) return;
-    if (fused)
-      vsm_launch_front(h->stream, h->prof, c.d_imgs, first, s0, s1, stride, w, frames, c.dims, 0);
-    else
-      vsm_launch_ingest(h->stream, h->prof, c.d_imgs, first, s0, s1, stride, w, frames, c.dims);
-  };
-  if (right) {
-    front(first_img, d0, d0 + img * n, img, n);
-  } else {
-    front(first_img, d0, d0 + img, 2 * img, n / 2);
-    if (n & 1) front(first_img + n - 1, d0 + img * (size_t)(n - 1), nullptr, img, 1);
-  }
+  enqueue_front_frames(h, c, first_img, sides, d0, img, d0 + img * n, img, w, n);
   HIPCHK(hipEventRecord(h->seq_stage_ev[slot], h->stream));
   return VSM_OK;
 }
 
 }  // extern "C"
 #include "vsm_seq2.inc"
+#include "vsm_seq1.inc"
 #include "vsm_multi.inc"
 extern "C" {
 
@@ -1641,8 +1320,6 @@ static int sequence_fallback(vsm_handle *h, const uint8_t *left, const uint8_t *
   // rarely used configurations (mono input, refinement==2) go frame by frame on a fresh ring
   (void)hipStreamSynchronize(h->stream);
   for (hipStream_t st : h->dc_stream)
-    if (st) (void)hipStreamSynchronize(st);
-  for (hipStream_t st : h->tie_stream)
     if (st) (void)hipStreamSynchronize(st);
   seq2_destroy(h);
   ctx_destroy(h->ring);
@@ -1668,7 +1345,6 @@ int vsm_sequence_run(vsm_handle *h, const uint8_t *left, const uint8_t *right, i
     fprintf(stderr, "ERROR: Image dimension mismatch!\n");
     return VSM_EDIMS;
   }
-  const double t_entry = now_us();
   HIPCHK(hipSetDevice(h->device));
   const vsm_params &p = h->param;
   h->seq_v2_frames = 0;
@@ -1677,12 +1353,12 @@ int vsm_sequence_run(vsm_handle *h, const uint8_t *left, const uint8_t *right, i
   h->seq_view.assign(n_frames, vsm_handle::SeqView());
   h->seq_src.resize(n_frames);
   for (int32_t f = 0; f < n_frames; f++) h->seq_src[f] = f;
-  // (mono input can only be flow-matched; the host-shared form below has no sub-pixel refinement - its fits and dropped matches
+  // (mono input can only be flow-matched; the host-shared form (vsm_seq1.inc) has no sub-pixel refinement - its fits and dropped matches
   // are the GPU-resident form's, or the per-frame code's)
   if ((!right && (method != 0 || !h->sw.seq_v2)) || (p.refinement == 2 && !h->sw.seq_v2))
     return sequence_fallback(h, left, right, frame_stride, on_device, n_frames, w, hh, bpl, method, Tr, Tr_valid);
 
-  // The GPU-resident form (vsm_seq2.inc) takes the run unless VSM_SEQ_V2=0 asks for the host-shared form below, or
+  // The GPU-resident form (vsm_seq2.inc) takes the run unless VSM_SEQ_V2=0 asks for the host-shared form (vsm_seq1.inc), or
   // it declines (lists beyond what its device-side vertex sort / kd order were written for).
   // The host-shared form lives off the rank's host threads (200 frames 1242x375, round 3: 7.6 ms with 14 pool threads, 15 with 8,
   // 24 with 2); the GPU-resident one keeps only Triangle's vertex sort and the closing of the result lists on the host (5.0-5.2 ms
@@ -1694,451 +1370,7 @@ int vsm_sequence_run(vsm_handle *h, const uint8_t *left, const uint8_t *right, i
     h->seq_v2_frames = 0;
     if (!right || p.refinement == 2) return sequence_fallback(h, left, right, frame_stride, on_device, n_frames, w, hh, bpl, method, Tr, Tr_valid);
   }
-  int C = h->sw.seq_chunk > 0 ? h->sw.seq_chunk : 50;
-  if (C > n_frames) C = n_frames;
-  VsmCtx &c = h->seq;
-  if (!c.ready || c.dims.w != w || c.dims.h != hh || h->seq_chunk != C || c.npairs != 2 * C || c.nframes != 3 * C) {
-    (void)hipStreamSynchronize(h->stream);
-    int rc = ctx_create(c, p, w, hh, 3 * C, 2 * C, h->stream, h->sw.match_heads != 0);  // three banks of frames, two of pairs
-    if (rc != VSM_OK) return rc;
-    h->seq_chunk = C;
-  }
-  // Software pipeline over chunks.  GPU order: pass 1 of chunk k, features of chunk k+1, pass 2 of
-  // chunk k - so the GPU has the next chunk's features to compute while the pool does chunk k's
-  // prior statistics, and the caller's thread never waits for features.  Frames live in three banks
-  // (chunk k+1's features must not overwrite the last frame of chunk k-1, which chunk k's first pair
-  // reads); pairs in two (the final host stage of chunk k reads pair bank k&1 in host-mapped memory
-  // while the GPU runs chunk k+1 on the other).
-  std::vector<VsmPool::Ticket> tickets;  // final stages that stay on the host ...
-  std::vector<int> ticket_chunk;         // ... and the chunk each belongs to
-  // final stage: see DcChunk above
-  // (options dc_gpu / dc_full, vsm_set_option.  Round 1's sub-variants of this form - per-lane sub-trees of VSM_DC_LEAF points
-  // with merge levels up to VSM_DC_TOP points in global memory, the kd order on the host, the vertex sort on one wave of
-  // the device - are compile-time choices now: tools/build_variant.sh NAME "-DVSM_DC_BLOCK_FORM=0 -DVSM_DC_LEAF=64 ...")
-#ifndef VSM_DC_LEAF
-#define VSM_DC_LEAF 16
-#endif
-#ifndef VSM_DC_KD_ON_GPU
-#define VSM_DC_KD_ON_GPU 1
-#endif
-#ifndef VSM_DC_BLOCK_FORM
-#define VSM_DC_BLOCK_FORM 1
-#endif
-#ifndef VSM_DC_TOP
-#define VSM_DC_TOP 240
-#endif
-#ifndef VSM_DC_TIES_ON_GPU
-#define VSM_DC_TIES_ON_GPU 0
-#endif
-  const VsmSwitches &sw = h->sw;
-  const bool dc_env = sw.dc_gpu != 0;
-  const bool dc_forced = sw.dc_gpu > 0;
-  const int dc_leaf = std::max(3, VSM_DC_LEAF);
-  const bool dc_kd = VSM_DC_KD_ON_GPU != 0;      // kd order of the keys on the GPU too
-  const bool dc_block = VSM_DC_BLOCK_FORM != 0;  // k_dc_block instead of leaf / top
-  // (with block) the merges above the sub-trees and the support test on the GPU too: a third less host work per
-  // pair, but the large merges are slow there (a dependent L2 round trip per step), so it pays when the host has
-  // few cores for this rank (200 frames 1242x375, ms: 16 threads 9.1 shared / 14.2 full, 8: 12.9 / 14.9, 4: 21.5 / 18.6,
-  // 2: 33.1 / 25.8; host only: 14.0, 25.3, 43.4, 70.8); option dc_full = 0 / 1 decides otherwise
-  const bool dc_full = sw.dc_full >= 0 ? sw.dc_full != 0 : h->pool->size() <= 6;
-  const int dc_top = VSM_DC_TOP;  // merge nodes up to this size follow on the GPU
-  bool dc_gpu = dc_env && !h->dc_gpu_broken;
-  h->seq_hip_error.store(0);
-  for (hipStream_t &st : h->dc_stream)
-    if (dc_gpu && !st) dc_gpu = hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess;  // (stream priorities make no measurable difference)
-  // -DVSM_DC_TIES_ON_GPU=1: Triangle's randomised vertex sort on the GPU too (k_dc_ties_of_keys, one wave per pair, started right
-  // behind the pass-2 compaction).  Exact, and it takes 150 us per pair off the host, but one wave needs 3.2 ms for a
-  // 7.4 k list (0.65 us per partition, all dependent scalar work) - longer than everything else of a chunk together, so
-  // the B stage ends up waiting for it: 13.4 ms per 200 frames against 9.0.  Off unless asked for.
-  const bool dc_ties = dc_gpu && VSM_DC_TIES_ON_GPU != 0;
-  if (dc_ties) {
-    bool ok = true;
-    for (hipStream_t &st : h->tie_stream)
-      if (ok && !st) ok = hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess;
-    if (ok && !h->tie_ev) ok = hipEventCreateWithFlags(&h->tie_ev, hipEventDisableTiming) == hipSuccess;
-    for (hipEvent_t &e : h->tie_copied)
-      if (ok && !e) ok = hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
-    h->tie_copied_set[0] = h->tie_copied_set[1] = false;
-    if (ok && (!h->hm_ties || h->ties_chunk < C)) {
-      if (h->hm_ties) (void)hipHostFree(h->hm_ties);
-      h->hm_ties = nullptr;
-      ok = hipHostMalloc((void **)&h->hm_ties, (size_t)vsm_handle::kDcBanks * C * VSM_DC_TIE_OUT_INTS * sizeof(int32_t), hipHostMallocMapped) == hipSuccess &&
-           hipHostGetDevicePointer((void **)&h->d_ties, h->hm_ties, 0) == hipSuccess;
-      h->ties_chunk = C;
-    }
-    if (!ok && h->hm_ties) {
-      (void)hipHostFree(h->hm_ties);
-      h->hm_ties = nullptr;
-    }
-  }
-  if (dc_gpu) {
-    for (int b = 0; b < vsm_handle::kDcBanks; b++)
-      if (!h->dc_bank[b]) h->dc_bank[b] = new DcBank();
-    if ((int)h->seq_work.size() < vsm_handle::kDcBanks * C) h->seq_work.resize((size_t)vsm_handle::kDcBanks * C);
-  }
-  std::vector<std::unique_ptr<DcChunk>> chunks;
-  struct Drain {  // whatever way this function is left, nothing of it may still be running
-    std::vector<std::unique_ptr<DcChunk>> &c;
-    ~Drain() {
-      for (auto &ch : c) dc_wait(ch.get());
-    }
-  } drain{chunks};
-  const int32_t dims_c[3] = {w, hh, c.dims.bpl};
-  int32_t nprev[2][2] = {{0, 0}, {0, 0}};  // feature counts [side][set] of the previous chunk's last frame
-  double tg = 0, thost = 0;
-  std::atomic<long long> mid_ns[2] = {};  // VSM_DEBUG_TIMING: pass-1 outlier removal, prior statistics (task time)
-  const double tstart = now_us();
-  // Chunk boundaries: chunks of C frames; a sequence of at least three chunks starts (and ends) with a half chunk - the
-  // host pool has nothing to do until the first chunk's lists exist, and nothing overlaps the last chunk's final stage
-  std::vector<int32_t> chunk_start;
-  {
-    const bool taper = true;
-    const int32_t half = C / 2;
-    int32_t f = 0;
-    if (taper && half >= 8 && n_frames >= 3 * C) {
-      chunk_start.push_back(0);
-      f = half;
-      while (n_frames - f > C + half) {
-        chunk_start.push_back(f);
-        f += C;
-      }
-      if (n_frames - f > C) {  // between C and 3C/2 frames left: a full chunk and a short one
-        chunk_start.push_back(f);
-        f = n_frames - std::min<int32_t>(half, n_frames - f - 1);
-      }
-      chunk_start.push_back(f);
-    } else {
-      for (; f < n_frames; f += C) chunk_start.push_back(f);
-    }
-    chunk_start.push_back(n_frames);
-  }
-  const int nchunks = (int)chunk_start.size() - 1;
-  auto launch_features_of = [&](int k) -> hipError_t {  // ingest + all feature kernels of chunk k, then the marker
-    const int32_t f0 = chunk_start[k];
-    const int n = chunk_start[k + 1] - f0;
-    const int first_img = 2 * (k % 3) * C;
-    const bool fused_front = p.half_resolution && h->sw.front;
-    if (on_device) {
-      if (fused_front)
-        vsm_launch_front(h->stream, h->prof, c.d_imgs, first_img, left + (size_t)f0 * frame_stride, right + (size_t)f0 * frame_stride,
-                         (size_t)frame_stride, bpl, n, c.dims, 0);
-      else
-        vsm_launch_ingest(h->stream, h->prof, c.d_imgs, first_img, left + (size_t)f0 * frame_stride,
-                          right + (size_t)f0 * frame_stride, (size_t)frame_stride, bpl, n, c.dims);
-    } else {
-      if (seq_ingest_host_frames(h, c, first_img, left, right, frame_stride, bpl, w, hh, f0, n) != VSM_OK) return hipErrorUnknown;
-    }
-    vsm_launch_features(h->stream, h->prof, c.d_imgs, first_img, 2 * n, c.dims, c.f1, c.f2, c.f_stride, p.nms_tau,
-                        p.multi_stage, p.half_resolution, p.match_binsize, c.h_imgs.data(), fused_front ? 1 : 0, (h->sw.fused_features ? 1 : 0) | (h->sw.feat_order ? 0 : 4));
-    return hipEventRecord(h->seq_ev[0], h->stream);
-  };
-  // what a chunk needs from one step to the next
-  struct SeqChunk {
-    int32_t f0 = 0;
-    int n = 0, bank = 0, first_img = 0, first_pair = 0;
-    int max_nq[2] = {0, 0};
-    std::shared_ptr<std::vector<char>> validp;
-    DcChunk *dc = nullptr;  // its final stage, if that is shared with the GPU
-    double t_pass2 = 0;
-  };
-  std::vector<SeqChunk> sc(nchunks);
-  // First step of chunk k: wait for its features, one job per frame, pass 1 (if there is one) and its export.
-  // Order on the stream: ... pass 2 of k-1, features of k+1, pass 1 of k+1, pass 2 of k, features of k+2 ...: while the
-  // pool computes chunk k's prior statistics the GPU has pass 2 of chunk k-1 and the features of chunk k+1 to do, and
-  // pass 1 of chunk k+1 is over before its prior statistics are wanted.
-  auto start_chunk = [&](int k, bool then_features) -> int {
-    SeqChunk &q = sc[k];
-    q.f0 = chunk_start[k];
-    q.n = chunk_start[k + 1] - q.f0;
-    q.bank = k & 1;
-    q.first_img = 2 * (k % 3) * C;
-    q.first_pair = q.bank * C;
-    const int32_t f0 = q.f0;
-    const int n = q.n, first_img = q.first_img, first_pair = q.first_pair;
-    const VsmPair *d_pairs = c.d_pairs + first_pair;
-    VsmJob *h_jobs = c.h_jobs + first_pair, *d_jobs = c.d_jobs + first_pair;
-    int *max_nq = q.max_nq;
-    const double tl0 = now_us();
-    HIPCHK(hipEventSynchronize(h->seq_ev[0]));  // the chunk's feature counts are in host-mapped memory
-    HIPCHK(hipGetLastError());
-    if (vsm_debug_timing()) fprintf(stderr, "  chunk %d: feature wait %.0f us\n", k, now_us() - tl0);
-    // ---- one job per frame of the chunk ----
-    max_nq[0] = max_nq[1] = 0;
-    q.validp = std::make_shared<std::vector<char>>(n, 0);
-    std::vector<char> &valid = *q.validp;
-    for (int i = 0; i < n; i++) {
-      const int32_t f = f0 + i;
-      VsmJob &jb = h_jobs[i];
-      memset(&jb, 0, sizeof(jb));
-      const int img_c = first_img + 2 * i;
-      int img_p;
-      int32_t cnt[4][2];
-      for (int s = 0; s < 2; s++) {
-        cnt[2][s] = c.hm_counts[img_c * 2 + s];
-        cnt[3][s] = c.hm_counts[(img_c + 1) * 2 + s];
-      }
-      if (method == 1) {
-        img_p = img_c;
-        for (int s = 0; s < 2; s++) cnt[0][s] = cnt[1][s] = 0;
-      } else if (i > 0) {
-        img_p = img_c - 2;
-        for (int s = 0; s < 2; s++) {
-          cnt[0][s] = c.hm_counts[img_p * 2 + s];
-          cnt[1][s] = c.hm_counts[(img_p + 1) * 2 + s];
-        }
-      } else {  // the previous frame is the last one of the previous chunk's bank
-        img_p = 2 * ((k + 2) % 3) * C + 2 * ((k > 0 ? chunk_start[k] - chunk_start[k - 1] : 1) - 1);
-        for (int s = 0; s < 2; s++) {
-          cnt[0][s] = f > 0 ? nprev[0][s] : 0;
-          cnt[1][s] = f > 0 ? nprev[1][s] : 0;
-        }
-      }
-      jb.img_prev = img_p;
-      jb.img_curr = img_c;
-      if (match_ready(p, method, cnt)) {
-        valid[i] = 1;
-        const int qimg = method == 2 ? 0 : 2;
-        jb.nq[0] = p.multi_stage ? cnt[qimg][0] : 0;
-        jb.nq[1] = cnt[qimg][1];
-        if (Tr && (!Tr_valid || Tr_valid[f])) {
-          jb.use_tr = 1;
-          memcpy(jb.t, Tr + (size_t)f * 12, 12 * sizeof(double));
-        }
-      }
-      h->seq_src[f] = valid[i] ? f : (f > 0 ? h->seq_src[f - 1] : -1);
-      max_nq[0] = std::max(max_nq[0], jb.nq[0]);
-      max_nq[1] = std::max(max_nq[1], jb.nq[1]);
-    }
-    for (int s = 0; s < 2; s++) {  // remember the last frame's counts for the next chunk
-      nprev[0][s] = c.hm_counts[(first_img + 2 * (n - 1)) * 2 + s];
-      nprev[1][s] = c.hm_counts[(first_img + 2 * (n - 1) + 1) * 2 + s];
-    }
-    HIPCHK(vsm_upload(h->stream, d_jobs, h_jobs, sizeof(VsmJob) * n));
-    if (p.multi_stage) {
-      VsmMatchCfg cfg = make_cfg(p, method, h->sw.match_heads && c.has_heads);
-      VsmJob dummy;
-      memset(&dummy, 0, sizeof(dummy));
-      cfg.sparse = 1;
-      cfg.use_prior = 0;
-      vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, n, c.dims, cfg, max_nq[0]);
-      vsm_launch_export(h->stream, h->prof, d_pairs, n, 0, max_nq[0]);
-      HIPCHK(hipEventRecord(h->seq_ev[1], h->stream));
-    }
-    if (then_features && k + 1 < nchunks) HIPCHK(launch_features_of(k + 1));
-    return VSM_OK;
-  };
-  // Last step of chunk j: its pass 2 is over, the final stage goes to the pool (and from there to the GPU and back)
-  VsmCtx *cp = &c;
-  auto finalize = [&](int j) -> int {
-    const SeqChunk &q = sc[j];
-    const double t0 = now_us();
-    HIPCHK(hipEventSynchronize(h->idle_wait));
-    HIPCHK(hipGetLastError());
-    // (kernel timing: the spans are read once, after the last chunk - the event pool grows over the sequence instead of
-    // the pipeline being drained per chunk, so the profiled pass overlaps its kernels like any other)
-    // (kernel timing is resolved at the end of the run, when the Delaunay streams have drained too)
-    if (vsm_debug_timing()) fprintf(stderr, "  chunk %d: pass2 launched %.0f us ago, waited %.0f us for it\n", j, t0 - q.t_pass2, now_us() - t0);
-    tg += now_us() - t0;
-    if (q.dc) {
-      dc_submit_a(q.dc);
-    } else {
-      const vsm_params pcopy = p;
-      const std::shared_ptr<std::vector<char>> validp = q.validp;
-      const int32_t f0 = q.f0;
-      const int first_pair = q.first_pair;
-      ticket_chunk.push_back(j);
-      tickets.push_back(h->pool->submit(q.n, [h, cp, pcopy, validp, f0, first_pair, method](int i) {
-        if (!(*validp)[i]) return;
-        static thread_local VsmHostWork tw;
-        const int pj = first_pair + i;
-        std::vector<vsm_p_match> &out = h->seq_matches[f0 + i];
-        // one wide copy out of the host-mapped export, then cache-resident work
-        tw.tmp_list.assign(cp->hm_list2[pj], cp->hm_list2[pj] + cp->hm_lcount[2 * pj + 1]);
-        vsm_host_remove_outliers_from(tw, pcopy, tw.tmp_list.data(), (int32_t)tw.tmp_list.size(), method, out);
-      }));
-    }
-    return VSM_OK;
-  };
-  HIPCHK(launch_features_of(0));
-  {
-    const int rc = start_chunk(0, true);
-    if (rc != VSM_OK) return rc;
-  }
-  for (int32_t k = 0; k < nchunks; k++) {
-    const SeqChunk &q = sc[k];
-    const int32_t f0 = q.f0;
-    const int n = q.n, bank = q.bank, first_pair = q.first_pair;
-    const VsmPair *d_pairs = c.d_pairs + first_pair;
-    const VsmJob *d_jobs = c.d_jobs + first_pair;
-    const int *max_nq = q.max_nq;
-    const std::shared_ptr<std::vector<char>> validp = q.validp;
-    const std::vector<char> &valid = *validp;
-    VsmMatchCfg cfg = make_cfg(p, method, h->sw.match_heads && c.has_heads);
-    VsmJob dummy;
-    memset(&dummy, 0, sizeof(dummy));
-    double ta = now_us();
-    if (p.multi_stage) {
-      const double tl1 = now_us();
-      HIPCHK(hipEventSynchronize(h->seq_ev[1]));
-      double tb = now_us();
-      if (vsm_debug_timing()) fprintf(stderr, "  chunk %d: pass1 sync %.0f us\n", k, tb - tl1);
-      tg += tb - ta;
-      h->pool->run(n, [&](int i) {  // queued behind the previous chunk's final stage (FIFO)
-        static thread_local VsmHostWork tw;
-        static thread_local std::vector<float> rg;
-        static thread_local std::vector<vsm_p_match> m1;
-        const int pj = first_pair + i;
-        const double t0 = now_us();
-        m1.clear();
-        if (valid[i]) m1.assign(c.hm_list1[pj], c.hm_list1[pj] + c.hm_lcount[2 * pj]);
-        vsm_host_remove_outliers(tw, p, m1, method);
-        const double t1 = now_us();
-        vsm_host_prior_statistics(p, dims_c, m1, method, rg);
-        ranges_to_device_layout(c.h_ranges + (size_t)pj * c.ranges_stride, rg.data(), rg.size());
-        mid_ns[0].fetch_add((long long)((t1 - t0) * 1e3), std::memory_order_relaxed);
-        mid_ns[1].fetch_add((long long)((now_us() - t1) * 1e3), std::memory_order_relaxed);
-      });
-      ta = now_us();
-      thost += ta - tb;
-      HIPCHK(vsm_upload(h->stream, c.d_ranges + (size_t)first_pair * c.ranges_stride, c.h_ranges + (size_t)first_pair * c.ranges_stride,
-                        c.ranges_stride * 4 * n));
-    }
-    if (k > 0) {  // pass 2 of the previous chunk ran meanwhile
-      const int rc = finalize(k - 1);
-      if (rc != VSM_OK) return rc;
-    }
-    if (k + 1 < nchunks) {  // pass 1 of the next chunk goes in front of this chunk's pass 2
-      const int rc = start_chunk(k + 1, false);
-      if (rc != VSM_OK) return rc;
-    }
-    ta = now_us();
-    // the export below overwrites this pair bank's host lists: chunk k-2 must be done with them
-    const double tw0 = now_us();
-    for (auto &ch : chunks)  // (they copied the lists out first thing)
-      if (ch->chunk <= k - 2 && !ch->a_waited) {
-        h->pool->wait(ch->a);
-        ch->a_waited = true;
-      }
-    for (size_t q = 0; q < tickets.size(); q++)
-      if (ticket_chunk[q] <= k - 2 && tickets[q]) {
-        h->pool->wait(tickets[q]);
-        tickets[q].reset();
-      }
-    if (vsm_debug_timing() && now_us() - tw0 > 2000) fprintf(stderr, "  chunk %d: waited %.0f us for chunk %d's final stage\n", k, now_us() - tw0, k - 2);
-    // the chunk's final stage is set up here already: the GPU's emulated vertex sorts start right behind the compaction
-    // The GPU share pays when the pool has other pairs to work on while the GPU has this chunk's (its part is
-    // latency-bound): a chunk with fewer pairs than pool threads stays on the host, unless VSM_DC_GPU=1 insists
-    bool use_dc = dc_gpu && (dc_forced || n >= h->pool->size());
-    const int dc_q = (int)chunks.size(), dc_b = dc_q % vsm_handle::kDcBanks;
-    if (use_dc) {
-      if (dc_q >= vsm_handle::kDcBanks) dc_wait(chunks[dc_q - vsm_handle::kDcBanks].get());  // its slabs are reused now
-      // slab sizes from this chunk's longest possible list (every pair's list is at most max_nq[1] long)
-      const int pts = ((max_nq[1] + 63) / 64) * 64 + 64, tsk = 2 * pts / std::max(dc_leaf, 2) + 16;
-      if (!h->dc_bank[dc_b]->reserve(C, pts, tsk)) {
-        fprintf(stderr, "visomatch: no memory for the GPU share of the Delaunay stage, staying on the host\n");
-        dc_gpu = use_dc = false;
-      }
-    }
-    if (use_dc) {
-      chunks.emplace_back(new DcChunk());
-      DcChunk *ch = chunks.back().get();
-      ch->h = h;
-      ch->ctx = cp;
-      ch->p = p;
-      ch->method = method;
-      ch->leaf = dc_leaf;
-      ch->top = dc_top;
-      ch->device_kd = dc_kd;
-      ch->block = dc_block;
-      ch->full = dc_full;
-      ch->chunk = k;
-      ch->bank = dc_b;
-      ch->n = n;
-      ch->f0 = f0;
-      ch->first_pair = first_pair;
-      ch->work0 = ch->bank * C;
-      ch->B = h->dc_bank[dc_b];
-      ch->work = h->seq_work.data() + ch->work0;
-      ch->stream = h->dc_stream[dc_b & 1];
-      ch->valid = validp;
-      ch->ties_gpu = dc_ties && ch->block && !ch->full && h->hm_ties != nullptr;
-      ch->ties = h->hm_ties + (size_t)dc_b * h->ties_chunk * VSM_DC_TIE_OUT_INTS;
-      sc[k].dc = ch;
-    }
-    // (this pair bank's pass-2 lists are about to be rewritten: the copy of chunk k-2's keys out of them comes first)
-    if (h->tie_copied_set[bank]) HIPCHK(hipStreamWaitEvent(h->stream, h->tie_copied[bank], 0));
-    cfg.sparse = 0;
-    cfg.use_prior = p.multi_stage ? 1 : 0;
-    vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, n, c.dims, cfg, max_nq[1]);
-    if (use_dc && chunks.back()->ties_gpu) {
-      DcChunk *ch = chunks.back().get();
-      hipStream_t ts = h->tie_stream[dc_b & 1];
-      ch->ties_done.store(0, std::memory_order_relaxed);
-      DcBank &B = *h->dc_bank[dc_b];
-      bool ok = hipEventRecord(h->tie_ev, h->stream) == hipSuccess && hipStreamWaitEvent(ts, h->tie_ev, 0) == hipSuccess;
-      if (ok) {
-        vsm_dc_launch_tie_keys(ts, d_pairs, n, max_nq[1], B.d_tie_keys, B.stride_pts, B.d_tie_n);
-        ok = hipEventRecord(h->tie_copied[bank], ts) == hipSuccess;
-        h->tie_copied_set[bank] = ok;
-      }
-      if (ok) {
-        vsm_dc_launch_ties_of_keys(ts, n, B.d_tie_keys, B.stride_pts, B.d_tie_n, h->d_ties + (size_t)dc_b * h->ties_chunk * VSM_DC_TIE_OUT_INTS,
-                                   VSM_DC_TIE_OUT_INTS);
-        ok = hipLaunchHostFunc(ts, [](void *arg) { ((DcChunk *)arg)->ties_done.store(1, std::memory_order_release); }, ch) == hipSuccess;
-      }
-      if (!ok) {  // the host does it then (in A, as without this)
-        (void)hipStreamSynchronize(ts);
-        ch->ties_gpu = false;
-        ch->ties_done.store(1, std::memory_order_relaxed);
-      }
-    }
-    if (p.refinement > 0)
-      vsm_launch_refine(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, n, c.dims, c.dims, method, p.refinement,
-                        max_nq[1]);
-    vsm_launch_export(h->stream, h->prof, d_pairs, n, 1, max_nq[1]);
-    sc[k].t_pass2 = now_us();
-    HIPCHK(hipEventRecord(h->idle_wait, h->stream));
-    if (k + 2 < nchunks) HIPCHK(launch_features_of(k + 2));
-    tg += now_us() - ta;
-  }
-  if (nchunks > 0) {
-    const int rc = finalize(nchunks - 1);
-    if (rc != VSM_OK) return rc;
-  }
-  {
-    const double tb = now_us();
-    for (auto &ch : chunks) dc_wait(ch.get());
-    if (vsm_debug_timing())
-      for (auto &ch : chunks)
-        fprintf(stderr, "  final stage of %d pairs: A %.0f..%.0f us (tasks %.0f us), G ..%.0f, B %.0f..%.0f (tasks %.0f us)\n", ch->n,
-                ch->t_a0 - tstart, ch->t_g0 - tstart, ch->a_ns.load() * 1e-3, ch->t_g1 - tstart, ch->t_b0 - tstart, ch->t_b1 - tstart,
-                ch->b_ns.load() * 1e-3);
-    if (vsm_debug_timing() && !chunks.empty()) {
-      double part[8] = {0};
-      for (auto &ch : chunks)
-        for (int q = 0; q < 8; q++) part[q] += ch->part_ns[q].load() * 1e-3 / n_frames;
-      fprintf(stderr, "  per pair, us: pass-1 outliers %.0f prior statistics %.0f | A copy %.0f arrays %.0f prepare %.0f | B records %.0f merges %.0f support+survivors %.0f; pairs with duplicate points: %.0f\n",
-              mid_ns[0].load() * 1e-3 / n_frames, mid_ns[1].load() * 1e-3 / n_frames, part[0], part[1], part[2], part[4], part[5], part[6], part[7] * n_frames * 1e3);
-    }
-    for (auto &t : tickets)
-      if (t) h->pool->wait(t);
-    thost += now_us() - tb;
-    if (h->prof.on) {
-      HIPCHK(hipStreamSynchronize(h->stream));
-      for (hipStream_t st : h->dc_stream)
-        if (st) HIPCHK(hipStreamSynchronize(st));
-      h->prof.resolve();
-    }
-  }
-  h->seq_timings[0] = tg;
-  h->seq_timings[1] = thost;
-  h->seq_timings[2] = now_us() - tstart;
-  h->seq_timings[3] = (double)C;
-  if (vsm_debug_timing())
-    fprintf(stderr, "seq: entry->start %.0f us, gpu %.0f, host %.0f, total %.0f\n", tstart - t_entry, tg, thost,
-            h->seq_timings[2]);
-  // (a Delaunay stream that failed: the lists are complete - the host finished those chunks - but the caller must know)
-  return h->seq_hip_error.load() ? VSM_EHIP : VSM_OK;
+  return sequence_run_v1(h, left, right, frame_stride, on_device, n_frames, w, hh, bpl, method, Tr, Tr_valid);
 }
 
 // the frame whose list stands after `frame` (vsm_handle::seq_src), -1: no list yet

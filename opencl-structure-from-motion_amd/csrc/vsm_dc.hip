@@ -898,32 +898,6 @@ __global__ void __launch_bounds__(64) k_dc_ties(const VsmDcJob *__restrict__ job
   tie_sort<VSM_DC_TIE_POINTS>(TieFromKeys{jb.tie_keys}, jb.n_in, jb.tie_out, tiny);
 }
 
-// The same for the pairs of a look-ahead chunk, as soon as their compacted pass-2 lists exist (refinement does
-// not move u1c, v1c).  Two kernels: the keys are copied out of the pair buffers first (those are overwritten two
-// chunks later, the caller orders that behind this copy), then one wave per pair sorts its private copy.
-__global__ void __launch_bounds__(256) k_dc_tie_keys(const VsmPair *__restrict__ pairs, int npairs, uint64_t *__restrict__ keys, int stride,
-                                                     int32_t *__restrict__ counts) {
-  const VsmPair pr = pairs[blockIdx.y];
-  const int n = pr.count[1];
-  if (blockIdx.x == 0 && threadIdx.x == 0) counts[blockIdx.y] = n;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n && i < stride) {
-    const vsm_p_match a = pr.list2[i];
-    keys[(size_t)blockIdx.y * stride + i] = ((uint64_t)(uint32_t)(int32_t)a.u1c << 34) | ((uint64_t)(uint32_t)(int32_t)a.v1c << 20) | (uint32_t)i;
-  }
-}
-
-__global__ void __launch_bounds__(64) k_dc_ties_of_keys(const uint64_t *__restrict__ keys, int stride, const int32_t *__restrict__ counts,
-                                                        int32_t *__restrict__ tie_out, int out_stride, const uint32_t *__restrict__ tiny) {
-  int32_t *out = tie_out + (size_t)blockIdx.x * out_stride;
-  const int n = counts[blockIdx.x];
-  if (n < 2 || n > stride) {
-    if (threadIdx.x == 0) out[0] = n < 2 ? 0 : -1;
-    return;
-  }
-  tie_sort<VSM_DC_TIE_POINTS>(TieFromKeys{keys + (size_t)blockIdx.x * stride}, n, out, tiny);
-}
-
 // The support test of removeOutliers (viso/matcher.cpp:1266-1364; vsm_host_outliers_end is the host form):
 // every triangle gives each of its three edges a vote for both end points if the two matches agree in flow
 // and / or disparity.  Differences, absolute values, one sum and a compare in float: the same values on
@@ -968,16 +942,6 @@ void vsm_dc_launch_support(hipStream_t s, const VsmDcJob *d_jobs, int njobs, int
 void vsm_dc_launch_ties(hipStream_t s, const VsmDcJob *d_jobs, int njobs) {
   if (njobs <= 0) return;
   hipLaunchKernelGGL(k_dc_ties, dim3(njobs), dim3(64), 0, s, d_jobs, njobs, dc2_tiny_table());
-}
-
-void vsm_dc_launch_tie_keys(hipStream_t s, const VsmPair *d_pairs, int npairs, int max_list, uint64_t *keys, int stride, int32_t *counts) {
-  if (npairs <= 0) return;
-  hipLaunchKernelGGL(k_dc_tie_keys, dim3((std::max(max_list, 1) + 255) / 256, npairs), dim3(256), 0, s, d_pairs, npairs, keys, stride, counts);
-}
-void vsm_dc_launch_ties_of_keys(hipStream_t s, int npairs, const uint64_t *keys, int stride, const int32_t *counts, int32_t *tie_out,
-                                int out_stride) {
-  if (npairs <= 0) return;
-  hipLaunchKernelGGL(k_dc_ties_of_keys, dim3(npairs), dim3(64), 0, s, keys, stride, counts, tie_out, out_stride, dc2_tiny_table());
 }
 
 // =======================================================================================

@@ -61,12 +61,6 @@ void vsm_dc_launch_support(hipStream_t s, const VsmDcJob *d_jobs, int njobs, int
                            float disp_tol);
 // one wave per job: the emulated vertex sort of the jobs that bring tie_keys
 void vsm_dc_launch_ties(hipStream_t s, const VsmDcJob *d_jobs, int njobs);
-// ... for the pairs of a chunk: the keys of their compacted pass-2 lists into keys[pair * stride ..] (lengths into
-// counts), then one wave per pair on that copy; tie_out (device-visible) + pair * out_stride gets the verdict
-struct VsmPair;
-void vsm_dc_launch_tie_keys(hipStream_t s, const VsmPair *d_pairs, int npairs, int max_list, uint64_t *keys, int stride, int32_t *counts);
-void vsm_dc_launch_ties_of_keys(hipStream_t s, int npairs, const uint64_t *keys, int stride, const int32_t *counts, int32_t *tie_out,
-                                int out_stride);
 #define VSM_DC_TIE_OUT_INTS 512
 // one thread per merge node of level `level`; max_nodes >= every job's node count on that level
 void vsm_dc_launch_merge_level(hipStream_t s, const VsmDcJob *d_jobs, int njobs, int level, int max_nodes);

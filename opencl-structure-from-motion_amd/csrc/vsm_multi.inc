@@ -135,19 +135,14 @@ int vsm_multi_process(vsm_multi *m, const uint8_t *left, const uint8_t *right, i
   } while (0)
   const double t0 = now_us();
   const int bank = (int)(m->step & 1), first_img = 2 * bank * K, prev_img = 2 * (bank ^ 1) * K;
-  const bool fused_front = p.half_resolution && h->sw.front;
   // ---- pushBack of K frames: one launch per kernel over 2 K images ----
   if (on_device) {
-    if (fused_front)
-      vsm_launch_front(h->stream, h->prof, c.d_imgs, first_img, left, right, (size_t)seq_stride, bpl, K, c.dims, 0);
-    else
-      vsm_launch_ingest(h->stream, h->prof, c.d_imgs, first_img, left, right, (size_t)seq_stride, bpl, K, c.dims);
+    enqueue_front_frames(h, c, first_img, 2, left, (size_t)seq_stride, right, (size_t)seq_stride, bpl, K);
   } else {
     const int rc = seq_ingest_host_frames(h, c, first_img, left, right, seq_stride, bpl, w, hh, 0, K);
     if (rc != VSM_OK) return fail(rc);
   }
-  vsm_launch_features(h->stream, h->prof, c.d_imgs, first_img, 2 * K, c.dims, c.f1, c.f2, c.f_stride, p.nms_tau, p.multi_stage, p.half_resolution,
-                      p.match_binsize, c.h_imgs.data(), fused_front ? 1 : 0, (h->sw.fused_features ? 1 : 0) | (h->sw.feat_order ? 0 : 4));
+  enqueue_features(h, c, first_img, 2 * K);
   MULTI_CHK(hipEventRecord(m->ev_feat, h->stream));
   MULTI_CHK(hipEventSynchronize(m->ev_feat));  // the feature counts are in host-mapped memory
   MULTI_CHK(hipGetLastError());
@@ -219,17 +214,7 @@ int vsm_multi_process(vsm_multi *m, const uint8_t *left, const uint8_t *right, i
       MULTI_CHK(hipEventSynchronize(m->ev_a));  // the lists are in host-mapped memory
       MULTI_CHK(hipGetLastError());
       const int32_t dims_c[3] = {w, hh, c.dims.bpl};
-      h->pool->run(K, [&](int i) {
-        static thread_local VsmHostWork tw;
-        static thread_local std::vector<float> rg;
-        static thread_local std::vector<vsm_p_match> m1;
-        m1.clear();
-        if (valid[i]) m1.assign(c.hm_list1[i], c.hm_list1[i] + std::max(c.hm_lcount[2 * i], 0));
-        vsm_host_remove_outliers(tw, p, m1, method);
-        vsm_host_prior_statistics(p, dims_c, m1, method, rg);
-        ranges_to_device_layout(c.h_ranges + (size_t)i * c.ranges_stride, rg.data(), rg.size());
-      });
-      MULTI_CHK(vsm_upload(h->stream, c.d_ranges, c.h_ranges, c.ranges_stride * 4 * K));
+      MULTI_CHK(host_pass1_boxes(h, c, 0, K, valid.data(), method, dims_c));
     } else if (p.multi_stage) {
       // ---- pass 1 and its chain: removeOutliers + computePriorStatistics on the device (viso/matcher.cpp:222-226) ----
       cfg.sparse = 1;

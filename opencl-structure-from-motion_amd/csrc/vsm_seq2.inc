@@ -1006,30 +1006,13 @@ struct Seq2Call {
     }
     return VSM_OK;
   }
-  // the front kernels number their images first + 2 * frame + side: consecutive mono frames go through as (even, odd) pairs
-  void front(int first, const uint8_t *s0, const uint8_t *s1, size_t stride, int pitch, int frames) {
-    if (frames <= 0) return;
-    if (p.half_resolution && sw.front)
-      vsm_launch_front(h->stream, h->prof, c.d_imgs, first, s0, s1, stride, pitch, frames, c.dims, 0);
-    else
-      vsm_launch_ingest(h->stream, h->prof, c.d_imgs, first, s0, s1, stride, pitch, frames, c.dims);
-  }
-  // n frames from s0, a frame every `step` bytes (pitch: bytes per source row); stereo: their right images from s1, every `stride2` bytes
-  void front_frames(int first_img, const uint8_t *s0, size_t step, const uint8_t *s1, size_t stride2, int pitch, int n) {
-    if (right) {
-      front(first_img, s0, s1, stride2, pitch, n);
-    } else {
-      front(first_img, s0, s0 + step, 2 * step, pitch, n / 2);
-      if (n & 1) front(first_img + n - 1, s0 + step * (size_t)(n - 1), nullptr, step, pitch, 1);
-    }
-  }
   hipError_t launch_features_of(int k) {
     const int32_t f0 = chunk_start[k];
     const int n = chunk_start[k + 1] - f0;
     const int first_img = sides * (k % kFrameBanks) * C;
-    const bool fused_front = p.half_resolution && sw.front;
     if (on_device) {
-      front_frames(first_img, left + (size_t)f0 * frame_stride, (size_t)frame_stride, right ? right + (size_t)f0 * frame_stride : nullptr, (size_t)frame_stride, bpl, n);
+      enqueue_front_frames(h, c, first_img, sides, left + (size_t)f0 * frame_stride, (size_t)frame_stride, right ? right + (size_t)f0 * frame_stride : nullptr,
+                           (size_t)frame_stride, bpl, n);
     } else {
       for (auto &pc : S.up_pieces) {  // the chunk's pieces: their copies are (being) enqueued by the pool
         if (pc->f0 < f0 || pc->f0 >= f0 + n) continue;
@@ -1042,12 +1025,12 @@ struct Seq2Call {
       }
       // (the pieces arrive row-tight; page-locked input is planar - left images, then right images -, gathered input frame by frame)
       if (host_pinned)
-        front_frames(first_img, S.up_d + (size_t)f0 * img_bytes, img_bytes, S.up_d + ((size_t)n_frames + f0) * img_bytes, img_bytes, w, n);
+        enqueue_front_frames(h, c, first_img, sides, S.up_d + (size_t)f0 * img_bytes, img_bytes, S.up_d + ((size_t)n_frames + f0) * img_bytes, img_bytes, w, n);
       else
-        front_frames(first_img, S.up_d + (size_t)sides * f0 * img_bytes, img_bytes, S.up_d + ((size_t)sides * f0 + 1) * img_bytes, 2 * img_bytes, w, n);
+        enqueue_front_frames(h, c, first_img, sides, S.up_d + (size_t)sides * f0 * img_bytes, img_bytes, S.up_d + ((size_t)sides * f0 + 1) * img_bytes, 2 * img_bytes,
+                             w, n);
     }
-    vsm_launch_features(h->stream, h->prof, c.d_imgs, first_img, sides * n, c.dims, c.f1, c.f2, c.f_stride, p.nms_tau, p.multi_stage,
-                        p.half_resolution, p.match_binsize, c.h_imgs.data(), fused_front ? 1 : 0, (h->sw.fused_features ? 1 : 0) | (h->sw.feat_order ? 0 : 4));
+    enqueue_features(h, c, first_img, sides * n);
     return hipEventRecord(h->seq_ev[0], h->stream);
   }
   // jobs of chunk k from its feature counts, pass 1 and the pass-1 chain
@@ -1071,54 +1054,8 @@ struct Seq2Call {
     HIPCHK(hipGetLastError());
     tg += now_us() - t0;
     dbg_counts.push_back(now_us());
-    q.max_nq[0] = q.max_nq[1] = 0;
-    for (int i = 0; i < n; i++) {
-      const int32_t f = q.f0 + i;
-      VsmJob &jb = h_jobs[i];
-      memset(&jb, 0, sizeof(jb));
-      const int img_c = first_img + sides * i;
-      int img_p;
-      int32_t cnt[4][2];
-      for (int s = 0; s < 2; s++) {
-        cnt[2][s] = c.hm_counts[img_c * 2 + s];
-        cnt[3][s] = right ? c.hm_counts[(img_c + 1) * 2 + s] : 0;
-      }
-      if (method == 1) {
-        img_p = img_c;
-        for (int s = 0; s < 2; s++) cnt[0][s] = cnt[1][s] = 0;
-      } else if (i > 0) {
-        img_p = img_c - sides;
-        for (int s = 0; s < 2; s++) {
-          cnt[0][s] = c.hm_counts[img_p * 2 + s];
-          cnt[1][s] = right ? c.hm_counts[(img_p + 1) * 2 + s] : 0;
-        }
-      } else {  // the previous frame is the last one of the previous chunk's bank
-        img_p = sides * ((k + kFrameBanks - 1) % kFrameBanks) * C + sides * ((k > 0 ? chunk_start[k] - chunk_start[k - 1] : 1) - 1);
-        for (int s = 0; s < 2; s++) {
-          cnt[0][s] = f > 0 ? nprev[0][s] : 0;
-          cnt[1][s] = f > 0 ? nprev[1][s] : 0;
-        }
-      }
-      jb.img_prev = img_p;
-      jb.img_curr = img_c;
-      const bool valid = match_ready(p, method, cnt);
-      if (valid) {
-        const int qimg = method == 2 ? 0 : 2;
-        jb.nq[0] = p.multi_stage ? cnt[qimg][0] : 0;
-        jb.nq[1] = cnt[qimg][1];
-        if (Tr && (!Tr_valid || Tr_valid[f])) {
-          jb.use_tr = 1;
-          memcpy(jb.t, Tr + (size_t)f * 12, 12 * sizeof(double));
-        }
-      }
-      h->seq_src[f] = valid ? f : (f > 0 ? h->seq_src[f - 1] : -1);
-      q.max_nq[0] = std::max(q.max_nq[0], jb.nq[0]);
-      q.max_nq[1] = std::max(q.max_nq[1], jb.nq[1]);
-    }
-    for (int s = 0; s < 2; s++) {
-      nprev[0][s] = c.hm_counts[(first_img + sides * (n - 1)) * 2 + s];
-      nprev[1][s] = right ? c.hm_counts[(first_img + sides * (n - 1) + 1) * 2 + s] : 0;
-    }
+    seq_chunk_jobs(p, method, sides, q.f0, n, first_img, seq_slot_before(chunk_start, k, sides, kFrameBanks, C), c.hm_counts, nprev, Tr, Tr_valid, h_jobs,
+                   nullptr, q.max_nq, h->seq_src.data());
     if (q.max_nq[0] > VSM_DC_TIE_POINTS || q.max_nq[1] > VSM_DC_KD_MAX_POINTS || (p.refinement == 2 && q.max_nq[1] > VSM_PARA_MAX_LIST) ||
         vsm_dc2_depth(std::max(q.max_nq[0], q.max_nq[1])) > VSM_DC2_MAX_DEPTH) {
       return VSM_SEQ2_DECLINED;  // (a pass-1 list longer than the device's vertex sort takes: the first form does this run)

@@ -34,7 +34,7 @@ EXPORTS = ["vsm_default_params", "vsm_create", "vsm_destroy", "vsm_set_intrinsic
            "vsm_num_features", "vsm_get_features", "vsm_set_stage_capture", "vsm_stage_size", "vsm_stage_get",
            "vsm_num_ranges", "vsm_get_ranges", "vsm_get_gradients", "vsm_get_filter_responses", "vsm_get_counters",
            "vsm_get_timings", "vsm_set_profiling", "vsm_num_kernels", "vsm_kernel_name", "vsm_get_kernel_stats",
-           "vsm_host_delaunay", "vsm_host_delaunay_split", "vsm_debug_delaunay_gpu", "vsm_debug_dc_bench", "vsm_host_ties", "vsm_debug_ties_gpu", "vsm_host_outliers_and_prior", "vsm_host_outliers_and_prior_threads", "vsm_debug_dc2", "vsm_debug_dc2_band_factor", "vsm_debug_predicates", "vsm_debug_seq_plan", "vsm_local_cpus", "vsm_forkjoin_cpus", "vsm_device_pool_stats", "vsm_device_pool_trim", "vsm_sequence_run", "vsm_sequence_num_matches", "vsm_sequence_get_matches",
+           "vsm_host_delaunay", "vsm_host_delaunay_split", "vsm_debug_delaunay_gpu", "vsm_debug_dc_bench", "vsm_host_ties", "vsm_debug_ties_gpu", "vsm_host_outliers_and_prior", "vsm_host_outliers_and_prior_threads", "vsm_debug_dc2", "vsm_debug_dc2_band_factor", "vsm_debug_predicates", "vsm_debug_seq_plan", "vsm_debug_chunk_jobs", "vsm_local_cpus", "vsm_forkjoin_cpus", "vsm_device_pool_stats", "vsm_device_pool_trim", "vsm_sequence_run", "vsm_sequence_num_matches", "vsm_sequence_get_matches",
            "vsm_sequence_get_timings", "vsm_sequence_path", "vsm_set_option", "vsm_version", "vsm_host_register", "vsm_host_unregister",
            "vsm_multi_create", "vsm_multi_destroy", "vsm_multi_process", "vsm_multi_num_sequences", "vsm_multi_get_motion",
            "vsm_multi_motion_valid", "vsm_multi_num_matches", "vsm_multi_get_matches", "vsm_multi_num_inliers", "vsm_multi_get_inliers",
@@ -158,6 +158,8 @@ def lib():
         L.vsm_debug_dc2_band_factor.argtypes = [i32]
         L.vsm_debug_predicates.argtypes = [vp, i32, vp]
         L.vsm_debug_seq_plan.argtypes = [i32, i32, i32, i32, i32, C.c_char_p, vp, vp, i32]
+        L.vsm_debug_chunk_jobs.restype = i32
+        L.vsm_debug_chunk_jobs.argtypes = [i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp]
         L.vsm_local_cpus.argtypes = [vp, i32]
         L.vsm_forkjoin_cpus.argtypes = [vp, i32]
         L.vsm_debug_dc2_band_factor.restype = None
@@ -385,6 +387,26 @@ def seq_plan(n_frames, pool_threads, host_in=False, seq_chunk=0, seq_first_chunk
     if n < 0:
         raise VisoMatchError("vsm_debug_seq_plan: bad arguments")
     return chunk.value, starts[:n + 1].tolist()
+
+
+def chunk_jobs(method, multi_stage, sides, banks, chunk, starts, counts, tr_valid=None):
+    """test hook (no GPU): the job tables of a look-ahead call's chunks - starts: [first frame of each chunk ..., n_frames];
+    counts[frame][side][set]: the feature counts; tr_valid: a flag per frame or None.  Returns (int32 [frames][7]: img_prev,
+    img_curr, nq[0], nq[1], use_tr, valid, seq_src; int32 [chunks][2]: max_nq)"""
+    starts = np.ascontiguousarray(starts, dtype=np.int32)
+    n_chunks, n_frames = len(starts) - 1, int(starts[-1])
+    counts = np.ascontiguousarray(counts, dtype=np.int32)
+    assert counts.shape == (n_frames, 2, 2)
+    tv = None if tr_valid is None else np.ascontiguousarray(tr_valid, dtype=np.uint8)
+    assert tv is None or tv.shape == (n_frames,)
+    frames = np.zeros((n_frames, 7), dtype=np.int32)
+    max_nq = np.zeros((n_chunks, 2), dtype=np.int32)
+    rc = lib().vsm_debug_chunk_jobs(method, int(bool(multi_stage)), sides, banks, chunk, starts.ctypes.data_as(C.c_void_p), n_chunks,
+                                    counts.ctypes.data_as(C.c_void_p), None if tv is None else tv.ctypes.data_as(C.c_void_p),
+                                    frames.ctypes.data_as(C.c_void_p), max_nq.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise VisoMatchError("vsm_debug_chunk_jobs: bad arguments")
+    return frames, max_nq
 
 
 def remove_outliers(matches, method, w, h, gpu=False, gpu_ties=False, copies=1, threads=1, **params):
