@@ -1486,7 +1486,7 @@ int32_t vsm_get_gradients(vsm_handle *h, int32_t which, int32_t full, uint8_t *d
   if (full && !h->param.half_resolution) return 0;
   const VsmImage &im = c.h_imgs[slot * 2 + side];
   const int32_t bytes = full ? c.dims.bpl * c.dims.h : c.dims.mbpl * c.dims.mh;
-  if (full) {  // the tiled plane (8 x 8 tiles; a tile row = du 0-3, dv 0-3, du 4-7, dv 4-7: vsm_tiled_at in vsm_kernels.hip), un-tiled here
+  if (full) {  // the tiled plane (8 x 8 tiles; a tile row = du 0-3, dv 0-3, du 4-7, dv 4-7: vsm_tiled_at in vsm_dev.h), un-tiled here
     const int bpl = c.dims.bpl, hh = c.dims.h;
     std::vector<uint8_t> t((size_t)bpl * ((hh + 7) & ~7) * 2);
     if (hipMemcpy(t.data(), im.duv_tiled, t.size(), hipMemcpyDeviceToHost) != hipSuccess) return 0;

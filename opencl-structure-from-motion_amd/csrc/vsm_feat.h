@@ -1,5 +1,5 @@
 // Fused matching-resolution image side (filters + non-maximum suppression out of one LDS tile), shared by the gfx950
-// kernels (vsm_kernels.hip: k_feat_dense, k_feat_sparse) and by the CPU emulation the "not gpu" tests run
+// kernels (vsm_image.hip: k_feat_dense, k_feat_sparse) and by the CPU emulation the "not gpu" tests run
 // (tests/emu/feat_emu.cpp walks the same per-thread functions tile by tile, thread by thread).
 //
 // What is fused (file:line = the reference):

@@ -1,4 +1,6 @@
-// gfx950 (MI355X, CDNA4) kernels of the matcher hot path.  Wave = 64 lanes.
+// gfx950 (MI355X, CDNA4) kernels of the image side of the matcher hot path: everything that only sees a VsmImage - ingest, front
+// end, filters, suppression, the fused tiles, feature records and bin order.  The pair side (match chain .. refinement) is
+// vsm_match.hip; what both use is vsm_dev.h.  Wave = 64 lanes.
 //
 // All kernels are integer/byte work bounded by HBM (or, for one 1242x375 pair, by launch and
 // dependent-load latency): no MFMA anywhere.  Every kernel takes a z (or y) grid dimension
@@ -13,50 +15,8 @@
 #include <algorithm>
 
 #include "vsm_internal.h"
+#include "vsm_dev.h"
 #include "vsm_feat.h"
-
-#define WAVE 64
-
-// XCD-aware block remap (MI355X: 8 XCDs, each with a private 4 MiB L2; hardware deals blocks
-// round-robin over the XCDs).  Batched launches are flattened to 1-D and logical block
-// L = (b % 8) * ceil(n/8) + b / 8, so every XCD walks one contiguous eighth of the (pair-major)
-// work and the eight L2s stop fetching the same image lines.  Speed only, never correctness.
-// Pointers that come out of the VsmImage / VsmSet tables are "generic" to the compiler, which then
-// emits flat_load (address-space check, and every wait on LDS traffic also waits for them).  They
-// all point into HBM: these helpers load through an explicit global-address-space pointer.
-#define VSM_AS1 __attribute__((address_space(1)))
-typedef uint32_t vsm_u4 __attribute__((ext_vector_type(4)));
-typedef int32_t vsm_i4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint4 ldg_u4(const void *p) {
-  const vsm_u4 v = *(const VSM_AS1 vsm_u4 *)p;
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ int4 ldg_i4(const void *p) {
-  const vsm_i4 v = *(const VSM_AS1 vsm_i4 *)p;
-  return make_int4(v.x, v.y, v.z, v.w);
-}
-// base + 32-bit byte offset: with a wave-uniform base the backend keeps the base in scalar registers and the offset in one
-// vector register (global_load ... v_off, s[base]) instead of building a 64-bit address per lane
-__device__ __forceinline__ uint4 ldg_u4_at(const void *base, uint32_t byte_off) {
-  const vsm_u4 v = *(const VSM_AS1 vsm_u4 *)((const VSM_AS1 char *)base + byte_off);
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
-// 16 bytes at a dword-aligned (not 16-byte-aligned) offset: one global_load_dwordx4 all the same
-typedef uint32_t vsm_u4_a4 __attribute__((ext_vector_type(4), aligned(4)));
-__device__ __forceinline__ uint4 ldg_u4_at_dw(const void *base, uint32_t byte_off) {
-  const vsm_u4_a4 v = *(const VSM_AS1 vsm_u4_a4 *)((const VSM_AS1 char *)base + byte_off);
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ uint32_t ldg_u32_at(const void *base, uint32_t byte_off) {
-  return *(const VSM_AS1 uint32_t *)((const VSM_AS1 char *)base + byte_off);
-}
-__device__ __forceinline__ int32_t ldg_i32(const void *p) { return *(const VSM_AS1 int32_t *)p; }
-__device__ __forceinline__ uint32_t ldg_u32(const void *p) { return *(const VSM_AS1 uint32_t *)p; }
-
-__device__ __forceinline__ int xcd_remap(int b, int nblocks) {
-  const int per = (nblocks + 7) >> 3;
-  return (b & 7) * per + (b >> 3);
-}
 
 #ifdef VSM_FEAT_TIMING  // experiments (tools/build_variant.sh NAME -DVSM_FEAT_TIMING, tools/feat_timing.py): cycles per phase of every wave
 __device__ unsigned int vsm_ft_rec[5][1 << 16][10];  // [kernel][wave] start (low bits), phase lengths ...
@@ -152,18 +112,6 @@ __global__ void __launch_bounds__(256) k_halve(const VsmImage *__restrict__ imgs
 // row it stores one dword of du, one of dv and, for the matching-resolution image, 8 bytes each
 // of f1 and f2.  FULL = true: full-resolution image -> du_full,dv_full only.
 // ---------------------------------------------------------------------------------------
-// ---------------------------------------------------------------------------------------
-// Full-resolution Sobel planes of half_resolution = 1 (read by the refinement only, as scattered 9 x 9 neighbourhoods):
-// ONE plane of 8 x 8-pixel tiles, 128 bytes each = one cache line; a tile row is 16 bytes: du of pixels 0-3, dv of pixels
-// 0-3, du of 4-7, dv of 4-7 (what a filter thread produces for its 4-pixel patch row is one 8-byte store).  A refinement
-// window (9 rows x 9 columns of both responses) lies in exactly 4 lines instead of 16, its row in two 16-byte loads.
-// du of pixel (x, y) at vsm_tiled_at(bpl, x, y), dv VSM_TILED_DV bytes further.
-// ---------------------------------------------------------------------------------------
-#define VSM_TILED_DV 4
-__host__ __device__ __forceinline__ size_t vsm_tiled_at(int bpl, int x, int y) {
-  return ((size_t)(y >> 3) * (size_t)(bpl >> 3) + (size_t)(x >> 3)) * 128 + (size_t)((y & 7) * 16 + ((x & 4) << 1) + (x & 3));
-}
-
 #define FPB(r, i) ((int)((Wn[(r)][(i) >> 2] >> (8 * ((i)&3))) & 0xffu))
 template <bool FULL>
 __global__ void __launch_bounds__(256)
@@ -260,9 +208,7 @@ __global__ void __launch_bounds__(256)
 // ---------------------------------------------------------------------------------------
 #define FRONT_TW 128
 #define FRONT_TH 64
-#ifndef FRONT_LPAD
 #define FRONT_LPAD 16  // (8 is all the patches read; with 16 a row is nine WHOLE 16-byte items and an interior tile never takes the dword path)
-#endif
 #define FRONT_LW (FRONT_TW + FRONT_LPAD)  // bytes per LDS row
 #define FRONT_LH (FRONT_TH + 4)
 __global__ void __launch_bounds__(256)
@@ -282,7 +228,7 @@ __global__ void __launch_bounds__(256)
   const int x0 = bx * FRONT_TW, y0 = by * FRONT_TH;
   const int t = threadIdx.x;
   // ---- tile of the padded stream into LDS ----
-  // Items of four LDS dwords (16 stream bytes; FRONT_LPAD = 8: the last item of a row has two).  An item that lies inside one image row
+  // Items of four LDS dwords (16 stream bytes; a row is nine whole items).  An item that lies inside one image row
   // takes ONE aligned 16-byte load plus one dword and four byte-aligns; the others (row ends, tile edges, rows outside the
   // image) go dword by dword: two aligned dwords + an align each, bytes beyond the row's w and positions outside the
   // image 0.  (Every 4-byte piece used to cost two loads: the kernel was bound by the texture addresser's lane rate.)
@@ -308,7 +254,8 @@ __global__ void __launch_bounds__(256)
   };
   FT_DECL;
   FT_STAMP;
-  constexpr int kItems = (FRONT_LW / 4 + 3) / 4;  // per row
+  static_assert((FRONT_LW & 15) == 0, "a row is whole 16-byte items");
+  constexpr int kItems = FRONT_LW / 16;  // per row
   constexpr int kIters = (FRONT_LH * kItems + 255) / 256;
   // (all of a thread's wide loads are requested before the first LDS store waits for one: three round trips become one)
   uint4 q[kIters];
@@ -317,6 +264,8 @@ __global__ void __launch_bounds__(256)
   for (int i = 0; i < kIters; i++) {
     const int e = t + 256 * i, r = e / kItems, g = e - r * kItems;
     const int y = y0 - 2 + r, x = x0 - 4 + 16 * g;
+    // dwords of the item.  A row is whole items, so this is always 4; it stays a min() because the compiler does not see
+    // that, keeps the dword loops below rolled, and so emits the device code of a9ef39f (1782 instructions; 2105 with a plain 4).
     const int nd = min(4, FRONT_LW / 4 - 4 * g);
     q[i] = make_uint4(0u, 0u, 0u, 0u);
     q4[i] = 0u;
@@ -332,7 +281,7 @@ __global__ void __launch_bounds__(256)
     const int e = t + 256 * i, r = e / kItems, g = e - r * kItems;
     if (e >= FRONT_LH * kItems) continue;
     const int y = y0 - 2 + r, x = x0 - 4 + 16 * g;
-    const int nd = min(4, FRONT_LW / 4 - 4 * g);
+    const int nd = min(4, FRONT_LW / 4 - 4 * g);  // (always 4; a min() for the same reason as above)
     if (nd == 4 && y >= 0 && y < h && x >= 0 && x + 20 <= w) {
       const uint32_t sh = (uint32_t)((uintptr_t)(src + (size_t)y * src_bpl + x) & 3);
       uint4 v;
@@ -340,14 +289,7 @@ __global__ void __launch_bounds__(256)
       v.y = __builtin_amdgcn_alignbyte(q[i].z, q[i].y, sh);
       v.z = __builtin_amdgcn_alignbyte(q[i].w, q[i].z, sh);
       v.w = __builtin_amdgcn_alignbyte(q4[i], q[i].w, sh);
-      if ((FRONT_LW & 15) == 0) {
-        *(uint4 *)&s_in[r][4 * g] = v;  // (rows of whole items are 16-byte aligned)
-      } else {
-        s_in[r][4 * g] = v.x;
-        s_in[r][4 * g + 1] = v.y;
-        s_in[r][4 * g + 2] = v.z;
-        s_in[r][4 * g + 3] = v.w;
-      }
+      *(uint4 *)&s_in[r][4 * g] = v;  // (rows of whole items are 16-byte aligned)
     } else if ((y < 0 || y >= h) && x >= 0 && x + 16 <= bpl) {  // a row outside the image whose item does not wrap into one inside
       for (int k = 0; k < nd; k++) s_in[r][4 * g + k] = 0u;
     } else {
@@ -391,60 +333,6 @@ __global__ void __launch_bounds__(256)
   static_assert(FRONT_TW == 128 && FRONT_TH == 64, "16 x 16 patches of 8 x 4 pixels");
   const int tx = t & 15, ty = t >> 4;
   const int x8 = x0 + 8 * tx, yb = y0 + 4 * ty;
-#ifndef FRONT_LINE_STORES
-#define FRONT_LINE_STORES 0
-#endif
-#if FRONT_LINE_STORES
-  // (Measured, off: 106.3 against 107.1 us per 200 images in the pipeline - the kernel is bound by its vector instructions,
-  // not by the shape of its stores - for 9 registers and 16 KB of LDS more.)
-  // The patch rows leave through LDS so that every store instruction writes WHOLE 128-byte lines of the tiled plane (a
-  // line = 8 rows of one 8-pixel column = the patches of two threads): a wave's 32 lines are staged in 4 KB of its own
-  // (pieces XOR-swizzled by the line so that the 16 lanes of a patch column do not share banks), then lane L of store k
-  // takes piece L & 7 of line 8 k + (L >> 3) - 1 KB of contiguous bytes per instruction instead of 16-byte pieces of 32 lines.
-  __shared__ __attribute__((aligned(16))) vsm_u4 s_out[4][256];
-  vsm_u4 o[4];
-#pragma unroll
-  for (int rr = 0; rr < 4; rr++) o[rr].x = o[rr].y = o[rr].z = o[rr].w = 0u;
-  if (x8 < bpl && yb < h) {
-    VfWindow<4> W;
-#pragma unroll
-    for (int r = 0; r < 8; r++) {
-#pragma unroll
-      for (int q = 0; q < 4; q++) W.w[r][q] = s_in[4 * ty + r][2 * tx + q];
-    }
-#pragma unroll
-    for (int rr = 0; rr < 4; rr++) {
-      const int y = yb + rr;
-      if (y >= h) break;
-      vf_s2 S[6], D[6];
-#pragma unroll
-      for (int j = 0; j < 6; j++) vf_columns_sobel<4>(W, rr, j, S[j], D[j]);
-      if (y < 3 || y > h - 4) vf_sobel_zero_outside(S, D, y * bpl + x8, 2 * bpl, (h - 2) * bpl);
-      uint32_t du[2], dv[2];
-      vf_sobel_row(S, D, du, dv);
-      o[rr].x = du[0];
-      o[rr].y = dv[0];
-      o[rr].z = du[1];
-      o[rr].w = dv[1];
-    }
-  }
-  {
-    const int wv = t >> 6, lane = t & 63, tyl = ty & 3;
-    const int lw = (tyl >> 1) * 16 + tx;  // the thread's line among its wave's 32
-#pragma unroll
-    for (int rr = 0; rr < 4; rr++) s_out[wv][lw * 8 + (((tyl & 1) * 4 + rr) ^ (lw & 7))] = o[rr];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const int l = k * 8 + (lane >> 3), pc = lane & 7;
-      const vsm_u4 v = s_out[wv][l * 8 + (pc ^ (l & 7))];
-      const int xx = x0 + 8 * (l & 15), yy = y0 + 16 * wv + 8 * (l >> 4) + pc;
-      if (xx < bpl && yy < h) *(VSM_AS1 vsm_u4 *)(im.duv_tiled + vsm_tiled_at(bpl, xx, yy)) = v;
-    }
-  }
-#else
   if (x8 >= bpl || yb >= h) return;
   VfWindow<4> W;
 #pragma unroll
@@ -452,10 +340,7 @@ __global__ void __launch_bounds__(256)
 #pragma unroll
     for (int q = 0; q < 4; q++) W.w[r][q] = s_in[4 * ty + r][2 * tx + q];
   }
-#ifndef FRONT_CASCADE
-#define FRONT_CASCADE 1  // the column sums of the patch's four rows share their stages (vf_columns_sobel_all)
-#endif
-#if FRONT_CASCADE
+  // the column sums of the patch's four rows share their stages (vf_columns_sobel_all)
   vf_s2 Sa[4][6], Da[4][6];
 #pragma unroll
   for (int j = 0; j < 6; j++) {
@@ -464,18 +349,11 @@ __global__ void __launch_bounds__(256)
 #pragma unroll
     for (int rr = 0; rr < 4; rr++) Sa[rr][j] = sj[rr], Da[rr][j] = dj[rr];
   }
-#endif
 #pragma unroll
   for (int rr = 0; rr < 4; rr++) {
     const int y = yb + rr;
     if (y >= h) break;
-#if FRONT_CASCADE
     vf_s2 (&S)[6] = Sa[rr], (&D)[6] = Da[rr];
-#else
-    vf_s2 S[6], D[6];
-#pragma unroll
-    for (int j = 0; j < 6; j++) vf_columns_sobel<4>(W, rr, j, S[j], D[j]);
-#endif
     if (y < 3 || y > h - 4) vf_sobel_zero_outside(S, D, y * bpl + x8, 2 * bpl, (h - 2) * bpl);
     uint32_t du[2], dv[2];
     vf_sobel_row(S, D, du, dv);
@@ -486,7 +364,6 @@ __global__ void __launch_bounds__(256)
     o.w = dv[1];
     *(VSM_AS1 vsm_u4 *)(im.duv_tiled + vsm_tiled_at(bpl, x8, y)) = o;
   }
-#endif
   FT_STAMP;
   FT_FLUSH(4);
 }
@@ -932,34 +809,6 @@ static void vsm_feat_tiles(const VsmDims &d, const VsmSet &dense, int &dx, int &
   dy = std::max((d.mh + 4 + 47) / 48, (dense.ncv + 2 + 11) / 12);
 }
 
-// block-wide exclusive scan of one int per thread (blockDim.x == 1024); returns the exclusive
-// prefix and the block total.  Wave shuffles + one LDS hop.
-__device__ __forceinline__ int block_excl_scan_1024(int v, int &total, int *s_w /*[17]*/) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  int x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    int y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  __syncthreads();  // protects s_w reuse across calls
-  if (lane == 63) s_w[wv] = x;
-  __syncthreads();
-  if (wv == 0) {
-    int w = lane < 16 ? s_w[lane] : 0;
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) {
-      int y = __shfl_up(w, o, 64);
-      if (lane >= o) w += y;
-    }
-    if (lane < 16) s_w[lane] = w;  // inclusive wave totals
-  }
-  __syncthreads();
-  total = s_w[15];
-  int wbase = wv ? s_w[wv - 1] : 0;
-  return wbase + x - v;
-}
-
 // ---------------------------------------------------------------------------------------
 // Feature index = rank in the reference's emission order (cells u-major / v-minor, classes
 // f1min,f1max,f2min,f2max inside a cell, viso/matcher.cpp:344-430): exclusive prefix sum of the
@@ -1027,29 +876,6 @@ __global__ void __launch_bounds__(1024) k_scan_cells(const VsmImage *__restrict_
 // ---------------------------------------------------------------------------------------
 __constant__ int8_t c_desc_dv[16] = {-1, +1, -1, +1, -1, +1, -1, +1, -5, +5, -5, +5, -3, +3, -3, +3};
 __constant__ int8_t c_desc_du[16] = {-3, -3, -1, -1, +3, +3, +1, +1, -1, -1, +1, +1, -5, -5, +5, +5};
-
-// fine v row of a (non-negative) coordinate: v-bin * VSM_VSUB + sub-row inside the bin; monotonic in v
-__device__ __forceinline__ int vfine_of(int v, int binsize, int vb) {
-  const int vbin = min(v / binsize, vb - 1);
-  return vbin * VSM_VSUB + min(((v - vbin * binsize) * VSM_VSUB) / binsize, VSM_VSUB - 1);
-}
-
-// fine bin id; id / VSM_VSUB is the reference's bin (class * ub + u_bin) * vb + v_bin (viso/matcher.cpp:881-888)
-__device__ __forceinline__ int bin_of(int u, int v, int c, int binsize, int ub, int vb) {
-  const int ubin = min(u / binsize, ub - 1);
-  return (c * ub + ubin) * (vb * VSM_VSUB) + vfine_of(v, binsize, vb);
-}
-
-// the same with the division by the bin size as a multiply-high (cfg.bin_magic): k_match runs it several times per stage,
-// and an integer division by a run-time value costs ~20 instructions.  Exact for 0 <= x < 2^32 / binsize; the arguments
-// here are below 2^17 and the host refuses bin sizes above 32768.
-__device__ __forceinline__ int div_bin(int x, const VsmMatchCfg &cfg) {
-  return cfg.binsize == 1 ? x : (int)__umulhi((uint32_t)x, cfg.bin_magic);
-}
-__device__ __forceinline__ int vfine_fast(int v, const VsmMatchCfg &cfg, int vb) {
-  const int vbin = min(div_bin(v, cfg), vb - 1);
-  return vbin * VSM_VSUB + min(div_bin((v - vbin * cfg.binsize) * VSM_VSUB, cfg), VSM_VSUB - 1);
-}
 
 // Tile kernel: a block owns a rectangle of NMS cells (up to 128 x 32 matching-resolution pixels).
 // It first stages the Sobel responses of that rectangle plus the 5-pixel descriptor halo in LDS,
@@ -1520,1223 +1346,13 @@ __global__ void __launch_bounds__(256) k_bin_rank(const VsmImage *__restrict__ i
   st.s_desc[2 * dst + 1] = *(const uint4 *)(rec + 8);
 }
 
-// ---------------------------------------------------------------------------------------
-// M2/M3 findMatch + matching, viso/matcher.cpp:892-963 and :965-1153.
-// A group of G lanes owns one query and walks the whole dependent chain (2 stages for flow /
-// stereo, 4 for quad).  In each stage the lanes stride over the candidates of the fine bins the
-// window touches (packed 4-byte coordinates, 16-byte loads; 32-byte descriptor reads only for
-// in-window candidates), cost = v_sad_u8 x 8 (+ 4*sqrt(du^2+dv^2) in double when a prediction is
-// active), and the winner is the lexicographic minimum of (cost, place in the reference's visiting
-// order) over the group -- exactly the reference's "first minimum in (u_bin, v_bin, index) order"
-// (:937-958).  Measured on MI355X the kernel is bound by instruction issue and dependent L2 round
-// trips, not by bytes (SQ counters in profiles/): fewer visited candidates, a 3-instruction window
-// test and judging candidates per lane rather than per visited slot are what made it faster.
-// ---------------------------------------------------------------------------------------
-#define VSM_NONE 0xffffffffu
-
-__device__ __forceinline__ uint32_t sad32(const uint4 &a0, const uint4 &a1, const uint4 &b0, const uint4 &b1) {
-  uint32_t s = __builtin_amdgcn_sad_u8(a0.x, b0.x, 0u);
-  s = __builtin_amdgcn_sad_u8(a0.y, b0.y, s);
-  s = __builtin_amdgcn_sad_u8(a0.z, b0.z, s);
-  s = __builtin_amdgcn_sad_u8(a0.w, b0.w, s);
-  s = __builtin_amdgcn_sad_u8(a1.x, b1.x, s);
-  s = __builtin_amdgcn_sad_u8(a1.y, b1.y, s);
-  s = __builtin_amdgcn_sad_u8(a1.z, b1.z, s);
-  s = __builtin_amdgcn_sad_u8(a1.w, b1.w, s);
-  return s;
-}
-
-// the feature a chain stage starts from: position, class and 32-byte descriptor, in registers
-struct VsmQuery {
-  uint32_t uv;  // u | v << 16
-  int c;
-  uint4 da, db;
-  __device__ __forceinline__ int u() const { return (int)(uv & 0xffffu); }
-  __device__ __forceinline__ int v() const { return (int)(uv >> 16); }
-};
-
-__device__ __forceinline__ VsmQuery load_query(const VsmSet &A, int i) {
-  const int32_t *rec = A.feat + (size_t)i * 12;
-  const int4 hd = ldg_i4(rec);
-  VsmQuery q;
-  q.uv = (uint32_t)hd.x | ((uint32_t)hd.y << 16);
-  q.c = hd.w;
-  q.da = ldg_u4(rec + 4);
-  q.db = ldg_u4(rec + 8);
-  return q;
-}
-
-// One findMatch (viso/matcher.cpp:892-963) for the query held in `q` against feature set B.
-// Returns the winner's position in B's bin-sorted arrays (VSM_NONE if the window is empty) and
-// REPLACES q by the winner (the lane that found it broadcasts coordinates + descriptor with
-// width-G shuffles), so the next stage of the chain starts without going back to memory; the
-// winner's feature index is only looked up once, at the end of the chain.  An empty window
-// yields feature 0 of B like the reference (min_ind = 0, :898), class included.
-#ifndef VSM_UVL
-#define VSM_UVL 1  // 16-byte coordinate loads in flight per lane (two cost the registers of the fifth wave per SIMD: 71 -> 56 us for the first pass, 180 -> 175 for the second)
-#endif
-#ifndef VSM_MATCH_BLOCK
-#define VSM_MATCH_BLOCK 256  // threads per block of k_match
-#endif
-#ifndef VSM_STEREO_BY_BIN
-#define VSM_STEREO_BY_BIN 1  // the stereo-type stages (window = a few rows x the disparity range: 2-3 bins, a few candidates each) scan by bin also under prior boxes: -3.5 %
-#endif
-#ifndef VSM_MATCH_BALANCE
-#define VSM_MATCH_BALANCE 0  // passes in which the lanes of a group even out their parked candidates before judging.  MEASURED with 2: judge rounds per wave 20.1 -> 16.6, time unchanged (alone 224-228 us either way): a wave's row of round trips is not what bounds the kernel - off
-#endif
-#ifndef VSM_SCAN_UNALIGNED
-#define VSM_SCAN_UNALIGNED 1  // coordinate loads start at the run's first candidate (dword-aligned 16-byte loads) instead of at the 16-byte line below it
-#endif
-#ifdef VSM_MATCH_TIMING
-extern __device__ unsigned long long vsm_mt_acc[16];
-#endif
-#if defined(VSM_MATCH_TIMING) && VSM_MATCH_TIMING == 2
-#define VSM_MT_TRIP(k)                                                                       \
-  do {                                                                                       \
-    if ((int)(threadIdx.x & 63) == __ffsll((long long)__ballot(1)) - 1) atomicAdd(&vsm_mt_acc[k], 1ull); \
-  } while (0)
-#else
-#define VSM_MT_TRIP(k)
-#endif
-typedef unsigned short vsm_us2 __attribute__((ext_vector_type(2)));
-
-template <int G, bool RELOAD = true, bool MAYPRED = true, bool BYBIN = false, bool HEADS = false>
-__device__ __forceinline__ uint32_t find_match(VsmQuery &q, const VsmSet &B, const VsmDims &d, const VsmMatchCfg &cfg,
-                                               bool prior, float r_umin, float r_umax, float r_vmin, float r_vmax,
-                                               bool flow, double u_, double v_, int lane, long long *ph = nullptr) {
-  float u_min, u_max, v_min, v_max;
-  const int qu = q.u(), qv = q.v();
-  if (prior) {
-    u_min = (float)qu + r_umin;
-    u_max = (float)qu + r_umax;
-    v_min = (float)qv + r_vmin;
-    v_max = (float)qv + r_vmax;
-  } else {
-    u_min = (float)(qu - cfg.radius);
-    u_max = (float)(qu + cfg.radius);
-    v_min = (float)(qv - cfg.radius);
-    v_max = (float)(qv + cfg.radius);
-  }
-  if (!flow) {
-    v_min = (float)(qv - cfg.disp_tol);
-    v_max = (float)(qv + cfg.disp_tol);
-  }
-  // The reference tests (float)u2 >= u_min && (float)u2 <= u_max (viso/matcher.cpp:943) on integer
-  // coordinates: the same as lo <= u2 <= hi with lo = ceil(u_min), hi = floor(u_max).  Coordinates
-  // are < 16384, so with both axes packed as 16-bit halves the whole window test is one wrapping
-  // packed subtract, one packed min and one compare per candidate.
-  const int lo_u = max((int)ceilf(u_min), 0), hi_u = min((int)floorf(u_max), 65535);
-  const int lo_v = max((int)ceilf(v_min), 0), hi_v = min((int)floorf(v_max), 65535);
-  const bool empty = hi_u < lo_u || hi_v < lo_v;
-  // u-bins that can hold an in-window candidate: those of lo_u .. hi_u (a feature's bin is u / binsize, k_emit) - inside
-  // the reference's floor(u_min / binsize) .. floor(u_max / binsize) (:929-932), and every candidate takes the exact window
-  // test anyway; who wins a tie is settled by the candidates' ranks, not by the order of the visit
-  const int ubmin = min(div_bin(min(lo_u, 65535), cfg), d.ub - 1);
-  const int ubmax = min(div_bin(max(hi_u, 0), cfg), d.ub - 1);
-  // fine rows that can hold an in-window candidate (a subset of the reference's v-bins vbmin..vbmax,
-  // :933-934; every candidate still takes the exact window test below)
-  const int vrows = d.vb * VSM_VSUB;
-  const int vfmin = vfine_fast(min(lo_v, d.vb * cfg.binsize - 1), cfg, d.vb);
-  const int vfmax = vfine_fast(min(max(hi_v, 0), d.vb * cfg.binsize - 1), cfg, d.vb);
-  const uint32_t lo_pk = (uint32_t)lo_u | ((uint32_t)lo_v << 16);
-  const uint32_t rng_pk = (uint32_t)(hi_u - lo_u) | ((uint32_t)(hi_v - lo_v) << 16);
-  const bool pred = MAYPRED && (u_ >= 0 && v_ >= 0);
-  // Two phases per stage.  (1) Walk the candidates: coordinates are packed (u | v << 16) and sorted
-  // by fine bin, so one aligned 16-byte load brings 4 consecutive candidates of this lane
-  // (VSM_UVL such loads in flight); the positions of the few that fall inside the window are parked
-  // in a 4-deep per-lane register queue.  (2) Judge the parked candidates: descriptor + reference
-  // rank fetch, SAD, and the double-precision distance term of a predicted match (:948-953) only
-  // when the integer SAD alone does not already exceed the best cost (cost >= SAD).  A wavefront
-  // runs phase 2 as many times as its busiest lane has candidates, not once per visited slot.
-  // The reference keeps the FIRST minimum in its (u_bin, v_bin, index) visiting order (:937-958):
-  // that is the minimum of (cost, rank), whatever order the candidates are judged in.
-  // A stage that cannot have a prediction (MAYPRED = false) compares one integer key, SAD << 32 | rank; the others keep
-  // the cost in double as the reference does.  The updates are selects, not branches.
-  // (Round 4 tried the judging spread over the wave instead - the lanes' parked candidates compacted onto one list per wave
-  // in LDS by ballots, 64 entries judged per round whoever found them, the owner's descriptor by cross-lane reads, the
-  // minimum of (cost, rank) per query by ds_min_u64: results identical, but a wave-stage has 56 candidates on average
-  // (1.74 per query), so four rounds become two, and the list's bookkeeping costs more than that: 345-370 us against 322.)
-  double best = 10000000.0;
-  uint64_t bkey = ~0ull;
-  uint32_t bestq = VSM_NONE, brank = VSM_NONE;
-  int nq = 0, q0p = 0, q1p = 0, q2p = 0, q3p = 0;
-  auto judge = [&](int p) {
-    VSM_MT_TRIP(2);
-    const uint4 a = ldg_u4_at(B.s_desc, (uint32_t)p * 32u), b = ldg_u4_at(B.s_desc, (uint32_t)p * 32u + 16u);
-    const uint32_t rk = ldg_u32_at(B.s_rank, (uint32_t)p * 4u);
-    const uint32_t sad = sad32(q.da, q.db, a, b);
-    if (!MAYPRED) {
-      const uint64_t key = ((uint64_t)sad << 32) | rk;
-      const bool better = key < bkey;
-      bkey = better ? key : bkey;
-      bestq = better ? (uint32_t)p : bestq;
-    } else {
-      double cost = (double)sad;
-      if (cost <= best) {
-        if (pred) {
-          const uint32_t w = ldg_u32_at(B.s_uv, (uint32_t)p * 4u);
-          double du = (double)(int)(w & 0xffffu) - u_;
-          double dv = (double)(int)(w >> 16) - v_;
-          double dist = sqrt(du * du + dv * dv);
-          cost += 4 * dist;
-        }
-        const bool better = cost < best || (cost == best && rk < brank);
-        best = better ? cost : best;
-        brank = better ? rk : brank;
-        bestq = better ? (uint32_t)p : bestq;
-      }
-    }
-  };
-  auto pop_and_judge = [&]() {  // lanes with a parked candidate take their newest one
-    if (nq > 0) {
-      const int p = q0p;
-      q0p = q1p;
-      q1p = q2p;
-      q2p = q3p;
-      nq--;
-      judge(p);
-    }
-  };
-  VSM_MT_TRIP(3);
-#if defined(VSM_MATCH_TIMING) && VSM_MATCH_TIMING == 1
-  const long long ph0 = clock64();
-#endif
-#if defined(VSM_MATCH_TIMING) && VSM_MATCH_TIMING == 2
-  int mt_maxrun = 0;  // the longest run of candidates this lane's scans went through (the bound of a per-bin head record)
-#define VSM_MT_RUN(len) mt_maxrun = max(mt_maxrun, (int)(len))
-#else
-#define VSM_MT_RUN(len)
-#endif
-  if (HEADS) {
-  // The window's u-bins one after the other; of a bin's head record (k_feat_heads: 64 bytes = the run's start + the first 15
-  // candidates' coordinates) every lane of the group loads its 16 / G dwords, next to the run's end: one round trip for
-  // what the forms below take two or more for (bin starts, then coordinate loads that need them).
-  constexpr int NDW = 16 / G;  // record dwords per lane
-  auto park = [&](uint32_t w, int p, int q1) {
-    const vsm_us2 off = __builtin_bit_cast(vsm_us2, w) - __builtin_bit_cast(vsm_us2, lo_pk);
-    const vsm_us2 cl = __builtin_elementwise_min(off, __builtin_bit_cast(vsm_us2, rng_pk));
-    if (__builtin_bit_cast(uint32_t, cl) == __builtin_bit_cast(uint32_t, off) && p < q1) {
-      if (nq == 4) {  // queue full (rare): make room first
-        const int pf = q3p;
-        nq = 3;
-        judge(pf);
-      }
-      q3p = q2p;
-      q2p = q1p;
-      q1p = q0p;
-      q0p = p;
-      nq++;
-    }
-  };
-  for (int ubin = ubmin; ubin <= ubmax && !empty; ubin++) {
-    VSM_MT_TRIP(0);
-    const int b0 = (q.c * d.ub + ubin) * vrows;
-    const uint32_t hb = (uint32_t)(b0 + vfmin) * 64u + (uint32_t)lane * (uint32_t)(4 * NDW);
-    uint32_t r[NDW];
-    if (NDW >= 4) {
-#pragma unroll
-      for (int j = 0; j < NDW / 4; j++) {
-        const uint4 v = ldg_u4_at(B.heads, hb + 16u * j);
-        r[4 * j + 0] = v.x;
-        r[4 * j + 1] = v.y;
-        r[4 * j + 2] = v.z;
-        r[4 * j + 3] = v.w;
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < NDW; j++) r[j] = ldg_u32_at(B.heads, hb + 4u * j);
-    }
-    const int q1 = (int)ldg_u32_at(B.bin_start, (uint32_t)(b0 + vfmax + 1) * 4u);
-    const int q0 = __shfl((int)r[0], 0, G);  // (the group's lane 0 holds the record's first dword: the start)
-    VSM_MT_RUN(q1 - q0);
-#pragma unroll
-    for (int i = 0; i < NDW; i++) {
-      const int k = lane * NDW + i - 1;  // candidate number of this dword (-1: the start itself)
-      if (i > 0 || lane > 0) park(r[i], q0 + k, q1);
-    }
-    for (int p0 = q0 + 15 + 4 * lane; p0 < q1; p0 += 4 * G) {  // a run of more than 15 candidates: the rest in 16-byte loads
-      VSM_MT_TRIP(1);
-      const uint4 wk = ldg_u4_at_dw(B.s_uv, (uint32_t)p0 * 4u);
-      park(wk.x, p0, q1);
-      park(wk.y, p0 + 1, q1);
-      park(wk.z, p0 + 2, q1);
-      park(wk.w, p0 + 3, q1);
-    }
-  }
-  } else if (BYBIN) {
-  // The lanes of a group take the window's u-bins in turn, each scanning its bin's run alone: a stereo stage's disparity
-  // range spans 2-3 bins and an unconstrained first-pass window nine, with a handful of candidates in each - the wave goes
-  // round ceil(bins / G) times instead of once per bin with most of a 16- or 32-slot sweep empty.  (BYBIN: the launches without prior
-  // boxes - 88 -> 70 us per 67 pairs; with them the windows are narrow and sharing a bin's run is 2 % quicker.)
-  for (int ubin = ubmin + lane; ubin <= ubmax && !empty; ubin += G) {
-    VSM_MT_TRIP(0);
-    const int b0 = (q.c * d.ub + ubin) * vrows;
-    const int q0 = (int)ldg_u32_at(B.bin_start, (uint32_t)(b0 + vfmin) * 4u), q1 = (int)ldg_u32_at(B.bin_start, (uint32_t)(b0 + vfmax + 1) * 4u);
-    VSM_MT_RUN(q1 - q0);
-    for (int p0 = q0; p0 < q1; p0 += 4 * VSM_UVL) {
-      VSM_MT_TRIP(1);
-      uint4 wk[VSM_UVL];
-#pragma unroll
-      for (int j = 0; j < VSM_UVL; j++) {
-        const int pj = p0 + j * 4;
-        wk[j] = pj < q1 ? ldg_u4_at_dw(B.s_uv, (uint32_t)pj * 4u) : make_uint4(0, 0, 0, 0);
-      }
-#pragma unroll
-      for (int j = 0; j < VSM_UVL; j++) {
-        const uint32_t w4[4] = {wk[j].x, wk[j].y, wk[j].z, wk[j].w};
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-          const int p = p0 + j * 4 + k;
-          const vsm_us2 off = __builtin_bit_cast(vsm_us2, w4[k]) - __builtin_bit_cast(vsm_us2, lo_pk);
-          const vsm_us2 cl = __builtin_elementwise_min(off, __builtin_bit_cast(vsm_us2, rng_pk));
-          if (__builtin_bit_cast(uint32_t, cl) == __builtin_bit_cast(uint32_t, off) && p < q1) {
-            if (nq == 4) {  // queue full (rare): make room first
-              const int pf = q3p;
-              nq = 3;
-              judge(pf);
-            }
-            q3p = q2p;
-            q2p = q1p;
-            q1p = q0p;
-            q0p = p;
-            nq++;
-          }
-        }
-      }
-    }
-  }
-  } else {
-  for (int ubin = ubmin; ubin <= ubmax && !empty; ubin++) {
-    VSM_MT_TRIP(0);
-    const int b0 = (q.c * d.ub + ubin) * vrows;
-    const int q0 = (int)ldg_u32_at(B.bin_start, (uint32_t)(b0 + vfmin) * 4u), q1 = (int)ldg_u32_at(B.bin_start, (uint32_t)(b0 + vfmax + 1) * 4u);
-    VSM_MT_RUN(q1 - q0);
-#if VSM_SCAN_UNALIGNED
-    for (int p0 = q0 + 4 * lane; p0 < q1; p0 += 4 * G * VSM_UVL) {  // (the run's first candidate first: only the tail needs a bound)
-#else
-    const uint32_t qn = (uint32_t)(q1 - q0);
-    for (int p0 = (q0 & ~3) + 4 * lane; p0 < q1; p0 += 4 * G * VSM_UVL) {
-#endif
-      VSM_MT_TRIP(1);
-      uint4 wk[VSM_UVL];
-#pragma unroll
-      for (int j = 0; j < VSM_UVL; j++) {
-        const int pj = p0 + j * 4 * G;
-#if VSM_SCAN_UNALIGNED
-        wk[j] = pj < q1 ? ldg_u4_at_dw(B.s_uv, (uint32_t)pj * 4u) : make_uint4(0, 0, 0, 0);
-#else
-        wk[j] = pj < q1 ? ldg_u4_at(B.s_uv, (uint32_t)pj * 4u) : make_uint4(0, 0, 0, 0);
-#endif
-      }
-#pragma unroll
-      for (int j = 0; j < VSM_UVL; j++) {
-        const uint32_t w4[4] = {wk[j].x, wk[j].y, wk[j].z, wk[j].w};
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-          const int p = p0 + j * 4 * G + k;
-          const vsm_us2 off = __builtin_bit_cast(vsm_us2, w4[k]) - __builtin_bit_cast(vsm_us2, lo_pk);
-          const vsm_us2 cl = __builtin_elementwise_min(off, __builtin_bit_cast(vsm_us2, rng_pk));
-#if VSM_SCAN_UNALIGNED
-          if (__builtin_bit_cast(uint32_t, cl) == __builtin_bit_cast(uint32_t, off) && p < q1) {
-#else
-          if (__builtin_bit_cast(uint32_t, cl) == __builtin_bit_cast(uint32_t, off) && (uint32_t)(p - q0) < qn) {
-#endif
-            if (nq == 4) {  // queue full (rare): make room first
-              const int pf = q3p;
-              nq = 3;
-              judge(pf);
-            }
-            q3p = q2p;
-            q2p = q1p;
-            q1p = q0p;
-            q0p = p;
-            nq++;
-          }
-        }
-      }
-    }
-  }
-  }
-#if defined(VSM_MATCH_TIMING) && VSM_MATCH_TIMING == 1
-  const long long ph1 = clock64();
-#endif
-#if defined(VSM_MATCH_TIMING) && VSM_MATCH_TIMING == 2
-  if (!cfg.sparse) {  // dense pass: in how many wave-stages would a head record of 3 / 7 / 15 inline candidates have spared EVERY lane its coordinate loads?
-    if (BYBIN) {  // (a lane scans its own bins: the record is one lane's)
-      VSM_MT_TRIP(11);
-      if (!__any(mt_maxrun > 3)) VSM_MT_TRIP(12);
-      if (!__any(mt_maxrun > 7)) VSM_MT_TRIP(13);
-      if (!__any(mt_maxrun > 15)) VSM_MT_TRIP(14);
-    } else {      // (a group shares a bin's run)
-      VSM_MT_TRIP(8);
-      if (!__any(mt_maxrun > 7)) VSM_MT_TRIP(9);
-      if (!__any(mt_maxrun > 15)) VSM_MT_TRIP(10);
-    }
-  }
-#endif
-#if VSM_MATCH_BALANCE
-  // The wave judges as many rounds as its busiest lane has parked candidates (a descriptor fetch each: a round trip), and
-  // who judges a candidate does not matter - the group's minimum of (cost, rank) is taken below.  So the lanes of a group
-  // even their queues out first: a lane with two candidates more than its partner hands its newest one over.
-  if (G >= 2) {
-#pragma unroll
-    for (int rep = 0; rep < VSM_MATCH_BALANCE; rep++) {
-#pragma unroll
-      for (int m = 1; m < G; m <<= 1) {
-        const int onq = __shfl_xor(nq, m, G);
-        const int sent = __shfl_xor(q0p, m, G);
-        const bool give = nq > onq + 1, take = onq > nq + 1;
-        if (give) {
-          q0p = q1p;
-          q1p = q2p;
-          q2p = q3p;
-          nq--;
-        }
-        if (take) {
-          q3p = q2p;
-          q2p = q1p;
-          q1p = q0p;
-          q0p = sent;
-          nq++;
-        }
-      }
-    }
-  }
-#endif
-  while (__any(nq > 0)) pop_and_judge();
-#if defined(VSM_MATCH_TIMING) && VSM_MATCH_TIMING == 1
-  const long long ph2 = clock64();
-  if (ph) {
-    ph[0] += ph1 - ph0;
-    ph[1] += ph2 - ph1;
-  }
-#endif
-#pragma unroll
-  for (int m = G / 2; m >= 1; m >>= 1) {
-    const uint32_t oq = (uint32_t)__shfl_xor((int)bestq, m, G);
-    if (!MAYPRED) {
-      const uint32_t olo = (uint32_t)__shfl_xor((int)(uint32_t)bkey, m, G), ohi = (uint32_t)__shfl_xor((int)(uint32_t)(bkey >> 32), m, G);
-      const uint64_t ok = ((uint64_t)ohi << 32) | olo;
-      const bool better = ok < bkey;
-      bkey = better ? ok : bkey;
-      bestq = better ? oq : bestq;
-    } else {
-      const double oc = __shfl_xor(best, m, G);
-      const uint32_t ork = (uint32_t)__shfl_xor((int)brank, m, G);
-      const bool better = oc < best || (oc == best && ork < brank);
-      best = better ? oc : best;
-      bestq = better ? oq : bestq;
-      brank = better ? ork : brank;
-    }
-  }
-  if (!RELOAD) return bestq;
-  if (bestq == VSM_NONE) {  // group-uniform
-    q = load_query(B, 0);
-    return VSM_NONE;
-  }
-  // every lane of the group fetches the winner's record (just touched, so it is in cache; handing it over from the lane
-  // that judged it costs 20 registers and was measured 3 % quicker on pass 2, 15 % slower on pass 1; fetched by ONE lane and
-  // passed on in nine shuffles - round 5 - 251 against 226 us alone: the shuffles and 32 bytes of spills cost more than the
-  // lane accesses they save)
-  q.uv = ldg_u32_at(B.s_uv, bestq * 4u);
-  q.da = ldg_u4_at(B.s_desc, bestq * 32u);
-  q.db = ldg_u4_at(B.s_desc, bestq * 32u + 16u);
-  return bestq;
-}
-
-// (floor((float)u / (float)binsize) of the reference, :1020-1022, is u / binsize for these integers: u < 2^14)
-__device__ __forceinline__ int stat_bin_of(int u, int v, const VsmMatchCfg &cfg, int ub, int vb) {
-  return min(div_bin(v, cfg), vb - 1) * ub + min(div_bin(u, cfg), ub - 1);
-}
-
-__device__ __forceinline__ int index_of(const VsmSet &B, uint32_t pos) { return pos == VSM_NONE ? 0 : ldg_i32(B.s_idx + pos); }
-
-#ifndef VSM_MATCH_WAVES
-#define VSM_MATCH_WAVES 5  // waves per SIMD the register allocator must leave room for (96 registers, no scratch; six would spill)
-#endif
-#ifdef VSM_MATCH_TIMING  // experiments (tools/build_variant.sh NAME -DVSM_MATCH_TIMING): life of every wave of the dense pass
-__device__ unsigned long long vsm_mt_acc[16];  // wave-level trip counts: [0] ubin iterations, [1] scan iterations, [2] judge rounds, [3] findMatch calls, [4..7] cycles of stage 1..4
-extern "C" int vsm_debug_match_acc(unsigned long long *out, int reset) {
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(vsm_mt_acc), sizeof(vsm_mt_acc)) != hipSuccess) return -1;
-  if (reset) {
-    static unsigned long long z[16];
-    if (hipMemcpyToSymbol(HIP_SYMBOL(vsm_mt_acc), z, sizeof(z)) != hipSuccess) return -1;
-  }
-  return 0;
-}
-__device__ unsigned int vsm_mt_n;
-__device__ unsigned int vsm_mt[1 << 18][8];  // life, stage 1..4, bins + scan, judging, start (low bits)
-extern "C" int vsm_debug_match_timing(unsigned int *out, unsigned int cap, int reset) {
-  unsigned int n = 0;
-  if (hipMemcpyFromSymbol(&n, HIP_SYMBOL(vsm_mt_n), 4) != hipSuccess) return -1;
-  if (n > (1u << 18)) n = 1u << 18;
-  if (n > cap) n = cap;
-  if (n && hipMemcpyFromSymbol(out, HIP_SYMBOL(vsm_mt), (size_t)n * 32) != hipSuccess) return -1;
-  if (reset) {
-    const unsigned int z = 0;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(vsm_mt_n), &z, 4) != hipSuccess) return -1;
-  }
-  return (int)n;
-}
-#endif
-template <int G, bool BYBIN = false, bool HEADS = false>
-__global__ void __launch_bounds__(VSM_MATCH_BLOCK, VSM_MATCH_WAVES)
-    k_match(const VsmImage *__restrict__ imgs, const VsmPair *__restrict__ pairs, const VsmJob *__restrict__ jobs,
-            VsmJob job0, VsmDims d, VsmMatchCfg cfg, int nbx, int npairs) {
-  // flattened grid: logical block -> (frame pair, block within pair), XCD-contiguous
-  // (jobs == nullptr: the single pair `job0`)
-  const int lb = xcd_remap(blockIdx.x, gridDim.x);
-  const int pj = lb / nbx, bx = lb - pj * nbx;
-  if (pj >= npairs) return;
-  const VsmJob &jb = jobs ? jobs[pj] : job0;
-  const VsmPair &pair = pairs[pj];
-  const int lane = threadIdx.x & (G - 1);
-  const int qi = (bx * blockDim.x + threadIdx.x) / G;
-  const int si = cfg.sparse ? 0 : 1;
-  if (qi >= jb.nq[si]) return;
-#ifdef VSM_MATCH_TIMING
-  const long long mt0 = clock64();
-#if VSM_MATCH_TIMING == 3
-  const long long mtw0 = wall_clock64();
-#endif
-  long long mtph_[2] = {0, 0}, *mtph = mtph_;
-  unsigned int mtst[4] = {0, 0, 0, 0};
-#else
-  long long *mtph = nullptr;
-#endif
-  const int img_prev = jb.img_prev, img_curr = jb.img_curr;
-  const VsmSet &s1p = imgs[img_prev].set[si], &s2p = imgs[img_prev + 1].set[si];
-  const VsmSet &s1c = imgs[img_curr].set[si], &s2c = imgs[img_curr + 1].set[si];
-  const bool prior = cfg.use_prior != 0;
-  vsm_p_match m;
-  bool ok = false;
-  // the statistics bin of a chain is that of its start feature (:1020-1022, :1104-1106); its four
-  // per-stage boxes are fetched once
-  VsmQuery q = load_query(cfg.method == 2 ? s1p : s1c, qi);
-  // (stage-major on the device: one 16-byte load per stage, issued one stage ahead of its use)
-  const float *rg = pair.ranges + 16 * stat_bin_of(q.u(), q.v(), cfg, d.ub, d.vb);
-  auto box = [&](int stage) {  // {u_min, u_max, v_min, v_max} offsets of a stage
-    if (!prior) return make_float4(0, 0, 0, 0);
-    const uint4 r = ldg_u4(rg + 4 * stage);
-    return make_float4(__uint_as_float(r.x), __uint_as_float(r.y), __uint_as_float(r.z), __uint_as_float(r.w));
-  };
-  const uint32_t w0 = q.uv;
-  const int u0 = q.u(), v0 = q.v();
-  if (cfg.method == 0) {  // flow, :1006-1041
-    const float4 r0 = box(0), r1 = box(1);
-    const uint32_t p1 = find_match<G, true, false, BYBIN, HEADS>(q, s1p, d, cfg, prior, r0.x, r0.y, r0.z, r0.w, true, -1, -1, lane);
-    const int u1p = q.u(), v1p = q.v();
-    const uint32_t p2 = find_match<G, true, false, BYBIN, HEADS>(q, s1c, d, cfg, prior, r1.x, r1.y, r1.z, r1.w, true, -1, -1, lane);
-    const int i1p = index_of(s1p, p1), i1c2 = index_of(s1c, p2);
-    ok = (i1c2 == qi);
-    m = {(float)u1p, (float)v1p, i1p, -1.f, -1.f, -1, (float)u0, (float)v0, qi, -1.f, -1.f, -1};
-  } else if (cfg.method == 1) {  // stereo, :1045-1084
-    const float4 r0 = box(0), r1 = box(1);
-    const uint32_t p1 = find_match<G, true, false, BYBIN || VSM_STEREO_BY_BIN, HEADS>(q, s2c, d, cfg, prior, r0.x, r0.y, r0.z, r0.w, false, -1, -1, lane);
-    const int u2c = q.u(), v2c = q.v();
-    const uint32_t p2 = find_match<G, true, false, BYBIN || VSM_STEREO_BY_BIN, HEADS>(q, s1c, d, cfg, prior, r1.x, r1.y, r1.z, r1.w, false, -1, -1, lane);
-    const int i2c = index_of(s2c, p1), i1c2 = index_of(s1c, p2);
-    ok = (i1c2 == qi) && (u0 >= u2c);
-    m = {-1.f, -1.f, -1, -1.f, -1.f, -1, (float)u0, (float)v0, qi, (float)u2c, (float)v2c, i2c};
-  } else {  // quad, :1088-1153
-    // (stage results stay packed u | v << 16 until the record is written: registers decide how many
-    // chains a SIMD keeps in flight)
-    const float4 r0 = box(0), r1 = box(1);
-    const uint32_t p1 = find_match<G, true, false, BYBIN || VSM_STEREO_BY_BIN, HEADS>(q, s2p, d, cfg, prior, r0.x, r0.y, r0.z, r0.w, false, -1, -1, lane, mtph);
-    const uint32_t w2p = q.uv;
-#ifdef VSM_MATCH_TIMING
-    const long long ms1 = clock64();
-#endif
-    double u2c_ = -1, v2c_ = -1;
-    if (jb.use_tr) {  // :1114-1126, contraction-free double arithmetic
-      double dd = (double)u0 - (double)q.u();
-      if (!(dd > 1.0)) dd = 1.0;
-      double x1p = ((double)u0 - cfg.cu) * cfg.base / dd;
-      double y1p = ((double)v0 - cfg.cv) * cfg.base / dd;
-      double z1p = cfg.f * cfg.base / dd;
-      double x2c = jb.t[0] * x1p + jb.t[1] * y1p + jb.t[2] * z1p + jb.t[3] - cfg.base;
-      double y2c = jb.t[4] * x1p + jb.t[5] * y1p + jb.t[6] * z1p + jb.t[7];
-      double z2c = jb.t[8] * x1p + jb.t[9] * y1p + jb.t[10] * z1p + jb.t[11];
-      u2c_ = cfg.f * x2c / z2c + cfg.cu;
-      v2c_ = cfg.f * y2c / z2c + cfg.cv;
-    }
-    const float4 r2 = box(2);
-    const uint32_t p2 = find_match<G, true, true, BYBIN, HEADS>(q, s2c, d, cfg, prior, r1.x, r1.y, r1.z, r1.w, true, u2c_, v2c_, lane, mtph);
-    const uint32_t w2c = q.uv;
-#ifdef VSM_MATCH_TIMING
-    const long long ms2 = clock64();
-#endif
-    const float4 r3 = box(3);
-    const uint32_t p3 = find_match<G, true, false, BYBIN || VSM_STEREO_BY_BIN, HEADS>(q, s1c, d, cfg, prior, r2.x, r2.y, r2.z, r2.w, false, -1, -1, lane, mtph);
-    const uint32_t w1c = q.uv;
-#ifdef VSM_MATCH_TIMING
-    const long long ms3 = clock64();
-#endif
-    // stage 4 predicts the chain's own start (:1134)
-    const uint32_t p4 = find_match<G, true, true, BYBIN, HEADS>(q, s1p, d, cfg, prior, r3.x, r3.y, r3.z, r3.w, true,
-                                      jb.use_tr ? (double)(int)(w0 & 0xffffu) : -1.0,
-                                      jb.use_tr ? (double)(int)(w0 >> 16) : -1.0, lane, mtph);
-    const int i1p2 = index_of(s1p, p4);
-#ifdef VSM_MATCH_TIMING
-    if (!cfg.sparse && (threadIdx.x & 63) == 0) {
-      const long long ms4 = clock64();
-      mtst[0] = (unsigned int)(ms1 - mt0);
-      mtst[1] = (unsigned int)(ms2 - ms1);
-      mtst[2] = (unsigned int)(ms3 - ms2);
-      mtst[3] = (unsigned int)(ms4 - ms3);
-    }
-#endif
-    const int u2p = (int)(w2p & 0xffffu), u2c = (int)(w2c & 0xffffu), u1c = (int)(w1c & 0xffffu);
-    ok = (i1p2 == qi) && (u0 >= u2p) && (u1c >= u2c);
-    if (ok)
-      m = {(float)u0, (float)v0, qi, (float)u2p, (float)(int)(w2p >> 16), index_of(s2p, p1), (float)u1c,
-           (float)(int)(w1c >> 16), index_of(s1c, p3), (float)u2c, (float)(int)(w2c >> 16), index_of(s2c, p2)};
-  }
-  if (lane == 0) {
-    pair.flag[qi] = ok ? 1 : 0;
-    if (ok) pair.raw[qi] = m;
-  }
-#ifdef VSM_MATCH_TIMING
-  if (!cfg.sparse && (threadIdx.x & 63) == 0) {
-    const long long mt1 = clock64();
-    const unsigned int k = atomicAdd(&vsm_mt_n, 1u);
-    if (k < (1u << 18)) {
-      vsm_mt[k][0] = (unsigned int)(mt1 - mt0);
-      vsm_mt[k][1] = mtst[0];
-      vsm_mt[k][2] = mtst[1];
-      vsm_mt[k][3] = mtst[2];
-      vsm_mt[k][4] = mtst[3];
-      vsm_mt[k][5] = (unsigned int)mtph_[0];
-#if VSM_MATCH_TIMING == 3  // wall clock (100 MHz, one counter for the whole device: s_memtime runs per XCD): life and start
-      vsm_mt[k][6] = (unsigned int)(wall_clock64() - mtw0);
-      vsm_mt[k][7] = (unsigned int)mtw0;
-#else
-      vsm_mt[k][6] = (unsigned int)mtph_[1];
-      vsm_mt[k][7] = (unsigned int)mt0;
-#endif
-    }
-  }
-#endif
-}
-
-// ordered compaction of the accepted queries (push_back order = ascending query index) with the
-// first-come pixel de-dup of flow / stereo (M[] in viso/matcher.cpp:1036-1039, :1078-1081):
-// features sharing a pixel come from one NMS cell, hence are at most 3 indices apart.
-// Two small kernels, 256 queries per block: k_compact_count leaves one survivor count per
-// block, k_compact_write sums the counts of the blocks before it (a few hundred at most) and
-// writes its survivors; nothing is serialised through one block.
-__device__ __forceinline__ bool match_kept(const VsmPair &pair, int method, int i) {
-  if (!pair.flag[i]) return false;
-  if (method < 2) {
-    const float u = pair.raw[i].u1c, v = pair.raw[i].v1c;
-    for (int j = max(i - 3, 0); j < i; j++)
-      if (pair.flag[j] && pair.raw[j].u1c == u && pair.raw[j].v1c == v) return false;
-  }
-  return true;
-}
-
-__global__ void __launch_bounds__(256)
-    k_compact_count(const VsmPair *__restrict__ pairs, const VsmJob *__restrict__ jobs, VsmJob job0, int method, int pass) {
-  __shared__ int s_cnt[4];
-  const VsmPair &pair = pairs[blockIdx.y];
-  const int n_query = (jobs ? jobs[blockIdx.y] : job0).nq[pass];
-  if ((int)blockIdx.x * 256 >= n_query && blockIdx.x > 0) return;
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  const bool keep = i < n_query && match_kept(pair, method, i);
-  const unsigned long long b = __ballot(keep);
-  if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = __popcll(b);
-  __syncthreads();
-  if (threadIdx.x == 0) pair.blockcnt[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-}
-
-__global__ void __launch_bounds__(256)
-    k_compact_write(const VsmPair *__restrict__ pairs, const VsmJob *__restrict__ jobs, VsmJob job0, int method, int pass) {
-  __shared__ int s_red[4];
-  __shared__ int s_cnt[4];
-  const VsmPair &pair = pairs[blockIdx.y];
-  const int n_query = (jobs ? jobs[blockIdx.y] : job0).nq[pass];
-  const int nblk = max((n_query + 255) / 256, 1);  // blocks that hold queries of this pair
-  if ((int)blockIdx.x >= nblk) return;
-  vsm_p_match *__restrict__ list = pass ? pair.list2 : pair.list1;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  // base = survivors of all earlier blocks
-  int part = 0;
-  for (int b = threadIdx.x; b < (int)blockIdx.x; b += 256) part += pair.blockcnt[b];
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) part += __shfl_xor(part, o, 64);
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  const bool keep = i < n_query && match_kept(pair, method, i);
-  const unsigned long long bal = __ballot(keep);
-  if (lane == 0) {
-    s_red[wv] = part;
-    s_cnt[wv] = __popcll(bal);
-  }
-  __syncthreads();
-  int pos = s_red[0] + s_red[1] + s_red[2] + s_red[3];
-  for (int w = 0; w < wv; w++) pos += s_cnt[w];
-  pos += __popcll(bal & ((1ull << lane) - 1ull));
-  if (keep) list[pos] = pair.raw[i];
-  if ((int)blockIdx.x == nblk - 1 && threadIdx.x == 255) {
-    const int total = pos + (keep ? 1 : 0);
-    pair.count[pass] = total;
-    pair.hcount[pass] = total;
-  }
-}
-
-// Quad matching keeps every accepted query (no pixel de-dup, viso/matcher.cpp:1139-1151): ordered compaction of raw[] into
-// the list in ONE launch (the lists behind it, and the Delaunay chain behind those, wait for it).  A workgroup of 256
-// threads takes QUAD_SPAN consecutive queries of a pair: it counts the acceptance flags in front of its span itself (every
-// workgroup reads the pair's flags up to its own - a few KB out of L2 - so no workgroup waits for another), scans its own and
-// moves the records as 16-byte pieces, consecutive lanes consecutive pieces of raw[].  Round 3's form - four workgroups of
-// 1024 threads and 16 KB of LDS per pair - took 35 us per 67 pairs with the GPU to itself and 100-170 us in the pipeline,
-// whatever was in it: a 16-wave workgroup needs four free wave slots on every SIMD of one compute unit plus its LDS at the
-// same moment, and beside the Delaunay chains it waits for that.  Four waves and 4 KB find a place at once.
-// EXPORT (the per-frame path, where a launch of its own for the copy is 8 us of a 0.5 ms frame): 1 - every piece goes to the
-// list's host-mapped copy as well (k_export_list's work), 2 - the pixel (u1c, v1c) of every match as x | y << 16 to xy_dst
-// (k_export_xy's).
-#define QUAD_SPAN 1024
-template <int EXPORT>
-__global__ void __launch_bounds__(256)
-    k_compact_quad(const VsmPair *__restrict__ pairs, const VsmJob *__restrict__ jobs, VsmJob job0, int pass, uint32_t *__restrict__ xy_dst) {
-  __shared__ int s_w[5];
-  __shared__ int s_base[4];
-  __shared__ int s_dst[QUAD_SPAN];  // place of every query of the span in the list, -1 = not accepted
-  const VsmPair &pair = pairs[blockIdx.y];
-  const int n_query = (jobs ? jobs[blockIdx.y] : job0).nq[pass];
-  const int q0 = (int)blockIdx.x * QUAD_SPAN, q1 = min(n_query, q0 + QUAD_SPAN);
-  if (q0 >= n_query && !(blockIdx.x == 0 && n_query == 0)) return;
-  vsm_p_match *__restrict__ list = pass ? pair.list2 : pair.list1;
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  // accepted queries in front of this span: four flags per thread and load
-  int before = 0;
-  {
-    const int4 *f4 = (const int4 *)pair.flag;  // (flag[] is 16-byte aligned, q0 a multiple of 4)
-    for (int i0 = t; i0 < q0 / 4; i0 += 4 * 256) {
-      int4 f[4];
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        const int i = i0 + 256 * k;
-        f[k] = i < q0 / 4 ? f4[i] : make_int4(0, 0, 0, 0);
-      }
-#pragma unroll
-      for (int k = 0; k < 4; k++) before += (f[k].x ? 1 : 0) + (f[k].y ? 1 : 0) + (f[k].z ? 1 : 0) + (f[k].w ? 1 : 0);
-    }
-  }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) before += __shfl_xor(before, o, 64);
-  if (lane == 0) s_base[wv] = before;
-  // own flags: thread t owns queries q0 + 4 t .. q0 + 4 t + 3
-  constexpr int RUN = QUAD_SPAN / 256;
-  int keep[RUN], cnt = 0;
-#pragma unroll
-  for (int k = 0; k < RUN; k++) {
-    const int i = q0 + t * RUN + k;
-    keep[k] = i < q1 ? (pair.flag[i] ? 1 : 0) : 0;
-    cnt += keep[k];
-  }
-  // exclusive scan over the 256 threads
-  int incl = cnt;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += y;
-  }
-  if (lane == 63) s_w[wv] = incl;
-  __syncthreads();
-  int pos = incl - cnt, total = 0, base = 0;
-#pragma unroll
-  for (int w = 0; w < 4; w++) {
-    pos += w < wv ? s_w[w] : 0;
-    total += s_w[w];
-    base += s_base[w];
-  }
-  pos += base;
-#pragma unroll
-  for (int k = 0; k < RUN; k++) s_dst[t * RUN + k] = keep[k] ? pos++ : -1;
-  __syncthreads();
-  {
-    const uint4 *src = (const uint4 *)(pair.raw + q0);
-    uint4 *dst = (uint4 *)list;
-    uint4 *hdst = EXPORT == 1 ? (uint4 *)(pass ? pair.hlist2 : pair.hlist1) : nullptr;
-    const int pieces = 3 * (q1 - q0);
-    for (int p0 = t; p0 < pieces; p0 += 4 * 256) {
-      uint4 v[4];
-      int d[4], part[4];
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        const int p = p0 + 256 * k;
-        const int e = p / 3;
-        part[k] = p - 3 * e;
-        d[k] = p < pieces ? s_dst[e] : -1;
-        if (d[k] >= 0) v[k] = src[p];
-      }
-#pragma unroll
-      for (int k = 0; k < 4; k++)
-        if (d[k] >= 0) {
-          dst[3 * (size_t)d[k] + part[k]] = v[k];
-          if (EXPORT == 1) hdst[3 * (size_t)d[k] + part[k]] = v[k];
-          if (EXPORT == 2 && part[k] == 1)  // (piece 1 of a record: v2p, i2p, u1c, v1c)
-            xy_dst[d[k]] = (uint32_t)(int32_t)__uint_as_float(v[k].z) | ((uint32_t)(int32_t)__uint_as_float(v[k].w) << 16);
-        }
-    }
-  }
-  if (q1 == n_query && t == 255) {  // the span that holds the last query
-    pair.count[pass] = base + total;
-    pair.hcount[pass] = base + total;
-  }
-}
-
-// wide copy of a finished list into host-mapped pinned memory (16 bytes per lane over PCIe):
-// the host reads it after the stream sync, no D2H copy call and no second round trip
-__global__ void __launch_bounds__(256)
-    k_export_list(const VsmPair *__restrict__ pairs, int pass) {
-  const VsmPair &pair = pairs[blockIdx.y];
-  const int n16 = pair.count[pass] * 3;
-  const uint4 *src = (const uint4 *)(pass ? pair.list2 : pair.list1);
-  uint4 *dst = (uint4 *)(pass ? pair.hlist2 : pair.hlist1);
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < n16; i += gridDim.x * 256) dst[i] = src[i];
-}
-
-// the pixel of every match of the compacted pass-2 list as x | y << 16, into host-mapped memory: all the final
-// removeOutliers' triangulation needs of the list ((u1c, v1c), which the refinement leaves alone, viso/matcher.cpp:1544-1577) -
-// the per-frame path's host starts on it while the refinement and the list's export still run
-__global__ void __launch_bounds__(256) k_export_xy(const VsmPair *__restrict__ pairs, uint32_t *__restrict__ dst) {
-  const VsmPair &pair = pairs[0];
-  const int n = pair.count[1];
-  const vsm_p_match *__restrict__ src = pair.list2;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256)
-    dst[i] = (uint32_t)(int32_t)src[i].u1c | ((uint32_t)(int32_t)src[i].v1c << 16);
-}
-
-// ---------------------------------------------------------------------------------------
-// R1 refinement, viso/matcher.cpp:1498-1585.  One thread per (match, relocation step) evaluates
-// the 25 candidate positions with the 16-byte ELAS descriptor (computeSmallDescriptor, :479-506)
-// from the full-resolution Sobel planes; first-wins argmin in (dv, du) order.  Steps: 0 -> (u1p,v1p) [flow, quad], 1 -> (u2c,v2c) [stereo,
-// quad], 2 -> (u2p,v2p) [quad]; each uses the unrefined (u1c,v1c) as its reference (:1544-1577).
-// refinement==2 (parabolicFitting, :1379-1454): 49 lanes of a wave evaluate the 7x7 costs, the
-// 3x3 neighbourhood around the minimum goes to the host, which solves the 9x6 least squares in
-// double exactly as Matrix::solve does.
-// ---------------------------------------------------------------------------------------
-__device__ __forceinline__ uint4 small_desc(const uint8_t *__restrict__ du, const uint8_t *__restrict__ dv, int bpl,
-                                            int u, int v) {
-  const int a2 = v * bpl + u, a1 = a2 - bpl, a0 = a1 - bpl, a3 = a2 + bpl, a4 = a3 + bpl;
-  uint4 r;
-  r.x = du[a0] | (du[a1 - 2] << 8) | (du[a1] << 16) | ((uint32_t)du[a1 + 2] << 24);
-  r.y = du[a2 - 1] | (du[a2] << 8) | (du[a2] << 16) | ((uint32_t)du[a2 + 1] << 24);
-  r.z = du[a3 - 2] | (du[a3] << 8) | (du[a3 + 2] << 16) | ((uint32_t)du[a4] << 24);
-  r.w = dv[a1] | (dv[a2 - 1] << 8) | (dv[a2 + 1] << 16) | ((uint32_t)dv[a3] << 24);
-  return r;
-}
-
-// the same descriptor from the tiled plane
-__device__ __forceinline__ uint4 small_desc_tiled(const uint8_t *__restrict__ t, int bpl, int u, int v) {
-#define TDU(x, y) ((uint32_t)t[vsm_tiled_at(bpl, (x), (y))])
-#define TDV(x, y) ((uint32_t)t[vsm_tiled_at(bpl, (x), (y)) + VSM_TILED_DV])
-  uint4 r;
-  r.x = TDU(u, v - 2) | (TDU(u - 2, v - 1) << 8) | (TDU(u, v - 1) << 16) | (TDU(u + 2, v - 1) << 24);
-  r.y = TDU(u - 1, v) | (TDU(u, v) << 8) | (TDU(u, v) << 16) | (TDU(u + 1, v) << 24);
-  r.z = TDU(u - 2, v + 1) | (TDU(u, v + 1) << 8) | (TDU(u + 2, v + 1) << 16) | (TDU(u, v + 2) << 24);
-  r.w = TDV(u, v - 1) | (TDV(u - 1, v) << 8) | (TDV(u + 1, v) << 16) | (TDV(u, v + 1) << 24);
-#undef TDU
-#undef TDV
-  return r;
-}
-
-__device__ __forceinline__ uint32_t sad16(const uint4 &a, const uint4 &b) {
-  uint32_t s = __builtin_amdgcn_sad_u8(a.x, b.x, 0u);
-  s = __builtin_amdgcn_sad_u8(a.y, b.y, s);
-  s = __builtin_amdgcn_sad_u8(a.z, b.z, s);
-  return __builtin_amdgcn_sad_u8(a.w, b.w, s);
-}
-
-// reference descriptor at (u1c, v1c) of the current left image (computeSmallDescriptor, :479-506):
-// 5 du rows + 3 dv rows, columns u-2..u+2, each as two aligned dwords re-based with a funnel shift
-// (8 wide loads instead of 16 byte gathers)
-template <bool TILED>
-__device__ __forceinline__ uint4 refine_ref_desc(const VsmImage &ref, const VsmDims &dc, int ru, int rv) {
-  uint4 rd;
-  const int b0 = (ru - 2) & ~3, rsh = 8 * ((ru - 2) - b0);
-  uint64_t wu[5], wv[3];
-  if (TILED) {
-    // the two 4-pixel blocks holding columns ru-2 .. ru+2 (vsm_tiled_at of their first pixels)
-    const int j0 = b0 >> 2;
-#pragma unroll
-    for (int r = 0; r < 5; r++) {
-      const uint8_t *row = ref.duv_tiled;
-      const uint32_t lo = ldg_u32(row + vsm_tiled_at(dc.bpl, 4 * j0, rv - 2 + r)), hi = ldg_u32(row + vsm_tiled_at(dc.bpl, 4 * j0 + 4, rv - 2 + r));
-      wu[r] = ((((uint64_t)hi) << 32) | lo) >> rsh;
-      if (r >= 1 && r <= 3) {
-        const uint32_t lv = ldg_u32(row + vsm_tiled_at(dc.bpl, 4 * j0, rv - 2 + r) + VSM_TILED_DV), hv = ldg_u32(row + vsm_tiled_at(dc.bpl, 4 * j0 + 4, rv - 2 + r) + VSM_TILED_DV);
-        wv[r - 1] = ((((uint64_t)hv) << 32) | lv) >> rsh;
-      }
-    }
-  } else {
-#pragma unroll
-    for (int r = 0; r < 5; r++) {
-      const uint32_t *pr = (const uint32_t *)(ref.du_full + (size_t)(rv - 2 + r) * dc.bpl + b0);
-      wu[r] = ((((uint64_t)pr[1]) << 32) | pr[0]) >> rsh;
-    }
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-      const uint32_t *pr = (const uint32_t *)(ref.dv_full + (size_t)(rv - 1 + r) * dc.bpl + b0);
-      wv[r] = ((((uint64_t)pr[1]) << 32) | pr[0]) >> rsh;
-    }
-  }
-#define WB(w, c) ((uint32_t)((w) >> (8 * (c))) & 0xffu)
-  rd.x = WB(wu[0], 2) | (WB(wu[1], 0) << 8) | (WB(wu[1], 2) << 16) | (WB(wu[1], 4) << 24);
-  rd.y = WB(wu[2], 1) | (WB(wu[2], 2) << 8) | (WB(wu[2], 2) << 16) | (WB(wu[2], 3) << 24);
-  rd.z = WB(wu[3], 0) | (WB(wu[3], 2) << 8) | (WB(wu[3], 4) << 16) | (WB(wu[4], 2) << 24);
-  rd.w = WB(wv[0], 2) | (WB(wv[1], 1) << 8) | (WB(wv[1], 3) << 16) | (WB(wv[2], 2) << 24);
-#undef WB
-  return rd;
-}
-
-template <bool TILED>
-__global__ void __launch_bounds__(256)
-    k_refine(const VsmImage *__restrict__ imgs, const VsmPair *__restrict__ pairs, const VsmJob *__restrict__ jobs,
-             VsmJob job0, VsmDims dp, VsmDims dc, int method, int nbx, int npairs) {
-  // One thread per (match, relocation step).  The 9 x 9 du / 7 x 9 dv neighbourhood of the target
-  // is pulled into registers with 48 independent dword loads (rows are 16-byte aligned, each row is
-  // re-based to column u2-4 with a funnel shift), then the 25 candidate descriptors are pure
-  // register byte-picks + v_sad_u8: no dependent gathers, no cross-lane traffic.
-  // flattened grid: logical block -> (pair, block within pair), XCD-contiguous
-  const int lb = xcd_remap(blockIdx.x, gridDim.x);
-  const int pj = lb / nbx, bx = lb - pj * nbx;
-  if (pj >= npairs) return;
-  const VsmJob &jb = jobs ? jobs[pj] : job0;
-  const VsmPair &pair = pairs[pj];
-  const int g = bx * blockDim.x + threadIdx.x;
-  const int mi = g / 3, step = g - mi * 3;
-  const VsmImage &ref = imgs[jb.img_curr];
-  // The reference descriptor of a match is the same for its three steps: lanes 0..21 of a wave compute those of the
-  // wave's (at most 22) matches, one each - a third of the lanes in contiguous quads, which is what the texture
-  // addresser's time goes by - and every lane picks its match's up with a cross-lane read.
-  uint4 rd;
-  {
-    const int lane = threadIdx.x & 63;
-    const int first_mi = (g - lane) / 3, rmi = first_mi + lane;
-    uint4 mine = make_uint4(0, 0, 0, 0);
-    if (lane < 22 && rmi < pair.count[1]) {
-      const vsm_p_match *rm = pair.list2 + rmi;
-      mine = refine_ref_desc<TILED>(ref, dc, (int)rm->u1c, (int)rm->v1c);
-    }
-    const int src = mi - first_mi;
-    rd.x = (uint32_t)__shfl((int)mine.x, src, 64);
-    rd.y = (uint32_t)__shfl((int)mine.y, src, 64);
-    rd.z = (uint32_t)__shfl((int)mine.z, src, 64);
-    rd.w = (uint32_t)__shfl((int)mine.w, src, 64);
-  }
-  if (mi >= pair.count[1]) return;
-  if (step == 0 && !(method == 0 || method == 2)) return;
-  if (step == 1 && !(method == 1 || method == 2)) return;
-  if (step == 2 && method != 2) return;
-  vsm_p_match *m = pair.list2 + mi;  // refined in place (each step owns its two fields)
-  const VsmImage &tgt = step == 0 ? imgs[jb.img_prev] : (step == 1 ? imgs[jb.img_curr + 1] : imgs[jb.img_prev + 1]);
-  const VsmDims &dt = step == 1 ? dc : dp;
-  float *pu = step == 0 ? &m->u1p : (step == 1 ? &m->u2c : &m->u2p);
-  float *pv = pu + 1;
-  const float u2 = *pu, v2 = *pv;
-  if (u2 - 2 < VSM_MARGIN || u2 + 2 > dt.w - 1 - VSM_MARGIN || v2 - 2 < VSM_MARGIN || v2 + 2 > dt.h - 1 - VSM_MARGIN)
-    return;
-  const int iu = (int)u2, iv = (int)v2;
-  uint32_t U[9][3], V[9][3];
-  if (TILED) {
-    // tiled plane: the 9 columns iu-4 .. iu+4 start at pixel o = (iu-4) & 7 of a tile row and end in the next tile; one
-    // 16-byte load per tile row brings du 0-3, dv 0-3, du 4-7, dv 4-7
-    const int o = (iu - 4) & 7, b = o >> 2;
-    const uint32_t sb = (uint32_t)(o & 3);
-#pragma unroll
-    for (int r = 0; r < 9; r++) {
-      const uint8_t *pr = tgt.duv_tiled + vsm_tiled_at(dt.bpl, (iu - 4) & ~7, iv - 4 + r);
-      const uint4 t0 = ldg_u4(pr), t1 = ldg_u4(pr + 128);
-      const uint32_t d0 = b ? t0.z : t0.x, d1 = b ? t1.x : t0.z, d2 = b ? t1.z : t1.x;
-      U[r][0] = __builtin_amdgcn_alignbyte(d1, d0, sb);
-      U[r][1] = __builtin_amdgcn_alignbyte(d2, d1, sb);
-      U[r][2] = d2 >> (8 * sb);
-      const uint32_t e0 = b ? t0.w : t0.y, e1 = b ? t1.y : t0.w, e2 = b ? t1.w : t1.y;
-      V[r][0] = __builtin_amdgcn_alignbyte(e1, e0, sb);
-      V[r][1] = __builtin_amdgcn_alignbyte(e2, e1, sb);
-      V[r][2] = e2 >> (8 * sb);
-    }
-  } else {
-    const int a0 = (iu - 4) & ~3, sh = 8 * ((iu - 4) - a0);
-#pragma unroll
-    for (int r = 0; r < 9; r++) {
-      const uint32_t *pr = (const uint32_t *)(tgt.du_full + (size_t)(iv - 4 + r) * dt.bpl + a0);
-      const uint32_t d0 = pr[0], d1 = pr[1], d2 = pr[2];
-      U[r][0] = (uint32_t)((((uint64_t)d1 << 32) | d0) >> sh);
-      U[r][1] = (uint32_t)((((uint64_t)d2 << 32) | d1) >> sh);
-      U[r][2] = d2 >> sh;
-      if (r >= 1 && r <= 7) {
-        const uint32_t *qr = (const uint32_t *)(tgt.dv_full + (size_t)(iv - 4 + r) * dt.bpl + a0);
-        const uint32_t e0 = qr[0], e1 = qr[1], e2 = qr[2];
-        V[r][0] = (uint32_t)((((uint64_t)e1 << 32) | e0) >> sh);
-        V[r][1] = (uint32_t)((((uint64_t)e2 << 32) | e1) >> sh);
-        V[r][2] = e2 >> sh;
-      } else {
-        V[r][0] = V[r][1] = V[r][2] = 0;
-      }
-    }
-  }
-#define UB(r, c) ((U[(r)][(c) >> 2] >> (8 * ((c)&3))) & 0xffu)
-#define VB(r, c) ((V[(r)][(c) >> 2] >> (8 * ((c)&3))) & 0xffu)
-  uint32_t best = 0xffffffffu;
-  int ind = 0;
-#pragma unroll
-  for (int ddv = 0; ddv < 5; ddv++) {
-#pragma unroll
-    for (int ddu = 0; ddu < 5; ddu++) {
-      const int r = ddv + 2, c = ddu + 2;  // candidate centre in window coordinates
-      uint4 t;
-      t.x = UB(r - 2, c) | (UB(r - 1, c - 2) << 8) | (UB(r - 1, c) << 16) | (UB(r - 1, c + 2) << 24);
-      t.y = UB(r, c - 1) | (UB(r, c) << 8) | (UB(r, c) << 16) | (UB(r, c + 1) << 24);
-      t.z = UB(r + 1, c - 2) | (UB(r + 1, c) << 8) | (UB(r + 1, c + 2) << 16) | (UB(r + 2, c) << 24);
-      t.w = VB(r - 1, c) | (VB(r, c - 1) << 8) | (VB(r, c + 1) << 16) | (VB(r + 1, c) << 24);
-      const uint32_t cost = sad16(rd, t);
-      if (cost < best) {  // first minimum in (dv, du) order, viso/matcher.cpp:1484-1491
-        best = cost;
-        ind = ddv * 5 + ddu;
-      }
-    }
-  }
-#undef UB
-#undef VB
-  *pu = (float)((double)u2 + ((double)(float)(ind % 5) - 2.0));
-  *pv = (float)((double)v2 + ((double)(float)(ind / 5) - 2.0));
-}
-
-__global__ void __launch_bounds__(256)
-    k_parabolic_costs(const VsmImage *__restrict__ imgs, const VsmPair *__restrict__ pairs,
-                      const VsmJob *__restrict__ jobs, VsmJob job0, VsmDims dp, VsmDims dc, int method) {
-  const VsmJob &jb = jobs ? jobs[blockIdx.y] : job0;
-  const VsmPair &pair = pairs[blockIdx.y];
-  const int img_prev = jb.img_prev, img_curr = jb.img_curr;
-  const int lane = threadIdx.x & 63;
-  const int g = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;  // one wave per (match, step)
-  const int mi = g / 3, step = g - mi * 3;
-  if (mi >= pair.count[1]) return;
-  int32_t *out = pair.pf + ((size_t)mi * 3 + step) * 12;
-  bool active = !((step == 0 && !(method == 0 || method == 2)) || (step == 1 && !(method == 1 || method == 2)) ||
-                  (step == 2 && method != 2));
-  if (!active) {
-    if (lane == 0) out[0] = 2;  // step not applicable
-    return;
-  }
-  const vsm_p_match *m = pair.list2 + mi;
-  const VsmImage &ref = imgs[img_curr];
-  const VsmImage &tgt = step == 0 ? imgs[img_prev] : (step == 1 ? imgs[img_curr + 1] : imgs[img_prev + 1]);
-  const VsmDims &dt = step == 1 ? dc : dp;
-  const float u2 = step == 0 ? m->u1p : (step == 1 ? m->u2c : m->u2p);
-  const float v2 = step == 0 ? m->v1p : (step == 1 ? m->v2c : m->v2p);
-  if (u2 - 3 < VSM_MARGIN || u2 + 3 > dt.w - 1 - VSM_MARGIN || v2 - 3 < VSM_MARGIN || v2 + 3 > dt.h - 1 - VSM_MARGIN) {
-    if (lane == 0) out[0] = 0;  // infeasible: match dropped (wave-uniform branch)
-    return;
-  }
-  const bool tiled = ref.duv_tiled != nullptr;
-  const uint4 r = tiled ? small_desc_tiled(ref.duv_tiled, dc.bpl, (int)m->u1c, (int)m->v1c)
-                        : small_desc(ref.du_full, ref.dv_full, dc.bpl, (int)m->u1c, (int)m->v1c);
-  uint32_t key = 0xffffffffu;
-  int cost = 0;
-  if (lane < 49) {
-    const int ddv = lane / 7, ddu = lane - ddv * 7;
-    const uint4 t = tiled ? small_desc_tiled(tgt.duv_tiled, dt.bpl, (int)u2 + ddu - 3, (int)v2 + ddv - 3)
-                          : small_desc(tgt.du_full, tgt.dv_full, dt.bpl, (int)u2 + ddu - 3, (int)v2 + ddv - 3);
-    cost = (int)sad16(r, t);
-    key = ((uint32_t)cost << 6) | (uint32_t)lane;
-  }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) key = min(key, (uint32_t)__shfl_xor((int)key, o, 64));
-  // key is now wave-uniform: first minimum in (dv, du) order
-  const int ind = key & 63, du = ind % 7, dv = ind / 7;
-  const bool border = (du == 0 || du == 6 || dv == 0 || dv == 6);
-  int c9[9];
-#pragma unroll
-  for (int k = 0; k < 9; k++) {
-    int src = border ? 0 : (dv + k / 3 - 1) * 7 + (du + k % 3 - 1);
-    c9[k] = __shfl(cost, src, 64);
-  }
-  if (lane == 0) {
-    if (border) {
-      out[0] = 0;
-    } else {
-      out[0] = 1;
-      out[1] = du;
-      out[2] = dv;
-#pragma unroll
-      for (int k = 0; k < 9; k++) out[3 + k] = c9[k];
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------
-// refinement==2 in the batched (look-ahead) path: the least-squares tail of parabolicFitting (viso/matcher.cpp:1425-1453;
-// host form: vsm_host_parabolic_update, vsm_host.cpp) and the removal of the matches whose fit fails (:1541-1581), on the
-// device.  Matrix::operator* and Matrix::solve (Gauss-Jordan with full pivoting, viso/matrix.cpp) are + - * / and
-// comparisons in double, evaluated here in the reference's order: IEEE arithmetic on either side, contraction off, so the
-// same bits.  One workgroup per pair: every thread fits its matches and parks the updated records in raw[], a scan over
-// the verdicts gives the survivors their places, the records move back into the list as 16-byte pieces.
-// ---------------------------------------------------------------------------------------
-// The system matrix At*A is the same for every fit, so the elimination's pivots, row swaps and multipliers are too: the
-// host runs Gauss-Jordan on it ONCE (same IEEE double arithmetic, contraction off) and records, per step, what the
-// reference does to the right-hand side - swap B[irow], B[icol]; B[icol] *= pivinv; B[ll] -= B[icol] * dum[ll] - and the
-// device replays exactly those operations on every fit's b: the same bits as solving the whole system each time, without
-// a 6 x 6 matrix per thread.
-struct VsmParaPlan {
-  int32_t ok, irow[6], icol[6];
-  double pivinv[6], dum[6][6];
-};
-static const double kParaA[9][6] = {{1, 1, 1, -1, -1, 1}, {0, 1, 0, 0, -1, 1}, {1, 1, -1, 1, -1, 1}, {1, 0, 0, -1, 0, 1}, {0, 0, 0, 0, 0, 1},
-                                    {1, 0, 0, 1, 0, 1},   {1, 1, -1, -1, 1, 1}, {0, 1, 0, 0, 1, 1},  {1, 1, 1, 1, 1, 1}};
-static VsmParaPlan make_para_plan() {  // Matrix::solve (viso/matrix.cpp) on At*A, the right-hand side's share recorded
-  VsmParaPlan pl = VsmParaPlan();
-  double A[6][6];
-  for (int i = 0; i < 6; i++)
-    for (int j = 0; j < 6; j++) {
-      double t = 0;
-      for (int k = 0; k < 9; k++) t += kParaA[k][i] * kParaA[k][j];
-      A[i][j] = t;
-    }
-  int ipiv[6] = {0, 0, 0, 0, 0, 0};
-  int icol = 0, irow = 0;
-  pl.ok = 1;
-  for (int i = 0; i < 6; i++) {
-    double big = 0.0;
-    for (int j = 0; j < 6; j++)
-      if (ipiv[j] != 1)
-        for (int k = 0; k < 6; k++)
-          if (ipiv[k] == 0 && fabs(A[j][k]) >= big) {
-            big = fabs(A[j][k]);
-            irow = j;
-            icol = k;
-          }
-    ++ipiv[icol];
-    pl.irow[i] = irow;
-    pl.icol[i] = icol;
-    if (irow != icol)
-      for (int l = 0; l < 6; l++) std::swap(A[irow][l], A[icol][l]);
-    if (fabs(A[icol][icol]) < 1e-20) {
-      pl.ok = 0;
-      return pl;
-    }
-    const double pivinv = 1.0 / A[icol][icol];
-    pl.pivinv[i] = pivinv;
-    A[icol][icol] = 1.0;
-    for (int l = 0; l < 6; l++) A[icol][l] *= pivinv;
-    for (int ll = 0; ll < 6; ll++)
-      if (ll != icol) {
-        const double dum = A[ll][icol];
-        pl.dum[i][ll] = dum;
-        A[ll][icol] = 0.0;
-        for (int l = 0; l < 6; l++) A[ll][l] -= A[icol][l] * dum;
-      }
-  }
-  return pl;
-}
-__device__ inline double para_get(const double b[6], int i) {
-  return i == 0 ? b[0] : (i == 1 ? b[1] : (i == 2 ? b[2] : (i == 3 ? b[3] : (i == 4 ? b[4] : b[5]))));
-}
-__device__ inline void para_set(double b[6], int i, double v) {
-#pragma unroll
-  for (int k = 0; k < 6; k++) b[k] = k == i ? v : b[k];
-}
-__device__ inline bool dev_parabolic_update(const VsmParaPlan &pl, const int32_t *c9, int du, int dv, float &u2, float &v2) {
-  constexpr double kA[9][6] = {{1, 1, 1, -1, -1, 1}, {0, 1, 0, 0, -1, 1}, {1, 1, -1, 1, -1, 1}, {1, 0, 0, -1, 0, 1}, {0, 0, 0, 0, 0, 1},
-                               {1, 0, 0, 1, 0, 1},   {1, 1, -1, -1, 1, 1}, {0, 1, 0, 0, 1, 1},  {1, 1, 1, 1, 1, 1}};
-  double b[6];
-#pragma unroll
-  for (int i = 0; i < 6; i++) {  // b = At * c (Matrix::operator*: the sum over k in order, zero terms included)
-    double s = 0;
-#pragma unroll
-    for (int k = 0; k < 9; k++) s += kA[k][i] * (double)c9[k];
-    b[i] = s;
-  }
-  if (!pl.ok) return false;
-#pragma unroll
-  for (int i = 0; i < 6; i++) {
-    const int irow = pl.irow[i], icol = pl.icol[i];
-    if (irow != icol) {
-      const double x = para_get(b, irow), y = para_get(b, icol);
-      para_set(b, irow, y);
-      para_set(b, icol, x);
-    }
-    const double bc = para_get(b, icol) * pl.pivinv[i];
-    para_set(b, icol, bc);
-#pragma unroll
-    for (int ll = 0; ll < 6; ll++)
-      if (ll != icol) b[ll] -= bc * pl.dum[i][ll];
-  }
-  const float divisor = (float)(b[2] * b[2] - 4.0 * b[0] * b[1]);
-  if ((double)fabsf(divisor) < 1e-8 || fabs(b[2]) < 1e-8) return false;
-  const float ddv = (float)((2.0 * b[0] * b[4] - b[2] * b[3]) / (double)divisor);
-  const float ddu = (float)(-(b[4] + 2.0 * b[1] * (double)ddv) / b[2]);
-  if ((double)fabsf(ddu) >= 1.0 || (double)fabsf(ddv) >= 1.0) return false;
-  u2 = (float)((double)u2 + ((double)(float)du - 3.0 + (double)ddu));
-  v2 = (float)((double)v2 + ((double)(float)dv - 3.0 + (double)ddv));
-  return true;
-}
-#define PARA_MAX_LIST 16384  // matches per pair this kernel takes (16-bit places in LDS)
-__global__ void __launch_bounds__(1024) k_parabolic_apply(const VsmPair *__restrict__ pairs, VsmParaPlan pl) {
-  __shared__ uint16_t s_dst[PARA_MAX_LIST];  // the match's place among the survivors, 0xffff = dropped
-  __shared__ int s_w[17];
-  const VsmPair &pair = pairs[blockIdx.x];
-  const int n = min(pair.count[1], PARA_MAX_LIST);
-  const int t = threadIdx.x;
-  // thread t owns the run of matches [t * run, t * run + run)
-  const int run = (n + 1023) / 1024;
-  int cnt = 0;
-  for (int k = 0; k < run; k++) {
-    const int i = t * run + k;
-    if (i >= n) break;
-    vsm_p_match m = pair.list2[i];
-    bool ok = true;
-    float *tu[3] = {&m.u1p, &m.u2c, &m.u2p}, *tv[3] = {&m.v1p, &m.v2c, &m.v2p};
-    for (int st = 0; st < 3 && ok; st++) {
-      const int32_t *r = pair.pf + ((size_t)i * 3 + st) * 12;
-      if (r[0] == 2) continue;  // step not applicable to the matching method
-      ok = r[0] == 1 && dev_parabolic_update(pl, r + 3, r[1], r[2], *tu[st], *tv[st]);
-    }
-    pair.raw[i] = m;
-    s_dst[i] = ok ? 1 : 0;
-    cnt += ok ? 1 : 0;
-  }
-  int total;
-  int pos = block_excl_scan_1024(cnt, total, s_w);
-  for (int k = 0; k < run; k++) {
-    const int i = t * run + k;
-    if (i >= n) break;
-    s_dst[i] = s_dst[i] ? (uint16_t)pos++ : (uint16_t)0xffffu;
-  }
-  __syncthreads();  // (raw[] written above is read below by other threads of this workgroup, and only by them)
-  const uint4 *src = (const uint4 *)pair.raw;
-  uint4 *dst = (uint4 *)pair.list2;
-  for (int p = t; p < 3 * n; p += 1024) {
-    const int e = p / 3;
-    const uint32_t d = s_dst[e];
-    if (d != 0xffffu) dst[3 * (size_t)d + (p - 3 * e)] = src[p];
-  }
-  if (t == 0) {
-    pair.count[1] = total;
-    pair.hcount[1] = total;
-  }
-}
-
-// ---------------------------------------------------------------------------------------
-// Small tables (job descriptions of a chunk: 10-20 KB) from pinned host memory to HBM by a kernel on the stream that needs
-// them, not by hipMemcpyAsync.  The runtime takes a copy of more than 16 KB to a DMA engine, and when that engine is busy
-// with another upload - two chunks' tables now and then - it falls back to a shader copy on a hardware queue of its own,
-// which it creates then and there: 180 MB of context-save area mapped and touched, 6-7 ms during which every launch of
-// the process waits (the "once per process" stall of round 4; tools/stall_probe.py, tools/shim/mmap_trace.c).
-// ---------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_upload(uint32_t *__restrict__ dst, const uint32_t *__restrict__ src, int n_words) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n_words) dst[i] = src[i];
-}
 // Head records of the dense set's fine bins (VsmSet::heads): dword 0 = the bin's start in the sorted arrays, dwords 1..15 = the
 // packed coordinates of the 15 candidates from there on, whatever bins they lie in (a search window's run of candidates is
 // consecutive in that order: fine rows vfmin..vfmax of one (class, u-bin) column).  k_match's second pass reads a window's bin
-// start AND its candidates' coordinates in one round trip: measured on the benchmark sequence (tools/match_timing.py,
-// -DVSM_MATCH_TIMING=2), 15 inline candidates cover every lane's longest run in 99.9-100 % of a wave's stages, 7 in 1.7 %
-// (groups sharing a run) / 41.7 % (a lane per bin), 3 in 0.4 % - a wave saves the trip only if all of its lanes do.
+// start AND its candidates' coordinates in one round trip: measured on the benchmark sequence (the trip-counting build of
+// k_match that a9ef39f was the last commit to carry), 15 inline candidates cover every lane's longest run in 99.9-100 % of
+// a wave's stages, 7 in 1.7 % (groups sharing a run) / 41.7 % (a lane per bin), 3 in 0.4 % - a wave saves the trip only if
+// all of its lanes do.
 // One thread per (bin, quarter of the record).
 __global__ void __launch_bounds__(256) k_feat_heads(const VsmImage *__restrict__ imgs, int first, int nb) {
   const VsmSet &st = imgs[first + blockIdx.y].set[1];
@@ -2752,18 +1368,9 @@ __global__ void __launch_bounds__(256) k_feat_heads(const VsmImage *__restrict__
   st.heads[b * 4 + j] = make_uint4(w[0], w[1], w[2], w[3]);
 }
 
-hipError_t vsm_upload(hipStream_t s, void *dst_device, const void *src_pinned, size_t bytes) {
-  if (bytes == 0) return hipSuccess;
-  if ((bytes & 3) || ((uintptr_t)dst_device & 3) || ((uintptr_t)src_pinned & 3)) return hipMemcpyAsync(dst_device, src_pinned, bytes, hipMemcpyHostToDevice, s);
-  const int n = (int)(bytes >> 2);
-  hipLaunchKernelGGL(k_upload, dim3((n + 255) / 256), dim3(256), 0, s, (uint32_t *)dst_device, (const uint32_t *)src_pinned, n);
-  return hipGetLastError();
-}
-
 // =======================================================================================
 // launchers
 // =======================================================================================
-static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // plan of k_feat_order for a geometry; false = it does not fit (huge search bins or suppression cells: the separate kernels)
 static bool vsm_order_plan(const VsmDims &d, const VsmImage &im, int set_lo, int binsize, int nb, VsmOrderPlan &pl) {
@@ -2954,100 +1561,3 @@ int vsm_launch_features(hipStream_t s, VsmProf &pf, const VsmImage *d_imgs, int 
   return (!fuse || (fused & 2)) ? 1 : 0;
 }
 
-// One launch serves `npairs` frame pairs (blockIdx.y); jobs == nullptr: the single pair job0.
-// pass: 0 = sparse lists (list1/hlist1/count[0]), 1 = dense lists.  max_nq bounds nq[pass].
-bool vsm_launch_match(hipStream_t s, VsmProf &pf, const VsmImage *d_imgs, const VsmPair *d_pairs, const VsmJob *d_jobs,
-                      const VsmJob &job0, int npairs, const VsmDims &d, const VsmMatchCfg &cfg, int max_nq, int fuse_export, uint32_t *xy_dst) {
-  // lanes per query: the chain is latency-bound per wavefront, so big batches want many
-  // queries per wave (G = 2..4) and a lone frame pair wants more lanes per query (G = 8).
-  const long total_q = (long)npairs * max_nq;
-#ifndef VSM_MATCH_GBIG
-#define VSM_MATCH_GBIG 2
-#endif
-  const int G = total_q >= 200000 ? VSM_MATCH_GBIG : (total_q >= 30000 ? 4 : 8);
-  const int pass = cfg.sparse ? 0 : 1;
-  if (max_nq > 0) {
-    pf.begin(cfg.sparse ? VSM_K_MATCH1 : VSM_K_MATCH2, s);
-    const int nbx = cdiv(max_nq * G, VSM_MATCH_BLOCK);
-    const dim3 grid(((nbx * npairs + 7) / 8) * 8);
-    // without prior boxes (first pass, single-pass matching) the lanes of a group take whole u-bins
-#define VSM_MATCH_LAUNCH(GG)                                                                                                       \
-  do {                                                                                                                             \
-    if (cfg.use_prior && cfg.heads && !cfg.sparse)                                                                                 \
-      hipLaunchKernelGGL((k_match<GG, false, true>), grid, dim3(VSM_MATCH_BLOCK), 0, s, d_imgs, d_pairs, d_jobs, job0, d, cfg, nbx, npairs); \
-    else if (cfg.use_prior)                                                                                                        \
-      hipLaunchKernelGGL((k_match<GG, false>), grid, dim3(VSM_MATCH_BLOCK), 0, s, d_imgs, d_pairs, d_jobs, job0, d, cfg, nbx, npairs); \
-    else                                                                                                                           \
-      hipLaunchKernelGGL((k_match<GG, true>), grid, dim3(VSM_MATCH_BLOCK), 0, s, d_imgs, d_pairs, d_jobs, job0, d, cfg, nbx, npairs);  \
-  } while (0)
-    if (G == 1)
-      VSM_MATCH_LAUNCH(1);
-    else if (G == 2)
-      VSM_MATCH_LAUNCH(2);
-    else if (G == 4)
-      VSM_MATCH_LAUNCH(4);
-    else if (G == 16)
-      VSM_MATCH_LAUNCH(16);
-    else
-      VSM_MATCH_LAUNCH(8);
-    pf.end(s);
-  }
-  const int nblk = max(cdiv(max_nq, 256), 1);
-  pf.begin(cfg.sparse ? VSM_K_COMPACT1 : VSM_K_COMPACT2, s);
-  bool fused = false;
-  if (cfg.method == 2) {
-    const dim3 grid(std::max(1, cdiv(max_nq, QUAD_SPAN)), npairs);
-    if (fuse_export == 1)
-      hipLaunchKernelGGL(k_compact_quad<1>, grid, dim3(256), 0, s, d_pairs, d_jobs, job0, pass, nullptr);
-    else if (fuse_export == 2 && xy_dst && npairs == 1)
-      hipLaunchKernelGGL(k_compact_quad<2>, grid, dim3(256), 0, s, d_pairs, d_jobs, job0, pass, xy_dst);
-    else
-      hipLaunchKernelGGL(k_compact_quad<0>, grid, dim3(256), 0, s, d_pairs, d_jobs, job0, pass, nullptr);
-    fused = fuse_export == 1 || (fuse_export == 2 && xy_dst && npairs == 1);
-  } else {
-    hipLaunchKernelGGL(k_compact_count, dim3(nblk, npairs), dim3(256), 0, s, d_pairs, d_jobs, job0, cfg.method, pass);
-    hipLaunchKernelGGL(k_compact_write, dim3(nblk, npairs), dim3(256), 0, s, d_pairs, d_jobs, job0, cfg.method, pass);
-  }
-  pf.end(s);
-  return fused;  // the export asked for went along with the compaction (quad matching): no launch of its own
-}
-
-void vsm_launch_export(hipStream_t s, VsmProf &pf, const VsmPair *d_pairs, int npairs, int pass, int n_upper) {
-  pf.begin(VSM_K_EXPORT, s);
-  hipLaunchKernelGGL(k_export_list, dim3(max(min(cdiv(n_upper * 3, 256), 256), 1), npairs), dim3(256), 0, s, d_pairs,
-                     pass);
-  pf.end(s);
-}
-
-void vsm_launch_export_xy(hipStream_t s, const VsmPair *d_pairs, uint32_t *dst_host_mapped, int n_upper) {
-  hipLaunchKernelGGL(k_export_xy, dim3(max(min(cdiv(n_upper, 256), 64), 1)), dim3(256), 0, s, d_pairs, dst_host_mapped);
-}
-
-// the batched tail of refinement==2 (behind vsm_launch_refine): fits, dropped matches, the lists closed up again
-void vsm_launch_parabolic_apply(hipStream_t s, VsmProf &pf, const VsmPair *d_pairs, int npairs) {
-  if (npairs <= 0) return;
-  static const VsmParaPlan plan = make_para_plan();
-  pf.begin(VSM_K_PARA_APPLY, s);
-  hipLaunchKernelGGL(k_parabolic_apply, dim3(npairs), dim3(1024), 0, s, d_pairs, plan);
-  pf.end(s);
-}
-
-void vsm_launch_refine(hipStream_t s, VsmProf &pf, const VsmImage *d_imgs, const VsmPair *d_pairs, const VsmJob *d_jobs,
-                       const VsmJob &job0, int npairs, const VsmDims &dp, const VsmDims &dc, int method, int refinement,
-                       int n_upper) {
-  // n_upper bounds the list sizes (they are still device-only); surplus groups exit at once
-  if (n_upper <= 0) return;
-  pf.begin(VSM_K_REFINE, s);
-  if (refinement == 2)
-    hipLaunchKernelGGL(k_parabolic_costs, dim3(cdiv(n_upper * 3 * 64, 256), npairs), dim3(256), 0, s, d_imgs, d_pairs,
-                       d_jobs, job0, dp, dc, method);
-  else
-  {
-    const int nbx = cdiv(n_upper * 3, 256), tot = ((nbx * npairs + 7) / 8) * 8;
-    if (dc.scale == 2)
-      hipLaunchKernelGGL(k_refine<true>, dim3(tot), dim3(256), 0, s, d_imgs, d_pairs, d_jobs, job0, dp, dc, method, nbx, npairs);
-    else
-      hipLaunchKernelGGL(k_refine<false>, dim3(tot), dim3(256), 0, s, d_imgs, d_pairs, d_jobs, job0, dp, dc, method, nbx, npairs);
-  }
-  pf.end(s);
-}

@@ -1,5 +1,5 @@
 // Internal structures shared by the host orchestration (vsm_api.cpp) and the gfx950 kernels
-// (vsm_kernels.hip).  Nothing here is part of the C-ABI (include/visomatch.h).
+// (vsm_image.hip, vsm_match.hip).  Nothing here is part of the C-ABI (include/visomatch.h).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -42,7 +42,7 @@ struct VsmImage {
   uint8_t *imgm;     // matching-resolution image: half image, or == img
   uint8_t *du, *dv;  // matching-resolution Sobel responses
   uint8_t *du_full, *dv_full;  // full-resolution Sobel responses when the matching resolution IS the full one (== du, dv); else null
-  uint8_t *duv_tiled;          // half_resolution: both full-resolution responses in 8 x 8 tiles (vsm_tiled_at in vsm_kernels.hip); else null
+  uint8_t *duv_tiled;          // half_resolution: both full-resolution responses in 8 x 8 tiles (vsm_tiled_at in vsm_dev.h); else null
   VsmSet set[2];     // 0 sparse, 1 dense
 };
 
@@ -159,13 +159,12 @@ struct VsmProf {
   }
 };
 
-// ---- launchers (vsm_kernels.hip) ----
-// small table in pinned (hipHostMalloc) memory -> HBM by a kernel on stream s (see k_upload)
-hipError_t vsm_upload(hipStream_t s, void *dst_device, const void *src_pinned, size_t bytes);
 // Device memory of the library's large blocks (vsm_api.cpp): a released block of 8 MB or more goes to a process-wide cache
 // instead of back to the driver, and the next request of about its size takes it from there.
 hipError_t vsm_dev_alloc(void **p, size_t bytes);
 void vsm_dev_free(void *p);
+
+// ---- launchers of the image side (vsm_image.hip) ----
 void vsm_launch_ingest(hipStream_t s, VsmProf &pf, const VsmImage *d_imgs, int first, const uint8_t *src0,
                        const uint8_t *src1, size_t frame_stride, int32_t src_bpl, int n_frames, const VsmDims &d);
 // fused: bit 0 = the fused filter + suppression tiles where the radii allow, bit 1 = they also write f1 / f2 (debug getter),
@@ -178,6 +177,10 @@ void vsm_launch_front(hipStream_t s, VsmProf &pf, const VsmImage *d_imgs, int fi
 int vsm_launch_features(hipStream_t s, VsmProf &pf, const VsmImage *d_imgs, int first, int n_img, const VsmDims &d,
                         int16_t *f1, int16_t *f2, size_t f_stride, int nms_tau, int multi_stage, int half_res,
                         int binsize, const VsmImage *h_imgs, int front_done = 0, int fused = 1);
+
+// ---- launchers of the pair side (vsm_match.hip) ----
+// small table in pinned (hipHostMalloc) memory -> HBM by a kernel on stream s (see k_upload)
+hipError_t vsm_upload(hipStream_t s, void *dst_device, const void *src_pinned, size_t bytes);
 // fuse_export (quad matching only; the return value says whether it happened): 1 - the compacted list also goes to its host-mapped
 // copy (what vsm_launch_export does), 2 - pair 0's pixels go to xy_dst (what vsm_launch_export_xy does)
 bool vsm_launch_match(hipStream_t s, VsmProf &pf, const VsmImage *d_imgs, const VsmPair *d_pairs, const VsmJob *d_jobs,

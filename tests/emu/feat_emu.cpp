@@ -1,4 +1,4 @@
-// CPU emulation of the fused matching-resolution kernels k_feat_dense / k_feat_sparse (vsm_kernels.hip): the very
+// CPU emulation of the fused matching-resolution kernels k_feat_dense / k_feat_sparse (vsm_image.hip): the very
 // per-thread functions of csrc/vsm_feat.h, walked tile by tile and thread by thread with the kernels' phase structure
 // (fill | patches | suppression; the sparse tile one plane at a time).  Test infrastructure only: `tests/test_feat_emu.py`
 // compares the planes and survivors with the oracle's filters and nonMaximumSuppression.

@@ -178,7 +178,7 @@ def _oracle_run(B, w, h, n, params, method):
 
 
 FUSED, FALLBACK = "k_feat_scan + k_feat_order", "k_scan_cells + k_emit + k_bin_*"
-# (frame, parameters, frames pushed, record / bin order the geometry takes - vsm_order_plan, vsm_kernels.hip)
+# (frame, parameters, frames pushed, record / bin order the geometry takes - vsm_order_plan, vsm_image.hip)
 GEOMETRIES = {
     "3000x1500 half, histogram 141 KB": (3000, 1500, {}, 2, FUSED),
     "3072x1536 half, histogram 150.2 KB": (3072, 1536, {}, 2, FALLBACK),
