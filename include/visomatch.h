@@ -136,6 +136,36 @@ void vsm_sequence_get_timings(vsm_handle *h, double *out4);
  * matching pass to the survivors; the host only runs Triangle's vertex sort), 1 = host-shared (VSM_SEQ_V2=0, or a list
  * the device chain declines) */
 int32_t vsm_sequence_path(vsm_handle *h);
+/* ---- arbitrary frame pairs of an image set in one call ----
+ * left / right: n_frames images frame_stride bytes apart, host memory or (on_device != 0) HBM, laid out as for
+ * vsm_sequence_run; right == NULL is mono input (one image per frame).  pairs: n_pairs x {previous frame, current frame}.
+ * The list of pair k = (a, b) is, byte for byte, getMatches() of a FRESH Matcher with the handle's parameters and
+ * intrinsics after
+ *     pushBack(frame a);  pushBack(frame b);  matchFeatures(method, Tr_delta of pair k if given and valid)
+ * so i1p / i2p index frame a's feature sets and i1c / i2c frame b's.  Where matchFeatures would return early (an image
+ * without features; mono input with method 1 or 2) the pair's list is empty and the call still returns VSM_OK.  With
+ * method 1 the previous frame is not read and may be -1.  a == b and repeated pairs are allowed.
+ * Tr_delta: NULL or n_pairs x 12 doubles, Tr_valid: NULL (all valid) or n_pairs flags - both per PAIR.
+ * VSM_EARG before anything is enqueued, the previous call's lists left in place: a frame index outside [0, n_frames) (a
+ * previous frame of -1 with method 0 or 2 included), n_pairs <= 0, pairs == NULL, a method outside 0..2.
+ * Every frame goes through the image side once, however many pairs name it, and all sides * n_frames images stay in HBM
+ * for the call (INTEGRATION.md has the bytes per image); the pairs then go through both matching passes, the refinement
+ * and the exact-Delaunay chains in chunks of at most C pairs (option "pairs_chunk"; 0 = the look-ahead call's chunk rule
+ * for device-resident frames), a chunk's survivors are copied into per-pair host lists, so host memory grows with the
+ * matches found.  What the device chain cannot take - more than 1024 statistics bins, a list beyond its limits, a list
+ * it declined - goes pair by pair through the per-frame code: the call never fails where the per-frame API would succeed.
+ * The streaming ring (vsm_push_back / vsm_match / vsm_get_matches and the stage views) and the results and state of
+ * vsm_sequence_run are not touched; only the handle's own stream is used.  Device pointers follow the contract stated at
+ * vsm_push_back_device: read asynchronously on the handle's stream, valid and unchanged until the call returns. */
+int vsm_pairs_run(vsm_handle *h, const uint8_t *left, const uint8_t *right, int64_t frame_stride, int on_device,
+                  int32_t n_frames, int32_t width, int32_t height, int32_t bpl, int32_t method,
+                  const int32_t *pairs, int32_t n_pairs, const double *Tr_delta, const uint8_t *Tr_valid);
+/* the list of pair `pair` of the last vsm_pairs_run (0 matches for an index outside it) */
+int32_t vsm_pairs_num_matches(vsm_handle *h, int32_t pair);
+int32_t vsm_pairs_get_matches(vsm_handle *h, int32_t pair, vsm_p_match *out, int32_t cap);
+/* wall-clock split of the last vsm_pairs_run on the caller's thread, microseconds: {image side of all frames, first passes +
+ * their outlier removal and prior boxes, second passes + refinement + final chains + copy-out, total} */
+void vsm_pairs_get_timings(vsm_handle *h, double *out4);
 /* Measurement / test switches of a handle.  They are read from the environment once, by vsm_create (VSM_SEQ_V2,
  * VSM_SEQ_CHUNK, VSM_SEQ_DC_STREAMS, VSM_SEQ_SERIAL, VSM_SEQ_GPU_SORTS, VSM_SEQ_EARLY_EXPORT); this call changes one
  * afterwards: name = the variable's name without the VSM_ prefix, in lower case ("seq_serial", "seq_chunk", ...).
@@ -301,6 +331,14 @@ int32_t vsm_debug_seq_plan(int32_t n_frames, int32_t pool_threads, int32_t host_
  * (-1: none); max_nq_out[chunk][2] = the chunk's longest query lists.  0, or -1 on a bad argument. */
 int32_t vsm_debug_chunk_jobs(int32_t method, int32_t multi_stage, int32_t sides, int32_t banks, int32_t chunk, const int32_t *starts,
                              int32_t n_chunks, const int32_t *counts, const uint8_t *tr_valid, int32_t *frames_out, int32_t *max_nq_out);
+/* Test hook of vsm_pairs_run's job table (pure arithmetic, no GPU, no HIP call): pairs[n_pairs][2] = (previous, current)
+ * frames of a set of n_frames frames of `sides` images whose feature counts are counts[frame][side][set] (as above), cut
+ * into chunks of `chunk` pairs; tr_valid: a byte per pair, or NULL (every pair brings a Tr).  pairs_out[pair][7] = image
+ * slot of the previous and of the current frame's left image (slot = sides * frame), queries of the first and the second
+ * pass, use_tr, valid, and the number (from 1) of the pair whose Tr the job took (0: none); max_nq_out[chunk][2] = the
+ * chunk's longest query lists.  Returns the number of chunks, or -1 on an argument vsm_pairs_run rejects. */
+int32_t vsm_debug_pair_jobs(int32_t method, int32_t multi_stage, int32_t sides, int32_t n_frames, const int32_t *counts, const int32_t *pairs,
+                            int32_t n_pairs, int32_t chunk, const uint8_t *tr_valid, int32_t *pairs_out, int32_t *max_nq_out);
 
 /* ---- stereo visual odometry on top of the matcher ----
  * class VisualOdometryStereo, viso/viso_stereo.h:28-88 + viso/viso.h:28-131: process() =

@@ -449,6 +449,7 @@ struct VsmSwitches {
   int feat_order = 1;        // feature records + bin-sorted copy by k_feat_scan / k_feat_order (tiles of whole search bins) or by k_scan_cells / k_emit / k_bin_* (0)
   int multi_host_pass1 = -1; // vsm_multi_process: the first-pass lists' removeOutliers + prior boxes on the host pool (1) or by the device chain (0); -1: host for K <= pool threads
   int multi_shared_ego = 0;  // vsm_multi_process: idle pool threads take RANSAC hypotheses of the sequences' egomotion (1: measured, no gain), every sequence on one thread (0)
+  int pairs_chunk = 0;       // vsm_pairs_run: pairs per step (0 = the look-ahead call's chunk rule for device-resident frames, seq2_plan)
   int frame_early_xy = 1;    // per-frame path: the pass-2 list's pixels cross in front of the list, the host triangulates while the refinement and the export run (vsm_match)
   int filter_planes = 0;     // vsm_push_back keeps f1 / f2 in HBM for vsm_get_filter_responses (the fused tiles write them on the side)
   static int env_int(const char *name, int dflt) {
@@ -498,6 +499,7 @@ struct VsmSwitches {
     else if (!strcmp(name, "frame_early_xy")) frame_early_xy = v != 0;
     else if (!strcmp(name, "multi_host_pass1")) multi_host_pass1 = v;
     else if (!strcmp(name, "multi_shared_ego")) multi_shared_ego = v;
+    else if (!strcmp(name, "pairs_chunk")) pairs_chunk = std::max(0, v);
     else return false;
     return true;
   }
@@ -563,6 +565,7 @@ struct vsm_handle {
   std::atomic<int> seq_hip_error{0};  // set by a chunk whose GPU share failed during the current vsm_sequence_run
   struct Seq2 *seq2 = nullptr;   // GPU-resident look-ahead path (vsm_seq2.inc): streams, slabs, result arena
   int32_t seq_v2_frames = 0;     // > 0: the last sequence's results are in seq2's arena, not in seq_matches
+  struct VsmPairs *pairs = nullptr;  // arbitrary frame pairs in one call (vsm_pairs.inc): its own context, banks and result lists
 
   uint8_t *stage_host = nullptr;  // pinned staging for host images
   size_t stage_bytes = 0;
@@ -591,6 +594,7 @@ VsmForkJoin *vsm_forkjoin_of(vsm_handle *h) { return h->fj; }
 double vsm_now_us() { return now_us(); }
 static void seq1_destroy(vsm_handle *h);  // vsm_seq1.inc
 static void seq2_destroy(vsm_handle *h);  // vsm_seq2.inc
+static void pairs_destroy(vsm_handle *h);  // vsm_pairs.inc
 
 extern "C" {
 
@@ -680,6 +684,7 @@ void vsm_destroy(vsm_handle *h) {
   for (hipStream_t st : h->dc_stream)
     if (st) (void)hipStreamSynchronize(st);
   seq2_destroy(h);
+  pairs_destroy(h);
   ctx_destroy(h->ring);
   ctx_destroy(h->seq);
   if (h->stage_host) (void)hipHostFree(h->stage_host);
@@ -997,6 +1002,93 @@ int32_t vsm_debug_chunk_jobs(int32_t method, int32_t multi_stage, int32_t sides,
   return 0;
 }
 
+// The job table of a list of arbitrary frame pairs (vsm_pairs_run): pair k = pairs[2 k], pairs[2 k + 1] = (previous frame,
+// current frame) of a frame set whose images all stand in one context, frame f's at slots sides * f (+ 1: its right image),
+// with the feature counts the device has written into `counts` ([image][set], the layout of VsmCtx::hm_counts).  Per pair
+// what a fresh matcher does after pushBack(previous), pushBack(current), matchFeatures(method, Tr of the pair): the job
+// (query counts and Tr only where matchFeatures would run, match_ready; queries come from the previous left image for quad
+// matching, from the current one otherwise), valid, and the longest query lists.  Stereo matching does not read the previous
+// frame: its slot is the current one's, whatever the pair names.  Tr / Tr_valid: per PAIR (NULL: none / all valid).
+// Pure arithmetic like seq_chunk_jobs: pinned through vsm_debug_pair_jobs (tests/test_pair_jobs.py).
+static void pair_jobs(const vsm_params &p, int method, int sides, const int32_t *counts, const int32_t *pairs, int n, const double *Tr,
+                      const uint8_t *Tr_valid, VsmJob *jobs, char *valid, int max_nq[2]) {
+  max_nq[0] = max_nq[1] = 0;
+  for (int k = 0; k < n; k++) {
+    VsmJob &jb = jobs[k];
+    memset(&jb, 0, sizeof(jb));
+    const int img_c = sides * pairs[2 * k + 1], img_p = method == 1 ? img_c : sides * pairs[2 * k];
+    int32_t cnt[4][2];
+    for (int s = 0; s < 2; s++) {
+      cnt[0][s] = method == 1 ? 0 : counts[img_p * 2 + s];
+      cnt[1][s] = method == 1 || sides != 2 ? 0 : counts[(img_p + 1) * 2 + s];
+      cnt[2][s] = counts[img_c * 2 + s];
+      cnt[3][s] = sides == 2 ? counts[(img_c + 1) * 2 + s] : 0;
+    }
+    jb.img_prev = img_p;
+    jb.img_curr = img_c;
+    const bool ready = match_ready(p, method, cnt);
+    if (ready) {
+      const int qimg = method == 2 ? 0 : 2;
+      jb.nq[0] = p.multi_stage ? cnt[qimg][0] : 0;
+      jb.nq[1] = cnt[qimg][1];
+      if (Tr && (!Tr_valid || Tr_valid[k])) {
+        jb.use_tr = 1;
+        memcpy(jb.t, Tr + (size_t)k * 12, 12 * sizeof(double));
+      }
+    }
+    if (valid) valid[k] = ready ? 1 : 0;
+    max_nq[0] = std::max(max_nq[0], jb.nq[0]);
+    max_nq[1] = std::max(max_nq[1], jb.nq[1]);
+  }
+}
+// the argument checks of vsm_pairs_run on its pair list: every current frame inside the set, every previous one too - or,
+// with stereo matching (which does not read it), -1
+static bool pair_list_ok(int method, int32_t n_frames, const int32_t *pairs, int32_t n_pairs) {
+  if (method < 0 || method > 2 || n_frames <= 0 || !pairs || n_pairs <= 0) return false;
+  for (int32_t k = 0; k < n_pairs; k++) {
+    const int32_t a = pairs[2 * k], b = pairs[2 * k + 1];
+    if (b < 0 || b >= n_frames || a >= n_frames || a < (method == 1 ? -1 : 0)) return false;
+  }
+  return true;
+}
+
+// (debug entry, include/visomatch.h)
+int32_t vsm_debug_pair_jobs(int32_t method, int32_t multi_stage, int32_t sides, int32_t n_frames, const int32_t *counts, const int32_t *pairs,
+                            int32_t n_pairs, int32_t chunk, const uint8_t *tr_valid, int32_t *pairs_out, int32_t *max_nq_out) {
+  if (sides < 1 || sides > 2 || chunk < 1 || !counts || !pairs_out || !max_nq_out || !pair_list_ok(method, n_frames, pairs, n_pairs)) return -1;
+  vsm_params p;
+  vsm_default_params(&p);
+  p.multi_stage = multi_stage;
+  std::vector<int32_t> img_counts((size_t)n_frames * sides * 2, 0);  // [frame][2 sides][set] -> [image][set]
+  for (int32_t f = 0; f < n_frames; f++)
+    for (int side = 0; side < sides; side++)
+      for (int s = 0; s < 2; s++) img_counts[((size_t)f * sides + side) * 2 + s] = counts[((size_t)f * 2 + side) * 2 + s];
+  std::vector<double> Tr((size_t)n_pairs * 12, 0.0);
+  for (int32_t k = 0; k < n_pairs; k++) Tr[(size_t)k * 12] = (double)(k + 1);  // (says which pair's Tr a job took)
+  std::vector<VsmJob> jobs(chunk);
+  std::vector<char> valid(chunk);
+  int32_t nchunks = 0;
+  for (int32_t k0 = 0; k0 < n_pairs; k0 += chunk, nchunks++) {
+    const int n = std::min(chunk, n_pairs - k0);
+    int max_nq[2];
+    pair_jobs(p, method, sides, img_counts.data(), pairs + 2 * (size_t)k0, n, Tr.data() + (size_t)k0 * 12, tr_valid ? tr_valid + k0 : nullptr, jobs.data(),
+              valid.data(), max_nq);
+    for (int i = 0; i < n; i++) {
+      int32_t *o = pairs_out + (size_t)(k0 + i) * 7;
+      o[0] = jobs[i].img_prev;
+      o[1] = jobs[i].img_curr;
+      o[2] = jobs[i].nq[0];
+      o[3] = jobs[i].nq[1];
+      o[4] = jobs[i].use_tr;
+      o[5] = valid[i];
+      o[6] = (int32_t)jobs[i].t[0];
+    }
+    max_nq_out[2 * nchunks] = max_nq[0];
+    max_nq_out[2 * nchunks + 1] = max_nq[1];
+  }
+  return nchunks;
+}
+
 // The pass-1 host stage of n pairs, first_pair onwards, on the pool (viso/matcher.cpp:222-226): a pair's pass-1 list out of
 // host-mapped memory (none for a pair that is not valid), removeOutliers, computePriorStatistics, the boxes in the device's
 // layout; then the boxes' upload on the handle's stream.  task_ns (may be NULL): the two steps' task time is added to
@@ -1306,6 +1398,7 @@ static int seq_ingest_host_frames(vsm_handle *h, VsmCtx &c, int first_img, const
 #include "vsm_seq2.inc"
 #include "vsm_seq1.inc"
 #include "vsm_multi.inc"
+#include "vsm_pairs.inc"
 extern "C" {
 
 // ---------------------------------------------------------------------------------------

@@ -34,8 +34,8 @@ EXPORTS = ["vsm_default_params", "vsm_create", "vsm_destroy", "vsm_set_intrinsic
            "vsm_num_features", "vsm_get_features", "vsm_set_stage_capture", "vsm_stage_size", "vsm_stage_get",
            "vsm_num_ranges", "vsm_get_ranges", "vsm_get_gradients", "vsm_get_filter_responses", "vsm_get_counters",
            "vsm_get_timings", "vsm_set_profiling", "vsm_num_kernels", "vsm_kernel_name", "vsm_get_kernel_stats",
-           "vsm_host_delaunay", "vsm_host_delaunay_split", "vsm_debug_delaunay_gpu", "vsm_debug_dc_bench", "vsm_host_ties", "vsm_debug_ties_gpu", "vsm_host_outliers_and_prior", "vsm_host_outliers_and_prior_threads", "vsm_debug_dc2", "vsm_debug_dc2_band_factor", "vsm_debug_predicates", "vsm_debug_seq_plan", "vsm_debug_chunk_jobs", "vsm_local_cpus", "vsm_forkjoin_cpus", "vsm_device_pool_stats", "vsm_device_pool_trim", "vsm_sequence_run", "vsm_sequence_num_matches", "vsm_sequence_get_matches",
-           "vsm_sequence_get_timings", "vsm_sequence_path", "vsm_set_option", "vsm_version", "vsm_host_register", "vsm_host_unregister",
+           "vsm_host_delaunay", "vsm_host_delaunay_split", "vsm_debug_delaunay_gpu", "vsm_debug_dc_bench", "vsm_host_ties", "vsm_debug_ties_gpu", "vsm_host_outliers_and_prior", "vsm_host_outliers_and_prior_threads", "vsm_debug_dc2", "vsm_debug_dc2_band_factor", "vsm_debug_predicates", "vsm_debug_seq_plan", "vsm_debug_chunk_jobs", "vsm_debug_pair_jobs", "vsm_local_cpus", "vsm_forkjoin_cpus", "vsm_device_pool_stats", "vsm_device_pool_trim", "vsm_sequence_run", "vsm_sequence_num_matches", "vsm_sequence_get_matches",
+           "vsm_sequence_get_timings", "vsm_sequence_path", "vsm_pairs_run", "vsm_pairs_num_matches", "vsm_pairs_get_matches", "vsm_pairs_get_timings", "vsm_set_option", "vsm_version", "vsm_host_register", "vsm_host_unregister",
            "vsm_multi_create", "vsm_multi_destroy", "vsm_multi_process", "vsm_multi_num_sequences", "vsm_multi_get_motion",
            "vsm_multi_motion_valid", "vsm_multi_num_matches", "vsm_multi_get_matches", "vsm_multi_num_inliers", "vsm_multi_get_inliers",
            "vsm_multi_get_timings",
@@ -160,6 +160,13 @@ def lib():
         L.vsm_debug_seq_plan.argtypes = [i32, i32, i32, i32, i32, C.c_char_p, vp, vp, i32]
         L.vsm_debug_chunk_jobs.restype = i32
         L.vsm_debug_chunk_jobs.argtypes = [i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp]
+        L.vsm_debug_pair_jobs.restype = i32
+        L.vsm_debug_pair_jobs.argtypes = [i32, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp]
+        L.vsm_pairs_run.argtypes = [vp, vp, vp, C.c_int64, C.c_int, i32, i32, i32, i32, i32, vp, i32, vp, vp]
+        L.vsm_pairs_num_matches.argtypes = [vp, i32]
+        L.vsm_pairs_get_matches.argtypes = [vp, i32, vp, i32]
+        L.vsm_pairs_get_timings.argtypes = [vp, vp]
+        L.vsm_pairs_get_timings.restype = None
         L.vsm_local_cpus.argtypes = [vp, i32]
         L.vsm_forkjoin_cpus.argtypes = [vp, i32]
         L.vsm_debug_dc2_band_factor.restype = None
@@ -407,6 +414,27 @@ def chunk_jobs(method, multi_stage, sides, banks, chunk, starts, counts, tr_vali
     if rc != 0:
         raise VisoMatchError("vsm_debug_chunk_jobs: bad arguments")
     return frames, max_nq
+
+
+def pair_jobs(method, multi_stage, sides, counts, pairs, chunk, tr_valid=None):
+    """test hook (no GPU): the job table of match_pairs - counts[frame][side][set]: the feature counts of the frame set;
+    pairs: [(previous frame, current frame), ...]; chunk: pairs per step; tr_valid: a flag per pair or None.  Returns (int32
+    [pairs][7]: img_prev, img_curr, nq[0], nq[1], use_tr, valid, number (from 1) of the pair whose Tr the job took;
+    int32 [chunks][2]: max_nq)"""
+    counts = np.ascontiguousarray(counts, dtype=np.int32)
+    assert counts.ndim == 3 and counts.shape[1:] == (2, 2)
+    pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    tv = None if tr_valid is None else np.ascontiguousarray(tr_valid, dtype=np.uint8)
+    assert tv is None or tv.shape == (len(pr),)
+    chunk = int(chunk)
+    out = np.zeros((len(pr), 7), dtype=np.int32)
+    max_nq = np.zeros((max(-(-len(pr) // max(chunk, 1)), 1), 2), dtype=np.int32)
+    n = lib().vsm_debug_pair_jobs(method, int(bool(multi_stage)), sides, len(counts), counts.ctypes.data_as(C.c_void_p),
+                                  pr.ctypes.data_as(C.c_void_p), len(pr), chunk, None if tv is None else tv.ctypes.data_as(C.c_void_p),
+                                  out.ctypes.data_as(C.c_void_p), max_nq.ctypes.data_as(C.c_void_p))
+    if n < 0:
+        raise VisoMatchError("vsm_debug_pair_jobs: bad arguments")
+    return out, max_nq[:n]
 
 
 def remove_outliers(matches, method, w, h, gpu=False, gpu_ties=False, copies=1, threads=1, **params):
@@ -658,6 +686,65 @@ class Matcher:
         if n:
             L.vsm_sequence_get_matches(self.h, f, a.ctypes.data_as(C.c_void_p), n)
         return a
+
+    # --- arbitrary frame pairs of an image set ---------------------------------------------
+    def match_pairs(self, left, right, pairs, method, Tr_delta=None, Tr_valid=None, fetch=True):
+        """left/right: [F,H,W] uint8 numpy arrays (host) or CUDA torch tensors (resident in HBM; a view with row and frame
+        strides is read in place), right=None: mono input.  pairs: [(previous frame, current frame), ...].  Tr_delta: None
+        or one matrix per pair ([P,4,4], [P,3,4] or [P,12]), Tr_valid: None or a flag per pair.  Returns the list of per-pair
+        match arrays - for (a, b): getMatches() of a fresh matcher after pushBack(a), pushBack(b), matchFeatures(method, Tr) -
+        or, with fetch=False, nothing (the lists stay in the handle: pair_matches(k)).  Every frame goes through the image
+        side once, however many pairs name it."""
+        L = lib()
+        if _is_torch(left):
+            assert left.is_cuda and left.dtype.__str__() == "torch.uint8" and left.dim() == 3 and left.stride(2) == 1
+            F, h, w = left.shape
+            bpl, fs = left.stride(1), left.stride(0)
+            _order_behind_torch(self.h, left)
+            pl = C.c_void_p(left.data_ptr())
+            pr = None
+            if right is not None:
+                assert right.is_cuda and right.dtype == left.dtype and right.shape == left.shape and right.stride() == left.stride()
+                pr = C.c_void_p(right.data_ptr())
+            dev = 1
+        else:
+            left = np.ascontiguousarray(left, dtype=np.uint8)
+            F, h, w = left.shape
+            bpl, fs = w, w * h
+            pl = left.ctypes.data_as(C.c_void_p)
+            pr = None
+            if right is not None:
+                right = np.ascontiguousarray(right, dtype=np.uint8)
+                assert right.shape == left.shape
+                pr = right.ctypes.data_as(C.c_void_p)
+            dev = 0
+        pa = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+        P = len(pa)
+        tp = vp_ = None
+        if Tr_delta is not None:
+            t = np.ascontiguousarray(np.asarray(Tr_delta, dtype=np.float64).reshape(P, -1)[:, :12])
+            tp = t.ctypes.data_as(C.c_void_p)
+            if Tr_valid is not None:
+                v = np.ascontiguousarray(np.asarray(Tr_valid).astype(np.uint8))
+                assert v.shape == (P,)
+                vp_ = v.ctypes.data_as(C.c_void_p)
+        rc = L.vsm_pairs_run(self.h, pl, pr, fs, dev, F, w, h, bpl, method, pa.ctypes.data_as(C.c_void_p), P, tp, vp_)
+        if rc != self.OK:
+            raise VisoMatchError(f"vsm_pairs_run failed with {rc}" + (" (VSM_EARG)" if rc == self.EARG else ""))
+        return [self.pair_matches(k) for k in range(P)] if fetch else None
+
+    def pair_matches(self, k):
+        L = lib()
+        n = L.vsm_pairs_num_matches(self.h, k)
+        a = np.zeros(n, dtype=P_MATCH)
+        if n:
+            L.vsm_pairs_get_matches(self.h, k, a.ctypes.data_as(C.c_void_p), n)
+        return a
+
+    def pair_timings(self):
+        t = np.zeros(4, dtype=np.float64)
+        lib().vsm_pairs_get_timings(self.h, t.ctypes.data_as(C.c_void_p))
+        return dict(zip(("image_side_us", "pass1_us", "pass2_us", "total_us"), t.tolist()))
 
     def sequence_path(self):
         """2: the last run_sequence went through the GPU-resident form, 1: through the host-shared form"""
