@@ -447,6 +447,25 @@ vsm_handle *vsm_vo_mono_matcher(vsm_vo_mono *v);
 /* 1 if the hypothesis fits and triangulations run on the GPU (the device reproduced the host's SVD
  * bit for bit in the creation-time self-test), 0 if they run on the host pool */
 int vsm_vo_mono_device_svd(vsm_vo_mono *v);
+/* which stages of the last estimate (process / process_matches) took their result from the GPU: bit 0 the hypothesis
+ * fits, bit 1 the inlier counts, bit 2 the triangulation, bit 3 the plane vote (at least 512 points in front of the
+ * camera).  A stage the estimate never reached, or ran on the host, leaves its bit clear. */
+int vsm_vo_mono_device_stages(vsm_vo_mono *v);
+/* Test hooks of the egomotion's four kernels: each runs ONE kernel on the caller's inputs, through the launch code the
+ * estimator uses, and returns everything the kernel wrote.  0 = ok, -1 = a bad argument (a null pointer, n < 1, K < 1,
+ * a pick outside [0, n)), -2 = a HIP error.
+ *   fit:         pts = n x {u1p, v1p, u1c, v1c} (normalised already), picks = K x 8 indices; F = K x 9.
+ *   count:       counts[k] = matches whose Sampson distance to F[k] is below thr; slice > 0 caps the hypotheses per
+ *                launch (0: the device's grid limit).
+ *   triangulate: the four candidates R[c] (3x3) | t[c] (3) with K = {f, cu, cv}; X[c][row][match] (4 x 4 x n), chir[4].
+ *   vote:        the plane vote of d[0 .. np) as the estimator runs it: sums[i] = the device's proposal for candidate i
+ *                (the 16 slices added up; 0 for d[i] <= threshold), *best = the chosen index.  Returns 1 where the host
+ *                ran the vote (np < 512): sums are then the exact sums. */
+int32_t vsm_debug_mono_fit(const float *pts, int32_t n, const int32_t *picks, int32_t K, double *F);
+int32_t vsm_debug_mono_count(const float *pts, int32_t n, const double *F, int32_t K, double thr, int32_t slice, int32_t *counts);
+int32_t vsm_debug_mono_triangulate(const vsm_p_match *m, int32_t n, double f, double cu, double cv, const double *R, const double *t,
+                                   double *X, int32_t *chir);
+int32_t vsm_debug_mono_vote(const double *d, int32_t np, double threshold, double weight, double *sums, int32_t *best);
 /* microseconds of the last process(): {matchFeatures, bucketing + copy, egomotion, total after the
  * push, then inside the egomotion: fundamental matrices, inlier counting, R|t + triangulation,
  * plane vote, 0, 0} */

@@ -182,6 +182,69 @@ __global__ void __launch_bounds__(64)
 
 namespace {
 
+// ---------------------------------------------------------------------------------------
+// launches: the one place each kernel's grid and block come from (MonoEgo::estimate, best_plane,
+// the context's self-test and the vsm_debug_mono_* entries all go through these).  Every launch is
+// followed by hipGetLastError; false = the launch was refused, the caller takes its host path.
+// ---------------------------------------------------------------------------------------
+enum { MONO_STAGE_FIT = 1, MONO_STAGE_COUNT = 2, MONO_STAGE_TRIANGULATE = 4, MONO_STAGE_VOTE = 8 };
+
+inline bool launched() { return hipGetLastError() == hipSuccess; }
+
+int mono_grid_y_limit() {  // hipDeviceAttributeMaxGridDimY of the current device
+  int dev = 0, lim = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&lim, hipDeviceAttributeMaxGridDimY, dev) != hipSuccess || lim < 1)
+    return 65535;
+  return lim;
+}
+
+bool launch_fit(hipStream_t stream, const MonoPt *d_pts, const int32_t *d_picks, int K, double *d_F) {
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(k_mono_fit, dim3((K + 15) / 16), dim3(256), 0, stream, d_pts, d_picks, K, d_F);
+  return launched();
+}
+
+// blockIdx.y = hypothesis: at most `slice` hypotheses per launch (slice <= 0: the device's grid-y limit)
+bool launch_count(hipStream_t stream, const MonoPt *d_pts, int n, const double *d_F, int K, double thr, int32_t *d_counts,
+                  int slice) {
+  static const int limit = mono_grid_y_limit();
+  if (slice <= 0 || slice > limit) slice = limit;
+  (void)hipGetLastError();
+  for (int k0 = 0; k0 < K; k0 += slice) {
+    hipLaunchKernelGGL(k_mono_inlier_count, dim3((n + 255) / 256, std::min(slice, K - k0)), dim3(256), 0, stream, d_pts, n,
+                       d_F + (size_t)9 * k0, thr, d_counts + k0);
+    if (!launched()) return false;
+  }
+  return true;
+}
+
+bool launch_triangulate(hipStream_t stream, const MonoPt *d_raw, int n, const MonoCams &cams, double *d_X, int32_t *d_chir) {
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(k_mono_triangulate, dim3((n + 63) / 64, 4), dim3(64), 0, stream, d_raw, n, cams, d_X, d_chir);
+  return launched();
+}
+
+bool launch_vote(hipStream_t stream, const double *d_d, int np, double threshold, double weight, double *d_sums) {
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(k_mono_plane_vote, dim3((np + 255) / 256, VOTE_SPLIT), dim3(256), 0, stream, d_d, np, threshold, weight,
+                     d_sums);
+  return launched();
+}
+
+// P1 = K [I | 0], P2[c] = K [R_c | t_c] for the four candidates of EtoRt
+void build_cams(const double *Kd, const double *const *Rs, const double *const *ts, MonoCams &cams) {
+  const double P1[12] = {Kd[0], Kd[1], Kd[2], 0, Kd[3], Kd[4], Kd[5], 0, Kd[6], Kd[7], Kd[8], 0};
+  memcpy(cams.P1, P1, sizeof(P1));
+  for (int c = 0; c < 4; c++) {
+    double Rt[12];
+    for (int i = 0; i < 3; i++) {
+      for (int j = 0; j < 3; j++) Rt[i * 4 + j] = Rs[c][i * 3 + j];
+      Rt[i * 4 + 3] = ts[c][i];
+    }
+    vsm_la::mul(Kd, Rt, cams.P2[c], 3, 3, 4);
+  }
+}
+
 struct MonoGpu {  // device side of one estimator
   hipStream_t stream = nullptr;
   MonoPt *d_pts = nullptr, *d_raw = nullptr;
@@ -219,7 +282,7 @@ struct MonoGpu {  // device side of one estimator
     std::vector<double> dev(K * 9);
     if (hipMemcpyAsync(d_pts, pts.data(), sizeof(MonoPt) * n, hipMemcpyHostToDevice, stream) != hipSuccess) return false;
     if (hipMemcpyAsync(d_picks, picks.data(), sizeof(int32_t) * K * 8, hipMemcpyHostToDevice, stream) != hipSuccess) return false;
-    hipLaunchKernelGGL(k_mono_fit, dim3((K + 15) / 16), dim3(256), 0, stream, d_pts, d_picks, K, d_F);
+    if (!launch_fit(stream, d_pts, d_picks, K, d_F)) return false;
     if (hipMemcpyAsync(dev.data(), d_F, sizeof(double) * K * 9, hipMemcpyDeviceToHost, stream) != hipSuccess) return false;
     if (hipStreamSynchronize(stream) != hipSuccess) return false;
     for (int k = 0; k < K; k++) {
@@ -348,6 +411,7 @@ class MonoEgo {
   std::vector<double> Fs, X4, dvals, sums, scratch;
   std::vector<int32_t> counts, picks, deck;
   double timings[6] = {0, 0, 0, 0, 0, 0};
+  int stages = 0;  // MONO_STAGE_* bits: what the last estimate (or best_plane) took from the GPU
 
   // normalizeFeaturePoints (viso/viso_mono.cpp:215-262): the fields are floats, every update rounds
   bool normalise(const vsm_p_match *m, int n, double *Tp, double *Tc) {
@@ -397,6 +461,7 @@ class MonoEgo {
   // replaced, -1 = failure before the RANSAC started (inlier list untouched, like the reference).
   template <class Runner>
   int estimate(const vsm_p_match *m, int n, Runner *pool, MonoGpu *gpu, double *tr6, std::vector<int32_t> &inliers) {
+    stages = 0;
     if (n < 10) return -1;
     const double t0 = vsm_now_us();
     double Tp[9], Tc[9];
@@ -432,10 +497,7 @@ class MonoEgo {
         memcpy(gpu->h_picks, picks.data(), sizeof(int32_t) * 8 * K);
         on_gpu = hipMemcpyAsync(gpu->d_picks, gpu->h_picks, sizeof(int32_t) * 8 * K, hipMemcpyHostToDevice, gpu->stream) ==
                  hipSuccess;
-        if (on_gpu) {
-          hipLaunchKernelGGL(k_mono_fit, dim3((K + 15) / 16), dim3(256), 0, gpu->stream, gpu->d_pts, gpu->d_picks, K, gpu->d_F);
-          fitted = true;
-        }
+        if (on_gpu) fitted = on_gpu = launch_fit(gpu->stream, gpu->d_pts, gpu->d_picks, K, gpu->d_F);
       }
     }
     if (!fitted) {
@@ -452,16 +514,16 @@ class MonoEgo {
     if (on_gpu) {
       on_gpu = hipMemsetAsync(gpu->d_counts, 0, sizeof(int32_t) * K, gpu->stream) == hipSuccess;
       if (on_gpu) {
-        hipLaunchKernelGGL(k_mono_inlier_count, dim3((n + 255) / 256, K), dim3(256), 0, gpu->stream, gpu->d_pts, n, gpu->d_F,
-                           par.inlier_threshold, gpu->d_counts);
-        on_gpu = hipMemcpyAsync(gpu->h_counts, gpu->d_counts, sizeof(int32_t) * K, hipMemcpyDeviceToHost, gpu->stream) ==
-                 hipSuccess;
+        on_gpu = launch_count(gpu->stream, gpu->d_pts, n, gpu->d_F, K, par.inlier_threshold, gpu->d_counts, 0) &&
+                 hipMemcpyAsync(gpu->h_counts, gpu->d_counts, sizeof(int32_t) * K, hipMemcpyDeviceToHost, gpu->stream) ==
+                     hipSuccess;
         if (on_gpu && fitted)
           on_gpu = hipMemcpyAsync(gpu->h_F, gpu->d_F, sizeof(double) * 9 * K, hipMemcpyDeviceToHost, gpu->stream) == hipSuccess;
         on_gpu = on_gpu && hipStreamSynchronize(gpu->stream) == hipSuccess;
         if (on_gpu) {
           memcpy(counts.data(), gpu->h_counts, sizeof(int32_t) * K);
           if (fitted) memcpy(Fs.data(), gpu->h_F, sizeof(double) * 9 * K);
+          stages |= MONO_STAGE_COUNT | (fitted ? MONO_STAGE_FIT : 0);
         }
       }
     }
@@ -533,32 +595,9 @@ class MonoEgo {
     // --- triangulateChieral for the four candidates (:394-431)
     int chir[4] = {0, 0, 0, 0};
     MonoCams cams;
-    {
-      const double P1[12] = {Kd[0], Kd[1], Kd[2], 0, Kd[3], Kd[4], Kd[5], 0, Kd[6], Kd[7], Kd[8], 0};
-      memcpy(cams.P1, P1, sizeof(P1));
-      for (int c = 0; c < 4; c++) {
-        double Rt[12];
-        for (int i = 0; i < 3; i++) {
-          for (int j = 0; j < 3; j++) Rt[i * 4 + j] = Rs[c][i * 3 + j];
-          Rt[i * 4 + 3] = ts[c][i];
-        }
-        vsm_la::mul(Kd, Rt, cams.P2[c], 3, 3, 4);
-      }
-    }
-    bool tri_gpu = gpu && gpu->ok && gpu->svd_on_device && gpu->reserve(n, 1);
-    if (tri_gpu) {
-      for (int i = 0; i < n; i++) gpu->h_pts[i] = {m[i].u1p, m[i].v1p, m[i].u1c, m[i].v1c};
-      tri_gpu = hipMemcpyAsync(gpu->d_raw, gpu->h_pts, sizeof(MonoPt) * n, hipMemcpyHostToDevice, gpu->stream) == hipSuccess &&
-                hipMemsetAsync(gpu->d_chir, 0, sizeof(int32_t) * 4, gpu->stream) == hipSuccess;
-      if (tri_gpu) {
-        hipLaunchKernelGGL(k_mono_triangulate, dim3((n + 63) / 64, 4), dim3(64), 0, gpu->stream, gpu->d_raw, n, cams, gpu->d_X,
-                           gpu->d_chir);
-        tri_gpu = hipMemcpyAsync(gpu->h_counts, gpu->d_chir, sizeof(int32_t) * 4, hipMemcpyDeviceToHost, gpu->stream) ==
-                      hipSuccess &&
-                  hipStreamSynchronize(gpu->stream) == hipSuccess;
-        if (tri_gpu) memcpy(chir, gpu->h_counts, sizeof(chir));
-      }
-    }
+    build_cams(Kd, Rs, ts, cams);
+    const bool tri_gpu = gpu && gpu->ok && gpu->svd_on_device && triangulate_gpu(gpu, m, n, cams, chir);
+    if (tri_gpu) stages |= MONO_STAGE_TRIANGULATE;
     if (!tri_gpu) {
       X4.resize((size_t)4 * 4 * n);  // [candidate][row][match]
       for (int c = 0; c < 4; c++) {
@@ -652,6 +691,21 @@ class MonoEgo {
     return 1;
   }
 
+  // the four candidates' triangulations on the device: X stays in gpu->d_X ([candidate][row][match]), the chirality
+  // counts come back.  false = some step was refused (chir untouched)
+  bool triangulate_gpu(MonoGpu *gpu, const vsm_p_match *m, int n, const MonoCams &cams, int *chir) {
+    if (!gpu->reserve(n, 1)) return false;
+    for (int i = 0; i < n; i++) gpu->h_pts[i] = {m[i].u1p, m[i].v1p, m[i].u1c, m[i].v1c};
+    if (hipMemcpyAsync(gpu->d_raw, gpu->h_pts, sizeof(MonoPt) * n, hipMemcpyHostToDevice, gpu->stream) != hipSuccess ||
+        hipMemsetAsync(gpu->d_chir, 0, sizeof(int32_t) * 4, gpu->stream) != hipSuccess ||
+        !launch_triangulate(gpu->stream, gpu->d_raw, n, cams, gpu->d_X, gpu->d_chir) ||
+        hipMemcpyAsync(gpu->h_counts, gpu->d_chir, sizeof(int32_t) * 4, hipMemcpyDeviceToHost, gpu->stream) != hipSuccess ||
+        hipStreamSynchronize(gpu->stream) != hipSuccess)
+      return false;
+    memcpy(chir, gpu->h_counts, sizeof(int32_t) * 4);
+    return true;
+  }
+
   // exact vote sum of candidate i: libm exp(), the reference's summation order
   double exact_sum(int i, int np, double weight) const {
     double sum = 0;
@@ -668,15 +722,15 @@ class MonoEgo {
     if (on_gpu) {
       on_gpu = hipMemcpyAsync(gpu->d_d, dvals.data(), sizeof(double) * np, hipMemcpyHostToDevice, gpu->stream) == hipSuccess;
       if (on_gpu) {
-        hipLaunchKernelGGL(k_mono_plane_vote, dim3((np + 255) / 256, VOTE_SPLIT), dim3(256), 0, gpu->stream, gpu->d_d, np,
-                           threshold, weight, gpu->d_sums);
-        on_gpu = hipMemcpyAsync(gpu->h_sums, gpu->d_sums, sizeof(double) * VOTE_SPLIT * np, hipMemcpyDeviceToHost,
+        on_gpu = launch_vote(gpu->stream, gpu->d_d, np, threshold, weight, gpu->d_sums) &&
+                 hipMemcpyAsync(gpu->h_sums, gpu->d_sums, sizeof(double) * VOTE_SPLIT * np, hipMemcpyDeviceToHost,
                                 gpu->stream) ==
                      hipSuccess &&
                  hipStreamSynchronize(gpu->stream) == hipSuccess;
       }
     }
     if (on_gpu) {
+      stages |= MONO_STAGE_VOTE;
       // the device exp() is within a few ulp of libm's: only candidates this close to the proposed
       // maximum can be the true first maximum; they are judged exactly, in index order
       double top = 0;
@@ -825,6 +879,72 @@ int32_t vsm_vo_mono_get_inliers(vsm_vo_mono *v, int32_t *out, int32_t cap) {
 float vsm_vo_mono_gain(vsm_vo_mono *v, const int32_t *inliers, int32_t n) { return vsm_gain(v->matcher, inliers, n); }
 vsm_handle *vsm_vo_mono_matcher(vsm_vo_mono *v) { return v->matcher; }
 int vsm_vo_mono_device_svd(vsm_vo_mono *v) { return v->gpu.svd_on_device ? 1 : 0; }
+int vsm_vo_mono_device_stages(vsm_vo_mono *v) { return v->ego.stages; }
+
+// ---- test hooks: one kernel each on caller-given inputs, through the launch functions the estimator uses.
+// 0 = ok, -1 = bad argument, -2 = HIP error (a context of their own per call: the stream and the buffers of a MonoGpu)
+int32_t vsm_debug_mono_fit(const float *pts, int32_t n, const int32_t *picks, int32_t K, double *F) {
+  if (!pts || !picks || !F || n < 1 || K < 1) return -1;
+  for (size_t i = 0; i < (size_t)K * 8; i++)
+    if (picks[i] < 0 || picks[i] >= n) return -1;
+  MonoGpu g;
+  if (!g.init() || !g.reserve(n, K)) return -2;
+  if (hipMemcpyAsync(g.d_pts, pts, sizeof(MonoPt) * n, hipMemcpyHostToDevice, g.stream) != hipSuccess ||
+      hipMemcpyAsync(g.d_picks, picks, sizeof(int32_t) * 8 * K, hipMemcpyHostToDevice, g.stream) != hipSuccess ||
+      !launch_fit(g.stream, g.d_pts, g.d_picks, K, g.d_F) ||
+      hipMemcpyAsync(F, g.d_F, sizeof(double) * 9 * K, hipMemcpyDeviceToHost, g.stream) != hipSuccess ||
+      hipStreamSynchronize(g.stream) != hipSuccess)
+    return -2;
+  return 0;
+}
+
+int32_t vsm_debug_mono_count(const float *pts, int32_t n, const double *F, int32_t K, double thr, int32_t slice, int32_t *counts) {
+  if (!pts || !F || !counts || n < 1 || K < 1 || slice < 0) return -1;
+  MonoGpu g;
+  if (!g.init() || !g.reserve(n, K)) return -2;
+  if (hipMemcpyAsync(g.d_pts, pts, sizeof(MonoPt) * n, hipMemcpyHostToDevice, g.stream) != hipSuccess ||
+      hipMemcpyAsync(g.d_F, F, sizeof(double) * 9 * K, hipMemcpyHostToDevice, g.stream) != hipSuccess ||
+      hipMemsetAsync(g.d_counts, 0, sizeof(int32_t) * K, g.stream) != hipSuccess ||
+      !launch_count(g.stream, g.d_pts, n, g.d_F, K, thr, g.d_counts, slice) ||
+      hipMemcpyAsync(counts, g.d_counts, sizeof(int32_t) * K, hipMemcpyDeviceToHost, g.stream) != hipSuccess ||
+      hipStreamSynchronize(g.stream) != hipSuccess)
+    return -2;
+  return 0;
+}
+
+int32_t vsm_debug_mono_triangulate(const vsm_p_match *m, int32_t n, double f, double cu, double cv, const double *R, const double *t,
+                                   double *X, int32_t *chir) {
+  if (!m || !R || !t || !X || !chir || n < 1) return -1;
+  const double Kd[9] = {f, 0, cu, 0, f, cv, 0, 0, 1};
+  const double *Rs[4] = {R, R + 9, R + 18, R + 27}, *ts[4] = {t, t + 3, t + 6, t + 9};
+  MonoCams cams;
+  build_cams(Kd, Rs, ts, cams);
+  MonoGpu g;
+  MonoEgo ego;
+  if (!g.init()) return -2;
+  int c4[4] = {0, 0, 0, 0};
+  if (!ego.triangulate_gpu(&g, m, n, cams, c4) ||
+      hipMemcpyAsync(X, g.d_X, sizeof(double) * 16 * n, hipMemcpyDeviceToHost, g.stream) != hipSuccess ||
+      hipStreamSynchronize(g.stream) != hipSuccess)
+    return -2;
+  for (int c = 0; c < 4; c++) chir[c] = c4[c];
+  return 0;
+}
+
+// best_plane itself on d[0 .. np): sums[i] = the proposals after the slices are added up, *best = the index it picks.
+// Returns 1 instead of 0 where best_plane took its host path (np < 512, or a refused step): sums are then the exact ones.
+int32_t vsm_debug_mono_vote(const double *d, int32_t np, double threshold, double weight, double *sums, int32_t *best) {
+  if (!d || !sums || !best || np < 1) return -1;
+  MonoGpu g;
+  MonoEgo ego;
+  if (!g.init()) return -2;
+  ego.dvals.assign(d, d + np);
+  ego.stages = 0;
+  *best = ego.best_plane((VsmPool *)nullptr, &g, np, threshold, weight);
+  const bool dev = (ego.stages & MONO_STAGE_VOTE) != 0;
+  memcpy(sums, dev ? g.h_sums : ego.sums.data(), sizeof(double) * np);
+  return dev ? 0 : 1;
+}
 void vsm_vo_mono_get_timings(vsm_vo_mono *v, double *out10) {
   memcpy(out10, v->timings, sizeof(v->timings));
   memcpy(out10 + 4, v->ego.timings, sizeof(v->ego.timings));

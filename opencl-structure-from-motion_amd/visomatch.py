@@ -48,7 +48,8 @@ EXPORTS = ["vsm_default_params", "vsm_create", "vsm_destroy", "vsm_set_intrinsic
            "vsm_vo_mono_process_device", "vsm_vo_mono_process_matches", "vsm_vo_mono_get_motion",
            "vsm_vo_mono_motion_valid", "vsm_vo_mono_num_matches", "vsm_vo_mono_get_matches", "vsm_vo_mono_num_inliers",
            "vsm_vo_mono_get_inliers", "vsm_vo_mono_gain", "vsm_vo_mono_matcher", "vsm_vo_mono_get_timings",
-           "vsm_vo_mono_device_svd",
+           "vsm_vo_mono_device_svd", "vsm_vo_mono_device_stages",
+           "vsm_debug_mono_fit", "vsm_debug_mono_count", "vsm_debug_mono_triangulate", "vsm_debug_mono_vote",
            "vsm_host_estimate_motion_mono"]
 
 
@@ -235,6 +236,11 @@ def lib():
         L.vsm_vo_mono_matcher.argtypes = [vp]
         L.vsm_vo_mono_get_timings.argtypes = [vp, vp]
         L.vsm_vo_mono_device_svd.argtypes = [vp]
+        L.vsm_vo_mono_device_stages.argtypes = [vp]
+        L.vsm_debug_mono_fit.argtypes = [vp, i32, vp, i32, vp]
+        L.vsm_debug_mono_count.argtypes = [vp, i32, vp, i32, C.c_double, i32, vp]
+        L.vsm_debug_mono_triangulate.argtypes = [vp, i32, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp]
+        L.vsm_debug_mono_vote.argtypes = [vp, i32, C.c_double, C.c_double, vp, vp]
         L.vsm_host_estimate_motion_mono.argtypes = [mop, vp, i32, i32, vp, vp, vp, vp]
         _lib = L
     return _lib
@@ -272,6 +278,67 @@ def host_estimate_motion_mono(matches, params, threads=1):
                                              tr.ctypes.data_as(C.c_void_p), T.ctypes.data_as(C.c_void_p),
                                              inl.ctypes.data_as(C.c_void_p), C.cast(C.byref(n), C.c_void_p))
     return rc, tr, T.reshape(4, 4), (inl[: n.value].copy() if rc >= 0 else None)
+
+
+MONO_STAGE_FIT, MONO_STAGE_COUNT, MONO_STAGE_TRIANGULATE, MONO_STAGE_VOTE = 1, 2, 4, 8
+
+
+def _mono_check(rc, name):
+    if rc == -1:
+        raise ValueError(name + ": bad argument")
+    if rc < 0:
+        raise VisoMatchError(name + ": HIP error")
+    return rc
+
+
+def _mono_pts(pts):
+    p = np.ascontiguousarray(pts, dtype=np.float32).reshape(-1, 4)   # u1p, v1p, u1c, v1c per row
+    return p
+
+
+def device_mono_fit(pts, picks):
+    """test hook: k_mono_fit alone.  pts [n, 4] normalised (u1p, v1p, u1c, v1c), picks [K, 8] -> F [K, 3, 3]"""
+    p = _mono_pts(pts)
+    k = np.ascontiguousarray(picks, dtype=np.int32).reshape(-1, 8)
+    F = np.zeros((len(k), 3, 3))
+    _mono_check(lib().vsm_debug_mono_fit(p.ctypes.data_as(C.c_void_p), len(p), k.ctypes.data_as(C.c_void_p), len(k),
+                                         F.ctypes.data_as(C.c_void_p)), "vsm_debug_mono_fit")
+    return F
+
+
+def device_mono_count(pts, F, thr, slice=0):
+    """test hook: k_mono_inlier_count alone, at most `slice` hypotheses per launch (0: the device's limit) -> counts [K]"""
+    p = _mono_pts(pts)
+    F = np.ascontiguousarray(F, dtype=np.float64).reshape(-1, 9)
+    out = np.zeros(len(F), dtype=np.int32)
+    _mono_check(lib().vsm_debug_mono_count(p.ctypes.data_as(C.c_void_p), len(p), F.ctypes.data_as(C.c_void_p), len(F),
+                                           float(thr), int(slice), out.ctypes.data_as(C.c_void_p)), "vsm_debug_mono_count")
+    return out
+
+
+def device_mono_triangulate(matches, f, cu, cv, R4, t4):
+    """test hook: k_mono_triangulate alone for four candidates R4 [4, 3, 3], t4 [4, 3] -> (X [4, 4, n], chir [4])"""
+    m = np.ascontiguousarray(matches, dtype=P_MATCH)
+    R = np.ascontiguousarray(R4, dtype=np.float64).reshape(4, 9)
+    t = np.ascontiguousarray(t4, dtype=np.float64).reshape(4, 3)
+    X = np.zeros((4, 4, len(m)))
+    chir = np.zeros(4, dtype=np.int32)
+    _mono_check(lib().vsm_debug_mono_triangulate(m.ctypes.data_as(C.c_void_p), len(m), float(f), float(cu), float(cv),
+                                                 R.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p),
+                                                 X.ctypes.data_as(C.c_void_p), chir.ctypes.data_as(C.c_void_p)),
+                "vsm_debug_mono_triangulate")
+    return X, chir
+
+
+def device_mono_vote(d, threshold, weight):
+    """test hook: the estimator's plane vote on d [np] -> (sums [np], chosen index, True if the GPU proposed the sums)"""
+    d = np.ascontiguousarray(d, dtype=np.float64).ravel()
+    sums = np.zeros(len(d))
+    best = C.c_int32(-1)
+    rc = _mono_check(lib().vsm_debug_mono_vote(d.ctypes.data_as(C.c_void_p), len(d), float(threshold), float(weight),
+                                               sums.ctypes.data_as(C.c_void_p), C.cast(C.byref(best), C.c_void_p)),
+                     "vsm_debug_mono_vote")
+    return sums, int(best.value), rc == 0
 
 
 def vo_stereo_params(f=1.0, cu=0.0, cv=0.0, base=1.0, bucket=(2, 50.0, 50.0), ransac_iters=200, inlier_threshold=2.0,
@@ -1023,6 +1090,10 @@ class VisualOdometryMono:
 
     def device_svd(self):
         return bool(lib().vsm_vo_mono_device_svd(self.h))
+
+    def device_stages(self):
+        """MONO_STAGE_* bits of the stages the last estimate took from the GPU"""
+        return int(lib().vsm_vo_mono_device_stages(self.h))
 
     bucketed = get_matches
     inliers = get_inlier_indices

@@ -140,6 +140,9 @@ def oracle_lib():
         L.vo_matrix_det.restype = C.c_double
         L.vo_mono_fundamental.argtypes = [C.c_void_p, _p_i32, C.c_int32, _p_f64]
         L.vo_estimate_motion_mono.argtypes = [C.c_void_p, C.c_int32, C.POINTER(VoMonoParams), _p_f64, _p_i32, _p_i32]
+        L.vo_mono_inlier_count.argtypes = [C.c_void_p, C.c_int32, _p_f64, C.c_double]
+        L.vo_mono_triangulate.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_double, _p_f64, _p_f64, _p_f64]
+        L.vo_mono_plane_vote.argtypes = [_p_f64, C.c_int32, C.c_double, C.c_double, _p_f64]
         L.vo_mono_create.restype = C.c_void_p
         L.vo_mono_create.argtypes = [C.POINTER(VoParams), C.c_int32, C.c_double, C.c_double, C.POINTER(VoMonoParams)]
         L.vo_mono_destroy.argtypes = [C.c_void_p]
@@ -640,6 +643,38 @@ def oracle_fundamental(m, active):
     F = np.zeros(9)
     oracle_lib().vo_mono_fundamental(m.ctypes.data, _i32(a), len(a), F.ctypes.data_as(_p_f64))
     return F.reshape(3, 3)
+
+
+def oracle_mono_inlier_count(m, F, thr):
+    """getInlier's count for one F (3x3) on (normalised) matches"""
+    m = np.ascontiguousarray(m, dtype=MATCH_DTYPE)
+    F = np.ascontiguousarray(F, dtype=np.float64).reshape(9)
+    return int(oracle_lib().vo_mono_inlier_count(m.ctypes.data, len(m), F.ctypes.data_as(_p_f64), float(thr)))
+
+
+def oracle_mono_triangulate(m, f, cu, cv, R, t):
+    """triangulateChieral for one (R, t) on raw matches -> (X [4, n], chirality count)"""
+    m = np.ascontiguousarray(m, dtype=MATCH_DTYPE)
+    R = np.ascontiguousarray(R, dtype=np.float64).reshape(9)
+    t = np.ascontiguousarray(t, dtype=np.float64).reshape(3)
+    X = np.zeros((4, len(m)))
+    c = oracle_lib().vo_mono_triangulate(m.ctypes.data, len(m), float(f), float(cu), float(cv), R.ctypes.data_as(_p_f64),
+                                         t.ctypes.data_as(_p_f64), X.ctypes.data_as(_p_f64))
+    return X, int(c)
+
+
+def oracle_mono_plane_vote(d, threshold, weight):
+    """findBestPlane's vote -> (every candidate's sum in the reference's order with libm exp, the chosen index)"""
+    d = np.ascontiguousarray(d, dtype=np.float64).ravel()
+    sums = np.zeros(len(d))
+    i = oracle_lib().vo_mono_plane_vote(d.ctypes.data_as(_p_f64), len(d), float(threshold), float(weight),
+                                        sums.ctypes.data_as(_p_f64))
+    return sums, int(i)
+
+
+def oracle_mono_last_in_front():
+    """points in front of the camera in the oracle's last mono estimate (-1: it failed before counting them)"""
+    return int(oracle_lib().vo_mono_last_in_front())
 
 
 class OracleMonoVO:

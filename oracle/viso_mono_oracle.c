@@ -547,6 +547,54 @@ static int32_t mono_triangulate(const vo_match *m, int32_t n, const dm *K, const
   return num;
 }
 
+/* the vote of findBestPlane, viso/viso_mono.cpp:75-101: the first candidate d[i] > threshold with the largest
+ * sum_j exp(-(d[j] - d[i])^2 * weight); sums (may be 0) receives every candidate's sum, 0 where d[i] <= threshold */
+static int32_t mono_best_plane(const double *d, int32_t np, double threshold, double weight, double *sums) {
+  double best_sum = 0;
+  int32_t best_idx = 0;
+  for (int32_t i = 0; i < np; i++) {
+    if (sums) sums[i] = 0;
+    if (d[i] > threshold) {
+      double sum = 0;
+      for (int32_t j = 0; j < np; j++) {
+        double dd = d[j] - d[i];
+        sum += exp(-dd * dd * weight);
+      }
+      if (sums) sums[i] = sum;
+      if (sum > best_sum) {
+        best_sum = sum;
+        best_idx = i;
+      }
+    }
+  }
+  return best_idx;
+}
+
+/* thin views of the pieces above, for tests that compare one kernel of the product at a time */
+int32_t vo_mono_inlier_count(const vo_match *m, int32_t n, const double *F9, double thr) {
+  int32_t *tmp = (int32_t *)malloc(sizeof(int32_t) * (size_t)(n > 0 ? n : 1));
+  int32_t c = mono_inliers(m, n, F9, thr, tmp);
+  free(tmp);
+  return c;
+}
+int32_t vo_mono_triangulate(const vo_match *m, int32_t n, double f, double cu, double cv, const double *R9, const double *t3,
+                            double *X4n) {
+  const double Kd[9] = {f, 0, cu, 0, f, cv, 0, 0, 1};
+  dm K = dm_from(3, 3, Kd), R = dm_from(3, 3, R9), t = dm_from(3, 1, t3), X;
+  int32_t num = mono_triangulate(m, n, &K, &R, &t, &X);
+  memcpy(X4n, X.a, sizeof(double) * 4 * (size_t)n);
+  dm_free(&K);
+  dm_free(&R);
+  dm_free(&t);
+  dm_free(&X);
+  return num;
+}
+int32_t vo_mono_plane_vote(const double *d, int32_t np, double threshold, double weight, double *sums) {
+  return mono_best_plane(d, np, threshold, weight, sums);
+}
+static int32_t g_last_in_front = -1; /* points in front of the camera in the last estimate, -1: not reached */
+int32_t vo_mono_last_in_front(void) { return g_last_in_front; }
+
 static int cmp_double(const void *a, const void *b) {
   double x = *(const double *)a, y = *(const double *)b;
   return (x > y) - (x < y);
@@ -558,6 +606,7 @@ static int cmp_double(const void *a, const void *b) {
 int32_t vo_estimate_motion_mono(const vo_match *matched, int32_t n, const vo_mono_params *p, double *tr6,
                                 int32_t *inliers, int32_t *n_inliers) {
   *n_inliers = -1;
+  g_last_in_front = -1;
   if (n < 10) return 0;
   const double Kd[9] = {p->f, 0, p->cu, 0, p->f, p->cv, 0, 0, 1};
   dm K = dm_from(3, 3, Kd);
@@ -656,6 +705,7 @@ int32_t vo_estimate_motion_mono(const vo_match *matched, int32_t n, const vo_mon
           np++;
         }
       }
+      g_last_in_front = np;
       if (np >= 10) {
         double *sorted = (double *)malloc(sizeof(double) * (size_t)np);
         memcpy(sorted, dist, sizeof(double) * (size_t)np);
@@ -675,21 +725,7 @@ int32_t vo_estimate_motion_mono(const vo_match *matched, int32_t n, const vo_mon
             s += n1 * zc[i];
             d[i] = s;
           }
-          double best_sum = 0;
-          int32_t best_idx = 0;
-          for (int32_t i = 0; i < np; i++) {
-            if (d[i] > threshold) {
-              double sum = 0;
-              for (int32_t j = 0; j < np; j++) {
-                double dd = d[j] - d[i];
-                sum += exp(-dd * dd * weight);
-              }
-              if (sum > best_sum) {
-                best_sum = sum;
-                best_idx = i;
-              }
-            }
-          }
+          int32_t best_idx = mono_best_plane(d, np, threshold, weight, 0);
           double best_d = d[best_idx];
           double ry = asin(AT(R, 0, 2));
           double rx = asin(-AT(R, 1, 2) / cos(ry));

@@ -140,6 +140,14 @@ void vo_mono_fundamental(const vo_match *m, const int32_t *active, int32_t na, d
  * inlier list would be left untouched (early exits before the RANSAC) */
 int32_t vo_estimate_motion_mono(const vo_match *m, int32_t n, const vo_mono_params *p, double *tr6, int32_t *inliers,
                                 int32_t *n_inliers);
+/* single pieces of the estimate: getInlier's count (:296-344); triangulateChieral for one (R, t) (:394-431, X4n = 4 x n,
+ * returns the chirality count); findBestPlane's vote (:75-101, sums[i] = 0 where d[i] <= threshold, returns the index);
+ * the number of points the last vo_estimate_motion_mono found in front of the camera (-1: it did not get that far) */
+int32_t vo_mono_inlier_count(const vo_match *m, int32_t n, const double *F9, double thr);
+int32_t vo_mono_triangulate(const vo_match *m, int32_t n, double f, double cu, double cv, const double *R9, const double *t3,
+                            double *X4n);
+int32_t vo_mono_plane_vote(const double *d, int32_t np, double threshold, double weight, double *sums);
+int32_t vo_mono_last_in_front(void);
 typedef struct vo_mono vo_mono; /* VisualOdometryMono, viso/viso_mono.h:28-90 */
 vo_mono *vo_mono_create(const vo_params *mp, int32_t bucket_max, double bucket_w, double bucket_h,
                         const vo_mono_params *ep);

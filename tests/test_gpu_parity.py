@@ -945,12 +945,22 @@ def test_multi_sequence_rejects_wrong_shapes_before_the_call(vm):
 
 # ---- monocular egomotion: HIP inlier counting + plane vote ----------
 
+def _mono_on_device(vm):
+    """VisualOdometryMono whose hypothesis fits and triangulations run on the GPU: a context whose self-test sent them to
+    the host would pass every comparison below without running k_mono_fit or k_mono_triangulate"""
+    def make(*a, **k):
+        v = vm.VisualOdometryMono(*a, **k)
+        assert v.device_svd() == 1
+        return v
+    return make
+
+
 def test_vo_mono_cases_golden(vm):
-    G.replay_mono_cases(_load_golden("mono_cases"), vm.VisualOdometryMono, vm.vo_sampler_seed)
+    G.replay_mono_cases(_load_golden("mono_cases"), _mono_on_device(vm), vm.vo_sampler_seed)
 
 
 def test_vo_mono_sequence_golden(vm, synth):
-    G.replay_mono_sequence(_load_golden("mono_seq12_640x480"), synth, vm.VisualOdometryMono, vm.vo_sampler_seed)
+    G.replay_mono_sequence(_load_golden("mono_seq12_640x480"), synth, _mono_on_device(vm), vm.vo_sampler_seed)
 
 
 def test_vo_mono_large_vs_oracle(vm, B):
@@ -971,8 +981,11 @@ def test_vo_mono_large_vs_oracle(vm, B):
         o.close()
         vm.vo_sampler_seed(71)
         v = vm.VisualOdometryMono(f, cu, cv, **kw)
+        assert v.device_svd() == 1
         ok_v, T_v = v.process_matches(m)
         assert ok_v == ok_o and ok_o
+        if n == 2500:   # fits, counts, triangulation and the vote all came from the GPU
+            assert v.device_stages() == (vm.MONO_STAGE_FIT | vm.MONO_STAGE_COUNT | vm.MONO_STAGE_TRIANGULATE | vm.MONO_STAGE_VOTE)
         assert np.array_equal(v.get_inlier_indices(), inl_o)
         assert T_v.tobytes() == T_o.tobytes()
         v.close()
@@ -1003,6 +1016,7 @@ def test_vo_mono_dropin_header(vm, tmp_path):
     rec = np.fromfile(out, dtype=np.float64)
     vm.vo_sampler_seed(71)
     v = vm.VisualOdometryMono(f, cu, cv, height=1.65, pitch=-0.08, ransac_iters=300)
+    assert v.device_svd() == 1
     ok, T = v.process_matches(m)
     assert bool(rec[0]) == ok and int(rec[1]) == v.get_number_of_inliers()
     assert rec[2:].reshape(4, 4).tobytes() == T.tobytes()
