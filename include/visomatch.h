@@ -166,6 +166,56 @@ int32_t vsm_pairs_get_matches(vsm_handle *h, int32_t pair, vsm_p_match *out, int
 /* wall-clock split of the last vsm_pairs_run on the caller's thread, microseconds: {image side of all frames, first passes +
  * their outlier removal and prior boxes, second passes + refinement + final chains + copy-out, total} */
 void vsm_pairs_get_timings(vsm_handle *h, double *out4);
+/* ---- multi-view feature tracks from pair match lists ----
+ * No counterpart in the reference, which links consecutive frames only, one list at a time: matlab/plotTrack.m walks
+ * i_matched backwards frame by frame, Reconstruction::update (viso/reconstruction.cpp:71-104) keeps a track_map keyed by
+ * last_idx.  These calls generalise both to arbitrary pairs.
+ * Input: n_frames; pairs: n_pairs x {previous frame a, current frame b}; one match list per pair (lists[k], counts[k]);
+ * side 0 links i1p -> i1c (the left images), 1 links i2p -> i2c.  A NODE is a (frame, feature index) that at least one match
+ * names; match m of pair k is an edge between (a, ip) and (b, ic).  A TRACK is a connected component; its observations are
+ * its nodes in ascending (frame, feature) order.  Tracks with fewer than min_length observations are dropped; the kept
+ * ones are numbered 0 .. T-1 in ascending order of their smallest node.  Results, all exact integers:
+ *   offsets[T + 1]   track t's observations are rows offsets[t] .. offsets[t + 1] - 1
+ *   obs[n_obs][4]    {frame, feature, pair, 2 * match + end}: (pair, match, end 0 = previous / 1 = current) is the first
+ *                    match, in that order, that names the node - pixel coordinates and, for quad lists, the other image's
+ *                    index are read from it
+ *   flags[T]         bit 0 = inconsistent: two observations in one frame (a self pair a == b; mismatches that merge two points)
+ *   per pair, track_of_match[counts[k]]: the track of every match, -1 where its track was dropped
+ * The result depends on the inputs only, not on thread order; the partition into tracks not on the order of the pairs.
+ * VSM_EARG, nothing enqueued and the last result kept: side outside 0..1, min_length < 1, a frame index outside
+ * [0, n_frames) (a previous frame of -1 is a stereo-only list: tracks across time are not defined for it), a negative
+ * feature index on the chosen side, a NULL list with a positive count, more than 2^31 - 2 node ids (the sum over the frames
+ * of 1 + the largest index named) or 2^30 - 1 matches.  No pair with a match: VSM_OK, 0 tracks.
+ * vsm_tracks_run takes lists in host memory, wherever they came from (vsm_pairs_run, vsm_sequence_run with pairs
+ * (f - 1, f), the per-frame API), and runs on the handle's device and stream: the index pairs go up in one copy (8 bytes
+ * per match), the results come back in one.  It has no CPU path.  Segments of at most VSM_TRACKS_WAVE_MAX observations
+ * are ordered by a wave, of at most VSM_TRACKS_BLOCK_MAX by a workgroup, longer ones by the host. */
+#define VSM_TRACKS_WAVE_MAX 64
+#define VSM_TRACKS_BLOCK_MAX 2048
+int vsm_tracks_run(vsm_handle *h, int32_t n_frames, const int32_t *pairs, int32_t n_pairs, const vsm_p_match *const *lists,
+                   const int32_t *counts, int32_t side, int32_t min_length);
+/* the same on the pairs and lists of the last vsm_pairs_run, which stay as they are, like all other state of the handle.
+ * VSM_ENOTREADY without such a run, VSM_EARG after one with method 1. */
+int vsm_pairs_tracks(vsm_handle *h, int32_t side, int32_t min_length);
+/* the handle's last track result: T; n_obs; the three arrays (any may be NULL; returns T); the tracks of pair `pair`'s
+ * matches (copies at most cap, returns the pair's match count) */
+int32_t vsm_tracks_count(vsm_handle *h);
+int32_t vsm_tracks_num_obs(vsm_handle *h);
+int32_t vsm_tracks_get(vsm_handle *h, int32_t *offsets, int32_t *obs, uint8_t *flags);
+int32_t vsm_tracks_of_matches(vsm_handle *h, int32_t pair, int32_t *out, int32_t cap);
+/* {node ids, edges, tracks kept, inconsistent tracks, segments ordered by a wave, by a workgroup, by the host, items per
+ * workgroup of the device scan} */
+void vsm_tracks_get_stats(vsm_handle *h, int64_t *out8);
+/* wall-clock split of the last call, microseconds: {packing, upload, kernels (with the one wait for the totals), download +
+ * host part} */
+void vsm_tracks_get_timings(vsm_handle *h, double *out4);
+/* The same definition by a plain sequential union-find on the host: no GPU, no handle (the CPU suite's subject and the
+ * device path's second opinion - not a fallback).  Returns T, or VSM_EARG with the output arrays untouched.  Outputs may be
+ * NULL: call once for T and *n_obs, then with offsets[T + 1], obs[n_obs][4], flags[T] and track_of_match[sum of counts]
+ * (pair after pair). */
+int32_t vsm_host_tracks(int32_t n_frames, const int32_t *pairs, int32_t n_pairs, const vsm_p_match *const *lists,
+                        const int32_t *counts, int32_t side, int32_t min_length, int32_t *offsets, int32_t *obs, uint8_t *flags,
+                        int32_t *track_of_match, int32_t *n_obs);
 /* Measurement / test switches of a handle.  They are read from the environment once, by vsm_create (VSM_SEQ_V2,
  * VSM_SEQ_CHUNK, VSM_SEQ_DC_STREAMS, VSM_SEQ_SERIAL, VSM_SEQ_GPU_SORTS, VSM_SEQ_EARLY_EXPORT); this call changes one
  * afterwards: name = the variable's name without the VSM_ prefix, in lower case ("seq_serial", "seq_chunk", ...).

@@ -103,6 +103,9 @@ enum VsmKernelId {
   VSM_K_FEAT_SCAN, VSM_K_FEAT_ORDER,
   // refinement = 2 on the device: the sub-pixel fits' least-squares tail and the removal of failed matches
   VSM_K_PARA_APPLY,
+  // feature tracks from pair match lists (vsm_tracks.hip)
+  VSM_K_TRK_INIT, VSM_K_TRK_HOOK, VSM_K_TRK_FLATTEN, VSM_K_TRK_KEEP, VSM_K_TRK_SCAN_REDUCE, VSM_K_TRK_SCAN_TOP, VSM_K_TRK_SCAN_APPLY, VSM_K_TRK_MATCH_TRACKS,
+  VSM_K_TRK_FILL, VSM_K_TRK_ORDER_WAVE, VSM_K_TRK_ORDER_BLOCK,
   VSM_K_COUNT
 };
 struct VsmProf {

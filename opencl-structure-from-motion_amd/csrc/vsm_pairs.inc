@@ -17,6 +17,9 @@ struct VsmPairs {
   int32_t *res_cnt = nullptr, *res_cnt_dev = nullptr;
   size_t slot = 0;
   std::vector<std::vector<vsm_p_match>> lists;  // per pair of the last call
+  std::vector<int32_t> pair_list;  // ... its pairs, frame count and method, for vsm_pairs_tracks; done: it ran to its end
+  int32_t n_frames = 0, method = -1;
+  bool done = false;
   double timings[4] = {0, 0, 0, 0};  // image side, first passes + chains, second passes + chains, total; us
   void free_arena() {
     if (res) (void)hipHostFree(res);
@@ -143,6 +146,10 @@ int vsm_pairs_run(vsm_handle *h, const uint8_t *left, const uint8_t *right, int6
   const double t0 = now_us();
   P.lists.resize((size_t)n_pairs);  // (keeps the capacity of earlier calls)
   for (auto &v : P.lists) v.clear();
+  P.pair_list.assign(pairs, pairs + 2 * (size_t)n_pairs);
+  P.n_frames = n_frames;
+  P.method = method;
+  P.done = false;
   memset(P.timings, 0, sizeof(P.timings));
   const int sides = right ? 2 : 1;
   PairsRingSave save;  // (armed by the first fallback; puts the caller's ring back however the call is left)
@@ -151,6 +158,7 @@ int vsm_pairs_run(vsm_handle *h, const uint8_t *left, const uint8_t *right, int6
       (size_t)ceilf((float)w / (float)p.match_binsize) * (size_t)ceilf((float)hh / (float)p.match_binsize) > 1024) {
     const int rc = pairs_fallback(h, P, save, left, right, frame_stride, on_device, w, hh, bpl, method, pairs, 0, n_pairs, Tr, Tr_valid);
     P.timings[3] = now_us() - t0;
+    P.done = rc == VSM_OK;
     return rc;
   }
   const int C = seq2_plan(n_pairs, h->pool->size(), false, h->sw.pairs_chunk, 0, nullptr).C;
@@ -328,6 +336,7 @@ int vsm_pairs_run(vsm_handle *h, const uint8_t *left, const uint8_t *right, int6
   }
   if (h->prof.on) h->prof.resolve();
   P.timings[3] = now_us() - t0;
+  P.done = true;
   return VSM_OK;
 #undef PAIRS_CHK
 }

@@ -26,6 +26,9 @@ assert P_MATCH.itemsize == 48
 
 INT_PARAMS = ["nms_n", "nms_tau", "match_binsize", "match_radius", "match_disp_tolerance",
               "outlier_disp_tolerance", "outlier_flow_tolerance", "multi_stage", "half_resolution", "refinement"]
+# include/visomatch.h: the longest track segment a wave / a workgroup puts into order (longer ones: the host)
+TRACKS_WAVE_MAX = 64
+TRACKS_BLOCK_MAX = 2048
 FEATURE_SETS = {"1p1": 0, "2p1": 1, "1c1": 2, "2c1": 3, "1p2": 4, "2p2": 5, "1c2": 6, "2c2": 7}
 
 # every symbol include/visomatch.h declares
@@ -35,7 +38,9 @@ EXPORTS = ["vsm_default_params", "vsm_create", "vsm_destroy", "vsm_set_intrinsic
            "vsm_num_ranges", "vsm_get_ranges", "vsm_get_gradients", "vsm_get_filter_responses", "vsm_get_counters",
            "vsm_get_timings", "vsm_set_profiling", "vsm_num_kernels", "vsm_kernel_name", "vsm_get_kernel_stats",
            "vsm_host_delaunay", "vsm_host_delaunay_split", "vsm_debug_delaunay_gpu", "vsm_debug_dc_bench", "vsm_host_ties", "vsm_debug_ties_gpu", "vsm_host_outliers_and_prior", "vsm_host_outliers_and_prior_threads", "vsm_debug_dc2", "vsm_debug_dc2_band_factor", "vsm_debug_predicates", "vsm_debug_seq_plan", "vsm_debug_chunk_jobs", "vsm_debug_pair_jobs", "vsm_local_cpus", "vsm_forkjoin_cpus", "vsm_device_pool_stats", "vsm_device_pool_trim", "vsm_sequence_run", "vsm_sequence_num_matches", "vsm_sequence_get_matches",
-           "vsm_sequence_get_timings", "vsm_sequence_path", "vsm_pairs_run", "vsm_pairs_num_matches", "vsm_pairs_get_matches", "vsm_pairs_get_timings", "vsm_set_option", "vsm_version", "vsm_host_register", "vsm_host_unregister",
+           "vsm_sequence_get_timings", "vsm_sequence_path", "vsm_pairs_run", "vsm_pairs_num_matches", "vsm_pairs_get_matches", "vsm_pairs_get_timings",
+           "vsm_tracks_run", "vsm_pairs_tracks", "vsm_tracks_count", "vsm_tracks_num_obs", "vsm_tracks_get", "vsm_tracks_of_matches",
+           "vsm_tracks_get_stats", "vsm_tracks_get_timings", "vsm_host_tracks", "vsm_set_option", "vsm_version", "vsm_host_register", "vsm_host_unregister",
            "vsm_multi_create", "vsm_multi_destroy", "vsm_multi_process", "vsm_multi_num_sequences", "vsm_multi_get_motion",
            "vsm_multi_motion_valid", "vsm_multi_num_matches", "vsm_multi_get_matches", "vsm_multi_num_inliers", "vsm_multi_get_inliers",
            "vsm_multi_get_timings",
@@ -168,6 +173,18 @@ def lib():
         L.vsm_pairs_get_matches.argtypes = [vp, i32, vp, i32]
         L.vsm_pairs_get_timings.argtypes = [vp, vp]
         L.vsm_pairs_get_timings.restype = None
+        L.vsm_tracks_run.argtypes = [vp, i32, vp, i32, vp, vp, i32, i32]
+        L.vsm_pairs_tracks.argtypes = [vp, i32, i32]
+        L.vsm_tracks_count.argtypes = [vp]
+        L.vsm_tracks_num_obs.argtypes = [vp]
+        L.vsm_tracks_get.argtypes = [vp, vp, vp, vp]
+        L.vsm_tracks_of_matches.argtypes = [vp, i32, vp, i32]
+        L.vsm_tracks_get_stats.argtypes = [vp, vp]
+        L.vsm_tracks_get_stats.restype = None
+        L.vsm_tracks_get_timings.argtypes = [vp, vp]
+        L.vsm_tracks_get_timings.restype = None
+        L.vsm_host_tracks.restype = i32
+        L.vsm_host_tracks.argtypes = [i32, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp]
         L.vsm_local_cpus.argtypes = [vp, i32]
         L.vsm_forkjoin_cpus.argtypes = [vp, i32]
         L.vsm_debug_dc2_band_factor.restype = None
@@ -504,6 +521,60 @@ def pair_jobs(method, multi_stage, sides, counts, pairs, chunk, tr_valid=None):
     return out, max_nq[:n]
 
 
+TRACK_STATS = ("nodes", "edges", "tracks", "inconsistent", "by_wave", "by_workgroup", "by_host", "scan_block")
+TRACK_TIMINGS = ("pack_us", "upload_us", "kernels_us", "download_host_us")
+
+
+class Tracks:
+    """multi-view feature tracks (include/visomatch.h, vsm_tracks_run): offsets [T+1], obs [n_obs, 4] = {frame, feature,
+    pair, 2 * match + end}, flags [T] (bit 0: two observations in one frame); of_pair(k): the track of every match of pair k
+    (-1: dropped); stats / timings: dicts (empty for the host view)."""
+
+    def __init__(self, offsets, obs, flags, of_pairs, stats=None, timings=None):
+        self.offsets, self.obs, self.flags, self._of_pairs = offsets, obs, flags, of_pairs
+        self.stats, self.timings = stats or {}, timings or {}
+
+    def __len__(self):
+        return len(self.flags)
+
+    def of_pair(self, k):
+        return self._of_pairs[k]
+
+    def track(self, t):
+        return self.obs[self.offsets[t]:self.offsets[t + 1]]
+
+
+def _track_inputs(pairs, lists):
+    """(pairs [P,2] int32, the lists as contiguous P_MATCH arrays, their addresses, their counts)"""
+    pa = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+    ls = [None if l is None else np.ascontiguousarray(l, dtype=P_MATCH) for l in lists]
+    assert len(ls) == len(pa)
+    ptrs = (C.c_void_p * max(len(ls), 1))(*[None if l is None or len(l) == 0 else l.ctypes.data for l in ls])
+    counts = np.array([0 if l is None else len(l) for l in ls], dtype=np.int32)
+    return pa, ls, ptrs, counts
+
+
+def host_tracks(n_frames, pairs, lists, side=0, min_length=2, counts=None):
+    """vsm_host_tracks: the tracks of the match lists `lists` (one P_MATCH array per pair of `pairs`) by a sequential
+    union-find on the host - no GPU.  counts: override the lists' lengths (argument tests).  Returns a Tracks object;
+    raises VisoMatchError on VSM_EARG."""
+    L = lib()
+    pa, ls, ptrs, cnt = _track_inputs(pairs, lists)
+    if counts is not None:
+        cnt = np.ascontiguousarray(counts, dtype=np.int32)
+    args = (int(n_frames), pa.ctypes.data_as(C.c_void_p), len(pa), ptrs, cnt.ctypes.data_as(C.c_void_p), int(side), int(min_length))
+    n_obs = C.c_int32(0)
+    T = L.vsm_host_tracks(*args, None, None, None, None, C.byref(n_obs))
+    if T < 0:
+        raise VisoMatchError(f"vsm_host_tracks failed with {T}" + (" (VSM_EARG)" if T == Matcher.EARG else ""))
+    offsets, obs, flags = np.zeros(T + 1, np.int32), np.zeros((n_obs.value, 4), np.int32), np.zeros(T, np.uint8)
+    tom = np.zeros(int(cnt.sum()), np.int32)
+    got = L.vsm_host_tracks(*args, offsets.ctypes.data_as(C.c_void_p), obs.ctypes.data_as(C.c_void_p), flags.ctypes.data_as(C.c_void_p),
+                            tom.ctypes.data_as(C.c_void_p), C.byref(n_obs))
+    assert got == T
+    return Tracks(offsets, obs, flags, np.split(tom, np.cumsum(cnt)[:-1]) if len(cnt) else [])
+
+
 def remove_outliers(matches, method, w, h, gpu=False, gpu_ties=False, copies=1, threads=1, **params):
     """Matcher::removeOutliers + computePriorStatistics on a match list: host code of the per-frame path (gpu=False; threads > 1:
     split over fork-join threads the way vsm_match runs a frame's final list) or the GPU-resident chain of the look-ahead path;
@@ -574,6 +645,7 @@ class Matcher:
     OK, EDIMS, ENOTREADY, EHIP, EARG = 0, -1, -2, -3, -4
 
     _inputs = None
+    _n_pairs = 0  # pairs of the last successful match_pairs call
 
     def __init__(self, stage_capture=False, options=None, **params):
         """params: fields of the reference's Matcher::parameters; options: measurement / test switches of the handle
@@ -798,6 +870,7 @@ class Matcher:
         rc = L.vsm_pairs_run(self.h, pl, pr, fs, dev, F, w, h, bpl, method, pa.ctypes.data_as(C.c_void_p), P, tp, vp_)
         if rc != self.OK:
             raise VisoMatchError(f"vsm_pairs_run failed with {rc}" + (" (VSM_EARG)" if rc == self.EARG else ""))
+        self._n_pairs = P
         return [self.pair_matches(k) for k in range(P)] if fetch else None
 
     def pair_matches(self, k):
@@ -807,6 +880,40 @@ class Matcher:
         if n:
             L.vsm_pairs_get_matches(self.h, k, a.ctypes.data_as(C.c_void_p), n)
         return a
+
+    # --- feature tracks from pair match lists --------------------------------------------------
+    def _tracks_result(self, rc, what, n_pairs):
+        L = lib()
+        if rc != self.OK:
+            names = {self.EARG: " (VSM_EARG)", self.ENOTREADY: " (VSM_ENOTREADY)"}
+            raise VisoMatchError(f"{what} failed with {rc}" + names.get(rc, ""))
+        T, n_obs = L.vsm_tracks_count(self.h), L.vsm_tracks_num_obs(self.h)
+        offsets, obs, flags = np.zeros(T + 1, np.int32), np.zeros((n_obs, 4), np.int32), np.zeros(T, np.uint8)
+        L.vsm_tracks_get(self.h, offsets.ctypes.data_as(C.c_void_p), obs.ctypes.data_as(C.c_void_p), flags.ctypes.data_as(C.c_void_p))
+        of_pairs = []
+        for k in range(n_pairs):
+            n = L.vsm_tracks_of_matches(self.h, k, None, 0)
+            a = np.zeros(n, np.int32)
+            if n:
+                L.vsm_tracks_of_matches(self.h, k, a.ctypes.data_as(C.c_void_p), n)
+            of_pairs.append(a)
+        st, tm = np.zeros(8, np.int64), np.zeros(4, np.float64)
+        L.vsm_tracks_get_stats(self.h, st.ctypes.data_as(C.c_void_p))
+        L.vsm_tracks_get_timings(self.h, tm.ctypes.data_as(C.c_void_p))
+        return Tracks(offsets, obs, flags, of_pairs, dict(zip(TRACK_STATS, st.tolist())), dict(zip(TRACK_TIMINGS, tm.tolist())))
+
+    def tracks(self, n_frames, pairs, lists, side=0, min_length=2):
+        """vsm_tracks_run: the connected components of the match lists `lists` (one P_MATCH array per (previous, current)
+        pair of `pairs`), on the device.  Returns a Tracks object."""
+        pa, ls, ptrs, cnt = _track_inputs(pairs, lists)
+        rc = lib().vsm_tracks_run(self.h, int(n_frames), pa.ctypes.data_as(C.c_void_p), len(pa), ptrs, cnt.ctypes.data_as(C.c_void_p),
+                                  int(side), int(min_length))
+        return self._tracks_result(rc, "vsm_tracks_run", len(pa))
+
+    def pair_tracks(self, side=0, min_length=2):
+        """vsm_pairs_tracks: the tracks of the last match_pairs call's lists (fetched or not), which stay as they are"""
+        rc = lib().vsm_pairs_tracks(self.h, int(side), int(min_length))
+        return self._tracks_result(rc, "vsm_pairs_tracks", self._n_pairs)
 
     def pair_timings(self):
         t = np.zeros(4, dtype=np.float64)
