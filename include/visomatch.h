@@ -216,6 +216,73 @@ void vsm_tracks_get_timings(vsm_handle *h, double *out4);
 int32_t vsm_host_tracks(int32_t n_frames, const int32_t *pairs, int32_t n_pairs, const vsm_p_match *const *lists,
                         const int32_t *counts, int32_t side, int32_t min_length, int32_t *offsets, int32_t *obs, uint8_t *flags,
                         int32_t *track_of_match, int32_t *n_obs);
+/* ---- triangulation of feature tracks into 3-D points ----
+ * The per-track mathematics of the reference's Reconstruction class (viso/reconstruction.{h,cpp}), in a batch form of this
+ * library's own: the class is incremental over consecutive frames, caps a track at 6 pixels, keeps points as float and pairs
+ * a track's first and last pixel with the pose of the frame AFTER the one they were seen in; here every observation uses
+ * its own frame's matrices, a track has any length and everything is double.
+ * Input: n_frames poses, camera to world, 12 doubles each (rows 0..2 of [R | c], row-major), pose_valid: a byte per frame
+ * (NULL: all valid); the intrinsics f, cu, cv; the tracks as vsm_tracks_get gives them: offsets[T + 1] (offsets[0] = 0),
+ * per observation its frame (ascending within a track) and its pixel uv = (u, v) as two floats; flags[T] (may be NULL).
+ * Per frame, once, on the host: inv = [R^T | -R^T c] - the rigid inverse, not the reference's general Matrix::inv - and
+ * proj = K * inv, every entry a sum over k ascending from the k = 0 product.  Tr_cam_road is built on the host from
+ * cam_pitch and cam_height as Reconstruction::setCalibration does.
+ * Per track, the steps of reconstruction.cpp:121-139 in that order; the first status that applies wins:
+ *   1  the track is flagged inconsistent (flags bit 0): not attempted
+ *   2  an observation's frame has no valid pose
+ *   3  fewer than min_track_length observations
+ *   4  initPoint on the first and last observation (4x4 J, Matrix::svd, w = V[3][3] kept as a double): |w| < 1e-10
+ *   5  pointType with the first and last observation's frames (-1 not visible, 0 below the road, 1 road, 2 obstacle) is
+ *      below point_type
+ *   6  refinePoint: an updatePoint(step 1, eps 1e-5) failed - cc < 1e-10 at an observation, or Matrix::solve (Gauss-Jordan,
+ *      full pivoting, eps 1e-20) found no pivot.  Every update uses ALL the track's observations and sums over i ascending.
+ *   7  not converged after the reference loop's 22 updates
+ *   8  pointDistance from the centre of frame (first frame + last frame) / 2 (integer division; without a valid pose there,
+ *      the nearest lower frame with one) is not below max_dist
+ *   9  rayAngle between the rays to the first and last observation's centres is not above min_angle.  The device writes
+ *      |v1 . v2| (1000 for a centre on the point); the host applies libm's acos(..) * 180 / pi and decides.
+ *   0  kept
+ * Results per track, all exact: status; xyz[3], the point as it stood when the status was decided (zeros for 1..4); type
+ * (-2 where pointType was not reached); updates, the number of updatePoint calls; dist and angle (0 where not reached). */
+typedef struct vsm_triangulate_params {
+  int32_t point_type;        /* 1 */
+  int32_t min_track_length;  /* 2 */
+  double max_dist;           /* 30.0 */
+  double min_angle;          /* 2.0 (degrees) */
+  double cam_pitch;          /* -0.08 */
+  double cam_height;         /* 1.6    (defaults: reconstruction.h:62, reconstruction.cpp:37-38) */
+} vsm_triangulate_params;
+void vsm_triangulate_default_params(vsm_triangulate_params *p);
+/* The general form, on the caller's arrays.  Runs on the handle's device and stream: one copy up (27 doubles per frame, 12
+ * bytes per observation, 5 per track), the kernel (a 16-lane group per track), one copy back (52 bytes per track).  It has
+ * no CPU path.  VSM_EARG, nothing enqueued and the last result kept: a frame index outside [0, n_frames), offsets that do
+ * not start at 0 or decrease, a NULL array with a positive count, params NULL or min_track_length < 1.  Nothing else of the
+ * handle is touched: not the streaming ring, not the vsm_pairs_run lists, not the track result. */
+int vsm_triangulate_run(vsm_handle *h, int32_t n_frames, const double *poses, const uint8_t *pose_valid, double f, double cu, double cv,
+                        int32_t n_tracks, const int32_t *offsets, const int32_t *obs_frames, const float *uv, const uint8_t *flags,
+                        const vsm_triangulate_params *params);
+/* The same on the handle's last track result (frame count and side as given to that call; poses: one per frame).  The
+ * pixel of observation {frame, feature, pair, 2 * match + end} is read from match `match` of lists[pair]: u1p / v1p (end 0)
+ * or u1c / v1c (end 1) for side 0, u2p / v2p or u2c / v2c for side 1.  lists == NULL: the lists of the last vsm_pairs_run
+ * (counts is not read).  VSM_ENOTREADY: no track result; or lists == NULL and the tracks did not come from vsm_pairs_tracks
+ * (or a later vsm_pairs_run has replaced the lists).  VSM_EARG: counts disagree with the track result's, a NULL list with a
+ * positive count, params as above. */
+int vsm_tracks_triangulate(vsm_handle *h, const vsm_p_match *const *lists, const int32_t *counts, const double *poses,
+                           const uint8_t *pose_valid, double f, double cu, double cv, const vsm_triangulate_params *params);
+/* the handle's last point result: T; the six arrays (any may be NULL; returns T): status[T], xyz[T][3], type[T], updates[T],
+ * dist[T], angle[T] */
+int32_t vsm_points_count(vsm_handle *h);
+int32_t vsm_points_get(vsm_handle *h, int32_t *status, double *xyz, int32_t *type, int32_t *updates, double *dist, double *angle);
+/* tracks per status value 0..9 */
+void vsm_points_get_stats(vsm_handle *h, int64_t *out10);
+/* wall-clock split of the last call, microseconds: {gather / packing, upload, kernel, download + host part} */
+void vsm_points_get_timings(vsm_handle *h, double *out4);
+/* The same definition on one host thread: no GPU, no handle (the CPU suite's subject and the device path's second opinion -
+ * not a fallback).  Returns T, or VSM_EARG with the output arrays untouched.  Outputs may be NULL. */
+int32_t vsm_host_triangulate(int32_t n_frames, const double *poses, const uint8_t *pose_valid, double f, double cu, double cv,
+                             int32_t n_tracks, const int32_t *offsets, const int32_t *obs_frames, const float *uv, const uint8_t *flags,
+                             const vsm_triangulate_params *params, int32_t *status, double *xyz, int32_t *type, int32_t *updates,
+                             double *dist, double *angle);
 /* Measurement / test switches of a handle.  They are read from the environment once, by vsm_create (VSM_SEQ_V2,
  * VSM_SEQ_CHUNK, VSM_SEQ_DC_STREAMS, VSM_SEQ_SERIAL, VSM_SEQ_GPU_SORTS, VSM_SEQ_EARLY_EXPORT); this call changes one
  * afterwards: name = the variable's name without the VSM_ prefix, in lower case ("seq_serial", "seq_chunk", ...).

@@ -27,6 +27,7 @@
 #include "vsm_dc_gpu.h"
 #include "vsm_internal.h"
 #include "vsm_tracks.h"
+#include "vsm_points.h"
 
 #define HIPCHK(expr)                                                                              \
   do {                                                                                            \
@@ -567,6 +568,7 @@ struct vsm_handle {
   struct Seq2 *seq2 = nullptr;   // GPU-resident look-ahead path (vsm_seq2.inc): streams, slabs, result arena
   int32_t seq_v2_frames = 0;     // > 0: the last sequence's results are in seq2's arena, not in seq_matches
   struct VsmPairs *pairs = nullptr;  // arbitrary frame pairs in one call (vsm_pairs.inc): its own context, banks and result lists
+  struct VsmPoints *points = nullptr;  // track triangulation (vsm_points.inc): staging, device block, last result
   struct VsmTracks *tracks = nullptr;  // feature tracks from pair match lists (vsm_tracks.inc): staging, device block, last result
 
   uint8_t *stage_host = nullptr;  // pinned staging for host images
@@ -598,6 +600,7 @@ static void seq1_destroy(vsm_handle *h);  // vsm_seq1.inc
 static void seq2_destroy(vsm_handle *h);  // vsm_seq2.inc
 static void pairs_destroy(vsm_handle *h);  // vsm_pairs.inc
 static void tracks_destroy(vsm_handle *h);  // vsm_tracks.inc
+static void points_destroy(vsm_handle *h);  // vsm_points.inc
 
 extern "C" {
 
@@ -689,6 +692,7 @@ void vsm_destroy(vsm_handle *h) {
   seq2_destroy(h);
   pairs_destroy(h);
   tracks_destroy(h);
+  points_destroy(h);
   ctx_destroy(h->ring);
   ctx_destroy(h->seq);
   if (h->stage_host) (void)hipHostFree(h->stage_host);
@@ -1404,6 +1408,7 @@ static int seq_ingest_host_frames(vsm_handle *h, VsmCtx &c, int first_img, const
 #include "vsm_multi.inc"
 #include "vsm_pairs.inc"
 #include "vsm_tracks.inc"
+#include "vsm_points.inc"
 extern "C" {
 
 // ---------------------------------------------------------------------------------------
@@ -1617,7 +1622,7 @@ static const char *kKernelNames[VSM_K_COUNT] = {
     "k_dc_keys", "k_dc_vertex_sort", "k_dc_prepare_kd_order", "k_dc_block", "k_dc_merge", "k_dc_support", "k_dc_compact", "k_dc_prior",
     "k_feat_dense", "k_feat_sparse", "k_feat_scan", "k_feat_order", "k_parabolic_apply",
     "k_trk_init", "k_trk_hook", "k_trk_flatten", "k_trk_keep", "k_trk_scan_reduce", "k_trk_scan_top", "k_trk_scan_apply", "k_trk_match_tracks", "k_trk_fill",
-    "k_trk_order_wave", "k_trk_order_block"};
+    "k_trk_order_wave", "k_trk_order_block", "k_pts_triangulate"};
 
 void vsm_set_profiling(vsm_handle *h, int on) {
   h->prof.on = on != 0;

@@ -106,6 +106,8 @@ enum VsmKernelId {
   // feature tracks from pair match lists (vsm_tracks.hip)
   VSM_K_TRK_INIT, VSM_K_TRK_HOOK, VSM_K_TRK_FLATTEN, VSM_K_TRK_KEEP, VSM_K_TRK_SCAN_REDUCE, VSM_K_TRK_SCAN_TOP, VSM_K_TRK_SCAN_APPLY, VSM_K_TRK_MATCH_TRACKS,
   VSM_K_TRK_FILL, VSM_K_TRK_ORDER_WAVE, VSM_K_TRK_ORDER_BLOCK,
+  // track triangulation (vsm_points.hip)
+  VSM_K_PTS_TRIANGULATE,
   VSM_K_COUNT
 };
 struct VsmProf {

@@ -18,6 +18,9 @@ struct VsmTracks {
   double timings[4] = {0, 0, 0, 0};
   std::vector<int32_t> max_p, max_c;
   std::vector<uint8_t> bad;
+  // what vsm_tracks_triangulate needs to find the observations' pixels (vsm_points.inc)
+  int32_t n_frames = 0, side = 0;
+  bool from_pairs = false;  // the lists were those of vsm_pairs_run (vsm_pairs_tracks)
 };
 
 static void tracks_destroy(vsm_handle *h) {
@@ -80,6 +83,9 @@ static int tracks_run(vsm_handle *h, int32_t n_frames, const int32_t *pairs, int
   const int32_t n_nodes = p_feat_base[n_frames];
   // ---- from here on the call replaces the last result ----
   T.have = false;
+  T.n_frames = n_frames;
+  T.side = side;
+  T.from_pairs = false;
   memset(T.stats, 0, sizeof(T.stats));
   memset(T.timings, 0, sizeof(T.timings));
   T.stats[7] = TRK_SCAN_BLOCK;
@@ -246,7 +252,9 @@ int vsm_pairs_tracks(vsm_handle *h, int32_t side, int32_t min_length) {
     lists[k] = P->lists[k].data();
     counts[k] = (int32_t)P->lists[k].size();
   }
-  return tracks_run(h, P->n_frames, P->pair_list.data(), n_pairs, lists.data(), counts.data(), side, min_length);
+  const int rc = tracks_run(h, P->n_frames, P->pair_list.data(), n_pairs, lists.data(), counts.data(), side, min_length);
+  if (rc == VSM_OK) h->tracks->from_pairs = true;
+  return rc;
 }
 
 int32_t vsm_tracks_count(vsm_handle *h) { return (h && h->tracks && h->tracks->have) ? (int32_t)h->tracks->flags.size() : 0; }

@@ -40,7 +40,9 @@ EXPORTS = ["vsm_default_params", "vsm_create", "vsm_destroy", "vsm_set_intrinsic
            "vsm_host_delaunay", "vsm_host_delaunay_split", "vsm_debug_delaunay_gpu", "vsm_debug_dc_bench", "vsm_host_ties", "vsm_debug_ties_gpu", "vsm_host_outliers_and_prior", "vsm_host_outliers_and_prior_threads", "vsm_debug_dc2", "vsm_debug_dc2_band_factor", "vsm_debug_predicates", "vsm_debug_seq_plan", "vsm_debug_chunk_jobs", "vsm_debug_pair_jobs", "vsm_local_cpus", "vsm_forkjoin_cpus", "vsm_device_pool_stats", "vsm_device_pool_trim", "vsm_sequence_run", "vsm_sequence_num_matches", "vsm_sequence_get_matches",
            "vsm_sequence_get_timings", "vsm_sequence_path", "vsm_pairs_run", "vsm_pairs_num_matches", "vsm_pairs_get_matches", "vsm_pairs_get_timings",
            "vsm_tracks_run", "vsm_pairs_tracks", "vsm_tracks_count", "vsm_tracks_num_obs", "vsm_tracks_get", "vsm_tracks_of_matches",
-           "vsm_tracks_get_stats", "vsm_tracks_get_timings", "vsm_host_tracks", "vsm_set_option", "vsm_version", "vsm_host_register", "vsm_host_unregister",
+           "vsm_tracks_get_stats", "vsm_tracks_get_timings", "vsm_host_tracks",
+           "vsm_triangulate_default_params", "vsm_triangulate_run", "vsm_tracks_triangulate", "vsm_points_count", "vsm_points_get",
+           "vsm_points_get_stats", "vsm_points_get_timings", "vsm_host_triangulate", "vsm_set_option", "vsm_version", "vsm_host_register", "vsm_host_unregister",
            "vsm_multi_create", "vsm_multi_destroy", "vsm_multi_process", "vsm_multi_num_sequences", "vsm_multi_get_motion",
            "vsm_multi_motion_valid", "vsm_multi_num_matches", "vsm_multi_get_matches", "vsm_multi_num_inliers", "vsm_multi_get_inliers",
            "vsm_multi_get_timings",
@@ -74,6 +76,11 @@ class VsmVoMonoParams(C.Structure):
                 ("bucket_height", C.c_double), ("f", C.c_double), ("cu", C.c_double), ("cv", C.c_double),
                 ("height", C.c_double), ("pitch", C.c_double), ("ransac_iters", C.c_int32),
                 ("inlier_threshold", C.c_double), ("motion_threshold", C.c_double)]
+
+
+class VsmTriangulateParams(C.Structure):
+    _fields_ = [("point_type", C.c_int32), ("min_track_length", C.c_int32), ("max_dist", C.c_double), ("min_angle", C.c_double),
+                ("cam_pitch", C.c_double), ("cam_height", C.c_double)]
 
 
 def host_register(arr):
@@ -185,6 +192,19 @@ def lib():
         L.vsm_tracks_get_timings.restype = None
         L.vsm_host_tracks.restype = i32
         L.vsm_host_tracks.argtypes = [i32, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp]
+        f64 = C.c_double
+        L.vsm_triangulate_default_params.argtypes = [C.POINTER(VsmTriangulateParams)]
+        L.vsm_triangulate_default_params.restype = None
+        L.vsm_triangulate_run.argtypes = [vp, i32, vp, vp, f64, f64, f64, i32, vp, vp, vp, vp, C.POINTER(VsmTriangulateParams)]
+        L.vsm_tracks_triangulate.argtypes = [vp, vp, vp, vp, vp, f64, f64, f64, C.POINTER(VsmTriangulateParams)]
+        L.vsm_points_count.argtypes = [vp]
+        L.vsm_points_get.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+        L.vsm_points_get_stats.argtypes = [vp, vp]
+        L.vsm_points_get_stats.restype = None
+        L.vsm_points_get_timings.argtypes = [vp, vp]
+        L.vsm_points_get_timings.restype = None
+        L.vsm_host_triangulate.restype = i32
+        L.vsm_host_triangulate.argtypes = [i32, vp, vp, f64, f64, f64, i32, vp, vp, vp, vp, C.POINTER(VsmTriangulateParams)] + [vp] * 6
         L.vsm_local_cpus.argtypes = [vp, i32]
         L.vsm_forkjoin_cpus.argtypes = [vp, i32]
         L.vsm_debug_dc2_band_factor.restype = None
@@ -575,6 +595,86 @@ def host_tracks(n_frames, pairs, lists, side=0, min_length=2, counts=None):
     return Tracks(offsets, obs, flags, np.split(tom, np.cumsum(cnt)[:-1]) if len(cnt) else [])
 
 
+POINT_STATUS = ("kept", "flagged", "no_pose", "too_short", "at_infinity", "type", "update_failed", "not_converged", "too_far", "small_angle")
+POINT_TIMINGS = ("gather_us", "upload_us", "kernels_us", "download_host_us")
+
+
+class Points:
+    """triangulated tracks (include/visomatch.h, vsm_triangulate_run): per track status [T] int32 (0 = kept, POINT_STATUS names
+    the values), xyz [T, 3] float64, type [T] int32, updates [T] int32, dist [T] and angle [T] float64; stats: tracks per
+    status name, timings: dict (both empty for the host view)."""
+
+    def __init__(self, status, xyz, type, updates, dist, angle, stats=None, timings=None):
+        self.status, self.xyz, self.type, self.updates, self.dist, self.angle = status, xyz, type, updates, dist, angle
+        self.stats, self.timings = stats or {}, timings or {}
+
+    def __len__(self):
+        return len(self.status)
+
+    @property
+    def kept(self):
+        return self.status == 0
+
+
+def triangulate_params(**kw):
+    """vsm_triangulate_default_params with fields overridden by keyword"""
+    p = VsmTriangulateParams()
+    lib().vsm_triangulate_default_params(C.byref(p))
+    for k, v in kw.items():
+        assert hasattr(p, k), k
+        setattr(p, k, v)
+    return p
+
+
+def _as_params(params):
+    if isinstance(params, VsmTriangulateParams):
+        return params
+    return triangulate_params(**(params or {}))
+
+
+def _pose_inputs(poses, pose_valid, n_frames=None):
+    """(poses [F, 12] float64 - from [F, 12], [F, 3, 4] or [F, 4, 4] -, validity bytes or None)"""
+    po = np.asarray(poses, dtype=np.float64)
+    po = np.ascontiguousarray(po.reshape(len(po), -1)[:, :12]) if po.size else np.zeros((0, 12))
+    if n_frames is not None:
+        assert len(po) == n_frames, (len(po), n_frames)
+    pv = None if pose_valid is None else np.ascontiguousarray(np.asarray(pose_valid).astype(np.uint8))
+    assert pv is None or pv.shape == (len(po),)
+    return po, pv
+
+
+def _triangulate_inputs(poses, pose_valid, offsets, obs_frames, uv, flags):
+    po, pv = _pose_inputs(poses, pose_valid)
+    off = np.ascontiguousarray(offsets, dtype=np.int32)
+    fr = np.ascontiguousarray(obs_frames, dtype=np.int32)
+    px = np.ascontiguousarray(np.asarray(uv, dtype=np.float32).reshape(-1, 2))
+    fl = None if flags is None else np.ascontiguousarray(flags, dtype=np.uint8)
+    return po, pv, off, fr, px, fl
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _points_arrays(T):
+    return (np.zeros(T, np.int32), np.zeros((T, 3), np.float64), np.zeros(T, np.int32), np.zeros(T, np.int32), np.zeros(T, np.float64),
+            np.zeros(T, np.float64))
+
+
+def host_triangulate(poses, f, cu, cv, offsets, obs_frames, uv, flags=None, pose_valid=None, params=None, n_tracks=None):
+    """vsm_host_triangulate: the tracks' 3-D points on one host thread - no GPU.  n_tracks: override len(offsets) - 1 (argument
+    tests).  Returns a Points object; raises VisoMatchError on VSM_EARG."""
+    po, pv, off, fr, px, fl = _triangulate_inputs(poses, pose_valid, offsets, obs_frames, uv, flags)
+    T = max(len(off) - 1, 0) if n_tracks is None else int(n_tracks)
+    out = _points_arrays(max(T, 0))
+    got = lib().vsm_host_triangulate(len(po), _ptr(po), _ptr(pv), float(f), float(cu), float(cv), T, _ptr(off), _ptr(fr), _ptr(px), _ptr(fl),
+                                     C.byref(_as_params(params)), *[_ptr(a) for a in out])
+    if got < 0:
+        raise VisoMatchError(f"vsm_host_triangulate failed with {got}" + (" (VSM_EARG)" if got == Matcher.EARG else ""))
+    assert got == T
+    return Points(*out)
+
+
 def remove_outliers(matches, method, w, h, gpu=False, gpu_ties=False, copies=1, threads=1, **params):
     """Matcher::removeOutliers + computePriorStatistics on a match list: host code of the per-frame path (gpu=False; threads > 1:
     split over fork-join threads the way vsm_match runs a frame's final list) or the GPU-resident chain of the look-ahead path;
@@ -646,6 +746,7 @@ class Matcher:
 
     _inputs = None
     _n_pairs = 0  # pairs of the last successful match_pairs call
+    _pairs_frames = _track_frames = None  # frames of the last successful match_pairs / tracks or pair_tracks call
 
     def __init__(self, stage_capture=False, options=None, **params):
         """params: fields of the reference's Matcher::parameters; options: measurement / test switches of the handle
@@ -870,7 +971,7 @@ class Matcher:
         rc = L.vsm_pairs_run(self.h, pl, pr, fs, dev, F, w, h, bpl, method, pa.ctypes.data_as(C.c_void_p), P, tp, vp_)
         if rc != self.OK:
             raise VisoMatchError(f"vsm_pairs_run failed with {rc}" + (" (VSM_EARG)" if rc == self.EARG else ""))
-        self._n_pairs = P
+        self._n_pairs, self._pairs_frames = P, F
         return [self.pair_matches(k) for k in range(P)] if fetch else None
 
     def pair_matches(self, k):
@@ -908,12 +1009,52 @@ class Matcher:
         pa, ls, ptrs, cnt = _track_inputs(pairs, lists)
         rc = lib().vsm_tracks_run(self.h, int(n_frames), pa.ctypes.data_as(C.c_void_p), len(pa), ptrs, cnt.ctypes.data_as(C.c_void_p),
                                   int(side), int(min_length))
-        return self._tracks_result(rc, "vsm_tracks_run", len(pa))
+        res = self._tracks_result(rc, "vsm_tracks_run", len(pa))
+        self._track_frames = int(n_frames)
+        return res
 
     def pair_tracks(self, side=0, min_length=2):
         """vsm_pairs_tracks: the tracks of the last match_pairs call's lists (fetched or not), which stay as they are"""
         rc = lib().vsm_pairs_tracks(self.h, int(side), int(min_length))
-        return self._tracks_result(rc, "vsm_pairs_tracks", self._n_pairs)
+        res = self._tracks_result(rc, "vsm_pairs_tracks", self._n_pairs)
+        self._track_frames = self._pairs_frames
+        return res
+
+    # --- tracks into 3-D points -------------------------------------------------------------------
+    def _points_result(self, rc, what):
+        L = lib()
+        if rc != self.OK:
+            names = {self.EARG: " (VSM_EARG)", self.ENOTREADY: " (VSM_ENOTREADY)"}
+            raise VisoMatchError(f"{what} failed with {rc}" + names.get(rc, ""))
+        out = _points_arrays(L.vsm_points_count(self.h))
+        L.vsm_points_get(self.h, *[_ptr(a) for a in out])
+        st, tm = np.zeros(10, np.int64), np.zeros(4, np.float64)
+        L.vsm_points_get_stats(self.h, _ptr(st))
+        L.vsm_points_get_timings(self.h, _ptr(tm))
+        return Points(*out, dict(zip(POINT_STATUS, st.tolist())), dict(zip(POINT_TIMINGS, tm.tolist())))
+
+    def triangulate(self, poses, f, cu, cv, offsets, obs_frames, uv, flags=None, pose_valid=None, params=None, n_tracks=None):
+        """vsm_triangulate_run: the 3-D point of every track, on the device.  poses [F, 12] (or [F, 3, 4] / [F, 4, 4]) camera to
+        world; offsets [T + 1], obs_frames [n_obs], uv [n_obs, 2]; params: a dict of vsm_triangulate_params fields or the
+        struct.  Returns a Points object."""
+        po, pv, off, fr, px, fl = _triangulate_inputs(poses, pose_valid, offsets, obs_frames, uv, flags)
+        T = max(len(off) - 1, 0) if n_tracks is None else int(n_tracks)
+        rc = lib().vsm_triangulate_run(self.h, len(po), _ptr(po), _ptr(pv), float(f), float(cu), float(cv), T, _ptr(off), _ptr(fr), _ptr(px), _ptr(fl),
+                                       C.byref(_as_params(params)))
+        return self._points_result(rc, "vsm_triangulate_run")
+
+    def track_points(self, poses, f, cu, cv, lists=None, pose_valid=None, params=None, counts=None):
+        """vsm_tracks_triangulate: the 3-D points of the handle's last track result.  lists: the match lists the tracks were
+        built from (None: those of the last match_pairs call, for tracks from pair_tracks).  counts: override the lists' lengths
+        (argument tests)."""
+        po, pv = _pose_inputs(poses, pose_valid, self._track_frames)  # (the library reads one pose per frame of the track call)
+        ptrs = cnt = None
+        if lists is not None:
+            _, ls, ptrs, cnt = _track_inputs(np.zeros((len(lists), 2), np.int32), lists)
+            if counts is not None:
+                cnt = np.ascontiguousarray(counts, dtype=np.int32)
+        rc = lib().vsm_tracks_triangulate(self.h, ptrs, _ptr(cnt), _ptr(po), _ptr(pv), float(f), float(cu), float(cv), C.byref(_as_params(params)))
+        return self._points_result(rc, "vsm_tracks_triangulate")
 
     def pair_timings(self):
         t = np.zeros(4, dtype=np.float64)
