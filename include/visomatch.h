@@ -600,6 +600,64 @@ int32_t vsm_host_estimate_motion_mono(const vsm_vo_mono_params *p, const vsm_p_m
 int32_t vsm_host_estimate_motion_stereo(const vsm_vo_stereo_params *p, const vsm_p_match *m, int32_t n, int32_t threads,
                                         double *tr6, double *T16, int32_t *inliers, int32_t *n_inliers);
 
+/* ---- the monocular motion of every pair of a pair set in one call (no counterpart in the reference,
+ * which estimates frame by frame) ----
+ * For pair k with list m_k of n_k flow matches the result - the return value rc (1, 0 or -1), tr6, T16 and the inlier
+ * indices - is byte for byte that of vsm_vo_sampler_seed(71) followed by vsm_host_estimate_motion_mono(params, m_k, n_k):
+ * VisualOdometryMono::estimateMotion with the sampler of a fresh process (viso/viso.cpp:93).  With bucket != 0 the list is
+ * first bucketed as a fresh VisualOdometryMono buckets on its second process() (the parameters' bucket_* fields, a rand()
+ * stream seeded 0 of the pair's own); the bucketed list is part of the result and the inlier indices refer to it.  Every
+ * pair owns its sampler and its rand() stream: the process-wide sampler and libc's rand() are neither read nor advanced, and
+ * the result does not depend on the pairs' order, the chunking or the number of threads.
+ * A pair that fails does not fail the call; `stage` says where its estimate ended: 0 fewer than 10 matches (rc -1),
+ * 1 normalisation degenerate (rc -1), 2 fewer than 10 inliers, 3 no R|t candidate with a point in front, 4 fewer than 10
+ * points in front, 5 median above motion_threshold (rc 0), 6 success (rc 1).  Where rc is not 1, tr6 is zero and T16 the
+ * identity.  On rc -1 the inlier list is empty (this API's choice: the reference leaves the list of the estimate before).
+ *
+ * vsm_motions_run: lists in host memory, on the handle's device and stream.  Of params only the egomotion, calibration and
+ * bucketing fields are read.  VSM_EARG - nothing enqueued, the last result kept - for NULL params, n_pairs <= 0, a NULL list
+ * with a positive count, a negative count, ransac_iters < 0, a flow coordinate (u1p, v1p, u1c, v1c) that is not finite and, with
+ * bucket != 0, a negative u1c or v1c or a bucket size that is not positive (bucketFeatures would index outside its buckets).  VSM_EHIP after a HIP error (nothing further is launched; there
+ * is then no result).  Option "motions_chunk": pairs per chunk, 0 = the memory rule of INTEGRATION.md.
+ * vsm_pairs_motions: the same on the lists of the last vsm_pairs_run, which stay untouched; VSM_ENOTREADY without such a run,
+ * VSM_EARG after one with method 1.
+ * Nothing else of the handle changes: not the streaming ring, the pairs lists, the track or the point results. */
+int vsm_motions_run(vsm_handle *h, const vsm_vo_mono_params *params, int32_t n_pairs, const vsm_p_match *const *lists, const int32_t *counts,
+                    int32_t bucket);
+int vsm_pairs_motions(vsm_handle *h, const vsm_vo_mono_params *params, int32_t bucket);
+/* the last result: the number of pairs (0: none); per-pair arrays rc[P], stage[P], tr6[P][6], T16[P][16], n_inliers[P], any
+ * of them NULL; a pair's inlier indices / the list its estimate saw (out = NULL: their number) */
+int32_t vsm_motions_count(vsm_handle *h);
+int32_t vsm_motions_get(vsm_handle *h, int32_t *rc, int32_t *stage, double *tr6, double *T16, int32_t *n_inliers);
+int32_t vsm_motions_inliers(vsm_handle *h, int32_t pair, int32_t *out, int32_t cap);
+int32_t vsm_motions_matches(vsm_handle *h, int32_t pair, vsm_p_match *out, int32_t cap);
+/* out13: pairs per stage value 0 .. 6; pairs whose hypothesis fits, inlier counts (with the winner and its inlier list),
+ * triangulation and plane vote came from the device (the vote runs on the device for every pair that reaches it, whatever
+ * its number of points); chunks; stream waits */
+void vsm_motions_get_stats(vsm_handle *h, int64_t *out13);
+/* microseconds, summed over the chunks: sampling + packing + upload; fit + count + winner; host fits and E -> R|t;
+ * triangulation; median + vote; total (a handle's first call also runs the SVD self-test, which shows in the total only) */
+void vsm_motions_get_timings(vsm_handle *h, double *out6);
+/* 1 if the handle's self-test (run by the first motions call) found the device's SVD bit-equal to the host's, so that the
+ * calls run on the device; 0 before such a call, or where it did not: the calls then go through the host view */
+int vsm_motions_device_svd(vsm_handle *h);
+/* The same definition on `threads` host threads, no GPU and no handle: a loop of bucketing + the host estimator with
+ * per-pair samplers (the CPU suite's subject and the device path's second opinion - not a fallback).  Per-pair arrays as
+ * above, any of them NULL; pair k's inlier indices start at inliers[counts[0] + .. + counts[k - 1]], the list its estimate saw
+ * at the same offset of matches (both hold the sum of all counts).  Returns n_pairs, or VSM_EARG with the outputs untouched. */
+int32_t vsm_host_pairs_motions(const vsm_vo_mono_params *params, int32_t n_pairs, const vsm_p_match *const *lists, const int32_t *counts,
+                               int32_t bucket, int32_t threads, int32_t *rc, int32_t *stage, double *tr6, double *T16, int32_t *n_inliers,
+                               int32_t *inliers, int32_t *n_matches, vsm_p_match *matches);
+/* Pair motions into the camera-to-world poses vsm_tracks_triangulate takes (host only).  pose[root] = identity; repeated
+ * passes over the pairs in index order: a pair (a, b) with rc 1 whose a has a pose and whose b has none gives pose[b] =
+ * pose[a] * inv(T) (Tr_total = Tr_total * inv(motion), viso/sfm.hh:57-58), one whose b has a pose and whose a has none gives
+ * pose[a] = pose[b] * T; self pairs and pairs between two posed frames are skipped; it stops after a pass that sets nothing.
+ * inv is the rigid inverse [R' | -R' t]; every product entry is a sum over k ascending from the k = 0 product.  poses12 =
+ * n_frames x 12 (rows 0..2, zero where invalid), pose_valid = n_frames bytes.  Returns the number of frames with a pose, or
+ * VSM_EARG for a root or a frame index outside [0, n_frames). */
+int32_t vsm_chain_poses(int32_t n_frames, const int32_t *pairs, int32_t n_pairs, const double *T16, const int32_t *rc, int32_t root,
+                        double *poses12, uint8_t *pose_valid);
+
 const char *vsm_version(void);
 
 #ifdef __cplusplus

@@ -28,6 +28,7 @@
 #include "vsm_internal.h"
 #include "vsm_tracks.h"
 #include "vsm_points.h"
+#include "vsm_motions.h"
 
 #define HIPCHK(expr)                                                                              \
   do {                                                                                            \
@@ -452,6 +453,7 @@ struct VsmSwitches {
   int multi_host_pass1 = -1; // vsm_multi_process: the first-pass lists' removeOutliers + prior boxes on the host pool (1) or by the device chain (0); -1: host for K <= pool threads
   int multi_shared_ego = 0;  // vsm_multi_process: idle pool threads take RANSAC hypotheses of the sequences' egomotion (1: measured, no gain), every sequence on one thread (0)
   int pairs_chunk = 0;       // vsm_pairs_run: pairs per step (0 = the look-ahead call's chunk rule for device-resident frames, seq2_plan)
+  int motions_chunk = 0;     // vsm_motions_run / vsm_pairs_motions: pairs per chunk (0 = as many as the memory rule of vsm_motions.inc allows)
   int frame_early_xy = 1;    // per-frame path: the pass-2 list's pixels cross in front of the list, the host triangulates while the refinement and the export run (vsm_match)
   int filter_planes = 0;     // vsm_push_back keeps f1 / f2 in HBM for vsm_get_filter_responses (the fused tiles write them on the side)
   static int env_int(const char *name, int dflt) {
@@ -502,6 +504,7 @@ struct VsmSwitches {
     else if (!strcmp(name, "multi_host_pass1")) multi_host_pass1 = v;
     else if (!strcmp(name, "multi_shared_ego")) multi_shared_ego = v;
     else if (!strcmp(name, "pairs_chunk")) pairs_chunk = std::max(0, v);
+    else if (!strcmp(name, "motions_chunk")) motions_chunk = std::max(0, v);
     else return false;
     return true;
   }
@@ -569,6 +572,7 @@ struct vsm_handle {
   int32_t seq_v2_frames = 0;     // > 0: the last sequence's results are in seq2's arena, not in seq_matches
   struct VsmPairs *pairs = nullptr;  // arbitrary frame pairs in one call (vsm_pairs.inc): its own context, banks and result lists
   struct VsmPoints *points = nullptr;  // track triangulation (vsm_points.inc): staging, device block, last result
+  struct VsmMotions *motions = nullptr;  // monocular pair motions (vsm_motions_api.inc): staging, device block, last result
   struct VsmTracks *tracks = nullptr;  // feature tracks from pair match lists (vsm_tracks.inc): staging, device block, last result
 
   uint8_t *stage_host = nullptr;  // pinned staging for host images
@@ -601,6 +605,7 @@ static void seq2_destroy(vsm_handle *h);  // vsm_seq2.inc
 static void pairs_destroy(vsm_handle *h);  // vsm_pairs.inc
 static void tracks_destroy(vsm_handle *h);  // vsm_tracks.inc
 static void points_destroy(vsm_handle *h);  // vsm_points.inc
+static void motions_destroy(vsm_handle *h);  // vsm_motions_api.inc
 
 extern "C" {
 
@@ -693,6 +698,7 @@ void vsm_destroy(vsm_handle *h) {
   pairs_destroy(h);
   tracks_destroy(h);
   points_destroy(h);
+  motions_destroy(h);
   ctx_destroy(h->ring);
   ctx_destroy(h->seq);
   if (h->stage_host) (void)hipHostFree(h->stage_host);
@@ -1409,6 +1415,7 @@ static int seq_ingest_host_frames(vsm_handle *h, VsmCtx &c, int first_img, const
 #include "vsm_pairs.inc"
 #include "vsm_tracks.inc"
 #include "vsm_points.inc"
+#include "vsm_motions_api.inc"
 extern "C" {
 
 // ---------------------------------------------------------------------------------------

@@ -53,13 +53,7 @@ struct Sampler {
   }
   // the same draw with the two divisions of a (lo, hi) pair hoisted out: RANSAC draws from the same
   // few ranges thousands of times.  v / per_cell = (v * magic) >> 64 exactly for v < 2^32.
-  uint32_t between(const VsmDrawPlan &p) {
-    uint64_t v;
-    do v = next() - 1;
-    while (v >= p.reject_from);
-    if (p.per_cell) v = (uint64_t)(((__uint128_t)v * p.magic) >> 64);
-    return (uint32_t)(v + p.lo);
-  }
+  uint32_t between(const VsmDrawPlan &p) { return vsm_minstd_draw(state, p); }
 };
 Sampler g_sampler;
 

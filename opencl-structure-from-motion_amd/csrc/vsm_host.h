@@ -97,6 +97,17 @@ struct VsmDrawPlan {  // a (lo, hi) range with the divisions of the distribution
 };
 VsmDrawPlan vsm_sampler_plan(uint32_t lo, uint32_t hi);
 uint32_t vsm_sampler_draw(const VsmDrawPlan &p);          // call with the lock held
+// the same draw from an engine state of the caller's own (seed 71 = a fresh process of the reference): what the process-wide
+// sampler runs on its state, and what every pair of a batched mono estimate (vsm_motions.inc) runs on its own
+inline uint32_t vsm_minstd_draw(uint32_t &state, const VsmDrawPlan &p) {
+  uint64_t v;
+  do {
+    state = (uint32_t)(((uint64_t)state * 16807ull) % 2147483647ull);
+    v = (uint64_t)state - 1;
+  } while (v >= p.reject_from);
+  if (p.per_cell) v = (uint64_t)(((__uint128_t)v * p.magic) >> 64);
+  return (uint32_t)(v + p.lo);
+}
 void vsm_pose_matrix(const double *tr6, double *T16);
 
 // Lock-free fork-join pool for the fine-grained phases inside ONE Delaunay (a dozen tasks of

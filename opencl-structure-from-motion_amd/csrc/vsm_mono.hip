@@ -23,6 +23,7 @@
 //     PROPOSES: candidates within 1e-9 (relative) of the best sum are re-evaluated on the host with
 //     libm's exp() in the reference's summation order, and the first maximum among them wins.
 // Without a GPU context (vsm_host_estimate_motion_mono) both inner loops run on the host threads.
+// The batch form - every pair of a pair set through each of these steps together, vsm_motions_run - is vsm_motions.inc below.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
@@ -35,6 +36,7 @@
 
 #include "vsm_host.h"
 #include "vsm_linalg.h"
+#include "vsm_motions.h"
 #include "vsm_svd_coop.h"
 
 // ---------------------------------------------------------------------------------------
@@ -43,6 +45,19 @@
 struct MonoPt {
   float u1p, v1p, u1c, v1c;
 };
+
+// getInlier's test for one match (viso/viso_mono.cpp:296-344): +, *, / and a compare, the same on the host and on the device
+__host__ __device__ inline bool sampson_in(const MonoPt &p, const double *F, double thr) {
+  const double u1 = p.u1p, v1 = p.v1p, u2 = p.u1c, v2 = p.v1c;
+  const double Fx1u = F[0] * u1 + F[1] * v1 + F[2];
+  const double Fx1v = F[3] * u1 + F[4] * v1 + F[5];
+  const double Fx1w = F[6] * u1 + F[7] * v1 + F[8];
+  const double Ftx2u = F[0] * u2 + F[3] * v2 + F[6];
+  const double Ftx2v = F[1] * u2 + F[4] * v2 + F[7];
+  const double x2tFx1 = u2 * Fx1u + v2 * Fx1v + Fx1w;
+  const double d = x2tFx1 * x2tFx1 / (Fx1u * Fx1u + Fx1v * Fx1v + Ftx2u * Ftx2u + Ftx2v * Ftx2v);
+  return fabs(d) < thr;
+}
 
 // getInlier (viso/viso_mono.cpp:296-344) for every (hypothesis, match): blockIdx.y = hypothesis,
 // one match per lane; the nine doubles of F are wave-uniform.  counts[k] += inliers.
@@ -105,15 +120,13 @@ __global__ void __launch_bounds__(256)
 // 16 lanes per hypothesis (vsm_svd_coop.h): the matrices of a group live in LDS, the lanes share the
 // independent column / row loops of the SVD, 16 hypotheses per 256-thread block.
 #define FIT_GROUP_DOUBLES 192  // U 72 + V 81 + W 9 + RV 9, padded
-__global__ void __launch_bounds__(256)
-    k_mono_fit(const MonoPt *__restrict__ pts, const int32_t *__restrict__ picks, int K, double *__restrict__ Fs) {
-  __shared__ double s_m[16 * FIT_GROUP_DOUBLES];
-  const int grp = threadIdx.x >> 4, ln = threadIdx.x & 15;
-  const int k = blockIdx.x * 16 + grp;
-  if (k >= K) return;  // whole groups leave together
-  volatile double *A = s_m + grp * FIT_GROUP_DOUBLES, *v = A + 72, *w = v + 81, *rv1 = w + 9;
+// One group's fit: pick8 = the hypothesis' eight indices into pts, A = the group's FIT_GROUP_DOUBLES doubles of LDS, F = where
+// its nine doubles go.  Shared by k_mono_fit and the batched k_motions_fit (vsm_motions.inc).
+__device__ __forceinline__ void mono_fit_group(const MonoPt *__restrict__ pts, const int32_t *__restrict__ pick8, volatile double *A, int ln,
+                                               double *__restrict__ Fout) {
+  volatile double *v = A + 72, *w = v + 81, *rv1 = w + 9;
   if (ln < 8) {  // lane i fills row i of the constraint matrix
-    const MonoPt q = pts[picks[k * 8 + ln]];
+    const MonoPt q = pts[pick8[ln]];
     volatile double *r = A + ln * 9;
     r[0] = q.u1c * q.u1p;
     r[1] = q.u1c * q.v1p;
@@ -144,8 +157,16 @@ __global__ void __launch_bounds__(256)
     vsm_la::mul(u, D, UD, 3, 3, 3);
     vsm_la::transpose(vv, Vt, 3, 3);
     vsm_la::mul(UD, Vt, F, 3, 3, 3);
-    for (int i = 0; i < 9; i++) Fs[(size_t)k * 9 + i] = F[i];
+    for (int i = 0; i < 9; i++) Fout[i] = F[i];
   }
+}
+__global__ void __launch_bounds__(256)
+    k_mono_fit(const MonoPt *__restrict__ pts, const int32_t *__restrict__ picks, int K, double *__restrict__ Fs) {
+  __shared__ double s_m[16 * FIT_GROUP_DOUBLES];
+  const int grp = threadIdx.x >> 4, ln = threadIdx.x & 15;
+  const int k = blockIdx.x * 16 + grp;
+  if (k >= K) return;  // whole groups leave together
+  mono_fit_group(pts, picks + k * 8, s_m + grp * FIT_GROUP_DOUBLES, ln, Fs + (size_t)k * 9);
 }
 
 // triangulateChieral (viso/viso_mono.cpp:394-431): thread per (candidate blockIdx.y, match).
@@ -153,29 +174,32 @@ __global__ void __launch_bounds__(256)
 struct MonoCams {
   double P1[12], P2[4][12];
 };
+#define TRI_LDS_DOUBLES ((16 + 16 + 4 + 4 + 4) * 64)
+// One match against one camera pair: J = the thread's column of the block's TRI_LDS_DOUBLES doubles (stride 64), Xi = where
+// its first coordinate goes, the other three n doubles apart each.  Returns whether the point is in front of both cameras.
+// Shared by k_mono_triangulate and the batched k_motions_triangulate (vsm_motions.inc).
+__device__ __forceinline__ bool mono_triangulate_one(const MonoPt q, const double *P1, const double *P2, double *J, double *__restrict__ Xi, size_t n) {
+  double *v4 = J + 16 * 64, *w4 = v4 + 16 * 64, *r4 = w4 + 4 * 64, *c4 = r4 + 4 * 64;
+  for (int j = 0; j < 4; j++) {
+    J[(0 * 4 + j) * 64] = P1[2 * 4 + j] * q.u1p - P1[0 * 4 + j];
+    J[(1 * 4 + j) * 64] = P1[2 * 4 + j] * q.v1p - P1[1 * 4 + j];
+    J[(2 * 4 + j) * 64] = P2[2 * 4 + j] * q.u1c - P2[0 * 4 + j];
+    J[(3 * 4 + j) * 64] = P2[2 * 4 + j] * q.v1c - P2[1 * 4 + j];
+  }
+  vsm_la::svd_nr<64>(J, 4, 4, 4, w4, v4, r4, c4);
+  double x[4];
+  for (int r = 0; r < 4; r++) x[r] = Xi[(size_t)r * n] = v4[(r * 4 + 3) * 64];
+  double ax = 0, bx = 0;
+  for (int k = 0; k < 4; k++) ax += P1[2 * 4 + k] * x[k];
+  for (int k = 0; k < 4; k++) bx += P2[2 * 4 + k] * x[k];
+  return ax * x[3] > 0 && bx * x[3] > 0;
+}
 __global__ void __launch_bounds__(64)
     k_mono_triangulate(const MonoPt *__restrict__ raw, int n, MonoCams cams, double *__restrict__ X, int32_t *__restrict__ chir) {
-  __shared__ double s_m[(16 + 16 + 4 + 4 + 4) * 64];
+  __shared__ double s_m[TRI_LDS_DOUBLES];
   const int i = blockIdx.x * blockDim.x + threadIdx.x, c = blockIdx.y;
   bool front = false;
-  if (i < n) {
-    const MonoPt q = raw[i];
-    const double *P1 = cams.P1, *P2 = cams.P2[c];
-    double *J = s_m + threadIdx.x, *v4 = J + 16 * 64, *w4 = v4 + 16 * 64, *r4 = w4 + 4 * 64, *c4 = r4 + 4 * 64;
-    for (int j = 0; j < 4; j++) {
-      J[(0 * 4 + j) * 64] = P1[2 * 4 + j] * q.u1p - P1[0 * 4 + j];
-      J[(1 * 4 + j) * 64] = P1[2 * 4 + j] * q.v1p - P1[1 * 4 + j];
-      J[(2 * 4 + j) * 64] = P2[2 * 4 + j] * q.u1c - P2[0 * 4 + j];
-      J[(3 * 4 + j) * 64] = P2[2 * 4 + j] * q.v1c - P2[1 * 4 + j];
-    }
-    vsm_la::svd_nr<64>(J, 4, 4, 4, w4, v4, r4, c4);
-    double x[4];
-    for (int r = 0; r < 4; r++) x[r] = X[((size_t)c * 4 + r) * n + i] = v4[(r * 4 + 3) * 64];
-    double ax = 0, bx = 0;
-    for (int k = 0; k < 4; k++) ax += P1[2 * 4 + k] * x[k];
-    for (int k = 0; k < 4; k++) bx += P2[2 * 4 + k] * x[k];
-    front = ax * x[3] > 0 && bx * x[3] > 0;
-  }
+  if (i < n) front = mono_triangulate_one(raw[i], cams.P1, cams.P2[c], s_m + threadIdx.x, X + (size_t)c * 4 * n + i, (size_t)n);
   const unsigned long long b = __ballot(front);
   if ((threadIdx.x & 63) == 0 && b) atomicAdd(&chir[c], (int32_t)__popcll(b));
 }
@@ -358,18 +382,6 @@ struct MonoGpu {  // device side of one estimator
   }
 };
 
-inline bool sampson_in(const MonoPt &p, const double *F, double thr) {
-  const double u1 = p.u1p, v1 = p.v1p, u2 = p.u1c, v2 = p.v1c;
-  const double Fx1u = F[0] * u1 + F[1] * v1 + F[2];
-  const double Fx1v = F[3] * u1 + F[4] * v1 + F[5];
-  const double Fx1w = F[6] * u1 + F[7] * v1 + F[8];
-  const double Ftx2u = F[0] * u2 + F[3] * v2 + F[6];
-  const double Ftx2v = F[1] * u2 + F[4] * v2 + F[7];
-  const double x2tFx1 = u2 * Fx1u + v2 * Fx1v + Fx1w;
-  const double d = x2tFx1 * x2tFx1 / (Fx1u * Fx1u + Fx1v * Fx1v + Ftx2u * Ftx2u + Ftx2v * Ftx2v);
-  return fabs(d) < thr;
-}
-
 // fundamentalMatrix (viso/viso_mono.cpp:264-294) on normalised points; `rows` x 9 scratch in A
 void fundamental(const MonoPt *pts, const int32_t *active, int na, double *A, double *col, double *F) {
   for (int i = 0; i < na; i++) {
@@ -457,15 +469,23 @@ class MonoEgo {
     return true;
   }
 
-  // estimateMotion (viso/viso_mono.cpp:103-187).  1 = success, 0 = failure with the inlier list
-  // replaced, -1 = failure before the RANSAC started (inlier list untouched, like the reference).
-  template <class Runner>
-  int estimate(const vsm_p_match *m, int n, Runner *pool, MonoGpu *gpu, double *tr6, std::vector<int32_t> &inliers) {
+  // ---- estimateMotion (viso/viso_mono.cpp:103-187) in steps.  estimate() below runs them for one list; the batched form
+  // (vsm_motions.inc) runs each step for all pairs of a chunk, with the device's results in between.  `stage` says where the
+  // last estimate ended (VSM_MOT_*).
+  uint32_t *own_sampler = nullptr;  // the engine state the samples are drawn from; nullptr: the process-wide sampler
+  int stage = 0;
+  double Tp[9], Tc[9], Ra[9], Rb[9], tt[3], tneg[3];
+  MonoCams cams;
+  std::vector<double> yz;
+  double vote_threshold = 0, vote_weight = 0;
+
+  // the checks before the RANSAC, the normalised points and the K x 8 samples.  false: the estimate is over (rc -1)
+  bool begin(const vsm_p_match *m, int n) {
     stages = 0;
-    if (n < 10) return -1;
-    const double t0 = vsm_now_us();
-    double Tp[9], Tc[9];
-    if (!normalise(m, n, Tp, Tc)) return -1;
+    stage = VSM_MOT_FEW_MATCHES;
+    if (n < 10) return false;
+    stage = VSM_MOT_DEGENERATE;
+    if (!normalise(m, n, Tp, Tc)) return false;
     const int K = std::max(par.ransac_iters, 0);
     // --- samples: partial Fisher-Yates on a persistent identity deck, undone after each draw
     picks.resize((size_t)K * 8);
@@ -473,17 +493,195 @@ class MonoEgo {
     for (int i = 0; i < n; i++) deck[i] = i;
     VsmDrawPlan plan[8];
     for (int i = 0; i < 8; i++) plan[i] = vsm_sampler_plan((uint32_t)i, (uint32_t)(n - 1));
-    vsm_sampler_lock();
-    for (int k = 0; k < K; k++) {
-      int swapped[8];
-      for (int i = 0; i < 8; i++) {
-        swapped[i] = (int)vsm_sampler_draw(plan[i]);
-        std::swap(deck[i], deck[swapped[i]]);
+    auto draw_all = [&](auto &&draw) {
+      for (int k = 0; k < K; k++) {
+        int swapped[8];
+        for (int i = 0; i < 8; i++) {
+          swapped[i] = (int)draw(plan[i]);
+          std::swap(deck[i], deck[swapped[i]]);
+        }
+        for (int i = 0; i < 8; i++) picks[(size_t)k * 8 + i] = deck[i];
+        for (int i = 7; i >= 0; i--) std::swap(deck[i], deck[swapped[i]]);
       }
-      for (int i = 0; i < 8; i++) picks[(size_t)k * 8 + i] = deck[i];
-      for (int i = 7; i >= 0; i--) std::swap(deck[i], deck[swapped[i]]);
+    };
+    if (own_sampler) {
+      uint32_t state = *own_sampler;
+      draw_all([&](const VsmDrawPlan &p) { return vsm_minstd_draw(state, p); });
+      *own_sampler = state;
+    } else {
+      vsm_sampler_lock();
+      draw_all([](const VsmDrawPlan &p) { return vsm_sampler_draw(p); });
+      vsm_sampler_unlock();
     }
-    vsm_sampler_unlock();
+    return true;
+  }
+
+  template <class Runner>
+  void fit_host(Runner *pool, int K) {
+    parallel_for(pool, K, 8, [&](int lo, int hi) {
+      double A[72], col[9];
+      for (int k = lo; k < hi; k++) fundamental(pts.data(), &picks[(size_t)k * 8], 8, A, col, &Fs[(size_t)k * 9]);
+    });
+  }
+
+  // the winner among the counted hypotheses - the first with strictly more inliers than all before it - and its inlier list
+  void winner_host(int n, int K, std::vector<int32_t> &inliers) {
+    int best = -1, best_count = 0;
+    for (int k = 0; k < K; k++)
+      if (counts[k] > best_count) {
+        best_count = counts[k];
+        best = k;
+      }
+    inliers.clear();
+    if (best >= 0)
+      for (int i = 0; i < n; i++)
+        if (sampson_in(pts[i], &Fs[(size_t)best * 9], par.inlier_threshold)) inliers.push_back(i);
+  }
+
+  // F from all inliers, denormalise, essential matrix (:69-72, :121-129), EtoRt (:346-392) -> Ra, Rb, tt, tneg and the cameras
+  void motion_candidates(const std::vector<int32_t> &inliers) {
+    double F[9];
+    {
+      scratch.resize((size_t)inliers.size() * 10);
+      fundamental(pts.data(), inliers.data(), (int)inliers.size(), scratch.data(), scratch.data() + inliers.size() * 9, F);
+    }
+    double TcT[9], a[9], Fd[9], Kt[9], b[9], E0[9], E[9];
+    const double Kd[9] = {par.f, 0, par.cu, 0, par.f, par.cv, 0, 0, 1};
+    vsm_la::transpose(Tc, TcT, 3, 3);
+    vsm_la::mul(TcT, F, a, 3, 3, 3);
+    vsm_la::mul(a, Tp, Fd, 3, 3, 3);
+    vsm_la::transpose(Kd, Kt, 3, 3);
+    vsm_la::mul(Kt, Fd, b, 3, 3, 3);
+    vsm_la::mul(b, Kd, E0, 3, 3, 3);
+    vsm_la::rank2_3x3(E0, E);
+    double U[9], S[3], V[9], rv1[3], col3[3];
+    memcpy(U, E, sizeof(U));
+    vsm_la::svd_nr(U, 3, 3, 3, S, V, rv1, col3);
+    const double Wd[9] = {0, -1, 0, +1, 0, 0, 0, 0, 1}, Zd[9] = {0, +1, 0, -1, 0, 0, 0, 0, 0};
+    double Ut[9], Vt[9], Wt[9], UZ[9], T[9], UW[9], UWt[9];
+    vsm_la::transpose(U, Ut, 3, 3);
+    vsm_la::transpose(V, Vt, 3, 3);
+    vsm_la::transpose(Wd, Wt, 3, 3);
+    vsm_la::mul(U, Zd, UZ, 3, 3, 3);
+    vsm_la::mul(UZ, Ut, T, 3, 3, 3);
+    vsm_la::mul(U, Wd, UW, 3, 3, 3);
+    vsm_la::mul(UW, Vt, Ra, 3, 3, 3);
+    vsm_la::mul(U, Wt, UWt, 3, 3, 3);
+    vsm_la::mul(UWt, Vt, Rb, 3, 3, 3);
+    tt[0] = T[2 * 3 + 1];
+    tt[1] = T[0 * 3 + 2];
+    tt[2] = T[1 * 3 + 0];
+    for (int i = 0; i < 3; i++) tneg[i] = -tt[i];
+    if (vsm_la::det3(Ra) < 0)
+      for (double &x : Ra) x = -x;
+    if (vsm_la::det3(Rb) < 0)
+      for (double &x : Rb) x = -x;
+    const double *Rs[4] = {Ra, Ra, Rb, Rb}, *ts[4] = {tt, tneg, tt, tneg};
+    build_cams(Kd, Rs, ts, cams);
+  }
+  const double *cand_R(int c) const { return c < 2 ? Ra : Rb; }
+  const double *cand_t(int c) const { return (c & 1) ? tneg : tt; }
+
+  // triangulateChieral for the four candidates (:394-431) on the host -> X4 [candidate][row][match], chir
+  template <class Runner>
+  void triangulate_host(Runner *pool, const vsm_p_match *m, int n, int *chir) {
+    X4.resize((size_t)4 * 4 * n);
+    for (int c = 0; c < 4; c++) {
+      const double *P1 = cams.P1, *P2 = cams.P2[c];
+      double *Xc = &X4[(size_t)c * 4 * n];
+      std::atomic<int> num{0};
+      parallel_for(pool, n, 64, [&](int lo, int hi) {
+        int local = 0;
+        for (int i = lo; i < hi; i++) {
+          double J[16], w4[4], v4[16], r4[4], c4[4];
+          for (int j = 0; j < 4; j++) {
+            J[0 * 4 + j] = P1[2 * 4 + j] * m[i].u1p - P1[0 * 4 + j];
+            J[1 * 4 + j] = P1[2 * 4 + j] * m[i].v1p - P1[1 * 4 + j];
+            J[2 * 4 + j] = P2[2 * 4 + j] * m[i].u1c - P2[0 * 4 + j];
+            J[3 * 4 + j] = P2[2 * 4 + j] * m[i].v1c - P2[1 * 4 + j];
+          }
+          vsm_la::svd_nr(J, 4, 4, 4, w4, v4, r4, c4);
+          double x[4];
+          for (int r = 0; r < 4; r++) x[r] = Xc[(size_t)r * n + i] = v4[r * 4 + 3];
+          double ax = 0, bx = 0;  // third rows of P1*X and P2*X
+          for (int k = 0; k < 4; k++) ax += P1[2 * 4 + k] * x[k];
+          for (int k = 0; k < 4; k++) bx += P2[2 * 4 + k] * x[k];
+          if (ax * x[3] > 0 && bx * x[3] > 0) local++;
+        }
+        num.fetch_add(local, std::memory_order_relaxed);
+      });
+      chir[c] = num.load();
+    }
+  }
+  static int pick_candidate(const int32_t *chir) {  // the first candidate with the most points in front; -1: none has any
+    int pick = -1, max_in = 0;
+    for (int c = 0; c < 4; c++)
+      if (chir[c] > max_in) {
+        max_in = chir[c];
+        pick = c;
+      }
+    return pick;
+  }
+
+  // points in front of the camera, median of their L1 norms (:137-161, :189-213), the plane vote's inputs (:75-101).
+  // Xc = the chosen candidate's [row][match].  Returns the number of points in front, or -1 where the estimate ends (stage set).
+  int front_points(const double *Xc, int n) {
+    dvals.clear();
+    std::vector<double> &l1 = sums;
+    l1.clear();
+    yz.clear();
+    yz.reserve((size_t)2 * n);
+    for (int i = 0; i < n; i++) {
+      const double w4 = Xc[(size_t)3 * n + i];
+      const double x0 = w4 != 0 ? Xc[i] / w4 : 0, x1 = w4 != 0 ? Xc[(size_t)n + i] / w4 : 0,
+                   x2 = w4 != 0 ? Xc[(size_t)2 * n + i] / w4 : 0;
+      if (x2 > 0) {
+        yz.push_back(x1);
+        yz.push_back(x2);
+        l1.push_back(fabs(x0) + fabs(x1) + fabs(x2));
+      }
+    }
+    const int np = (int)l1.size();
+    stage = VSM_MOT_FEW_IN_FRONT;
+    if (np < 10) return -1;
+    std::nth_element(l1.begin(), l1.begin() + np / 2, l1.end());
+    const double median = l1[np / 2];
+    stage = VSM_MOT_MEDIAN;
+    if (median > par.motion_threshold) return -1;
+    const double sigma = median / 50.0;
+    vote_weight = 1.0 / (2.0 * sigma * sigma);
+    vote_threshold = median / par.motion_threshold;
+    const double n0 = cos(-par.pitch), n1 = sin(-par.pitch);
+    dvals.resize((size_t)np);
+    for (int i = 0; i < np; i++) {
+      double s = 0;
+      s += n0 * yz[2 * i];
+      s += n1 * yz[2 * i + 1];
+      dvals[i] = s;
+    }
+    return np;
+  }
+
+  void finish(int pick, int best_idx, double *tr6) {
+    const double *R = cand_R(pick), *t = cand_t(pick);
+    const double best_d = dvals[best_idx];
+    const double ry = asin(R[0 * 3 + 2]);
+    const double rx = asin(-R[1 * 3 + 2] / cos(ry));
+    const double rz = asin(-R[0 * 3 + 1] / cos(ry));
+    tr6[0] = rx;
+    tr6[1] = ry;
+    tr6[2] = rz;
+    for (int i = 0; i < 3; i++) tr6[3 + i] = t[i] * par.height / best_d;
+    stage = VSM_MOT_OK;
+  }
+
+  // 1 = success, 0 = failure with the inlier list replaced, -1 = failure before the RANSAC started (inlier list untouched,
+  // like the reference).
+  template <class Runner>
+  int estimate(const vsm_p_match *m, int n, Runner *pool, MonoGpu *gpu, double *tr6, std::vector<int32_t> &inliers) {
+    const double t0 = vsm_now_us();
+    if (!begin(m, n)) return -1;
+    const int K = std::max(par.ransac_iters, 0);
     // --- fundamental matrices of all hypotheses and their inlier counts
     Fs.resize((size_t)K * 9);
     counts.assign((size_t)K, 0);
@@ -501,10 +699,7 @@ class MonoEgo {
       }
     }
     if (!fitted) {
-      parallel_for(pool, K, 8, [&](int lo, int hi) {
-        double A[72], col[9];
-        for (int k = lo; k < hi; k++) fundamental(pts.data(), &picks[(size_t)k * 8], 8, A, col, &Fs[(size_t)k * 9]);
-      });
+      fit_host(pool, K);
       if (on_gpu) {
         memcpy(gpu->h_F, Fs.data(), sizeof(double) * 9 * K);
         on_gpu = hipMemcpyAsync(gpu->d_F, gpu->h_F, sizeof(double) * 9 * K, hipMemcpyHostToDevice, gpu->stream) == hipSuccess;
@@ -528,12 +723,7 @@ class MonoEgo {
       }
     }
     if (!on_gpu) {
-      if (fitted) {  // (a failed launch after a device fit: redo the fits on the host)
-        parallel_for(pool, K, 8, [&](int lo, int hi) {
-          double A[72], col[9];
-          for (int k = lo; k < hi; k++) fundamental(pts.data(), &picks[(size_t)k * 8], 8, A, col, &Fs[(size_t)k * 9]);
-        });
-      }
+      if (fitted) fit_host(pool, K);  // (a failed launch after a device fit: redo the fits on the host)
       parallel_for(pool, K, 4, [&](int lo, int hi) {
         for (int k = lo; k < hi; k++) {
           int c = 0;
@@ -542,101 +732,23 @@ class MonoEgo {
         }
       });
     }
-    int best = -1, best_count = 0;
-    for (int k = 0; k < K; k++)
-      if (counts[k] > best_count) {
-        best_count = counts[k];
-        best = k;
-      }
-    inliers.clear();
-    if (best >= 0)
-      for (int i = 0; i < n; i++)
-        if (sampson_in(pts[i], &Fs[(size_t)best * 9], par.inlier_threshold)) inliers.push_back(i);
+    winner_host(n, K, inliers);
     const double t2 = vsm_now_us();
     timings[0] = t1 - t0;  // (with device fits the kernel is only enqueued here; it shows up in [1])
     timings[1] = t2 - t1;
+    stage = VSM_MOT_FEW_INLIERS;
     if ((int)inliers.size() < 10) return 0;
-    // --- F from all inliers, denormalise, essential matrix (:69-72, :121-129)
-    double F[9];
-    {
-      scratch.resize((size_t)inliers.size() * 10);
-      fundamental(pts.data(), inliers.data(), (int)inliers.size(), scratch.data(), scratch.data() + inliers.size() * 9, F);
-    }
-    double TcT[9], a[9], Fd[9], Kt[9], b[9], E0[9], E[9];
-    const double Kd[9] = {par.f, 0, par.cu, 0, par.f, par.cv, 0, 0, 1};
-    vsm_la::transpose(Tc, TcT, 3, 3);
-    vsm_la::mul(TcT, F, a, 3, 3, 3);
-    vsm_la::mul(a, Tp, Fd, 3, 3, 3);
-    vsm_la::transpose(Kd, Kt, 3, 3);
-    vsm_la::mul(Kt, Fd, b, 3, 3, 3);
-    vsm_la::mul(b, Kd, E0, 3, 3, 3);
-    vsm_la::rank2_3x3(E0, E);
-    // --- EtoRt (:346-392)
-    double U[9], S[3], V[9], rv1[3], col3[3];
-    memcpy(U, E, sizeof(U));
-    vsm_la::svd_nr(U, 3, 3, 3, S, V, rv1, col3);
-    const double Wd[9] = {0, -1, 0, +1, 0, 0, 0, 0, 1}, Zd[9] = {0, +1, 0, -1, 0, 0, 0, 0, 0};
-    double Ut[9], Vt[9], Wt[9], UZ[9], T[9], UW[9], Ra[9], UWt[9], Rb[9];
-    vsm_la::transpose(U, Ut, 3, 3);
-    vsm_la::transpose(V, Vt, 3, 3);
-    vsm_la::transpose(Wd, Wt, 3, 3);
-    vsm_la::mul(U, Zd, UZ, 3, 3, 3);
-    vsm_la::mul(UZ, Ut, T, 3, 3, 3);
-    vsm_la::mul(U, Wd, UW, 3, 3, 3);
-    vsm_la::mul(UW, Vt, Ra, 3, 3, 3);
-    vsm_la::mul(U, Wt, UWt, 3, 3, 3);
-    vsm_la::mul(UWt, Vt, Rb, 3, 3, 3);
-    double tt[3] = {T[2 * 3 + 1], T[0 * 3 + 2], T[1 * 3 + 0]}, tneg[3] = {-tt[0], -tt[1], -tt[2]};
-    if (vsm_la::det3(Ra) < 0)
-      for (double &x : Ra) x = -x;
-    if (vsm_la::det3(Rb) < 0)
-      for (double &x : Rb) x = -x;
-    const double *Rs[4] = {Ra, Ra, Rb, Rb}, *ts[4] = {tt, tneg, tt, tneg};
-    // --- triangulateChieral for the four candidates (:394-431)
+    motion_candidates(inliers);
     int chir[4] = {0, 0, 0, 0};
-    MonoCams cams;
-    build_cams(Kd, Rs, ts, cams);
     const bool tri_gpu = gpu && gpu->ok && gpu->svd_on_device && triangulate_gpu(gpu, m, n, cams, chir);
     if (tri_gpu) stages |= MONO_STAGE_TRIANGULATE;
-    if (!tri_gpu) {
-      X4.resize((size_t)4 * 4 * n);  // [candidate][row][match]
-      for (int c = 0; c < 4; c++) {
-        const double *P1 = cams.P1, *P2 = cams.P2[c];
-        double *Xc = &X4[(size_t)c * 4 * n];
-        std::atomic<int> num{0};
-        parallel_for(pool, n, 64, [&](int lo, int hi) {
-          int local = 0;
-          for (int i = lo; i < hi; i++) {
-            double J[16], w4[4], v4[16], r4[4], c4[4];
-            for (int j = 0; j < 4; j++) {
-              J[0 * 4 + j] = P1[2 * 4 + j] * m[i].u1p - P1[0 * 4 + j];
-              J[1 * 4 + j] = P1[2 * 4 + j] * m[i].v1p - P1[1 * 4 + j];
-              J[2 * 4 + j] = P2[2 * 4 + j] * m[i].u1c - P2[0 * 4 + j];
-              J[3 * 4 + j] = P2[2 * 4 + j] * m[i].v1c - P2[1 * 4 + j];
-            }
-            vsm_la::svd_nr(J, 4, 4, 4, w4, v4, r4, c4);
-            double x[4];
-            for (int r = 0; r < 4; r++) x[r] = Xc[(size_t)r * n + i] = v4[r * 4 + 3];
-            double ax = 0, bx = 0;  // third rows of P1*X and P2*X
-            for (int k = 0; k < 4; k++) ax += P1[2 * 4 + k] * x[k];
-            for (int k = 0; k < 4; k++) bx += P2[2 * 4 + k] * x[k];
-            if (ax * x[3] > 0 && bx * x[3] > 0) local++;
-          }
-          num.fetch_add(local, std::memory_order_relaxed);
-        });
-        chir[c] = num.load();
-      }
-    }
-    int pick = -1, max_in = 0;
-    for (int c = 0; c < 4; c++)
-      if (chir[c] > max_in) {
-        max_in = chir[c];
-        pick = c;
-      }
+    if (!tri_gpu) triangulate_host(pool, m, n, chir);
+    const int pick = pick_candidate(chir);
     const double t3 = vsm_now_us();
     timings[2] = t3 - t2;
+    stage = VSM_MOT_NONE_IN_FRONT;
     if (pick < 0) return 0;  // (the reference would go on with an empty rotation matrix here)
-    const double *Xc = nullptr, *R = Rs[pick], *t = ts[pick];
+    const double *Xc = nullptr;
     if (tri_gpu) {  // only the chosen candidate's points come back
       if (hipMemcpyAsync(gpu->h_X, gpu->d_X + (size_t)pick * 4 * n, sizeof(double) * 4 * n, hipMemcpyDeviceToHost,
                          gpu->stream) != hipSuccess ||
@@ -646,48 +758,12 @@ class MonoEgo {
     } else {
       Xc = &X4[(size_t)pick * 4 * n];
     }
-    // --- points in front of the camera, median of their L1 norms (:137-161, :189-213)
-    dvals.clear();
-    std::vector<double> &l1 = sums;
-    l1.clear();
-    std::vector<double> yz;
-    yz.reserve((size_t)2 * n);
-    for (int i = 0; i < n; i++) {
-      const double w4 = Xc[(size_t)3 * n + i];
-      const double x0 = w4 != 0 ? Xc[i] / w4 : 0, x1 = w4 != 0 ? Xc[(size_t)n + i] / w4 : 0,
-                   x2 = w4 != 0 ? Xc[(size_t)2 * n + i] / w4 : 0;
-      if (x2 > 0) {
-        yz.push_back(x1);
-        yz.push_back(x2);
-        l1.push_back(fabs(x0) + fabs(x1) + fabs(x2));
-      }
-    }
-    const int np = (int)l1.size();
-    if (np < 10) return 0;
-    std::nth_element(l1.begin(), l1.begin() + np / 2, l1.end());
-    const double median = l1[np / 2];
-    if (median > par.motion_threshold) return 0;
-    const double sigma = median / 50.0, weight = 1.0 / (2.0 * sigma * sigma), threshold = median / par.motion_threshold;
-    // --- findBestPlane (:75-101)
-    const double n0 = cos(-par.pitch), n1 = sin(-par.pitch);
-    dvals.resize((size_t)np);
-    for (int i = 0; i < np; i++) {
-      double s = 0;
-      s += n0 * yz[2 * i];
-      s += n1 * yz[2 * i + 1];
-      dvals[i] = s;
-    }
-    const int best_idx = best_plane(pool, gpu, np, threshold, weight);
-    const double best_d = dvals[best_idx];
+    const int np = front_points(Xc, n);
+    if (np < 0) return 0;
+    const int best_idx = best_plane(pool, gpu, np, vote_threshold, vote_weight);
     const double t4 = vsm_now_us();
     timings[3] = t4 - t3;
-    const double ry = asin(R[0 * 3 + 2]);
-    const double rx = asin(-R[1 * 3 + 2] / cos(ry));
-    const double rz = asin(-R[0 * 3 + 1] / cos(ry));
-    tr6[0] = rx;
-    tr6[1] = ry;
-    tr6[2] = rz;
-    for (int i = 0; i < 3; i++) tr6[3 + i] = t[i] * par.height / best_d;
+    finish(pick, best_idx, tr6);
     return 1;
   }
 
@@ -716,6 +792,24 @@ class MonoEgo {
     return sum;
   }
 
+  // the device's sums are proposals: its exp() is within a few ulp of libm's, so only candidates this close to the
+  // proposed maximum can be the true first maximum; they are judged exactly, in index order
+  int resolve_vote(const double *proposed, int np, double threshold, double weight) const {
+    double top = 0;
+    for (int i = 0; i < np; i++) top = std::max(top, proposed[i]);
+    double best_sum = 0;
+    int best_idx = 0;
+    for (int i = 0; i < np; i++)
+      if (dvals[i] > threshold && proposed[i] >= top * (1.0 - 1e-9)) {
+        const double s = exact_sum(i, np, weight);
+        if (s > best_sum) {
+          best_sum = s;
+          best_idx = i;
+        }
+      }
+    return best_idx;
+  }
+
   template <class Runner>
   int best_plane(Runner *pool, MonoGpu *gpu, int np, double threshold, double weight) {
     bool on_gpu = gpu && gpu->ok && np >= 512 && gpu->reserve(np, 1);
@@ -731,26 +825,12 @@ class MonoEgo {
     }
     if (on_gpu) {
       stages |= MONO_STAGE_VOTE;
-      // the device exp() is within a few ulp of libm's: only candidates this close to the proposed
-      // maximum can be the true first maximum; they are judged exactly, in index order
-      double top = 0;
       for (int i = 0; i < np; i++) {  // add the slices up (into slice 0)
         double t = 0;
         for (int c = 0; c < VOTE_SPLIT; c++) t += gpu->h_sums[(size_t)c * np + i];
         gpu->h_sums[i] = t;
-        top = std::max(top, t);
       }
-      double best_sum = 0;
-      int best_idx = 0;
-      for (int i = 0; i < np; i++)
-        if (dvals[i] > threshold && gpu->h_sums[i] >= top * (1.0 - 1e-9)) {
-          const double s = exact_sum(i, np, weight);
-          if (s > best_sum) {
-            best_sum = s;
-            best_idx = i;
-          }
-        }
-      return best_idx;
+      return resolve_vote(gpu->h_sums, np, threshold, weight);
     }
     sums.assign((size_t)np, 0.0);
     parallel_for(pool, np, 16, [&](int lo, int hi) {
@@ -769,6 +849,8 @@ class MonoEgo {
 };
 
 }  // namespace
+
+#include "vsm_motions.inc"
 
 struct vsm_vo_mono {
   vsm_handle *matcher = nullptr;

@@ -57,7 +57,9 @@ EXPORTS = ["vsm_default_params", "vsm_create", "vsm_destroy", "vsm_set_intrinsic
            "vsm_vo_mono_get_inliers", "vsm_vo_mono_gain", "vsm_vo_mono_matcher", "vsm_vo_mono_get_timings",
            "vsm_vo_mono_device_svd", "vsm_vo_mono_device_stages",
            "vsm_debug_mono_fit", "vsm_debug_mono_count", "vsm_debug_mono_triangulate", "vsm_debug_mono_vote",
-           "vsm_host_estimate_motion_mono"]
+           "vsm_host_estimate_motion_mono",
+           "vsm_motions_run", "vsm_pairs_motions", "vsm_motions_count", "vsm_motions_get", "vsm_motions_inliers", "vsm_motions_matches",
+           "vsm_motions_get_stats", "vsm_motions_get_timings", "vsm_motions_device_svd", "vsm_host_pairs_motions", "vsm_chain_poses"]
 
 
 class VsmParams(C.Structure):
@@ -279,6 +281,21 @@ def lib():
         L.vsm_debug_mono_triangulate.argtypes = [vp, i32, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp]
         L.vsm_debug_mono_vote.argtypes = [vp, i32, C.c_double, C.c_double, vp, vp]
         L.vsm_host_estimate_motion_mono.argtypes = [mop, vp, i32, i32, vp, vp, vp, vp]
+        L.vsm_motions_run.argtypes = [vp, mop, i32, vp, vp, i32]
+        L.vsm_pairs_motions.argtypes = [vp, mop, i32]
+        L.vsm_motions_count.argtypes = [vp]
+        L.vsm_motions_get.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.vsm_motions_inliers.argtypes = [vp, i32, vp, i32]
+        L.vsm_motions_matches.argtypes = [vp, i32, vp, i32]
+        L.vsm_motions_get_stats.argtypes = [vp, vp]
+        L.vsm_motions_get_stats.restype = None
+        L.vsm_motions_get_timings.argtypes = [vp, vp]
+        L.vsm_motions_get_timings.restype = None
+        L.vsm_motions_device_svd.argtypes = [vp]
+        L.vsm_host_pairs_motions.restype = i32
+        L.vsm_host_pairs_motions.argtypes = [mop, i32, vp, vp, i32, i32] + [vp] * 8
+        L.vsm_chain_poses.restype = i32
+        L.vsm_chain_poses.argtypes = [i32, vp, i32, vp, vp, i32, vp, vp]
         _lib = L
     return _lib
 
@@ -614,6 +631,66 @@ class Points:
     @property
     def kept(self):
         return self.status == 0
+
+
+MOTION_STAGES = ("few_matches", "degenerate", "few_inliers", "none_in_front", "few_in_front", "median", "ok")
+MOTION_STATS = MOTION_STAGES + ("device_fit", "device_count", "device_triangulate", "device_vote", "chunks", "waits")
+MOTION_TIMINGS = ("sample_pack_upload_us", "fit_count_winner_us", "host_fits_us", "triangulate_us", "median_vote_us", "total_us")
+
+
+class Motions:
+    """monocular motions of a pair set (include/visomatch.h, vsm_motions_run): per pair rc [P] int32 (1, 0, -1), stage [P] int32
+    (MOTION_STAGES names the values), tr [P, 6] and T [P, 4, 4] float64 (zero / the identity where rc != 1); inliers(k): pair k's
+    inlier indices into matches(k), the list its estimate saw (bucketed where bucketing was on); stats / timings: dicts (the
+    host view's stats hold the stage counts only)."""
+
+    def __init__(self, rc, stage, tr, T, inliers, matches, stats=None, timings=None):
+        self.rc, self.stage, self.tr, self.T, self._inliers, self._matches = rc, stage, tr, T, inliers, matches
+        self.stats, self.timings = stats or {}, timings or {}
+
+    def __len__(self):
+        return len(self.rc)
+
+    def inliers(self, k):
+        return self._inliers[k]
+
+    def matches(self, k):
+        return self._matches[k]
+
+
+def host_pairs_motions(lists, params, bucket=False, threads=1, counts=None):
+    """vsm_host_pairs_motions: every list's mono motion on `threads` host threads - no GPU.  counts: override the lists'
+    lengths (argument tests).  Returns a Motions object; raises VisoMatchError on VSM_EARG."""
+    _, ls, ptrs, cnt = _track_inputs(np.zeros((len(lists), 2), np.int32), lists)
+    if counts is not None:
+        cnt = np.ascontiguousarray(counts, dtype=np.int32)
+    P, tot = len(ls), int(np.clip(cnt, 0, None).sum())
+    rc, stage, n_inl, n_m = (np.zeros(P, np.int32) for _ in range(4))
+    tr, T = np.zeros((P, 6)), np.zeros((P, 4, 4))
+    inl, mm = np.zeros(max(tot, 1), np.int32), np.zeros(max(tot, 1), P_MATCH)
+    got = lib().vsm_host_pairs_motions(None if params is None else C.byref(params), P, ptrs, _ptr(cnt), int(bool(bucket)), int(threads), _ptr(rc), _ptr(stage),
+                                       _ptr(tr), _ptr(T), _ptr(n_inl), _ptr(inl), _ptr(n_m), _ptr(mm))
+    if got < 0:
+        raise VisoMatchError(f"vsm_host_pairs_motions failed with {got}" + (" (VSM_EARG)" if got == Matcher.EARG else ""))
+    off = np.concatenate([[0], np.cumsum(cnt)])
+    st = np.bincount(stage, minlength=len(MOTION_STAGES))
+    return Motions(rc, stage, tr, T, [inl[off[k]:off[k] + n_inl[k]].copy() for k in range(P)], [mm[off[k]:off[k] + n_m[k]].copy() for k in range(P)],
+                   dict(zip(MOTION_STAGES, st.tolist())))
+
+
+def chain_poses(n_frames, pairs, T, rc, root=0):
+    """vsm_chain_poses: pair motions T [P, 4, 4] (or [P, 16]) with their rc into camera-to-world poses -> (poses [F, 12],
+    valid [F] uint8, frames with a pose); raises VisoMatchError on VSM_EARG."""
+    pa = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+    t = np.ascontiguousarray(np.asarray(T, dtype=np.float64).reshape(len(pa), 16)) if len(pa) else np.zeros((0, 16))
+    r = np.ascontiguousarray(rc, dtype=np.int32)
+    assert r.shape == (len(pa),)
+    n = max(int(n_frames), 0)
+    poses, valid = np.zeros((n, 12)), np.zeros(n, np.uint8)
+    got = lib().vsm_chain_poses(int(n_frames), _ptr(pa), len(pa), _ptr(t), _ptr(r), int(root), _ptr(poses), _ptr(valid))
+    if got < 0:
+        raise VisoMatchError(f"vsm_chain_poses failed with {got}" + (" (VSM_EARG)" if got == Matcher.EARG else ""))
+    return poses, valid, got
 
 
 def triangulate_params(**kw):
@@ -1055,6 +1132,51 @@ class Matcher:
                 cnt = np.ascontiguousarray(counts, dtype=np.int32)
         rc = lib().vsm_tracks_triangulate(self.h, ptrs, _ptr(cnt), _ptr(po), _ptr(pv), float(f), float(cu), float(cv), C.byref(_as_params(params)))
         return self._points_result(rc, "vsm_tracks_triangulate")
+
+    # --- monocular motions of a pair set ---------------------------------------------------------
+    def _motions_result(self, rc, what):
+        L = lib()
+        if rc != self.OK:
+            names = {self.EARG: " (VSM_EARG)", self.ENOTREADY: " (VSM_ENOTREADY)"}
+            raise VisoMatchError(f"{what} failed with {rc}" + names.get(rc, ""))
+        P = L.vsm_motions_count(self.h)
+        r, stage, n_inl = np.zeros(P, np.int32), np.zeros(P, np.int32), np.zeros(P, np.int32)
+        tr, T = np.zeros((P, 6)), np.zeros((P, 4, 4))
+        L.vsm_motions_get(self.h, _ptr(r), _ptr(stage), _ptr(tr), _ptr(T), _ptr(n_inl))
+        inl, mm = [], []
+        for k in range(P):
+            a = np.zeros(int(n_inl[k]), np.int32)
+            if len(a):
+                L.vsm_motions_inliers(self.h, k, _ptr(a), len(a))
+            inl.append(a)
+            m = np.zeros(L.vsm_motions_matches(self.h, k, None, 0), P_MATCH)
+            if len(m):
+                L.vsm_motions_matches(self.h, k, _ptr(m), len(m))
+            mm.append(m)
+        st, tm = np.zeros(len(MOTION_STATS), np.int64), np.zeros(6, np.float64)
+        L.vsm_motions_get_stats(self.h, _ptr(st))
+        L.vsm_motions_get_timings(self.h, _ptr(tm))
+        stats = dict(zip(MOTION_STATS, st.tolist()))
+        stats["device_svd"] = L.vsm_motions_device_svd(self.h)
+        return Motions(r, stage, tr, T, inl, mm, stats, dict(zip(MOTION_TIMINGS, tm.tolist())))
+
+    def motions(self, lists, params, bucket=False, counts=None):
+        """vsm_motions_run: the mono motion of every list (one P_MATCH array of flow matches per pair) in one batched call on
+        the device.  params: vo_mono_params(...).  Returns a Motions object."""
+        _, ls, ptrs, cnt = _track_inputs(np.zeros((len(lists), 2), np.int32), lists)
+        if counts is not None:
+            cnt = np.ascontiguousarray(counts, dtype=np.int32)
+        rc = lib().vsm_motions_run(self.h, None if params is None else C.byref(params), len(ls), ptrs, _ptr(cnt), int(bool(bucket)))
+        return self._motions_result(rc, "vsm_motions_run")
+
+    def pair_motions(self, params, bucket=False):
+        """vsm_pairs_motions: the same on the lists of the last match_pairs call (fetched or not), which stay as they are"""
+        rc = lib().vsm_pairs_motions(self.h, None if params is None else C.byref(params), int(bool(bucket)))
+        return self._motions_result(rc, "vsm_pairs_motions")
+
+    def last_motions(self):
+        """the handle's last motions result as it stands (None: there is none)"""
+        return self._motions_result(self.OK, "") if lib().vsm_motions_count(self.h) else None
 
     def pair_timings(self):
         t = np.zeros(4, dtype=np.float64)
