@@ -26,6 +26,7 @@
 #include "vsm_host.h"
 #include "vsm_dc_gpu.h"
 #include "vsm_internal.h"
+#include "vsm_stage.h"
 #include "vsm_tracks.h"
 #include "vsm_points.h"
 #include "vsm_motions.h"
@@ -41,7 +42,6 @@
   } while (0)
 
 static inline int32_t bpl16(int32_t w) { return w + 15 - (w - 1) % 16; }  // viso/matcher.cpp:160
-static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 // CPUs this process may actually use: the cgroup CPU quota (containers), else the hardware
 // thread count.  Spinning more threads than the quota only gets the whole process throttled.
 static int cpu_budget() {

@@ -164,11 +164,6 @@ struct VsmProf {
   }
 };
 
-// Device memory of the library's large blocks (vsm_api.cpp): a released block of 8 MB or more goes to a process-wide cache
-// instead of back to the driver, and the next request of about its size takes it from there.
-hipError_t vsm_dev_alloc(void **p, size_t bytes);
-void vsm_dev_free(void *p);
-
 // ---- launchers of the image side (vsm_image.hip) ----
 void vsm_launch_ingest(hipStream_t s, VsmProf &pf, const VsmImage *d_imgs, int first, const uint8_t *src0,
                        const uint8_t *src1, size_t frame_stride, int32_t src_bpl, int n_frames, const VsmDims &d);

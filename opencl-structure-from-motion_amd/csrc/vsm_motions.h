@@ -14,6 +14,7 @@
 
 #include "visomatch.h"
 #include "vsm_host.h"
+#include "vsm_stage.h"
 
 // where a pair's estimate ended (vsm_motions_get's `stage`)
 enum {
@@ -51,10 +52,9 @@ struct VsmMotionsResult {
   }
 };
 
-// staging of the device path: pinned blocks and one device block that only grow, and the self-test's verdict
+// the device path's staging (its events stay unused: the call times itself on the host) and the self-test's verdict
 struct VsmMotionsDev {
-  uint8_t *pin_in = nullptr, *pin_out = nullptr, *dev = nullptr;
-  size_t pin_in_bytes = 0, pin_out_bytes = 0, dev_bytes = 0;
+  VsmStage st;  // pinned input and output, the device block, the events (vsm_stage.h)
   bool tested = false, svd_on_device = false;
 };
 void vsm_motions_dev_release(VsmMotionsDev &D);

@@ -202,36 +202,10 @@ void mot_count_stages(VsmMotionsResult &out) {
     if (s >= 0 && s <= VSM_MOT_OK) out.stats[s]++;
 }
 
-struct MotLayout {
-  size_t at = 0;
-  size_t take(size_t bytes) {
-    const size_t o = at;
-    at = (at + bytes + 255) & ~(size_t)255;
-    return o;
-  }
-};
-
-bool mot_grow_pinned(uint8_t *&p, size_t &have, size_t need, hipStream_t stream) {
-  if (need <= have) return true;
-  (void)hipStreamSynchronize(stream);
-  if (p) (void)hipHostFree(p);
-  p = nullptr;
-  have = 0;
-  if (hipHostMalloc((void **)&p, need + need / 4, hipHostMallocDefault) != hipSuccess) return false;
-  have = need + need / 4;
-  return true;
-}
-
 }  // namespace
 
-// device memory of vsm_api.cpp's block cache
-hipError_t vsm_dev_alloc(void **p, size_t bytes);
-void vsm_dev_free(void *p);
-
 void vsm_motions_dev_release(VsmMotionsDev &D) {
-  if (D.pin_in) (void)hipHostFree(D.pin_in);
-  if (D.pin_out) (void)hipHostFree(D.pin_out);
-  if (D.dev) vsm_dev_free(D.dev);
+  D.st.release();
   D = VsmMotionsDev();
 }
 
@@ -289,19 +263,11 @@ int vsm_motions_device(VsmMotionsDev &D, hipStream_t stream, VsmPool *pool, cons
   chunk = std::min(chunk, (int)n_pairs);
   std::vector<MotPair> pairs((size_t)chunk);
   std::vector<int32_t> running;  // chunk-local indices of the pairs still in the estimate
-  auto fail = [&]() {
+  auto fail = [&](int rc) {
     (void)hipStreamSynchronize(stream);
     (void)hipGetLastError();
-    return VSM_EHIP;
+    return rc;
   };
-#define MOT_CHK(call)                                                              \
-  do {                                                                             \
-    const hipError_t e_ = (call);                                                  \
-    if (e_ != hipSuccess) {                                                        \
-      fprintf(stderr, "visomatch: %s failed: %s\n", #call, hipGetErrorString(e_)); \
-      return fail();                                                               \
-    }                                                                              \
-  } while (0)
   auto run_pairs = [&](const std::vector<int32_t> &which, const std::function<void(int)> &fn) {
     if (which.empty()) return;
     pool->run((int)which.size(), [&](int t) { fn(which[t]); });
@@ -336,32 +302,26 @@ int vsm_motions_device(VsmMotionsDev &D, hipStream_t stream, VsmPool *pool, cons
     if (running.empty()) continue;
     const size_t N = (size_t)base[Pc], PK = (size_t)Pc * K, T256 = tiles256.size(), T64 = (N + 63) / 64 + running.size();
     // ---- layout: the pinned input block and its device twin share offsets; device-only arrays and the results behind ----
-    MotLayout in;
+    VsmLayout in;
     const size_t o_base = in.take(((size_t)Pc + 1) * 4), o_t256 = in.take(T256 * sizeof(MotTile)), o_pts = in.take(N * sizeof(MonoPt)),
                  o_raw = in.take(N * sizeof(MonoPt)), o_picks = in.take(PK * 32 + 4);
     const size_t up1 = in.at;
     const size_t o_cams = in.take((size_t)Pc * sizeof(MonoCams)), o_t64 = in.take(T64 * sizeof(MotTile));
     const size_t up2 = in.at;
     const size_t o_votes = in.take((size_t)Pc * sizeof(MotVote)), o_vt = in.take(T256 * sizeof(MotTile)), o_d = in.take(N * 8);
-    MotLayout res;
+    VsmLayout res;
     const size_t r_best = res.take((size_t)Pc * 4), r_ninl = res.take((size_t)Pc * 4), r_fwin = res.take((size_t)Pc * 72), r_inl = res.take(N * 4);
     const size_t dn1 = res.at;
     const size_t r_chir = res.take((size_t)Pc * 16), r_xsel = res.take(N * 32);
     const size_t dn2 = res.at;
     const size_t r_sums = res.take(N * 8);
-    MotLayout dv;
+    VsmLayout dv;
     dv.at = in.at;
     const size_t d_res = dv.take(res.at), d_F = dv.take(PK * 72 + 8), d_counts = dv.take(PK * 4 + 4), d_X = dv.take(N * 128);
-    if (!mot_grow_pinned(D.pin_in, D.pin_in_bytes, in.at, stream) || !mot_grow_pinned(D.pin_out, D.pin_out_bytes, res.at, stream)) return fail();
-    if (dv.at > D.dev_bytes) {
-      (void)hipStreamSynchronize(stream);
-      if (D.dev) vsm_dev_free(D.dev);
-      D.dev = nullptr;
-      D.dev_bytes = 0;
-      MOT_CHK(vsm_dev_alloc((void **)&D.dev, dv.at + dv.at / 4));
-      D.dev_bytes = dv.at + dv.at / 4;
-    }
-    uint8_t *hin = D.pin_in, *hout = D.pin_out, *dev = D.dev, *dres = D.dev + d_res;
+    VSM_CHK(D.st.grow_in(in.at, stream));
+    VSM_CHK(D.st.grow_out(res.at, stream));
+    VSM_CHK(D.st.grow_dev(dv.at, stream));
+    uint8_t *hin = D.st.pin_in, *hout = D.st.pin_out, *dev = D.st.dev, *dres = D.st.dev + d_res;
     // ---- pack ----
     memcpy(hin + o_base, base.data(), ((size_t)Pc + 1) * 4);
     memcpy(hin + o_t256, tiles256.data(), T256 * sizeof(MotTile));
@@ -378,22 +338,22 @@ int vsm_motions_device(VsmMotionsDev &D, hipStream_t stream, VsmPool *pool, cons
     double *dF = (double *)(dev + d_F);
     int32_t *dcounts = (int32_t *)(dev + d_counts);
     // ---- fit, count, winner ----
-    MOT_CHK(hipMemcpyAsync(dev, hin, up1, hipMemcpyHostToDevice, stream));
+    VSM_CHK(hipMemcpyAsync(dev, hin, up1, hipMemcpyHostToDevice, stream));
     const double t1 = vsm_now_us();
     if (K > 0) {
-      MOT_CHK(hipMemsetAsync(dcounts, 0, PK * 4, stream));
+      VSM_CHK(hipMemsetAsync(dcounts, 0, PK * 4, stream));
       hipLaunchKernelGGL(k_motions_fit, dim3((unsigned)((PK + 15) / 16)), dim3(256), 0, stream, d_pts, d_base, (const int32_t *)(dev + o_picks), K, (int)PK, dF);
-      MOT_CHK(hipGetLastError());
+      VSM_CHK(hipGetLastError());
       const int hyps = std::max(16, (K + 65534) / 65535);
       hipLaunchKernelGGL(k_motions_count, dim3((unsigned)T256, (unsigned)((K + hyps - 1) / hyps)), dim3(256), 0, stream, d_pts, d_base,
                          (const MotTile *)(dev + o_t256), dF, K, hyps, par.inlier_threshold, dcounts);
-      MOT_CHK(hipGetLastError());
+      VSM_CHK(hipGetLastError());
     }
     hipLaunchKernelGGL(k_motions_winner, dim3((unsigned)Pc), dim3(256), 0, stream, d_pts, d_base, dF, dcounts, K, par.inlier_threshold,
                        (int32_t *)(dres + r_best), (double *)(dres + r_fwin), (int32_t *)(dres + r_inl), (int32_t *)(dres + r_ninl));
-    MOT_CHK(hipGetLastError());
-    MOT_CHK(hipMemcpyAsync(hout, dres, dn1, hipMemcpyDeviceToHost, stream));
-    MOT_CHK(hipStreamSynchronize(stream));
+    VSM_CHK(hipGetLastError());
+    VSM_CHK(hipMemcpyAsync(hout, dres, dn1, hipMemcpyDeviceToHost, stream));
+    VSM_CHK(hipStreamSynchronize(stream));
     out.stats[VSM_MOT_STAT_WAITS]++;
     if (K > 0) {
       out.stats[VSM_MOT_STAT_FIT] += (int64_t)running.size();
@@ -431,16 +391,16 @@ int vsm_motions_device(VsmMotionsDev &D, hipStream_t stream, VsmPool *pool, cons
     if (running.empty()) continue;
     // ---- triangulation of all (pair, candidate, match), the chosen candidates gathered ----
     memcpy(hin + o_t64, tiles.data(), tiles.size() * sizeof(MotTile));
-    MOT_CHK(hipMemcpyAsync(dev + o_cams, hin + o_cams, up2 - up1, hipMemcpyHostToDevice, stream));
-    MOT_CHK(hipMemsetAsync(dres + r_chir, 0, (size_t)Pc * 16, stream));
+    VSM_CHK(hipMemcpyAsync(dev + o_cams, hin + o_cams, up2 - up1, hipMemcpyHostToDevice, stream));
+    VSM_CHK(hipMemsetAsync(dres + r_chir, 0, (size_t)Pc * 16, stream));
     hipLaunchKernelGGL(k_motions_triangulate, dim3((unsigned)tiles.size(), 4), dim3(64), 0, stream, d_raw, d_base, (const MotTile *)(dev + o_t64),
                        (const MonoCams *)(dev + o_cams), (double *)(dev + d_X), (int32_t *)(dres + r_chir));
-    MOT_CHK(hipGetLastError());
+    VSM_CHK(hipGetLastError());
     hipLaunchKernelGGL(k_motions_gather, dim3((unsigned)tiles.size()), dim3(64), 0, stream, d_base, (const MotTile *)(dev + o_t64),
                        (const int32_t *)(dres + r_chir), (const double *)(dev + d_X), (double *)(dres + r_xsel));
-    MOT_CHK(hipGetLastError());
-    MOT_CHK(hipMemcpyAsync(hout + dn1, dres + dn1, dn2 - dn1, hipMemcpyDeviceToHost, stream));
-    MOT_CHK(hipStreamSynchronize(stream));
+    VSM_CHK(hipGetLastError());
+    VSM_CHK(hipMemcpyAsync(hout + dn1, dres + dn1, dn2 - dn1, hipMemcpyDeviceToHost, stream));
+    VSM_CHK(hipStreamSynchronize(stream));
     out.stats[VSM_MOT_STAT_WAITS]++;
     out.stats[VSM_MOT_STAT_TRI] += (int64_t)running.size();
     const double t4 = vsm_now_us();
@@ -488,12 +448,12 @@ int vsm_motions_device(VsmMotionsDev &D, hipStream_t stream, VsmPool *pool, cons
     }
     // ---- the plane vote of all surviving pairs (on the device whatever their size), settled exactly on the host ----
     memcpy(hin + o_vt, tiles.data(), tiles.size() * sizeof(MotTile));
-    MOT_CHK(hipMemcpyAsync(dev + o_votes, hin + o_votes, in.at - up2, hipMemcpyHostToDevice, stream));
+    VSM_CHK(hipMemcpyAsync(dev + o_votes, hin + o_votes, in.at - up2, hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(k_motions_vote, dim3((unsigned)tiles.size()), dim3(256), 0, stream, (const double *)(dev + o_d), (const MotVote *)(dev + o_votes),
                        (const MotTile *)(dev + o_vt), (double *)(dres + r_sums));
-    MOT_CHK(hipGetLastError());
-    MOT_CHK(hipMemcpyAsync(hout + r_sums, dres + r_sums, N * 8, hipMemcpyDeviceToHost, stream));
-    MOT_CHK(hipStreamSynchronize(stream));
+    VSM_CHK(hipGetLastError());
+    VSM_CHK(hipMemcpyAsync(hout + r_sums, dres + r_sums, N * 8, hipMemcpyDeviceToHost, stream));
+    VSM_CHK(hipStreamSynchronize(stream));
     out.stats[VSM_MOT_STAT_WAITS]++;
     out.stats[VSM_MOT_STAT_VOTE] += (int64_t)running.size();
     const MotVote *votes = (const MotVote *)(hin + o_votes);
@@ -508,7 +468,6 @@ int vsm_motions_device(VsmMotionsDev &D, hipStream_t stream, VsmPool *pool, cons
     out.timings[3] += t4 - t3;
     out.timings[4] += vsm_now_us() - t4;
   }
-#undef MOT_CHK
   mot_count_stages(out);
   out.timings[5] = vsm_now_us() - t_begin;
   out.have = true;

@@ -30,16 +30,12 @@ int vsm_motions_run(vsm_handle *h, const vsm_vo_mono_params *params, int32_t n_p
 
 int vsm_pairs_motions(vsm_handle *h, const vsm_vo_mono_params *params, int32_t bucket) {
   if (!h) return VSM_EARG;
-  const VsmPairs *PR = h->pairs;
-  if (!PR || !PR->done) return VSM_ENOTREADY;
-  if (PR->method == 1 || PR->lists.empty()) return VSM_EARG;  // stereo matches have no previous frame to move from
-  const int32_t n_pairs = (int32_t)PR->lists.size();
-  std::vector<const vsm_p_match *> lists((size_t)n_pairs);
-  std::vector<int32_t> counts((size_t)n_pairs);
-  for (int32_t k = 0; k < n_pairs; k++) {
-    lists[k] = PR->lists[k].data();
-    counts[k] = (int32_t)PR->lists[k].size();
-  }
+  std::vector<const vsm_p_match *> lists;
+  std::vector<int32_t> counts;
+  const VsmPairs *PR = pairs_last_lists(h, lists, counts);
+  if (!PR) return VSM_ENOTREADY;
+  if (PR->method == 1 || lists.empty()) return VSM_EARG;  // stereo matches have no previous frame to move from
+  const int32_t n_pairs = (int32_t)lists.size();
   if (!vsm_motions_args_ok(params, n_pairs, lists.data(), counts.data(), bucket)) return VSM_EARG;
   return motions_run(h, params, n_pairs, lists.data(), counts.data(), bucket);
 }
@@ -82,17 +78,11 @@ int32_t vsm_motions_matches(vsm_handle *h, int32_t pair, vsm_p_match *out, int32
 }
 void vsm_motions_get_stats(vsm_handle *h, int64_t *out13) {
   const VsmMotionsResult *R = motions_result(h);
-  if (R)
-    memcpy(out13, R->stats, sizeof(R->stats));
-  else
-    memset(out13, 0, VSM_MOT_STATS * sizeof(int64_t));
+  vsm_copy_or_zero(R ? &R->stats : nullptr, out13);
 }
 void vsm_motions_get_timings(vsm_handle *h, double *out6) {
   const VsmMotionsResult *R = motions_result(h);
-  if (R)
-    memcpy(out6, R->timings, sizeof(R->timings));
-  else
-    memset(out6, 0, 6 * sizeof(double));
+  vsm_copy_or_zero(R ? &R->timings : nullptr, out6);
 }
 int vsm_motions_device_svd(vsm_handle *h) { return (h && h->motions && h->motions->dev.tested && h->motions->dev.svd_on_device) ? 1 : 0; }
 

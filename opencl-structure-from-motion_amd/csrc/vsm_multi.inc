@@ -15,9 +15,7 @@ struct vsm_multi {
   int32_t w = 0, hh = 0;
   Dc2Bank bank1, bank2;
   hipEvent_t ev_feat = nullptr, ev_keys = nullptr, ev_a = nullptr, ev_b = nullptr;
-  uint8_t *res = nullptr, *res_dev = nullptr;  // host-mapped survivors, one slot per sequence
-  int32_t *res_cnt = nullptr, *res_cnt_dev = nullptr;
-  size_t slot = 0;
+  VsmResArena arena;  // host-mapped survivors, one slot per sequence
   struct Seq {
     VsmEgoSeq *ego = nullptr;
     double T[16];
@@ -42,8 +40,7 @@ static void multi_release(vsm_multi *m) {
     if (e) (void)hipEventDestroy(e);
   m->bank1.release();
   m->bank2.release();
-  if (m->res) (void)hipHostFree(m->res);
-  if (m->res_cnt) (void)hipHostFree(m->res_cnt);
+  m->arena.free();
   for (auto &s : m->seq) vsm_ego_seq_destroy(s.ego);
   if (m->h) vsm_destroy(m->h);
   delete m;
@@ -100,16 +97,7 @@ int vsm_multi_process(vsm_multi *m, const uint8_t *left, const uint8_t *right, i
     h->seq_chunk = K;
     m->step = 0;
     for (auto &s : m->seq) s.have_prev = false;
-    m->slot = ((size_t)c.cap_set[1] * sizeof(vsm_p_match) + 255) & ~(size_t)255;
-    if (m->res) (void)hipHostFree(m->res);
-    if (m->res_cnt) (void)hipHostFree(m->res_cnt);
-    m->res = nullptr;
-    m->res_cnt = nullptr;
-    if (hipHostMalloc((void **)&m->res, m->slot * K, hipHostMallocMapped) != hipSuccess ||
-        hipHostGetDevicePointer((void **)&m->res_dev, m->res, 0) != hipSuccess ||
-        hipHostMalloc((void **)&m->res_cnt, (size_t)K * 4, hipHostMallocMapped) != hipSuccess ||
-        hipHostGetDevicePointer((void **)&m->res_cnt_dev, m->res_cnt, 0) != hipSuccess) {
-      (void)hipGetLastError();
+    if (!m->arena.alloc(al256((size_t)c.cap_set[1] * sizeof(vsm_p_match)), (size_t)K)) {
       c.ready = false;  // (the next call sets the context up again instead of running with half of it)
       return VSM_EHIP;
     }
@@ -125,14 +113,6 @@ int vsm_multi_process(vsm_multi *m, const uint8_t *left, const uint8_t *right, i
     if (m->bank2.h_error) *m->bank2.h_error = 0;
     return rc;
   };
-#define MULTI_CHK(call)                                                                        \
-  do {                                                                                         \
-    const hipError_t e_ = (call);                                                              \
-    if (e_ != hipSuccess) {                                                                    \
-      fprintf(stderr, "visomatch: %s failed: %s\n", #call, hipGetErrorString(e_));             \
-      return fail(VSM_EHIP);                                                                   \
-    }                                                                                          \
-  } while (0)
   const double t0 = now_us();
   const int bank = (int)(m->step & 1), first_img = 2 * bank * K, prev_img = 2 * (bank ^ 1) * K;
   // ---- pushBack of K frames: one launch per kernel over 2 K images ----
@@ -143,9 +123,9 @@ int vsm_multi_process(vsm_multi *m, const uint8_t *left, const uint8_t *right, i
     if (rc != VSM_OK) return fail(rc);
   }
   enqueue_features(h, c, first_img, 2 * K);
-  MULTI_CHK(hipEventRecord(m->ev_feat, h->stream));
-  MULTI_CHK(hipEventSynchronize(m->ev_feat));  // the feature counts are in host-mapped memory
-  MULTI_CHK(hipGetLastError());
+  VSM_CHK(hipEventRecord(m->ev_feat, h->stream));
+  VSM_CHK(hipEventSynchronize(m->ev_feat));  // the feature counts are in host-mapped memory
+  VSM_CHK(hipGetLastError());
   const double t1 = now_us();
   // ---- one job per sequence ----
   VsmJob *h_jobs = c.h_jobs;
@@ -196,7 +176,7 @@ int vsm_multi_process(vsm_multi *m, const uint8_t *left, const uint8_t *right, i
     if ((p.multi_stage && !m->bank1.reserve(K, std::max(max_nq[0], 64), true)) || !m->bank2.reserve(K, std::max(max_nq[1], 64), true)) return fail(VSM_EHIP);
     const VsmPair *d_pairs = c.d_pairs;
     VsmJob *d_jobs = c.d_jobs;
-    MULTI_CHK(vsm_upload(h->stream, d_jobs, h_jobs, sizeof(VsmJob) * K));
+    VSM_CHK(vsm_upload(h->stream, d_jobs, h_jobs, sizeof(VsmJob) * K));
     VsmMatchCfg cfg = make_cfg(p, method, h->sw.match_heads && c.has_heads);
     VsmJob dummy;
     memset(&dummy, 0, sizeof(dummy));
@@ -210,11 +190,11 @@ int vsm_multi_process(vsm_multi *m, const uint8_t *left, const uint8_t *right, i
       cfg.use_prior = 0;
       if (!vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, K, c.dims, cfg, max_nq[0], 1))
         vsm_launch_export(h->stream, h->prof, d_pairs, K, 0, max_nq[0]);
-      MULTI_CHK(hipEventRecord(m->ev_a, h->stream));
-      MULTI_CHK(hipEventSynchronize(m->ev_a));  // the lists are in host-mapped memory
-      MULTI_CHK(hipGetLastError());
+      VSM_CHK(hipEventRecord(m->ev_a, h->stream));
+      VSM_CHK(hipEventSynchronize(m->ev_a));  // the lists are in host-mapped memory
+      VSM_CHK(hipGetLastError());
       const int32_t dims_c[3] = {w, hh, c.dims.bpl};
-      MULTI_CHK(host_pass1_boxes(h, c, 0, K, valid.data(), method, dims_c));
+      VSM_CHK(host_pass1_boxes(h, c, 0, K, valid.data(), method, dims_c));
     } else if (p.multi_stage) {
       // ---- pass 1 and its chain: removeOutliers + computePriorStatistics on the device (viso/matcher.cpp:222-226) ----
       cfg.sparse = 1;
@@ -222,13 +202,13 @@ int vsm_multi_process(vsm_multi *m, const uint8_t *left, const uint8_t *right, i
       vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, K, c.dims, cfg, max_nq[0]);
       Dc2Bank &B = m->bank1;
       for (int i = 0; i < K; i++) B.fill_job(i, c.h_pairs[i].list1, c.h_pairs[i].count, false, nullptr, nullptr, c.h_pairs[i].ranges);
-      MULTI_CHK(vsm_upload(h->stream, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * K));
+      VSM_CHK(vsm_upload(h->stream, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * K));
       vsm_dc2_launch_keys(h->stream, B.d_jobs, K, max_nq[0]);  // (also into host-mapped memory)
-      MULTI_CHK(hipEventRecord(m->ev_a, h->stream));
+      VSM_CHK(hipEventRecord(m->ev_a, h->stream));
       dc2_enqueue_mesh(h->stream, B, K, max_nq[0]);
       // Triangle's vertex sort of the K short lists on the pool (a few microseconds each) while the device triangulates: the
       // device's own sort of such a list is one wave for 0.36 ms, longer than the triangulation beside it
-      MULTI_CHK(hipEventSynchronize(m->ev_a));
+      VSM_CHK(hipEventSynchronize(m->ev_a));
       h->pool->run(K, [&](int i) {
         static thread_local ExactDelaunay sorter;
         const int32_t n = B.h_n[i];
@@ -244,18 +224,18 @@ int vsm_multi_process(vsm_multi *m, const uint8_t *left, const uint8_t *right, i
     vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, K, c.dims, cfg, max_nq[1]);
     Dc2Bank &B = m->bank2;
     for (int i = 0; i < K; i++)
-      B.fill_job(i, c.h_pairs[i].list2, c.h_pairs[i].count + 1, false, (vsm_p_match *)(m->res_dev + m->slot * i), m->res_cnt_dev + i, nullptr);
-    MULTI_CHK(vsm_upload(h->stream, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * K));
+      B.fill_job(i, c.h_pairs[i].list2, c.h_pairs[i].count + 1, false, (vsm_p_match *)(m->arena.res_dev + m->arena.slot * i), m->arena.res_cnt_dev + i, nullptr);
+    VSM_CHK(vsm_upload(h->stream, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * K));
     if (p.refinement == 2) {  // sub-pixel fits drop matches: they come before the keys of what is left (section 6b of DESIGN.md)
       vsm_launch_refine(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, K, c.dims, c.dims, method, p.refinement, max_nq[1]);
       vsm_launch_parabolic_apply(h->stream, h->prof, d_pairs, K);
     }
     vsm_dc2_launch_keys(h->stream, B.d_jobs, K, max_nq[1]);  // (also into host-mapped memory: the pool sorts them)
-    MULTI_CHK(hipEventRecord(m->ev_keys, h->stream));
+    VSM_CHK(hipEventRecord(m->ev_keys, h->stream));
     dc2_enqueue_mesh(h->stream, B, K, max_nq[1]);
     if (p.refinement == 1) vsm_launch_refine(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, K, c.dims, c.dims, method, p.refinement, max_nq[1]);
-    MULTI_CHK(hipGetLastError());
-    MULTI_CHK(hipEventSynchronize(m->ev_keys));
+    VSM_CHK(hipGetLastError());
+    VSM_CHK(hipEventSynchronize(m->ev_keys));
     t2 = now_us();
     // Triangle's vertex sort of every list on the pool while the device triangulates (which match stands for a shared pixel)
     h->pool->run(K, [&](int i) {
@@ -271,8 +251,8 @@ int vsm_multi_process(vsm_multi *m, const uint8_t *left, const uint8_t *right, i
       }
     });
     dc2_enqueue_votes(h->stream, B, K, max_nq[1], method, (float)p.outlier_flow_tolerance, (float)p.outlier_disp_tolerance);
-    MULTI_CHK(hipGetLastError());
-    MULTI_CHK(hipStreamSynchronize(h->stream));
+    VSM_CHK(hipGetLastError());
+    VSM_CHK(hipStreamSynchronize(h->stream));
     int declined = m->bank2.h_error ? *m->bank2.h_error : 0;
     if (m->bank1.h_error) declined |= *m->bank1.h_error;
     if (declined) {
@@ -293,8 +273,8 @@ int vsm_multi_process(vsm_multi *m, const uint8_t *left, const uint8_t *right, i
     }
     s.have_prev = true;
     if (valid[i]) {
-      const int32_t n = m->res_cnt[i];
-      const vsm_p_match *src = (const vsm_p_match *)(m->res + m->slot * i);
+      const int32_t n = m->arena.res_cnt[i];
+      const vsm_p_match *src = (const vsm_p_match *)(m->arena.res + m->arena.slot * i);
       s.final_list.assign(src, src + std::max(n, 0));
       s.matched = s.final_list;
     } else {
@@ -314,7 +294,6 @@ int vsm_multi_process(vsm_multi *m, const uint8_t *left, const uint8_t *right, i
   m->timings[2] = t3 - t2;
   m->timings[3] = t4 - t3;
   return VSM_OK;
-#undef MULTI_CHK
 }
 
 int32_t vsm_multi_num_sequences(vsm_multi *m) { return m ? m->K : 0; }

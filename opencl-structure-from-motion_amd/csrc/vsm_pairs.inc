@@ -13,20 +13,12 @@ struct VsmPairs {
   int chunk = 0;
   Dc2Bank bank1, bank2;
   hipEvent_t ev_feat = nullptr, ev_keys = nullptr, ev_a = nullptr;
-  uint8_t *res = nullptr, *res_dev = nullptr;  // the chunk's survivors, host-mapped: one slot per pair of the bank
-  int32_t *res_cnt = nullptr, *res_cnt_dev = nullptr;
-  size_t slot = 0;
+  VsmResArena arena;  // the chunk's survivors, host-mapped: one slot per pair of the bank
   std::vector<std::vector<vsm_p_match>> lists;  // per pair of the last call
   std::vector<int32_t> pair_list;  // ... its pairs, frame count and method, for vsm_pairs_tracks; done: it ran to its end
   int32_t n_frames = 0, method = -1;
   bool done = false;
   double timings[4] = {0, 0, 0, 0};  // image side, first passes + chains, second passes + chains, total; us
-  void free_arena() {
-    if (res) (void)hipHostFree(res);
-    if (res_cnt) (void)hipHostFree(res_cnt);
-    res = res_dev = nullptr;
-    res_cnt = res_cnt_dev = nullptr;
-  }
 };
 
 static void pairs_destroy(vsm_handle *h) {
@@ -36,10 +28,24 @@ static void pairs_destroy(vsm_handle *h) {
     if (e) (void)hipEventDestroy(e);
   P->bank1.release();
   P->bank2.release();
-  P->free_arena();
+  P->arena.free();
   ctx_destroy(P->ctx);
   delete P;
   h->pairs = nullptr;
+}
+
+// The lists of the last vsm_pairs_run that ran to its end, as the later stages take lists: a pointer and a count per pair,
+// into the caller's vectors.  Null: there is no such run (the vectors are then left alone).
+static const VsmPairs *pairs_last_lists(const vsm_handle *h, std::vector<const vsm_p_match *> &lists, std::vector<int32_t> &counts) {
+  const VsmPairs *P = h->pairs;
+  if (!P || !P->done) return nullptr;
+  lists.resize(P->lists.size());
+  counts.resize(P->lists.size());
+  for (size_t k = 0; k < P->lists.size(); k++) {
+    lists[k] = P->lists[k].data();
+    counts[k] = (int32_t)P->lists[k].size();
+  }
+  return P;
 }
 
 // The streaming ring of a handle, set aside while vsm_pairs_run's fallback matches pairs frame by frame on a ring of its
@@ -169,14 +175,7 @@ int vsm_pairs_run(vsm_handle *h, const uint8_t *left, const uint8_t *right, int6
     const int rc = ctx_create(c, p, w, hh, slots, C, h->stream, h->sw.match_heads != 0);
     if (rc != VSM_OK) return rc;
     P.chunk = C;
-    P.free_arena();
-    P.slot = al256((size_t)c.cap_set[1] * sizeof(vsm_p_match));
-    if (hipHostMalloc((void **)&P.res, P.slot * C, hipHostMallocMapped) != hipSuccess ||
-        hipHostGetDevicePointer((void **)&P.res_dev, P.res, 0) != hipSuccess ||
-        hipHostMalloc((void **)&P.res_cnt, (size_t)C * 4, hipHostMallocMapped) != hipSuccess ||
-        hipHostGetDevicePointer((void **)&P.res_cnt_dev, P.res_cnt, 0) != hipSuccess) {
-      (void)hipGetLastError();
-      P.free_arena();
+    if (!P.arena.alloc(al256((size_t)c.cap_set[1] * sizeof(vsm_p_match)), (size_t)C)) {
       c.ready = false;  // (the next call sets the context up again instead of running with half of it)
       return VSM_EHIP;
     }
@@ -191,14 +190,6 @@ int vsm_pairs_run(vsm_handle *h, const uint8_t *left, const uint8_t *right, int6
     if (P.bank2.h_error) P.bank2.h_error[0] = P.bank2.h_error[1] = 0;
     return rc;
   };
-#define PAIRS_CHK(call)                                                            \
-  do {                                                                             \
-    const hipError_t e_ = (call);                                                  \
-    if (e_ != hipSuccess) {                                                        \
-      fprintf(stderr, "visomatch: %s failed: %s\n", #call, hipGetErrorString(e_)); \
-      return fail(VSM_EHIP);                                                       \
-    }                                                                              \
-  } while (0)
   // ---- pushBack of every frame, once: chunks of frames through the front end and the feature kernels ----
   {
     const int Cf = std::min<int>(n_frames, 64);
@@ -217,9 +208,9 @@ int vsm_pairs_run(vsm_handle *h, const uint8_t *left, const uint8_t *right, int6
     h->seq_chunk = seq_chunk_before;
     if (rc != VSM_OK) return fail(rc);
   }
-  PAIRS_CHK(hipEventRecord(P.ev_feat, h->stream));
-  PAIRS_CHK(hipEventSynchronize(P.ev_feat));  // every image's feature counts are in host-mapped memory
-  PAIRS_CHK(hipGetLastError());
+  VSM_CHK(hipEventRecord(P.ev_feat, h->stream));
+  VSM_CHK(hipEventSynchronize(P.ev_feat));  // every image's feature counts are in host-mapped memory
+  VSM_CHK(hipGetLastError());
   P.timings[0] = now_us() - t0;
   // ---- the pairs, C at a time: what a vsm_multi_process step does for its K sequences ----
   const int32_t dims_c[3] = {w, hh, c.dims.bpl};
@@ -243,7 +234,7 @@ int vsm_pairs_run(vsm_handle *h, const uint8_t *left, const uint8_t *right, int6
     double t2 = t1;
     if (chain) {
       if ((p.multi_stage && !P.bank1.reserve(C, std::max(max_nq[0], 64), true)) || !P.bank2.reserve(C, std::max(max_nq[1], 64), true)) return fail(VSM_EHIP);
-      PAIRS_CHK(vsm_upload(h->stream, d_jobs, h_jobs, sizeof(VsmJob) * n));
+      VSM_CHK(vsm_upload(h->stream, d_jobs, h_jobs, sizeof(VsmJob) * n));
       VsmMatchCfg cfg = make_cfg(p, method, h->sw.match_heads && c.has_heads);
       // few pairs: the first-pass lists go to the host pool, a list per thread; else the device chain (vsm_multi.inc has the measurements)
       const bool host_p1 = p.multi_stage && (h->sw.multi_host_pass1 >= 0 ? h->sw.multi_host_pass1 != 0 : n <= h->pool->size());
@@ -253,10 +244,10 @@ int vsm_pairs_run(vsm_handle *h, const uint8_t *left, const uint8_t *right, int6
         cfg.use_prior = 0;
         if (!vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, n, c.dims, cfg, max_nq[0], 1))
           vsm_launch_export(h->stream, h->prof, d_pairs, n, 0, max_nq[0]);
-        PAIRS_CHK(hipEventRecord(P.ev_a, h->stream));
-        PAIRS_CHK(hipEventSynchronize(P.ev_a));  // the lists are in host-mapped memory
-        PAIRS_CHK(hipGetLastError());
-        PAIRS_CHK(host_pass1_boxes(h, c, 0, n, valid.data(), method, dims_c));
+        VSM_CHK(hipEventRecord(P.ev_a, h->stream));
+        VSM_CHK(hipEventSynchronize(P.ev_a));  // the lists are in host-mapped memory
+        VSM_CHK(hipGetLastError());
+        VSM_CHK(host_pass1_boxes(h, c, 0, n, valid.data(), method, dims_c));
       } else if (p.multi_stage) {
         // ---- pass 1 and its chain: removeOutliers + computePriorStatistics on the device ----
         cfg.sparse = 1;
@@ -264,11 +255,11 @@ int vsm_pairs_run(vsm_handle *h, const uint8_t *left, const uint8_t *right, int6
         vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, n, c.dims, cfg, max_nq[0]);
         Dc2Bank &B = P.bank1;
         for (int i = 0; i < n; i++) B.fill_job(i, c.h_pairs[i].list1, c.h_pairs[i].count, false, nullptr, nullptr, c.h_pairs[i].ranges);
-        PAIRS_CHK(vsm_upload(h->stream, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * n));
+        VSM_CHK(vsm_upload(h->stream, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * n));
         vsm_dc2_launch_keys(h->stream, B.d_jobs, n, max_nq[0]);  // (also into host-mapped memory)
-        PAIRS_CHK(hipEventRecord(P.ev_a, h->stream));
+        VSM_CHK(hipEventRecord(P.ev_a, h->stream));
         dc2_enqueue_mesh(h->stream, B, n, max_nq[0]);
-        PAIRS_CHK(hipEventSynchronize(P.ev_a));
+        VSM_CHK(hipEventSynchronize(P.ev_a));
         h->pool->run(n, [&](int i) {  // Triangle's vertex sort of the short lists on the pool while the device triangulates
           static thread_local ExactDelaunay sorter;
           const int32_t nl = B.h_n[i];
@@ -284,18 +275,18 @@ int vsm_pairs_run(vsm_handle *h, const uint8_t *left, const uint8_t *right, int6
       vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, n, c.dims, cfg, max_nq[1]);
       Dc2Bank &B = P.bank2;
       for (int i = 0; i < n; i++)
-        B.fill_job(i, c.h_pairs[i].list2, c.h_pairs[i].count + 1, false, (vsm_p_match *)(P.res_dev + P.slot * i), P.res_cnt_dev + i, nullptr);
-      PAIRS_CHK(vsm_upload(h->stream, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * n));
+        B.fill_job(i, c.h_pairs[i].list2, c.h_pairs[i].count + 1, false, (vsm_p_match *)(P.arena.res_dev + P.arena.slot * i), P.arena.res_cnt_dev + i, nullptr);
+      VSM_CHK(vsm_upload(h->stream, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * n));
       if (p.refinement == 2) {  // sub-pixel fits drop matches: they come before the keys of what is left
         vsm_launch_refine(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, n, c.dims, c.dims, method, p.refinement, max_nq[1]);
         vsm_launch_parabolic_apply(h->stream, h->prof, d_pairs, n);
       }
       vsm_dc2_launch_keys(h->stream, B.d_jobs, n, max_nq[1]);  // (also into host-mapped memory: the pool sorts them)
-      PAIRS_CHK(hipEventRecord(P.ev_keys, h->stream));
+      VSM_CHK(hipEventRecord(P.ev_keys, h->stream));
       dc2_enqueue_mesh(h->stream, B, n, max_nq[1]);
       if (p.refinement == 1) vsm_launch_refine(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, n, c.dims, c.dims, method, p.refinement, max_nq[1]);
-      PAIRS_CHK(hipGetLastError());
-      PAIRS_CHK(hipEventSynchronize(P.ev_keys));
+      VSM_CHK(hipGetLastError());
+      VSM_CHK(hipEventSynchronize(P.ev_keys));
       t2 = now_us();
       h->pool->run(n, [&](int i) {  // Triangle's vertex sort of every list on the pool while the device triangulates
         static thread_local ExactDelaunay sorter;
@@ -310,8 +301,8 @@ int vsm_pairs_run(vsm_handle *h, const uint8_t *left, const uint8_t *right, int6
         }
       });
       dc2_enqueue_votes(h->stream, B, n, max_nq[1], method, (float)p.outlier_flow_tolerance, (float)p.outlier_disp_tolerance);
-      PAIRS_CHK(hipGetLastError());
-      PAIRS_CHK(hipStreamSynchronize(h->stream));
+      VSM_CHK(hipGetLastError());
+      VSM_CHK(hipStreamSynchronize(h->stream));
       int declined = P.bank2.h_error ? P.bank2.h_error[0] : 0;
       if (P.bank1.h_error) declined |= P.bank1.h_error[0];
       if (declined) {
@@ -323,8 +314,8 @@ int vsm_pairs_run(vsm_handle *h, const uint8_t *left, const uint8_t *right, int6
       // the survivors out of the chunk's arena into the pairs' own lists: host memory grows with the matches found
       h->pool->run(n, [&](int i) {
         if (!valid[i]) return;
-        const vsm_p_match *src = (const vsm_p_match *)(P.res + P.slot * i);
-        P.lists[(size_t)k0 + i].assign(src, src + std::max(P.res_cnt[i], 0));
+        const vsm_p_match *src = (const vsm_p_match *)(P.arena.res + P.arena.slot * i);
+        P.lists[(size_t)k0 + i].assign(src, src + std::max(P.arena.res_cnt[i], 0));
       });
     } else {
       const int rc = pairs_fallback(h, P, save, left, right, frame_stride, on_device, w, hh, bpl, method, pairs, k0, n, Tr, Tr_valid);
@@ -338,7 +329,6 @@ int vsm_pairs_run(vsm_handle *h, const uint8_t *left, const uint8_t *right, int6
   P.timings[3] = now_us() - t0;
   P.done = true;
   return VSM_OK;
-#undef PAIRS_CHK
 }
 
 int32_t vsm_pairs_num_matches(vsm_handle *h, int32_t pair) {

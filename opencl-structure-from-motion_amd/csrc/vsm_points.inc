@@ -7,9 +7,7 @@
 // ray values, which decides status 9.  vsm_tracks_triangulate fills the same block from the handle's last track result,
 // reading every observation's pixel from the match it names.
 struct VsmPoints {
-  uint8_t *pin_in = nullptr, *pin_out = nullptr, *dev = nullptr;  // sizes that only grow
-  size_t pin_in_bytes = 0, pin_out_bytes = 0, dev_bytes = 0;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};  // start, uploaded, kernel done
+  VsmStage st;  // pinned input and output, the device block, the events (vsm_stage.h)
   bool have = false;
   std::vector<int32_t> status, type, updates;
   std::vector<double> xyz, dist, angle;
@@ -20,11 +18,7 @@ struct VsmPoints {
 static void points_destroy(vsm_handle *h) {
   VsmPoints *P = h->points;
   if (!P) return;
-  if (P->pin_in) (void)hipHostFree(P->pin_in);
-  if (P->pin_out) (void)hipHostFree(P->pin_out);
-  if (P->dev) vsm_dev_free(P->dev);
-  for (hipEvent_t e : P->ev)
-    if (e) (void)hipEventDestroy(e);
+  P->st.release();
   delete P;
   h->points = nullptr;
 }
@@ -37,57 +31,35 @@ static int points_run(vsm_handle *h, double t0, int32_t n_frames, const double *
   HIPCHK(hipSetDevice(h->device));
   if (!h->points) h->points = new VsmPoints();
   VsmPoints &P = *h->points;
+  VsmStage &S = P.st;
   const size_t T = (size_t)n_tracks;
-  TrkLayout in;
+  VsmLayout in;
   const size_t o_frames = in.take((size_t)n_frames * sizeof(PtsFrame) + 8), o_valid = in.take((size_t)n_frames + 1), o_offsets = in.take((T + 1) * 4),
                o_fr = in.take((size_t)n_obs * 4 + 4), o_uv = in.take((size_t)n_obs * 8 + 8), o_flags = in.take(T + 1);
-  TrkLayout out;
+  VsmLayout out;
   const size_t r_status = out.take(T * 4 + 4), r_type = out.take(T * 4 + 4), r_updates = out.take(T * 4 + 4), r_xyz = out.take(T * 24 + 8), r_dist = out.take(T * 8 + 8),
                r_ray = out.take(T * 8 + 8);
-  if (in.at > P.pin_in_bytes) {
-    (void)hipStreamSynchronize(h->stream);
-    if (P.pin_in) (void)hipHostFree(P.pin_in);
-    P.pin_in = nullptr;
-    P.pin_in_bytes = 0;
-    HIPCHK(hipHostMalloc((void **)&P.pin_in, in.at + in.at / 4, hipHostMallocDefault));
-    P.pin_in_bytes = in.at + in.at / 4;
-  }
-  if (out.at > P.pin_out_bytes) {
-    (void)hipStreamSynchronize(h->stream);
-    if (P.pin_out) (void)hipHostFree(P.pin_out);
-    P.pin_out = nullptr;
-    P.pin_out_bytes = 0;
-    HIPCHK(hipHostMalloc((void **)&P.pin_out, out.at + out.at / 4, hipHostMallocDefault));
-    P.pin_out_bytes = out.at + out.at / 4;
-  }
+  HIPCHK(S.grow_in(in.at, h->stream));
+  HIPCHK(S.grow_out(out.at, h->stream));
   // ---- pack ----
-  PtsFrame *p_frames = (PtsFrame *)(P.pin_in + o_frames);
-  uint8_t *p_valid = P.pin_in + o_valid;
+  PtsFrame *p_frames = (PtsFrame *)(S.pin_in + o_frames);
+  uint8_t *p_valid = S.pin_in + o_valid;
   for (int32_t k = 0; k < n_frames; k++) {
     pts_frame(poses + 12 * (size_t)k, f, cu, cv, p_frames + k);
     p_valid[k] = (!pose_valid || pose_valid[k]) ? 1 : 0;
   }
-  memcpy(P.pin_in + o_offsets, offsets, (T + 1) * 4);
+  memcpy(S.pin_in + o_offsets, offsets, (T + 1) * 4);
   if (flags)
-    memcpy(P.pin_in + o_flags, flags, T);
+    memcpy(S.pin_in + o_flags, flags, T);
   else
-    memset(P.pin_in + o_flags, 0, T);
-  if (!fill((int32_t *)(P.pin_in + o_fr), (float *)(P.pin_in + o_uv))) return VSM_EARG;
+    memset(S.pin_in + o_flags, 0, T);
+  if (!fill((int32_t *)(S.pin_in + o_fr), (float *)(S.pin_in + o_uv))) return VSM_EARG;
   // ---- from here on the call replaces the last result ----
   P.have = false;
   memset(P.stats, 0, sizeof(P.stats));
   memset(P.timings, 0, sizeof(P.timings));
-  const size_t need = al256(in.at) + out.at;
-  if (need > P.dev_bytes) {
-    (void)hipStreamSynchronize(h->stream);
-    if (P.dev) vsm_dev_free(P.dev);
-    P.dev = nullptr;
-    P.dev_bytes = 0;
-    HIPCHK(vsm_dev_alloc((void **)&P.dev, need + need / 4));
-    P.dev_bytes = need + need / 4;
-  }
-  for (hipEvent_t &e : P.ev)
-    if (!e) HIPCHK(hipEventCreate(&e));
+  HIPCHK(S.grow_dev(al256(in.at) + out.at, h->stream));
+  HIPCHK(S.events());
   const double t1 = now_us();
   P.timings[0] = t1 - t0;
   auto fail = [&](int rc) {
@@ -95,23 +67,15 @@ static int points_run(vsm_handle *h, double t0, int32_t n_frames, const double *
     (void)hipGetLastError();
     return rc;
   };
-#define POINTS_CHK(call)                                                           \
-  do {                                                                             \
-    const hipError_t e_ = (call);                                                  \
-    if (e_ != hipSuccess) {                                                        \
-      fprintf(stderr, "visomatch: %s failed: %s\n", #call, hipGetErrorString(e_)); \
-      return fail(VSM_EHIP);                                                       \
-    }                                                                              \
-  } while (0)
-  uint8_t *dout = P.dev + al256(in.at);
+  uint8_t *dout = S.dev + al256(in.at);
   PtsDevice d;
   memset(&d, 0, sizeof(d));
-  d.frames = (const PtsFrame *)(P.dev + o_frames);
-  d.valid = P.dev + o_valid;
-  d.offsets = (const int32_t *)(P.dev + o_offsets);
-  d.obs_frames = (const int32_t *)(P.dev + o_fr);
-  d.uv = (const float *)(P.dev + o_uv);
-  d.flags = P.dev + o_flags;
+  d.frames = (const PtsFrame *)(S.dev + o_frames);
+  d.valid = S.dev + o_valid;
+  d.offsets = (const int32_t *)(S.dev + o_offsets);
+  d.obs_frames = (const int32_t *)(S.dev + o_fr);
+  d.uv = (const float *)(S.dev + o_uv);
+  d.flags = S.dev + o_flags;
   d.status = (int32_t *)(dout + r_status);
   d.type = (int32_t *)(dout + r_type);
   d.updates = (int32_t *)(dout + r_updates);
@@ -125,22 +89,22 @@ static int points_run(vsm_handle *h, double t0, int32_t n_frames, const double *
   d.min_track_length = prm.min_track_length;
   float ms_up = 0, ms_k = 0;
   if (n_tracks > 0) {
-    POINTS_CHK(hipEventRecord(P.ev[0], h->stream));
-    POINTS_CHK(hipMemcpyAsync(P.dev, P.pin_in, in.at, hipMemcpyHostToDevice, h->stream));
-    POINTS_CHK(hipEventRecord(P.ev[1], h->stream));
+    VSM_CHK(hipEventRecord(S.ev[0], h->stream));
+    VSM_CHK(hipMemcpyAsync(S.dev, S.pin_in, in.at, hipMemcpyHostToDevice, h->stream));
+    VSM_CHK(hipEventRecord(S.ev[1], h->stream));
     vsm_points_launch(h->stream, h->prof, d);
-    POINTS_CHK(hipGetLastError());
-    POINTS_CHK(hipEventRecord(P.ev[2], h->stream));
-    POINTS_CHK(hipMemcpyAsync(P.pin_out, dout, out.at, hipMemcpyDeviceToHost, h->stream));
-    POINTS_CHK(hipStreamSynchronize(h->stream));
-    POINTS_CHK(hipGetLastError());
+    VSM_CHK(hipGetLastError());
+    VSM_CHK(hipEventRecord(S.ev[2], h->stream));
+    VSM_CHK(hipMemcpyAsync(S.pin_out, dout, out.at, hipMemcpyDeviceToHost, h->stream));
+    VSM_CHK(hipStreamSynchronize(h->stream));
+    VSM_CHK(hipGetLastError());
     if (h->prof.on) h->prof.resolve();
-    (void)hipEventElapsedTime(&ms_up, P.ev[0], P.ev[1]);
-    (void)hipEventElapsedTime(&ms_k, P.ev[1], P.ev[2]);
+    (void)hipEventElapsedTime(&ms_up, S.ev[0], S.ev[1]);
+    (void)hipEventElapsedTime(&ms_k, S.ev[1], S.ev[2]);
   }
   // ---- into the handle's vectors; the angle and status 9 need libm ----
-  const int32_t *o_st = (const int32_t *)(P.pin_out + r_status), *o_ty = (const int32_t *)(P.pin_out + r_type), *o_up = (const int32_t *)(P.pin_out + r_updates);
-  const double *o_xyz = (const double *)(P.pin_out + r_xyz), *o_di = (const double *)(P.pin_out + r_dist), *o_ray = (const double *)(P.pin_out + r_ray);
+  const int32_t *o_st = (const int32_t *)(S.pin_out + r_status), *o_ty = (const int32_t *)(S.pin_out + r_type), *o_up = (const int32_t *)(S.pin_out + r_updates);
+  const double *o_xyz = (const double *)(S.pin_out + r_xyz), *o_di = (const double *)(S.pin_out + r_dist), *o_ray = (const double *)(S.pin_out + r_ray);
   P.status.assign(o_st, o_st + T);
   P.type.assign(o_ty, o_ty + T);
   P.updates.assign(o_up, o_up + T);
@@ -156,8 +120,9 @@ static int points_run(vsm_handle *h, double t0, int32_t n_frames, const double *
   P.timings[3] = std::max(0.0, (t2 - t1) - P.timings[1] - P.timings[2]);
   P.have = true;
   return VSM_OK;
-#undef POINTS_CHK
 }
+
+static const VsmPoints *points_result(vsm_handle *h) { return (h && h->points && h->points->have) ? h->points : nullptr; }
 
 extern "C" {
 
@@ -186,14 +151,11 @@ int vsm_tracks_triangulate(vsm_handle *h, const vsm_p_match *const *lists, const
   const VsmTracks &T = *Tp;
   const int32_t n_pairs = (int32_t)T.pair_base.size() - 1;
   std::vector<const vsm_p_match *> own;
+  std::vector<int32_t> own_counts;
   if (!lists) {  // the lists of the last vsm_pairs_run, if the tracks came from them
-    const VsmPairs *PR = h->pairs;
-    if (!T.from_pairs || !PR || !PR->done || (int32_t)PR->lists.size() != n_pairs) return VSM_ENOTREADY;
-    own.resize((size_t)n_pairs);
-    for (int32_t k = 0; k < n_pairs; k++) {
-      if ((int32_t)PR->lists[k].size() != T.pair_base[k + 1] - T.pair_base[k]) return VSM_ENOTREADY;  // (a later vsm_pairs_run has replaced them)
-      own[k] = PR->lists[k].data();
-    }
+    if (!T.from_pairs || !pairs_last_lists(h, own, own_counts) || (int32_t)own.size() != n_pairs) return VSM_ENOTREADY;
+    for (int32_t k = 0; k < n_pairs; k++)
+      if (own_counts[k] != T.pair_base[k + 1] - T.pair_base[k]) return VSM_ENOTREADY;  // (a later vsm_pairs_run has replaced them)
     lists = own.data();
   } else {
     if (n_pairs > 0 && !counts) return VSM_EARG;
@@ -243,16 +205,12 @@ int32_t vsm_points_get(vsm_handle *h, int32_t *status, double *xyz, int32_t *typ
   return (int32_t)T;
 }
 void vsm_points_get_stats(vsm_handle *h, int64_t *out10) {
-  if (h && h->points && h->points->have)
-    memcpy(out10, h->points->stats, sizeof(h->points->stats));
-  else
-    memset(out10, 0, 10 * sizeof(int64_t));
+  const VsmPoints *P = points_result(h);
+  vsm_copy_or_zero(P ? &P->stats : nullptr, out10);
 }
 void vsm_points_get_timings(vsm_handle *h, double *out4) {
-  if (h && h->points && h->points->have)
-    memcpy(out4, h->points->timings, sizeof(h->points->timings));
-  else
-    memset(out4, 0, 4 * sizeof(double));
+  const VsmPoints *P = points_result(h);
+  vsm_copy_or_zero(P ? &P->timings : nullptr, out4);
 }
 
 }  // extern "C"

@@ -8,9 +8,7 @@
 // pinned block (8 bytes per match) and finds each frame's node count on the way, one copy takes the block up, one brings
 // offsets, observations, flags and the track of every match back.  Segments longer than a workgroup orders are sorted here.
 struct VsmTracks {
-  uint8_t *pin_in = nullptr, *pin_out = nullptr, *dev = nullptr;  // sizes that only grow
-  size_t pin_in_bytes = 0, pin_out_bytes = 0, dev_bytes = 0;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};  // (with timing) start, uploaded, kernels done
+  VsmStage st;  // pinned input and output, the device block, the events (vsm_stage.h)
   bool have = false;
   std::vector<int32_t> offsets, obs, track_of_match, pair_base;
   std::vector<uint8_t> flags;
@@ -26,24 +24,10 @@ struct VsmTracks {
 static void tracks_destroy(vsm_handle *h) {
   VsmTracks *T = h->tracks;
   if (!T) return;
-  if (T->pin_in) (void)hipHostFree(T->pin_in);
-  if (T->pin_out) (void)hipHostFree(T->pin_out);
-  if (T->dev) vsm_dev_free(T->dev);
-  for (hipEvent_t e : T->ev)
-    if (e) (void)hipEventDestroy(e);
+  T->st.release();
   delete T;
   h->tracks = nullptr;
 }
-
-// byte offsets of consecutive blocks, each 256-aligned
-struct TrkLayout {
-  size_t at = 0;
-  size_t take(size_t bytes) {
-    const size_t o = at;
-    at = al256(at + bytes);
-    return o;
-  }
-};
 
 static int tracks_run(vsm_handle *h, int32_t n_frames, const int32_t *pairs, int32_t n_pairs, const vsm_p_match *const *lists, const int32_t *counts,
                       int32_t side, int32_t min_length) {
@@ -54,20 +38,14 @@ static int tracks_run(vsm_handle *h, int32_t n_frames, const int32_t *pairs, int
   HIPCHK(hipSetDevice(h->device));
   if (!h->tracks) h->tracks = new VsmTracks();
   VsmTracks &T = *h->tracks;
+  VsmStage &S = T.st;
   // ---- pack: (ip, ic) of every match, behind the three tables, in one pinned block ----
-  TrkLayout in;
+  VsmLayout in;
   const size_t o_pair_base = in.take(((size_t)n_pairs + 1) * 4), o_pairs = in.take((size_t)n_pairs * 8 + 4), o_feat_base = in.take(((size_t)n_frames + 1) * 4),
                o_edges = in.take((size_t)n_edges * 8 + 4);
-  if (in.at > T.pin_in_bytes) {
-    (void)hipStreamSynchronize(h->stream);
-    if (T.pin_in) (void)hipHostFree(T.pin_in);
-    T.pin_in = nullptr;
-    T.pin_in_bytes = 0;
-    HIPCHK(hipHostMalloc((void **)&T.pin_in, in.at + in.at / 4, hipHostMallocDefault));
-    T.pin_in_bytes = in.at + in.at / 4;
-  }
-  int32_t *p_pair_base = (int32_t *)(T.pin_in + o_pair_base), *p_pairs = (int32_t *)(T.pin_in + o_pairs), *p_feat_base = (int32_t *)(T.pin_in + o_feat_base),
-          *p_edges = (int32_t *)(T.pin_in + o_edges);
+  HIPCHK(S.grow_in(in.at, h->stream));
+  int32_t *p_pair_base = (int32_t *)(S.pin_in + o_pair_base), *p_pairs = (int32_t *)(S.pin_in + o_pairs), *p_feat_base = (int32_t *)(S.pin_in + o_feat_base),
+          *p_edges = (int32_t *)(S.pin_in + o_edges);
   T.max_p.assign((size_t)n_pairs, -1);
   T.max_c.assign((size_t)n_pairs, -1);
   T.bad.assign((size_t)n_pairs, 0);
@@ -106,96 +84,70 @@ static int tracks_run(vsm_handle *h, int32_t n_frames, const int32_t *pairs, int
     n = (n + TRK_SCAN_BLOCK - 1) / TRK_SCAN_BLOCK;
     scan_part_items += (size_t)n;
   }
-  TrkLayout dl = in;
+  VsmLayout dl = in;
   const size_t N = (size_t)n_nodes;
   const size_t o_parent = dl.take(N * 4), o_first = dl.take(N * 4), o_size = dl.take(N * 4), o_cursor = dl.take(N * 4), o_scan = dl.take(N * 8),
                o_part = dl.take(scan_part_items * 8 + 8), o_totals = dl.take(8), o_mid = dl.take((N / (VSM_TRACKS_WAVE_MAX + 1) + 1) * 4), o_out = dl.take(0);
   // the results' upper bounds: every node an observation, every node a track
   const size_t out_cap = al256(16) + al256((N + 1) * 4) + al256(N * 16) + al256((size_t)n_edges * 4) + al256(N);
-  const size_t need = o_out + out_cap;
-  if (need > T.dev_bytes) {
-    (void)hipStreamSynchronize(h->stream);
-    if (T.dev) vsm_dev_free(T.dev);
-    T.dev = nullptr;
-    T.dev_bytes = 0;
-    HIPCHK(vsm_dev_alloc((void **)&T.dev, need + need / 4));
-    T.dev_bytes = need + need / 4;
-  }
-  for (hipEvent_t &e : T.ev)
-    if (!e) HIPCHK(hipEventCreate(&e));
-  if (T.pin_out_bytes < 256) {
-    HIPCHK(hipHostMalloc((void **)&T.pin_out, 4096, hipHostMallocDefault));
-    T.pin_out_bytes = 4096;
-  }
+  HIPCHK(S.grow_dev(o_out + out_cap, h->stream));
+  HIPCHK(S.events());
+  HIPCHK(S.grow_out(8, h->stream, 4096));  // (the totals; the first block is a page)
   // a call that fails after something was enqueued: drain the device, report
   auto fail = [&](int rc) {
     (void)hipStreamSynchronize(h->stream);
     (void)hipGetLastError();
     return rc;
   };
-#define TRACKS_CHK(call)                                                           \
-  do {                                                                             \
-    const hipError_t e_ = (call);                                                  \
-    if (e_ != hipSuccess) {                                                        \
-      fprintf(stderr, "visomatch: %s failed: %s\n", #call, hipGetErrorString(e_)); \
-      return fail(VSM_EHIP);                                                       \
-    }                                                                              \
-  } while (0)
   TrkDevice d;
   memset(&d, 0, sizeof(d));
-  d.pair_base = (const int32_t *)(T.dev + o_pair_base);
-  d.pairs = (const int32_t *)(T.dev + o_pairs);
-  d.feat_base = (const int32_t *)(T.dev + o_feat_base);
-  d.edges = (const int32_t *)(T.dev + o_edges);
-  d.parent = (int32_t *)(T.dev + o_parent);
-  d.first = (int32_t *)(T.dev + o_first);
-  d.size = (int32_t *)(T.dev + o_size);
-  d.cursor = (int32_t *)(T.dev + o_cursor);
-  d.scan = (int32_t *)(T.dev + o_scan);
-  d.scan_part = (int32_t *)(T.dev + o_part);
-  d.totals = (int32_t *)(T.dev + o_totals);
-  d.mid_list = (int32_t *)(T.dev + o_mid);
-  d.counters = (int32_t *)(T.dev + o_out);
+  d.pair_base = (const int32_t *)(S.dev + o_pair_base);
+  d.pairs = (const int32_t *)(S.dev + o_pairs);
+  d.feat_base = (const int32_t *)(S.dev + o_feat_base);
+  d.edges = (const int32_t *)(S.dev + o_edges);
+  d.parent = (int32_t *)(S.dev + o_parent);
+  d.first = (int32_t *)(S.dev + o_first);
+  d.size = (int32_t *)(S.dev + o_size);
+  d.cursor = (int32_t *)(S.dev + o_cursor);
+  d.scan = (int32_t *)(S.dev + o_scan);
+  d.scan_part = (int32_t *)(S.dev + o_part);
+  d.totals = (int32_t *)(S.dev + o_totals);
+  d.mid_list = (int32_t *)(S.dev + o_mid);
+  d.counters = (int32_t *)(S.dev + o_out);
   d.n_nodes = n_nodes;
   d.n_edges = n_edges;
   d.n_pairs = n_pairs;
   d.n_frames = n_frames;
   d.min_length = min_length;
-  TRACKS_CHK(hipEventRecord(T.ev[0], h->stream));
-  TRACKS_CHK(hipMemcpyAsync(T.dev, T.pin_in, in.at, hipMemcpyHostToDevice, h->stream));
-  TRACKS_CHK(hipEventRecord(T.ev[1], h->stream));
+  VSM_CHK(hipEventRecord(S.ev[0], h->stream));
+  VSM_CHK(hipMemcpyAsync(S.dev, S.pin_in, in.at, hipMemcpyHostToDevice, h->stream));
+  VSM_CHK(hipEventRecord(S.ev[1], h->stream));
   vsm_tracks_launch_link(h->stream, h->prof, d);
-  TRACKS_CHK(hipGetLastError());
+  VSM_CHK(hipGetLastError());
   // the totals size the results: the one place where the host waits in the middle of the call
-  TRACKS_CHK(hipMemcpyAsync(T.pin_out, d.totals, 8, hipMemcpyDeviceToHost, h->stream));
-  TRACKS_CHK(hipStreamSynchronize(h->stream));
-  const int32_t n_tracks = ((int32_t *)T.pin_out)[0], n_obs = ((int32_t *)T.pin_out)[1];
+  VSM_CHK(hipMemcpyAsync(S.pin_out, d.totals, 8, hipMemcpyDeviceToHost, h->stream));
+  VSM_CHK(hipStreamSynchronize(h->stream));
+  const int32_t n_tracks = ((int32_t *)S.pin_out)[0], n_obs = ((int32_t *)S.pin_out)[1];
   if (n_tracks < 0 || n_tracks > n_nodes || n_obs < 0 || n_obs > n_nodes) return fail(VSM_EHIP);  // (cannot be: nothing is sized by it then)
-  TrkLayout ol;
+  VsmLayout ol;
   ol.at = o_out;
   const size_t r_counters = ol.take(16), r_offsets = ol.take(((size_t)n_tracks + 1) * 4), r_obs = ol.take((size_t)n_obs * 16),
                r_tom = ol.take((size_t)n_edges * 4), r_flags = ol.take((size_t)n_tracks);
-  d.offsets = (int32_t *)(T.dev + r_offsets);
-  d.obs = (int32_t *)(T.dev + r_obs);
-  d.track_of_match = (int32_t *)(T.dev + r_tom);
-  d.flags = (uint8_t *)(T.dev + r_flags);
+  d.offsets = (int32_t *)(S.dev + r_offsets);
+  d.obs = (int32_t *)(S.dev + r_obs);
+  d.track_of_match = (int32_t *)(S.dev + r_tom);
+  d.flags = (uint8_t *)(S.dev + r_flags);
   const size_t out_bytes = ol.at - o_out;
-  if (out_bytes > T.pin_out_bytes) {
-    (void)hipHostFree(T.pin_out);
-    T.pin_out = nullptr;
-    T.pin_out_bytes = 0;
-    TRACKS_CHK(hipHostMalloc((void **)&T.pin_out, out_bytes + out_bytes / 4, hipHostMallocDefault));
-    T.pin_out_bytes = out_bytes + out_bytes / 4;
-  }
+  VSM_CHK(S.grow_out(out_bytes, h->stream));
   vsm_tracks_launch_emit(h->stream, h->prof, d, n_tracks, n_obs);
-  TRACKS_CHK(hipGetLastError());
-  TRACKS_CHK(hipEventRecord(T.ev[2], h->stream));
-  TRACKS_CHK(hipMemcpyAsync(T.pin_out, T.dev + o_out, out_bytes, hipMemcpyDeviceToHost, h->stream));
-  TRACKS_CHK(hipStreamSynchronize(h->stream));
-  TRACKS_CHK(hipGetLastError());
+  VSM_CHK(hipGetLastError());
+  VSM_CHK(hipEventRecord(S.ev[2], h->stream));
+  VSM_CHK(hipMemcpyAsync(S.pin_out, S.dev + o_out, out_bytes, hipMemcpyDeviceToHost, h->stream));
+  VSM_CHK(hipStreamSynchronize(h->stream));
+  VSM_CHK(hipGetLastError());
   if (h->prof.on) h->prof.resolve();
   // ---- into the handle's vectors; the segments no workgroup took are ordered here ----
-  const uint8_t *out = T.pin_out;
+  const uint8_t *out = S.pin_out;
   const int32_t *r_off = (const int32_t *)(out + (r_offsets - o_out));
   T.offsets.assign(r_off, r_off + n_tracks + 1);
   const int32_t *r_rows = (const int32_t *)(out + (r_obs - o_out));
@@ -221,16 +173,17 @@ static int tracks_run(vsm_handle *h, int32_t n_frames, const int32_t *pairs, int
   T.stats[5] = by_block;
   T.stats[6] = by_host;
   float ms_up = 0, ms_k = 0;
-  (void)hipEventElapsedTime(&ms_up, T.ev[0], T.ev[1]);
-  (void)hipEventElapsedTime(&ms_k, T.ev[1], T.ev[2]);
+  (void)hipEventElapsedTime(&ms_up, S.ev[0], S.ev[1]);
+  (void)hipEventElapsedTime(&ms_k, S.ev[1], S.ev[2]);
   const double t2 = now_us();
   T.timings[1] = ms_up * 1e3;
   T.timings[2] = ms_k * 1e3;
   T.timings[3] = std::max(0.0, (t2 - t1) - T.timings[1] - T.timings[2]);
   T.have = true;
   return VSM_OK;
-#undef TRACKS_CHK
 }
+
+static const VsmTracks *tracks_result(vsm_handle *h) { return (h && h->tracks && h->tracks->have) ? h->tracks : nullptr; }
 
 extern "C" {
 
@@ -242,17 +195,12 @@ int vsm_tracks_run(vsm_handle *h, int32_t n_frames, const int32_t *pairs, int32_
 
 int vsm_pairs_tracks(vsm_handle *h, int32_t side, int32_t min_length) {
   if (!h) return VSM_EARG;
-  const VsmPairs *P = h->pairs;
-  if (!P || !P->done) return VSM_ENOTREADY;
+  std::vector<const vsm_p_match *> lists;
+  std::vector<int32_t> counts;
+  const VsmPairs *P = pairs_last_lists(h, lists, counts);
+  if (!P) return VSM_ENOTREADY;
   if (P->method == 1) return VSM_EARG;  // (stereo-only lists: tracks across time are not defined)
-  const int32_t n_pairs = (int32_t)P->lists.size();
-  std::vector<const vsm_p_match *> lists((size_t)n_pairs);
-  std::vector<int32_t> counts((size_t)n_pairs);
-  for (int32_t k = 0; k < n_pairs; k++) {
-    lists[k] = P->lists[k].data();
-    counts[k] = (int32_t)P->lists[k].size();
-  }
-  const int rc = tracks_run(h, P->n_frames, P->pair_list.data(), n_pairs, lists.data(), counts.data(), side, min_length);
+  const int rc = tracks_run(h, P->n_frames, P->pair_list.data(), (int32_t)lists.size(), lists.data(), counts.data(), side, min_length);
   if (rc == VSM_OK) h->tracks->from_pairs = true;
   return rc;
 }
@@ -277,16 +225,12 @@ int32_t vsm_tracks_of_matches(vsm_handle *h, int32_t pair, int32_t *out, int32_t
   return n;
 }
 void vsm_tracks_get_stats(vsm_handle *h, int64_t *out8) {
-  if (h && h->tracks && h->tracks->have)
-    memcpy(out8, h->tracks->stats, sizeof(h->tracks->stats));
-  else
-    memset(out8, 0, 8 * sizeof(int64_t));
+  const VsmTracks *T = tracks_result(h);
+  vsm_copy_or_zero(T ? &T->stats : nullptr, out8);
 }
 void vsm_tracks_get_timings(vsm_handle *h, double *out4) {
-  if (h && h->tracks && h->tracks->have)
-    memcpy(out4, h->tracks->timings, sizeof(h->tracks->timings));
-  else
-    memset(out4, 0, 4 * sizeof(double));
+  const VsmTracks *T = tracks_result(h);
+  vsm_copy_or_zero(T ? &T->timings : nullptr, out4);
 }
 
 }  // extern "C"

@@ -111,6 +111,16 @@ class VisoMatchError(RuntimeError):
     pass
 
 
+_RC_NAMES = {-2: " (VSM_ENOTREADY)", -4: " (VSM_EARG)"}  # include/visomatch.h
+
+
+def _check(rc, what):
+    """a library call's return value: an error code (negative) raises VisoMatchError, anything else is handed on"""
+    if rc < 0:
+        raise VisoMatchError(f"{what} failed with {rc}" + _RC_NAMES.get(rc, ""))
+    return rc
+
+
 _lib = None
 
 
@@ -581,14 +591,28 @@ class Tracks:
         return self.obs[self.offsets[t]:self.offsets[t + 1]]
 
 
-def _track_inputs(pairs, lists):
-    """(pairs [P,2] int32, the lists as contiguous P_MATCH arrays, their addresses, their counts)"""
-    pa = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+def _list_inputs(lists, counts=None):
+    """(the lists as contiguous P_MATCH arrays, their addresses, their counts); counts: override the lists' lengths"""
     ls = [None if l is None else np.ascontiguousarray(l, dtype=P_MATCH) for l in lists]
-    assert len(ls) == len(pa)
     ptrs = (C.c_void_p * max(len(ls), 1))(*[None if l is None or len(l) == 0 else l.ctypes.data for l in ls])
-    counts = np.array([0 if l is None else len(l) for l in ls], dtype=np.int32)
-    return pa, ls, ptrs, counts
+    if counts is None:
+        counts = [0 if l is None else len(l) for l in ls]
+    return ls, ptrs, np.ascontiguousarray(counts, dtype=np.int32)
+
+
+def _track_inputs(pairs, lists, counts=None):
+    """(pairs [P,2] int32, then what _list_inputs gives for the pairs' lists)"""
+    pa = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+    assert len(lists) == len(pa)
+    return (pa,) + _list_inputs(lists, counts)
+
+
+def _stage_dicts(handle, get_stats, stat_names, get_timings, timing_names):
+    """(stats, timings) of a stage's last result on a handle, as dicts under the given names"""
+    st, tm = np.zeros(len(stat_names), np.int64), np.zeros(len(timing_names), np.float64)
+    get_stats(handle, _ptr(st))
+    get_timings(handle, _ptr(tm))
+    return dict(zip(stat_names, st.tolist())), dict(zip(timing_names, tm.tolist()))
 
 
 def host_tracks(n_frames, pairs, lists, side=0, min_length=2, counts=None):
@@ -596,14 +620,10 @@ def host_tracks(n_frames, pairs, lists, side=0, min_length=2, counts=None):
     union-find on the host - no GPU.  counts: override the lists' lengths (argument tests).  Returns a Tracks object;
     raises VisoMatchError on VSM_EARG."""
     L = lib()
-    pa, ls, ptrs, cnt = _track_inputs(pairs, lists)
-    if counts is not None:
-        cnt = np.ascontiguousarray(counts, dtype=np.int32)
+    pa, ls, ptrs, cnt = _track_inputs(pairs, lists, counts)
     args = (int(n_frames), pa.ctypes.data_as(C.c_void_p), len(pa), ptrs, cnt.ctypes.data_as(C.c_void_p), int(side), int(min_length))
     n_obs = C.c_int32(0)
-    T = L.vsm_host_tracks(*args, None, None, None, None, C.byref(n_obs))
-    if T < 0:
-        raise VisoMatchError(f"vsm_host_tracks failed with {T}" + (" (VSM_EARG)" if T == Matcher.EARG else ""))
+    T = _check(L.vsm_host_tracks(*args, None, None, None, None, C.byref(n_obs)), "vsm_host_tracks")
     offsets, obs, flags = np.zeros(T + 1, np.int32), np.zeros((n_obs.value, 4), np.int32), np.zeros(T, np.uint8)
     tom = np.zeros(int(cnt.sum()), np.int32)
     got = L.vsm_host_tracks(*args, offsets.ctypes.data_as(C.c_void_p), obs.ctypes.data_as(C.c_void_p), flags.ctypes.data_as(C.c_void_p),
@@ -661,17 +681,13 @@ class Motions:
 def host_pairs_motions(lists, params, bucket=False, threads=1, counts=None):
     """vsm_host_pairs_motions: every list's mono motion on `threads` host threads - no GPU.  counts: override the lists'
     lengths (argument tests).  Returns a Motions object; raises VisoMatchError on VSM_EARG."""
-    _, ls, ptrs, cnt = _track_inputs(np.zeros((len(lists), 2), np.int32), lists)
-    if counts is not None:
-        cnt = np.ascontiguousarray(counts, dtype=np.int32)
+    ls, ptrs, cnt = _list_inputs(lists, counts)
     P, tot = len(ls), int(np.clip(cnt, 0, None).sum())
     rc, stage, n_inl, n_m = (np.zeros(P, np.int32) for _ in range(4))
     tr, T = np.zeros((P, 6)), np.zeros((P, 4, 4))
     inl, mm = np.zeros(max(tot, 1), np.int32), np.zeros(max(tot, 1), P_MATCH)
-    got = lib().vsm_host_pairs_motions(None if params is None else C.byref(params), P, ptrs, _ptr(cnt), int(bool(bucket)), int(threads), _ptr(rc), _ptr(stage),
-                                       _ptr(tr), _ptr(T), _ptr(n_inl), _ptr(inl), _ptr(n_m), _ptr(mm))
-    if got < 0:
-        raise VisoMatchError(f"vsm_host_pairs_motions failed with {got}" + (" (VSM_EARG)" if got == Matcher.EARG else ""))
+    _check(lib().vsm_host_pairs_motions(None if params is None else C.byref(params), P, ptrs, _ptr(cnt), int(bool(bucket)), int(threads), _ptr(rc), _ptr(stage),
+                                        _ptr(tr), _ptr(T), _ptr(n_inl), _ptr(inl), _ptr(n_m), _ptr(mm)), "vsm_host_pairs_motions")
     off = np.concatenate([[0], np.cumsum(cnt)])
     st = np.bincount(stage, minlength=len(MOTION_STAGES))
     return Motions(rc, stage, tr, T, [inl[off[k]:off[k] + n_inl[k]].copy() for k in range(P)], [mm[off[k]:off[k] + n_m[k]].copy() for k in range(P)],
@@ -687,9 +703,7 @@ def chain_poses(n_frames, pairs, T, rc, root=0):
     assert r.shape == (len(pa),)
     n = max(int(n_frames), 0)
     poses, valid = np.zeros((n, 12)), np.zeros(n, np.uint8)
-    got = lib().vsm_chain_poses(int(n_frames), _ptr(pa), len(pa), _ptr(t), _ptr(r), int(root), _ptr(poses), _ptr(valid))
-    if got < 0:
-        raise VisoMatchError(f"vsm_chain_poses failed with {got}" + (" (VSM_EARG)" if got == Matcher.EARG else ""))
+    got = _check(lib().vsm_chain_poses(int(n_frames), _ptr(pa), len(pa), _ptr(t), _ptr(r), int(root), _ptr(poses), _ptr(valid)), "vsm_chain_poses")
     return poses, valid, got
 
 
@@ -744,10 +758,8 @@ def host_triangulate(poses, f, cu, cv, offsets, obs_frames, uv, flags=None, pose
     po, pv, off, fr, px, fl = _triangulate_inputs(poses, pose_valid, offsets, obs_frames, uv, flags)
     T = max(len(off) - 1, 0) if n_tracks is None else int(n_tracks)
     out = _points_arrays(max(T, 0))
-    got = lib().vsm_host_triangulate(len(po), _ptr(po), _ptr(pv), float(f), float(cu), float(cv), T, _ptr(off), _ptr(fr), _ptr(px), _ptr(fl),
-                                     C.byref(_as_params(params)), *[_ptr(a) for a in out])
-    if got < 0:
-        raise VisoMatchError(f"vsm_host_triangulate failed with {got}" + (" (VSM_EARG)" if got == Matcher.EARG else ""))
+    got = _check(lib().vsm_host_triangulate(len(po), _ptr(po), _ptr(pv), float(f), float(cu), float(cv), T, _ptr(off), _ptr(fr), _ptr(px), _ptr(fl),
+                                            C.byref(_as_params(params)), *[_ptr(a) for a in out]), "vsm_host_triangulate")
     assert got == T
     return Points(*out)
 
@@ -806,9 +818,7 @@ def _order_behind_torch(handle, *tensors):
     whatever torch's current stream holds (the kernels or copies that produce the tensors) - vsm_wait_for_stream"""
     import torch
     dev = tensors[0].device
-    rc = lib().vsm_wait_for_stream(handle, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != 0:
-        raise VisoMatchError(f"vsm_wait_for_stream failed with {rc}")
+    _check(lib().vsm_wait_for_stream(handle, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "vsm_wait_for_stream")
 
 
 def _is_torch(x):
@@ -879,9 +889,7 @@ class Matcher:
             t = np.ascontiguousarray(np.asarray(Tr_delta, dtype=np.float64).reshape(-1)[:12])
             tp = t.ctypes.data_as(C.c_void_p)
         rc = lib().vsm_match(self.h, method, tp)
-        if rc not in (self.OK, self.ENOTREADY):
-            raise VisoMatchError(f"vsm_match failed with {rc}")
-        return rc
+        return rc if rc == self.ENOTREADY else _check(rc, "vsm_match")
 
     def get_matches(self):
         n = lib().vsm_num_matches(self.h)
@@ -991,9 +999,7 @@ class Matcher:
             if Tr_valid is not None:
                 v = np.ascontiguousarray(np.asarray(Tr_valid).astype(np.uint8))
                 vp_ = v.ctypes.data_as(C.c_void_p)
-        rc = L.vsm_sequence_run(self.h, pl, pr, fs, dev, F, w, h, bpl, method, tp, vp_)
-        if rc != self.OK:
-            raise VisoMatchError(f"vsm_sequence_run failed with {rc}")
+        _check(L.vsm_sequence_run(self.h, pl, pr, fs, dev, F, w, h, bpl, method, tp, vp_), "vsm_sequence_run")
         return [self.sequence_matches(f) for f in range(F)] if fetch else None
 
     def sequence_matches(self, f):
@@ -1045,9 +1051,7 @@ class Matcher:
                 v = np.ascontiguousarray(np.asarray(Tr_valid).astype(np.uint8))
                 assert v.shape == (P,)
                 vp_ = v.ctypes.data_as(C.c_void_p)
-        rc = L.vsm_pairs_run(self.h, pl, pr, fs, dev, F, w, h, bpl, method, pa.ctypes.data_as(C.c_void_p), P, tp, vp_)
-        if rc != self.OK:
-            raise VisoMatchError(f"vsm_pairs_run failed with {rc}" + (" (VSM_EARG)" if rc == self.EARG else ""))
+        _check(L.vsm_pairs_run(self.h, pl, pr, fs, dev, F, w, h, bpl, method, pa.ctypes.data_as(C.c_void_p), P, tp, vp_), "vsm_pairs_run")
         self._n_pairs, self._pairs_frames = P, F
         return [self.pair_matches(k) for k in range(P)] if fetch else None
 
@@ -1062,9 +1066,7 @@ class Matcher:
     # --- feature tracks from pair match lists --------------------------------------------------
     def _tracks_result(self, rc, what, n_pairs):
         L = lib()
-        if rc != self.OK:
-            names = {self.EARG: " (VSM_EARG)", self.ENOTREADY: " (VSM_ENOTREADY)"}
-            raise VisoMatchError(f"{what} failed with {rc}" + names.get(rc, ""))
+        _check(rc, what)
         T, n_obs = L.vsm_tracks_count(self.h), L.vsm_tracks_num_obs(self.h)
         offsets, obs, flags = np.zeros(T + 1, np.int32), np.zeros((n_obs, 4), np.int32), np.zeros(T, np.uint8)
         L.vsm_tracks_get(self.h, offsets.ctypes.data_as(C.c_void_p), obs.ctypes.data_as(C.c_void_p), flags.ctypes.data_as(C.c_void_p))
@@ -1075,10 +1077,7 @@ class Matcher:
             if n:
                 L.vsm_tracks_of_matches(self.h, k, a.ctypes.data_as(C.c_void_p), n)
             of_pairs.append(a)
-        st, tm = np.zeros(8, np.int64), np.zeros(4, np.float64)
-        L.vsm_tracks_get_stats(self.h, st.ctypes.data_as(C.c_void_p))
-        L.vsm_tracks_get_timings(self.h, tm.ctypes.data_as(C.c_void_p))
-        return Tracks(offsets, obs, flags, of_pairs, dict(zip(TRACK_STATS, st.tolist())), dict(zip(TRACK_TIMINGS, tm.tolist())))
+        return Tracks(offsets, obs, flags, of_pairs, *_stage_dicts(self.h, L.vsm_tracks_get_stats, TRACK_STATS, L.vsm_tracks_get_timings, TRACK_TIMINGS))
 
     def tracks(self, n_frames, pairs, lists, side=0, min_length=2):
         """vsm_tracks_run: the connected components of the match lists `lists` (one P_MATCH array per (previous, current)
@@ -1100,15 +1099,10 @@ class Matcher:
     # --- tracks into 3-D points -------------------------------------------------------------------
     def _points_result(self, rc, what):
         L = lib()
-        if rc != self.OK:
-            names = {self.EARG: " (VSM_EARG)", self.ENOTREADY: " (VSM_ENOTREADY)"}
-            raise VisoMatchError(f"{what} failed with {rc}" + names.get(rc, ""))
+        _check(rc, what)
         out = _points_arrays(L.vsm_points_count(self.h))
         L.vsm_points_get(self.h, *[_ptr(a) for a in out])
-        st, tm = np.zeros(10, np.int64), np.zeros(4, np.float64)
-        L.vsm_points_get_stats(self.h, _ptr(st))
-        L.vsm_points_get_timings(self.h, _ptr(tm))
-        return Points(*out, dict(zip(POINT_STATUS, st.tolist())), dict(zip(POINT_TIMINGS, tm.tolist())))
+        return Points(*out, *_stage_dicts(self.h, L.vsm_points_get_stats, POINT_STATUS, L.vsm_points_get_timings, POINT_TIMINGS))
 
     def triangulate(self, poses, f, cu, cv, offsets, obs_frames, uv, flags=None, pose_valid=None, params=None, n_tracks=None):
         """vsm_triangulate_run: the 3-D point of every track, on the device.  poses [F, 12] (or [F, 3, 4] / [F, 4, 4]) camera to
@@ -1127,18 +1121,14 @@ class Matcher:
         po, pv = _pose_inputs(poses, pose_valid, self._track_frames)  # (the library reads one pose per frame of the track call)
         ptrs = cnt = None
         if lists is not None:
-            _, ls, ptrs, cnt = _track_inputs(np.zeros((len(lists), 2), np.int32), lists)
-            if counts is not None:
-                cnt = np.ascontiguousarray(counts, dtype=np.int32)
+            ls, ptrs, cnt = _list_inputs(lists, counts)
         rc = lib().vsm_tracks_triangulate(self.h, ptrs, _ptr(cnt), _ptr(po), _ptr(pv), float(f), float(cu), float(cv), C.byref(_as_params(params)))
         return self._points_result(rc, "vsm_tracks_triangulate")
 
     # --- monocular motions of a pair set ---------------------------------------------------------
     def _motions_result(self, rc, what):
         L = lib()
-        if rc != self.OK:
-            names = {self.EARG: " (VSM_EARG)", self.ENOTREADY: " (VSM_ENOTREADY)"}
-            raise VisoMatchError(f"{what} failed with {rc}" + names.get(rc, ""))
+        _check(rc, what)
         P = L.vsm_motions_count(self.h)
         r, stage, n_inl = np.zeros(P, np.int32), np.zeros(P, np.int32), np.zeros(P, np.int32)
         tr, T = np.zeros((P, 6)), np.zeros((P, 4, 4))
@@ -1153,19 +1143,14 @@ class Matcher:
             if len(m):
                 L.vsm_motions_matches(self.h, k, _ptr(m), len(m))
             mm.append(m)
-        st, tm = np.zeros(len(MOTION_STATS), np.int64), np.zeros(6, np.float64)
-        L.vsm_motions_get_stats(self.h, _ptr(st))
-        L.vsm_motions_get_timings(self.h, _ptr(tm))
-        stats = dict(zip(MOTION_STATS, st.tolist()))
+        stats, timings = _stage_dicts(self.h, L.vsm_motions_get_stats, MOTION_STATS, L.vsm_motions_get_timings, MOTION_TIMINGS)
         stats["device_svd"] = L.vsm_motions_device_svd(self.h)
-        return Motions(r, stage, tr, T, inl, mm, stats, dict(zip(MOTION_TIMINGS, tm.tolist())))
+        return Motions(r, stage, tr, T, inl, mm, stats, timings)
 
     def motions(self, lists, params, bucket=False, counts=None):
         """vsm_motions_run: the mono motion of every list (one P_MATCH array of flow matches per pair) in one batched call on
         the device.  params: vo_mono_params(...).  Returns a Motions object."""
-        _, ls, ptrs, cnt = _track_inputs(np.zeros((len(lists), 2), np.int32), lists)
-        if counts is not None:
-            cnt = np.ascontiguousarray(counts, dtype=np.int32)
+        ls, ptrs, cnt = _list_inputs(lists, counts)
         rc = lib().vsm_motions_run(self.h, None if params is None else C.byref(params), len(ls), ptrs, _ptr(cnt), int(bool(bucket)))
         return self._motions_result(rc, "vsm_motions_run")
 
@@ -1273,8 +1258,7 @@ class MultiVisualOdometryStereo:
             K, h, w = left.shape
             rc = L.vsm_multi_process(self.h, left.ctypes.data_as(C.c_void_p), right.ctypes.data_as(C.c_void_p), w * h, 0, w, h, w,
                                      ok.ctypes.data_as(C.c_void_p))
-        if rc != 0:
-            raise VisoMatchError(f"vsm_multi_process failed with {rc}")
+        _check(rc, "vsm_multi_process")
         return ok.astype(bool)
 
     def get_motion(self, k):
