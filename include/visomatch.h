@@ -456,6 +456,28 @@ int32_t vsm_debug_chunk_jobs(int32_t method, int32_t multi_stage, int32_t sides,
  * chunk's longest query lists.  Returns the number of chunks, or -1 on an argument vsm_pairs_run rejects. */
 int32_t vsm_debug_pair_jobs(int32_t method, int32_t multi_stage, int32_t sides, int32_t n_frames, const int32_t *counts, const int32_t *pairs,
                             int32_t n_pairs, int32_t chunk, const uint8_t *tr_valid, int32_t *pairs_out, int32_t *max_nq_out);
+/* Test hooks of the refinement kernels (Matcher::refinement, viso/matcher.cpp:1498-1585) on match lists of the caller.
+ * vsm_debug_refine: P pass-2 lists (1 <= P <= 64; lists[k] holds counts[k] matches) as the P pairs of ONE launch, every pair
+ * on the handle's current frames as vsm_push_back left them (no vsm_match needed; mono frames serve method 0) through a job
+ * table: the relocation (refinement = 1) or the 7 x 7 costs and, always on the device, the fits and the removal of failed
+ * matches (refinement = 2), with the handle's refinement and half_resolution.  out[k] (room for counts[k] matches) gets pair
+ * k's refined list, out_counts[k] its length.  The handle's last match result (matches, stages) is invalidated.
+ * The kernels read around (u1c, v1c) unguarded, so VSM_EARG - before anything is launched, the handle still usable - for: a
+ * coordinate that is not finite, a u1c / v1c that is not integer-valued or lies outside [6, w - 7] x [6, h - 7], a count
+ * above 16384 or below 0, P outside 1..64, a method outside 0..2, refinement = 0.  The other coordinates may be any finite
+ * float (the kernels' margin tests guard them).  VSM_ENOTREADY: the frames the method needs have not been pushed.
+ * vsm_debug_refine_check: the list checks alone for frames of w x h pixels (pure arithmetic, no GPU): VSM_OK or VSM_EARG.
+ * vsm_debug_parabolic_apply: no images, no handle - k_parabolic_apply over P pairs on the caller's lists and the caller's
+ * records[k][counts[k]][3][12] = {status (0 failed, 1 fit, 2 step not applicable), du, dv, c0..c8}; outputs as above.
+ * VSM_EARG for a count above 16384 (the kernel would truncate the list) or below 0, P outside 1..64, a NULL argument.
+ * vsm_host_parabolic_fits: the host's least-squares tail of the fit (no GPU) on n records [12] = {-, du, dv, c0..c8}:
+ * uv[i][2] is updated where the fit succeeds, ok[i] = 1 / 0; returns n, or VSM_EARG. */
+int32_t vsm_debug_refine(vsm_handle *h, int32_t method, const vsm_p_match *const *lists, const int32_t *counts, int32_t P,
+                         vsm_p_match *const *out, int32_t *out_counts);
+int32_t vsm_debug_refine_check(int32_t w, int32_t h, const vsm_p_match *const *lists, const int32_t *counts, int32_t P);
+int32_t vsm_debug_parabolic_apply(const vsm_p_match *const *lists, const int32_t *const *records, const int32_t *counts, int32_t P,
+                                  vsm_p_match *const *out, int32_t *out_counts);
+int32_t vsm_host_parabolic_fits(const int32_t *records, int32_t n, float *uv, int32_t *ok);
 
 /* ---- stereo visual odometry on top of the matcher ----
  * class VisualOdometryStereo, viso/viso_stereo.h:28-88 + viso/viso.h:28-131: process() =

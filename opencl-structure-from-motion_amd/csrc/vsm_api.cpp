@@ -2024,6 +2024,176 @@ int32_t vsm_debug_dc2(const vsm_params *p, const vsm_p_match *list, int32_t n, i
   return result;
 }
 
+// ---- test hooks of the refinement kernels (k_refine<TILED>, k_parabolic_costs, k_parabolic_apply) on lists of the caller ----
+#define VSM_DEBUG_REFINE_MAX_PAIRS 64
+
+// The refinement reads 5 x 5 bytes around (u1c, v1c) unguarded and converts the point to int: every reference point must be a
+// pixel inside the margin.  The targets only have to be finite (the kernels' own margin tests guard them; the conversion of
+// a float they let through is defined).  Pure arithmetic: the CPU suite calls it (vsm_debug_refine_check).
+static int refine_lists_check(int32_t w, int32_t hh, const vsm_p_match *const *lists, const int32_t *counts, int32_t P) {
+  if (P < 1 || P > VSM_DEBUG_REFINE_MAX_PAIRS || !lists || !counts) return VSM_EARG;
+  if (w < 2 * VSM_MARGIN + 1 || hh < 2 * VSM_MARGIN + 1) return VSM_EARG;
+  const float u_lo = (float)VSM_MARGIN, u_hi = (float)(w - 1 - VSM_MARGIN), v_hi = (float)(hh - 1 - VSM_MARGIN);
+  for (int32_t k = 0; k < P; k++) {
+    if (counts[k] < 0 || counts[k] > VSM_PARA_MAX_LIST || (counts[k] > 0 && !lists[k])) return VSM_EARG;
+    for (int32_t i = 0; i < counts[k]; i++) {
+      const vsm_p_match &m = lists[k][i];
+      const float xy[8] = {m.u1p, m.v1p, m.u2p, m.v2p, m.u1c, m.v1c, m.u2c, m.v2c};
+      for (float x : xy)
+        if (!std::isfinite(x)) return VSM_EARG;
+      if (!(m.u1c >= u_lo && m.u1c <= u_hi && m.v1c >= u_lo && m.v1c <= v_hi)) return VSM_EARG;
+      if (m.u1c != floorf(m.u1c) || m.v1c != floorf(m.v1c)) return VSM_EARG;
+    }
+  }
+  return VSM_OK;
+}
+
+// P caller-given pass-2 lists as the P pairs of one launch: per pair list2, raw, (records) and the counts in one device
+// block, the pair table, and a job table whose entries all name the same frames
+struct DebugPairs {
+  uint8_t *block = nullptr;
+  VsmPair *d_pairs = nullptr;
+  VsmJob *d_jobs = nullptr;
+  std::vector<VsmPair> pairs;
+  ~DebugPairs() {
+    if (block) (void)hipFree(block);
+  }
+  hipError_t create(hipStream_t s, const vsm_p_match *const *lists, const int32_t *const *records, const int32_t *counts, int32_t P, bool with_pf,
+                    const VsmJob &job) {
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+      const size_t o = off;
+      off += al256(bytes);
+      return o;
+    };
+    struct Off {
+      size_t l2, raw, pf, cnt;
+    };
+    std::vector<Off> po(P);
+    for (int32_t k = 0; k < P; k++) {
+      const size_t cap = (size_t)std::max(counts[k], 1);
+      po[k].l2 = take(cap * sizeof(vsm_p_match));
+      po[k].raw = take(cap * sizeof(vsm_p_match));
+      po[k].pf = with_pf ? take(cap * 36 * sizeof(int32_t)) : 0;
+      po[k].cnt = take(4 * sizeof(int32_t));
+    }
+    const size_t o_pairs = take((size_t)P * sizeof(VsmPair)), o_jobs = take((size_t)P * sizeof(VsmJob));
+    hipError_t e = hipMalloc((void **)&block, off);
+    if (e != hipSuccess) return e;
+    if ((e = hipMemsetAsync(block, 0, off, s)) != hipSuccess) return e;
+    pairs.assign(P, VsmPair());
+    std::vector<VsmJob> jobs(P, job);
+    std::vector<int32_t> cnt((size_t)P * 2, 0);  // (sources of asynchronous copies: alive until the synchronisation below)
+    for (int32_t k = 0; k < P; k++) {
+      VsmPair &pr = pairs[k];
+      memset(&pr, 0, sizeof(pr));
+      pr.list2 = (vsm_p_match *)(block + po[k].l2);
+      pr.raw = (vsm_p_match *)(block + po[k].raw);
+      pr.pf = with_pf ? (int32_t *)(block + po[k].pf) : nullptr;
+      pr.count = (int32_t *)(block + po[k].cnt);
+      pr.hcount = pr.count + 2;  // (no host-mapped twin here: the tail's second count goes beside the first)
+      cnt[2 * k + 1] = counts[k];
+      if ((e = hipMemcpyAsync(pr.count, &cnt[2 * k], 2 * sizeof(int32_t), hipMemcpyHostToDevice, s)) != hipSuccess) return e;
+      if (counts[k] > 0 && (e = hipMemcpyAsync(pr.list2, lists[k], (size_t)counts[k] * sizeof(vsm_p_match), hipMemcpyHostToDevice, s)) != hipSuccess)
+        return e;
+      if (counts[k] > 0 && records &&
+          (e = hipMemcpyAsync(pr.pf, records[k], (size_t)counts[k] * 36 * sizeof(int32_t), hipMemcpyHostToDevice, s)) != hipSuccess)
+        return e;
+    }
+    d_pairs = (VsmPair *)(block + o_pairs);
+    d_jobs = (VsmJob *)(block + o_jobs);
+    if ((e = hipMemcpyAsync(d_pairs, pairs.data(), (size_t)P * sizeof(VsmPair), hipMemcpyHostToDevice, s)) != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(d_jobs, jobs.data(), (size_t)P * sizeof(VsmJob), hipMemcpyHostToDevice, s)) != hipSuccess) return e;
+    return hipStreamSynchronize(s);  // (the sources are the caller's and this function's pageable memory)
+  }
+  // the lists as the kernels left them; shorter: the tail of refinement == 2 has rewritten the counts
+  hipError_t fetch(const int32_t *counts, int32_t P, bool shorter, vsm_p_match *const *out, int32_t *out_counts) {
+    for (int32_t k = 0; k < P; k++) {
+      int32_t n = counts[k];
+      if (shorter) {
+        int32_t cnt[4] = {0, 0, 0, 0};
+        const hipError_t e = hipMemcpy(cnt, pairs[k].count, sizeof(cnt), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return e;
+        if (cnt[1] < 0 || cnt[1] > counts[k] || cnt[3] != cnt[1]) return hipErrorUnknown;
+        n = cnt[1];
+      }
+      out_counts[k] = n;
+      if (n > 0) {
+        const hipError_t e = hipMemcpy(out[k], pairs[k].list2, (size_t)n * sizeof(vsm_p_match), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return e;
+      }
+    }
+    return hipSuccess;
+  }
+};
+
+int32_t vsm_debug_refine_check(int32_t w, int32_t hh, const vsm_p_match *const *lists, const int32_t *counts, int32_t P) {
+  return refine_lists_check(w, hh, lists, counts, P);
+}
+
+int32_t vsm_debug_refine(vsm_handle *h, int32_t method, const vsm_p_match *const *lists, const int32_t *counts, int32_t P,
+                         vsm_p_match *const *out, int32_t *out_counts) {
+  if (!h || method < 0 || method > 2 || !out || !out_counts) return VSM_EARG;
+  VsmCtx &c = h->ring;
+  if (!c.ready) return VSM_ENOTREADY;
+  const vsm_params &p = h->param;
+  if (p.refinement != 1 && p.refinement != 2) return VSM_EARG;
+  {
+    const int rc = refine_lists_check(c.dims.w, c.dims.h, lists, counts, P);
+    if (rc != VSM_OK) return rc;
+  }
+  HIPCHK(hipSetDevice(h->device));
+  {
+    const int rc = settle(h);
+    if (rc != VSM_OK) return rc;
+  }
+  const int sc = h->cur, sp = h->cur ^ 1;
+  if (!h->have[sc] || (method != 1 && !h->have[sp]) || (method != 0 && !h->right[sc]) || (method == 2 && !h->right[sp])) return VSM_ENOTREADY;
+  for (int s = 0; s < 5; s++) h->stage[s].clear();
+  h->stage3_in_hm = false;
+  h->matched.clear();
+  VsmJob job;
+  memset(&job, 0, sizeof(job));
+  job.img_prev = (method == 1 ? sc : sp) * 2;  // (as in vsm_match)
+  job.img_curr = sc * 2;
+  int32_t n_upper = 0;
+  for (int32_t k = 0; k < P; k++) n_upper = std::max(n_upper, counts[k]);
+  DebugPairs D;
+  HIPCHK(D.create(h->stream, lists, nullptr, counts, P, p.refinement == 2, job));
+  vsm_launch_refine(h->stream, h->prof, c.d_imgs, D.d_pairs, D.d_jobs, job, P, c.dims, c.dims, method, p.refinement, n_upper);
+  if (p.refinement == 2) vsm_launch_parabolic_apply(h->stream, h->prof, D.d_pairs, P);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(h->stream));
+  h->prof.resolve();
+  HIPCHK(D.fetch(counts, P, p.refinement == 2, out, out_counts));
+  return VSM_OK;
+}
+
+int32_t vsm_debug_parabolic_apply(const vsm_p_match *const *lists, const int32_t *const *records, const int32_t *counts, int32_t P,
+                                  vsm_p_match *const *out, int32_t *out_counts) {
+  if (P < 1 || P > VSM_DEBUG_REFINE_MAX_PAIRS || !lists || !records || !counts || !out || !out_counts) return VSM_EARG;
+  for (int32_t k = 0; k < P; k++)
+    if (counts[k] < 0 || counts[k] > VSM_PARA_MAX_LIST || (counts[k] > 0 && (!lists[k] || !records[k]))) return VSM_EARG;
+  VsmJob job;
+  memset(&job, 0, sizeof(job));
+  DebugPairs D;
+  HIPCHK(D.create(nullptr, lists, records, counts, P, true, job));
+  vsm_launch_parabolic_apply(nullptr, g_no_prof, D.d_pairs, P);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(D.fetch(counts, P, true, out, out_counts));
+  return VSM_OK;
+}
+
+int32_t vsm_host_parabolic_fits(const int32_t *records, int32_t n, float *uv, int32_t *ok) {
+  if (n < 0 || (n > 0 && (!records || !uv || !ok))) return VSM_EARG;
+  for (int32_t i = 0; i < n; i++) {
+    const int32_t *r = records + (size_t)i * 12;
+    ok[i] = vsm_host_parabolic_update(r + 3, r[1], r[2], uv[2 * i], uv[2 * i + 1]) ? 1 : 0;
+  }
+  return n;
+}
+
 void vsm_get_counters(vsm_handle *h, int64_t *out5) { memcpy(out5, h->counters, sizeof(h->counters)); }
 void vsm_get_timings(vsm_handle *h, double *out5) { memcpy(out5, h->timings, sizeof(h->timings)); }
 

@@ -37,7 +37,7 @@ EXPORTS = ["vsm_default_params", "vsm_create", "vsm_destroy", "vsm_set_intrinsic
            "vsm_num_features", "vsm_get_features", "vsm_set_stage_capture", "vsm_stage_size", "vsm_stage_get",
            "vsm_num_ranges", "vsm_get_ranges", "vsm_get_gradients", "vsm_get_filter_responses", "vsm_get_counters",
            "vsm_get_timings", "vsm_set_profiling", "vsm_num_kernels", "vsm_kernel_name", "vsm_get_kernel_stats",
-           "vsm_host_delaunay", "vsm_host_delaunay_split", "vsm_debug_delaunay_gpu", "vsm_debug_dc_bench", "vsm_host_ties", "vsm_debug_ties_gpu", "vsm_host_outliers_and_prior", "vsm_host_outliers_and_prior_threads", "vsm_debug_dc2", "vsm_debug_dc2_band_factor", "vsm_debug_predicates", "vsm_debug_seq_plan", "vsm_debug_chunk_jobs", "vsm_debug_pair_jobs", "vsm_local_cpus", "vsm_forkjoin_cpus", "vsm_device_pool_stats", "vsm_device_pool_trim", "vsm_sequence_run", "vsm_sequence_num_matches", "vsm_sequence_get_matches",
+           "vsm_host_delaunay", "vsm_host_delaunay_split", "vsm_debug_delaunay_gpu", "vsm_debug_dc_bench", "vsm_host_ties", "vsm_debug_ties_gpu", "vsm_host_outliers_and_prior", "vsm_host_outliers_and_prior_threads", "vsm_debug_dc2", "vsm_debug_dc2_band_factor", "vsm_debug_predicates", "vsm_debug_seq_plan", "vsm_debug_chunk_jobs", "vsm_debug_pair_jobs", "vsm_debug_refine", "vsm_debug_refine_check", "vsm_debug_parabolic_apply", "vsm_host_parabolic_fits", "vsm_local_cpus", "vsm_forkjoin_cpus", "vsm_device_pool_stats", "vsm_device_pool_trim", "vsm_sequence_run", "vsm_sequence_num_matches", "vsm_sequence_get_matches",
            "vsm_sequence_get_timings", "vsm_sequence_path", "vsm_pairs_run", "vsm_pairs_num_matches", "vsm_pairs_get_matches", "vsm_pairs_get_timings",
            "vsm_tracks_run", "vsm_pairs_tracks", "vsm_tracks_count", "vsm_tracks_num_obs", "vsm_tracks_get", "vsm_tracks_of_matches",
            "vsm_tracks_get_stats", "vsm_tracks_get_timings", "vsm_host_tracks",
@@ -187,6 +187,10 @@ def lib():
         L.vsm_debug_chunk_jobs.argtypes = [i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp]
         L.vsm_debug_pair_jobs.restype = i32
         L.vsm_debug_pair_jobs.argtypes = [i32, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp]
+        L.vsm_debug_refine.argtypes = [vp, i32, vp, vp, i32, vp, vp]
+        L.vsm_debug_refine_check.argtypes = [i32, i32, vp, vp, i32]
+        L.vsm_debug_parabolic_apply.argtypes = [vp, vp, vp, i32, vp, vp]
+        L.vsm_host_parabolic_fits.argtypes = [vp, i32, vp, vp]
         L.vsm_pairs_run.argtypes = [vp, vp, vp, C.c_int64, C.c_int, i32, i32, i32, i32, i32, vp, i32, vp, vp]
         L.vsm_pairs_num_matches.argtypes = [vp, i32]
         L.vsm_pairs_get_matches.argtypes = [vp, i32, vp, i32]
@@ -791,6 +795,53 @@ def remove_outliers(matches, method, w, h, gpu=False, gpu_ties=False, copies=1, 
     return out[:k].copy(), rg, us.value
 
 
+def _refine_inputs(lists):
+    """P match lists -> (the arrays, their lengths, the pointer table the library takes)"""
+    ms = [np.ascontiguousarray(m, dtype=P_MATCH) for m in lists]
+    cnt = np.array([len(m) for m in ms], dtype=np.int32)
+    return ms, cnt, (C.c_void_p * max(len(ms), 1))(*[m.ctypes.data if len(m) else None for m in ms])
+
+
+def _refine_outputs(counts):
+    outs = [np.zeros(max(int(n), 0), dtype=P_MATCH) for n in counts]
+    return outs, np.full(len(outs), -1, dtype=np.int32), (C.c_void_p * max(len(outs), 1))(*[o.ctypes.data if len(o) else None for o in outs])
+
+
+def refine_check(w, h, lists, counts=None):
+    """test hook: the list checks of Matcher.refine_lists for frames of w x h pixels, host arithmetic only -> the return code
+    (0, or Matcher.EARG); counts: the lengths handed to the library instead of the lists' own"""
+    ms, cnt, ptrs = _refine_inputs(lists)
+    if counts is not None:
+        cnt = np.ascontiguousarray(counts, dtype=np.int32)
+    return lib().vsm_debug_refine_check(int(w), int(h), ptrs, _ptr(cnt), len(ms))
+
+
+def device_parabolic_apply(lists, records, counts=None):
+    """test hook: k_parabolic_apply alone over len(lists) pairs in one launch.  lists[k]: n_k matches, records[k]:
+    [n_k, 3, 12] int32 {status, du, dv, c0..c8} per relocation step -> the lists after the fits, failed matches removed.
+    counts: the lengths handed to the library instead of the lists' own (argument checks)."""
+    ms, cnt, ptrs = _refine_inputs(lists)
+    rs = [np.ascontiguousarray(r, dtype=np.int32).reshape(-1, 3, 12) for r in records]
+    assert len(rs) == len(ms) and all(len(r) == len(m) for r, m in zip(rs, ms))
+    rptrs = (C.c_void_p * max(len(rs), 1))(*[r.ctypes.data if len(r) else None for r in rs])
+    if counts is not None:
+        cnt = np.ascontiguousarray(counts, dtype=np.int32)
+    outs, oc, optrs = _refine_outputs([len(m) for m in ms])
+    _check(lib().vsm_debug_parabolic_apply(ptrs, rptrs, _ptr(cnt), len(ms), optrs, _ptr(oc)), "vsm_debug_parabolic_apply")
+    return [o[:n].copy() for o, n in zip(outs, oc)]
+
+
+def host_parabolic_fits(records, uv):
+    """the host's least-squares tail of the sub-pixel fit (vsm_host_parabolic_update, no GPU) on records [n, 12] int32
+    {-, du, dv, c0..c8} and targets uv [n, 2] float32 -> (uv after the fits, ok [n])"""
+    r = np.ascontiguousarray(records, dtype=np.int32).reshape(-1, 12)
+    out = np.array(uv, dtype=np.float32).reshape(-1, 2).copy()
+    assert len(out) == len(r)
+    ok = np.zeros(len(r), dtype=np.int32)
+    _check(lib().vsm_host_parabolic_fits(_ptr(r), len(r), _ptr(out), _ptr(ok)), "vsm_host_parabolic_fits")
+    return out, ok
+
+
 def local_cpus():
     """the CPUs of the GPU's NUMA node the library keeps its own host threads on (after the first Matcher exists); [] = no
     restriction.  os.sched_setaffinity(0, local_cpus()) puts the calling thread there too."""
@@ -953,6 +1004,17 @@ class Matcher:
         f2 = np.zeros(n, dtype=np.int16)
         lib().vsm_get_filter_responses(self.h, f1.ctypes.data_as(C.c_void_p), f2.ctypes.data_as(C.c_void_p))
         return f1, f2
+
+    def refine_lists(self, method, lists, counts=None):
+        """test hook: the refinement kernels alone on len(lists) caller-given pass-2 lists as the pairs of one launch, over the
+        frames pushed last (vsm_debug_refine; the last match result is gone afterwards) -> the refined lists.  counts: the
+        lengths handed to the library instead of the lists' own (argument checks).  A rejected argument raises."""
+        ms, cnt, ptrs = _refine_inputs(lists)
+        if counts is not None:
+            cnt = np.ascontiguousarray(counts, dtype=np.int32)
+        outs, oc, optrs = _refine_outputs([len(m) for m in ms])
+        _check(lib().vsm_debug_refine(self.h, int(method), ptrs, _ptr(cnt), len(ms), optrs, _ptr(oc)), "vsm_debug_refine")
+        return [o[:n].copy() for o, n in zip(outs, oc)]
 
     def counters(self):
         c = np.zeros(5, dtype=np.int64)

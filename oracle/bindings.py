@@ -63,6 +63,12 @@ def have_ref():
     return os.path.exists(REF_SO)
 
 
+def have_ref_refine():
+    """the compiled reference is there and its harness has ref_matcher_refine (one that `make ref` built before that
+    entry existed, and that cannot be rebuilt where the reference's sources are missing, still serves every other test)"""
+    return have_ref() and hasattr(ref_lib(), "ref_matcher_refine")
+
+
 _p_u8 = C.POINTER(C.c_uint8)
 _p_i16 = C.POINTER(C.c_int16)
 _p_i32 = C.POINTER(C.c_int32)
@@ -111,6 +117,10 @@ def oracle_lib():
         L.vo_get_features.argtypes = [C.c_void_p, C.c_int32, _p_i32]
         L.vo_get_gradients.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _p_u8, _p_u8]
         L.vo_get_counters.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        L.vo_refine.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
+        L.vo_parabolic_update.argtypes = [_p_i32, C.c_int32, C.c_int32, _p_f32, _p_f32]
+        L.vo_refine_census.argtypes = [C.POINTER(C.c_int64)]
+        L.vo_refine_census.restype = None
         L.vo_half_image.argtypes = [_p_u8, C.c_int32, C.c_int32, C.c_int32, _p_u8]
         L.vo_sobel5x5.argtypes = [_p_u8, _p_u8, _p_u8, C.c_int32, C.c_int32]
         L.vo_blob5x5.argtypes = [_p_u8, _p_i16, C.c_int32, C.c_int32]
@@ -180,6 +190,8 @@ def ref_lib():
         L.ref_matcher_num_features.argtypes = [C.c_void_p, C.c_int32]
         L.ref_matcher_get_features.argtypes = [C.c_void_p, C.c_int32, _p_i32]
         L.ref_matcher_get_gradients.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _p_u8, _p_u8]
+        if hasattr(L, "ref_matcher_refine"):    # a _ref built from an earlier harness lacks it: have_ref_refine()
+            L.ref_matcher_refine.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
         L.ref_sobel5x5.argtypes = [_p_u8, _p_u8, _p_u8, C.c_int32, C.c_int32]
         L.ref_blob5x5.argtypes = [_p_u8, _p_i16, C.c_int32, C.c_int32]
         L.ref_checkerboard5x5.argtypes = [_p_u8, _p_i16, C.c_int32, C.c_int32]
@@ -331,6 +343,12 @@ class CpuMatcher:
         a = np.ascontiguousarray(inliers, dtype=np.int32)
         return float((self.L.vo_get_gain if self.kind == "oracle" else self.L.ref_matcher_gain)(self.h, _i32(a), len(a)))
 
+    def refine(self, matches, method):
+        """Matcher::refinement alone on a list of the caller, over the frames pushed so far -> the refined list"""
+        m = np.array(matches, dtype=MATCH_DTYPE)
+        fn = self.L.vo_refine if self.kind == "oracle" else self.L.ref_matcher_refine
+        return m[:fn(self.h, m.ctypes.data, len(m), method)].copy()
+
     def counters(self):
         assert self.kind == "oracle"
         c = (C.c_int64 * 8)()
@@ -392,6 +410,35 @@ def delaunay(kind, pts):
     k = fn(pts.ctypes.data_as(_p_f32), n, _i32(tris), cap)
     assert k <= cap
     return tris[:k]
+
+
+REFINE_CENSUS = ("reloc_margin", "reloc_moved", "reloc_tied", "fit_margin", "fit_border", "fit_singular", "fit_divisor", "fit_b2",
+                 "fit_range", "fit_ok", "fit_tied", "fit_ok_nonzero")
+
+
+def oracle_refine_census():
+    """how often the oracle took each exit of relocateMinimum / parabolicFitting since the last call (the call resets them)"""
+    c = (C.c_int64 * 16)()
+    oracle_lib().vo_refine_census(c)
+    return dict(zip(REFINE_CENSUS, [int(x) for x in c]))
+
+
+def oracle_parabolic_fits(records, uv):
+    """vo_parabolic_update on records [n, 12] int32 {-, du, dv, c0..c8} and targets uv [n, 2] float32
+    -> (uv after the fits, ok [n])"""
+    L = oracle_lib()
+    r = np.ascontiguousarray(records, dtype=np.int32).reshape(-1, 12)
+    out = np.array(uv, dtype=np.float32).reshape(-1, 2).copy()
+    assert len(out) == len(r)
+    ok = np.zeros(len(r), dtype=np.int32)
+    i4, f4 = C.sizeof(C.c_int32), C.sizeof(C.c_float)
+    pr, pu = r.ctypes.data, out.ctypes.data
+    fn = L.vo_parabolic_update
+    du, dv = r[:, 1].tolist(), r[:, 2].tolist()
+    for i in range(len(r)):
+        ok[i] = fn(C.cast(pr + (12 * i + 3) * i4, _p_i32), du[i], dv[i], C.cast(pu + 2 * i * f4, _p_f32),
+                   C.cast(pu + (2 * i + 1) * f4, _p_f32))
+    return out, ok
 
 
 def remove_outliers(kind, matches, method, **params):

@@ -375,6 +375,16 @@ int32_t ref_remove_outliers(const int32_t *ip, const double *dp, void *matches, 
   return (int32_t)v.size();
 }
 
+// Matcher::refinement on an arbitrary match list (viso/matcher.cpp:1498), over the frames pushed into the matcher; the
+// list is refined in place, its new length returned
+int32_t ref_matcher_refine(void *h, void *matches, int32_t n, int32_t method) {
+  Matcher *m = ((RefMatcher *)h)->m;
+  std::vector<Matcher::p_match> v((Matcher::p_match *)matches, (Matcher::p_match *)matches + n);
+  m->refinement(v, method);
+  if (!v.empty()) memcpy(matches, v.data(), v.size() * sizeof(Matcher::p_match));
+  return (int32_t)v.size();
+}
+
 // ---- VisualOdometryStereo (viso/viso_stereo.cpp:33) for Tr_delta fixtures ---
 
 void *ref_vo_stereo_create(const int32_t *ip, double f, double cu, double cv, double base, int32_t bucket_max,

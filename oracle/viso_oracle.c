@@ -1257,14 +1257,23 @@ int32_t vo_remove_outliers(const vo_params *p, vo_match *m, int32_t n, int32_t m
 /* ------------------------------------------------------------------------- */
 /* R1  refinement / relocateMinimum / parabolicFitting, :1379-1585             */
 /* ------------------------------------------------------------------------- */
+/* census of the exits of relocate_minimum / parabolic_fitting since the last vo_refine_census() (tests only; one thread) */
+enum {
+  CEN_RELOC_MARGIN, CEN_RELOC_MOVED, CEN_RELOC_TIED, CEN_FIT_MARGIN, CEN_FIT_BORDER, CEN_FIT_SINGULAR, CEN_FIT_DIVISOR,
+  CEN_FIT_B2, CEN_FIT_RANGE, CEN_FIT_OK, CEN_FIT_TIED, CEN_FIT_OK_NONZERO, CEN_COUNT
+};
+static int64_t census[16];
+
 static void relocate_minimum(const uint8_t *du1, const uint8_t *dv1, const int32_t *dims1, const uint8_t *du2,
                              const uint8_t *dv2, const int32_t *dims2, float u1, float v1, float *u2, float *v2) {
   if (*u2 - 2 < VO_MARGIN || *u2 + 2 > dims2[0] - 1 - VO_MARGIN || *v2 - 2 < VO_MARGIN ||
-      *v2 + 2 > dims2[1] - 1 - VO_MARGIN)
+      *v2 + 2 > dims2[1] - 1 - VO_MARGIN) {
+    census[CEN_RELOC_MARGIN]++;
     return;
+  }
   uint8_t ref[16], cur[16];
   small_descriptor(du1, dv1, dims1[2], (int32_t)u1, (int32_t)v1, ref);
-  int32_t min_ind = 0, min_cost = 0;
+  int32_t min_ind = 0, min_cost = 0, n_min = 0;
   for (int32_t dv = 0; dv < 5; dv++)
     for (int32_t du = 0; du < 5; du++) {
       small_descriptor(du2, dv2, dims2[2], (int32_t)*u2 + du - 2, (int32_t)*v2 + dv - 2, cur);
@@ -1272,8 +1281,12 @@ static void relocate_minimum(const uint8_t *du1, const uint8_t *dv1, const int32
       if ((dv == 0 && du == 0) || c < min_cost) {
         min_ind = dv * 5 + du;
         min_cost = c;
+        n_min = 0;
       }
+      if (c == min_cost) n_min++; /* (census only) */
     }
+  census[CEN_RELOC_MOVED]++;
+  if (n_min > 1) census[CEN_RELOC_TIED]++;
   *u2 += (float)(min_ind % 5) - 2.0;
   *v2 += (float)(min_ind / 5) - 2.0;
 }
@@ -1328,11 +1341,40 @@ static const double PF_A[9][6] = {{1, 1, 1, -1, -1, 1}, {0, 1, 0, 0, -1, 1}, {1,
                                   {1, 0, 0, -1, 0, 1},  {0, 0, 0, 0, 0, 1},  {1, 0, 0, 1, 0, 1},
                                   {1, 1, -1, -1, 1, 1}, {0, 1, 0, 0, 1, 1},  {1, 1, 1, 1, 1, 1}}; /* :1508-1516 */
 
+/* the least-squares tail of parabolicFitting, :1425-1453, from b = At*c on: c9 = the 3 x 3 costs around the minimum (du, dv) */
+int32_t vo_parabolic_update(const int32_t *c9, int32_t du, int32_t dv, float *u2, float *v2) {
+  double c[9];
+  for (int32_t i = 0; i < 9; i++) c[i] = c9[i];
+  /* b = At*c ; AtA = At*A   (Matrix::operator*, viso/matrix.cpp, k-innermost accumulation from 0) */
+  double b[6], AtA[6][6];
+  for (int i = 0; i < 6; i++) {
+    double s = 0;
+    for (int k = 0; k < 9; k++) s += PF_A[k][i] * c[k];
+    b[i] = s;
+    for (int j = 0; j < 6; j++) {
+      double t = 0;
+      for (int k = 0; k < 9; k++) t += PF_A[k][i] * PF_A[k][j];
+      AtA[i][j] = t;
+    }
+  }
+  if (!gaussj6(AtA, b)) return census[CEN_FIT_SINGULAR]++, 0;
+  float divisor = (float)(b[2] * b[2] - 4.0 * b[0] * b[1]);
+  if (fabsf(divisor) < 1e-8 || fabs(b[2]) < 1e-8) return census[fabsf(divisor) < 1e-8 ? CEN_FIT_DIVISOR : CEN_FIT_B2]++, 0;
+  float ddv = (float)((2.0 * b[0] * b[4] - b[2] * b[3]) / divisor);
+  float ddu = (float)(-(b[4] + 2.0 * b[1] * ddv) / b[2]);
+  if (fabsf(ddu) >= 1.0 || fabsf(ddv) >= 1.0) return census[CEN_FIT_RANGE]++, 0;
+  *u2 = (float)(*u2 + ((float)du - 3.0 + ddu));
+  *v2 = (float)(*v2 + ((float)dv - 3.0 + ddv));
+  census[CEN_FIT_OK]++;
+  if (c9[4] != 0) census[CEN_FIT_OK_NONZERO]++;
+  return 1;
+}
+
 static int parabolic_fitting(const uint8_t *du1, const uint8_t *dv1, const int32_t *dims1, const uint8_t *du2,
                              const uint8_t *dv2, const int32_t *dims2, float u1, float v1, float *u2, float *v2) {
   if (*u2 - 3 < VO_MARGIN || *u2 + 3 > dims2[0] - 1 - VO_MARGIN || *v2 - 3 < VO_MARGIN ||
       *v2 + 3 > dims2[1] - 1 - VO_MARGIN)
-    return 0;
+    return census[CEN_FIT_MARGIN]++, 0;
   uint8_t ref[16], cur[16];
   small_descriptor(du1, dv1, dims1[2], (int32_t)u1, (int32_t)v1, ref);
   int32_t cost[49];
@@ -1347,32 +1389,17 @@ static int parabolic_fitting(const uint8_t *du1, const uint8_t *dv1, const int32
       min_ind = i;
       min_cost = cost[i];
     }
-  int32_t du = min_ind % 7, dv = min_ind / 7;
-  if (du == 0 || du == 6 || dv == 0 || dv == 6) return 0;
-  double c[9];
-  for (int32_t i = -1; i <= 1; i++)
-    for (int32_t j = -1; j <= 1; j++) c[(i + 1) * 3 + (j + 1)] = cost[(dv + i) * 7 + (du + j)];
-  /* b = At*c ; AtA = At*A   (Matrix::operator*, viso/matrix.cpp, k-innermost accumulation from 0) */
-  double b[6], AtA[6][6];
-  for (int i = 0; i < 6; i++) {
-    double s = 0;
-    for (int k = 0; k < 9; k++) s += PF_A[k][i] * c[k];
-    b[i] = s;
-    for (int j = 0; j < 6; j++) {
-      double t = 0;
-      for (int k = 0; k < 9; k++) t += PF_A[k][i] * PF_A[k][j];
-      AtA[i][j] = t;
+  for (int32_t i = 0; i < 49; i++)
+    if (i != min_ind && cost[i] == min_cost) {
+      census[CEN_FIT_TIED]++;
+      break;
     }
-  }
-  if (!gaussj6(AtA, b)) return 0;
-  float divisor = (float)(b[2] * b[2] - 4.0 * b[0] * b[1]);
-  if (fabsf(divisor) < 1e-8 || fabs(b[2]) < 1e-8) return 0;
-  float ddv = (float)((2.0 * b[0] * b[4] - b[2] * b[3]) / divisor);
-  float ddu = (float)(-(b[4] + 2.0 * b[1] * ddv) / b[2]);
-  if (fabsf(ddu) >= 1.0 || fabsf(ddv) >= 1.0) return 0;
-  *u2 = (float)(*u2 + ((float)du - 3.0 + ddu));
-  *v2 = (float)(*v2 + ((float)dv - 3.0 + ddv));
-  return 1;
+  int32_t du = min_ind % 7, dv = min_ind / 7;
+  if (du == 0 || du == 6 || dv == 0 || dv == 6) return census[CEN_FIT_BORDER]++, 0;
+  int32_t c9[9];
+  for (int32_t i = -1; i <= 1; i++)
+    for (int32_t j = -1; j <= 1; j++) c9[(i + 1) * 3 + (j + 1)] = cost[(dv + i) * 7 + (du + j)];
+  return vo_parabolic_update(c9, du, dv, u2, v2);
 }
 
 static int32_t refinement(vo_matcher *M, vo_match *pm, int32_t n, int32_t method) { /* :1498-1585 */
@@ -1409,6 +1436,13 @@ static int32_t refinement(vo_matcher *M, vo_match *pm, int32_t n, int32_t method
     if (ok) pm[out++] = it;
   }
   return out;
+}
+
+int32_t vo_refine(vo_matcher *M, vo_match *matches, int32_t n, int32_t method) { return refinement(M, matches, n, method); }
+
+void vo_refine_census(int64_t *out12) {
+  memcpy(out12, census, CEN_COUNT * sizeof(int64_t));
+  memset(census, 0, sizeof(census));
 }
 
 /* ------------------------------------------------------------------------- */

@@ -85,6 +85,20 @@ void vo_get_features(const vo_matcher *m, int32_t which, int32_t *out);
 /* which: 0=1p 1=2p 2=1c 3=2c; returns plane bytes or 0 */
 int32_t vo_get_gradients(const vo_matcher *m, int32_t which, int32_t full, uint8_t *du, uint8_t *dv);
 
+/* ---- the refinement alone (tests of the refinement kernels) ---- */
+/* the static refinement() (Matcher::refinement, :1498-1585) with M's refinement / half_resolution on a list of the caller,
+ * over the frames pushed into M; refined in place, returns the new length.  The reference points (u1c, v1c) are read
+ * unguarded: they must be pixels inside the margin. */
+int32_t vo_refine(vo_matcher *m, vo_match *matches, int32_t n, int32_t method);
+/* the tail of parabolicFitting from b = At*c on (:1425-1453): c9 = the 3 x 3 costs around the minimum at (du, dv) of the
+ * 7 x 7 window; 1: (*u2, *v2) updated, 0: the fit fails */
+int32_t vo_parabolic_update(const int32_t *c9, int32_t du, int32_t dv, float *u2, float *v2);
+/* how often each exit of relocateMinimum / parabolicFitting was taken since the last call (process-wide, one thread):
+ * {relocation: margin exit, moved, ... of which with a tied minimum; fit: margin exit, minimum on the border, singular
+ * system, |divisor| < 1e-8, |b2| < 1e-8, |ddu| or |ddv| >= 1, success, windows with a tied minimum, successes with a
+ * non-zero minimum cost} */
+void vo_refine_census(int64_t *out12);
+
 /* work counters of the last vo_match_features() (for the bench's algorithmic-bytes model,
  * SURVEY.md section 8d): {findMatch calls Q, candidates visited C, SADs S, matches refined M, matches out,
  * and the pass-1 share Q1, C1, S1} */
