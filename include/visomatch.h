@@ -284,7 +284,7 @@ int32_t vsm_host_triangulate(int32_t n_frames, const double *poses, const uint8_
                              const vsm_triangulate_params *params, int32_t *status, double *xyz, int32_t *type, int32_t *updates,
                              double *dist, double *angle);
 /* Measurement / test switches of a handle.  They are read from the environment once, by vsm_create (VSM_SEQ_V2,
- * VSM_SEQ_CHUNK, VSM_SEQ_DC_STREAMS, VSM_SEQ_SERIAL, VSM_SEQ_GPU_SORTS, VSM_SEQ_EARLY_EXPORT); this call changes one
+ * VSM_SEQ_CHUNK, VSM_SEQ_DC_STREAMS, VSM_SEQ_SERIAL, VSM_SEQ_GPU_SORTS, VSM_SEQ_EARLY_EXPORT, VSM_FUSED_KEYS); this call changes one
  * afterwards: name = the variable's name without the VSM_ prefix, in lower case ("seq_serial", "seq_chunk", ...).
  * Option-only names (never read from the environment): "front" (0: separate ingest / halving / Sobel passes instead of the
  * fused front end), "dc_gpu", "dc_full", "dc_watchdog_ms", "dc_fault_inject" (the GPU's share of the final stage in the
@@ -296,6 +296,9 @@ int32_t vsm_host_triangulate(int32_t n_frames, const double *poses, const uint8_
  * second matching pass on 64-byte per-bin head records - measured slower); "fused_features" / "feat_order" (0: the separate filter, suppression, record and bin kernels
  * instead of k_feat_dense / k_feat_sparse / k_feat_scan / k_feat_order) and "filter_planes" (1: vsm_push_back keeps the
  * blob / corner responses in HBM for vsm_get_filter_responses; the fused kernels leave them in LDS otherwise).
+ * "fused_keys" (VSM_FUSED_KEYS; 1, the default: the batched forms' compactions write the Delaunay chains' keys and the chains'
+ * job tables go up ahead of the matching launches; 0: every chain uploads its table and makes its keys itself behind the
+ * compaction, which refinement = 2 always does).
  * None of them changes a result.  Returns VSM_OK, or VSM_EARG for an unknown name.  (No counterpart in the reference.) */
 int vsm_set_option(vsm_handle *h, const char *name, int32_t value);
 /* Host threads near the GPU: the library confines the threads IT creates (host pool, look-ahead poller) to the CPUs of the
@@ -478,6 +481,20 @@ int32_t vsm_debug_refine_check(int32_t w, int32_t h, const vsm_p_match *const *l
 int32_t vsm_debug_parabolic_apply(const vsm_p_match *const *lists, const int32_t *const *records, const int32_t *counts, int32_t P,
                                   vsm_p_match *const *out, int32_t *out_counts);
 int32_t vsm_host_parabolic_fits(const int32_t *records, int32_t n, float *uv, int32_t *ok);
+/* Test hook of the matching passes' ordered compaction and the Delaunay chains' keys it writes (no images, no handle): P pairs
+ * (1 <= P <= 64) in ONE launch, pair k with n_query[k] queries whose acceptance flags flag[k][n_query[k]] and per-query records
+ * raw[k][n_query[k]] the caller gives; method 0 / 1 (flow, stereo: with the first-come pixel de-dup) or 2 (quad), pass 0 / 1.
+ * Out per pair: list_out[k] (room for n_query[k] + 1 records), count_out[k], keys_out[k] (room for key_cap[k] + 8 words):
+ * key[d] = (uint32)(int32)u1c << 34 | (uint32)(int32)v1c << 20 | d for every list position d < min(count, key_cap[k]).  List
+ * and key arrays hold 0xA5 bytes before the launch, so everything the kernels leave alone - the record and the eight words
+ * behind the arrays, keys from the count or the capacity on - comes back as that pattern.  old_keys = 1: the compaction
+ * without its key store and k_dc2_keys behind it (what option fused_keys = 0 runs); the two must agree byte for byte.
+ * old_keys = 2: the key store also writes a host-mapped array per pair (the batched forms' pool reads its keys there), and
+ * keys_out gets that array.
+ * VSM_OK, VSM_EARG, or VSM_EHIP. */
+int32_t vsm_debug_compact_keys(int32_t method, int32_t pass, int32_t P, const int32_t *n_query, const int32_t *const *flag,
+                               const vsm_p_match *const *raw, const int32_t *key_cap, int32_t old_keys, vsm_p_match *const *list_out,
+                               int32_t *count_out, uint64_t *const *keys_out);
 
 /* ---- stereo visual odometry on top of the matcher ----
  * class VisualOdometryStereo, viso/viso_stereo.h:28-88 + viso/viso.h:28-131: process() =

@@ -88,6 +88,7 @@ struct VsmCtx {
   size_t f_stride = 0;
   int32_t cap_set[2] = {0, 0};
   size_t ranges_stride = 0;  // floats per pair
+  size_t pair_stride = 0;    // bytes from one pair's buffers (raw, lists, keys ...) to the next pair's
   float *d_ranges = nullptr;
   // pinned host memory.  hm_* is host-mapped: kernels write feature counts and exported match
   // lists straight into it, so results need a stream sync but no D2H copy.
@@ -306,7 +307,7 @@ static int ctx_create(VsmCtx &c, const vsm_params &p, int32_t w, int32_t hh, int
   const size_t qcap = (size_t)(c.cap_set[0] > c.cap_set[1] ? c.cap_set[0] : c.cap_set[1]);
   c.ranges_stride = (size_t)d.ub * d.vb * 16;
   struct PairOff {
-    size_t raw, flag, bc, l1, l2, cnt, pf;
+    size_t raw, flag, bc, l1, l2, cnt, pf, k1, k2;
   };
   std::vector<PairOff> po(npairs);
   for (int j = 0; j < npairs; j++) {
@@ -317,7 +318,11 @@ static int ctx_create(VsmCtx &c, const vsm_params &p, int32_t w, int32_t hh, int
     po[j].l2 = take(qcap * 48);
     po[j].cnt = take(16);
     po[j].pf = p.refinement == 2 ? take(qcap * 3 * 12 * 4) : 0;  // (per-frame ring: one pair; look-ahead banks: every pair)
+    // the chains' keys beside the lists they index (every pair takes the same room: one stride from pair to pair, pair_stride)
+    po[j].k1 = take((size_t)c.cap_set[0] * 8);
+    po[j].k2 = take(qcap * 8);
   }
+  c.pair_stride = npairs > 0 ? (off - po[0].raw) / npairs : 0;
   const size_t o_rng = take(c.ranges_stride * 4 * npairs);
   const size_t o_imgs = take((size_t)nimg * sizeof(VsmImage));
   const size_t o_pairs = take((size_t)npairs * sizeof(VsmPair));
@@ -386,6 +391,10 @@ static int ctx_create(VsmCtx &c, const vsm_params &p, int32_t w, int32_t hh, int
     pr.count = (int32_t *)(b + po[j].cnt);
     pr.ranges = c.d_ranges + (size_t)j * c.ranges_stride;
     pr.pf = po[j].pf ? (int32_t *)(b + po[j].pf) : nullptr;
+    pr.keys[0] = (uint64_t *)(b + po[j].k1);
+    pr.keys[1] = (uint64_t *)(b + po[j].k2);
+    pr.key_cap[0] = c.cap_set[0];
+    pr.key_cap[1] = (int32_t)qcap;
     const size_t lo = hc + hl + (l1 + l2) * j;
     c.hm_list1[j] = (vsm_p_match *)(c.hm_block + lo);
     c.hm_list2[j] = (vsm_p_match *)(c.hm_block + lo + l1);
@@ -455,6 +464,9 @@ struct VsmSwitches {
   int pairs_chunk = 0;       // vsm_pairs_run: pairs per step (0 = the look-ahead call's chunk rule for device-resident frames, seq2_plan)
   int motions_chunk = 0;     // vsm_motions_run / vsm_pairs_motions: pairs per chunk (0 = as many as the memory rule of vsm_motions.inc allows)
   int frame_early_xy = 1;    // per-frame path: the pass-2 list's pixels cross in front of the list, the host triangulates while the refinement and the export run (vsm_match)
+  int fused_keys = 1;        // VSM_FUSED_KEYS: the batched forms' compactions write the Delaunay chains' keys with the lists and the chains' job tables are uploaded ahead of the
+                             // matching launch (1), or every chain starts with
+                             // its job table's upload and k_dc2_keys behind the compaction (0); refinement = 2 always takes 0
   int filter_planes = 0;     // vsm_push_back keeps f1 / f2 in HBM for vsm_get_filter_responses (the fused tiles write them on the side)
   static int env_int(const char *name, int dflt) {
     const char *e = getenv(name);
@@ -469,6 +481,7 @@ struct VsmSwitches {
     seq_early_export = env_int("VSM_SEQ_EARLY_EXPORT", -1);
     multi_host_pass1 = env_int("VSM_MULTI_HOST_PASS1", -1);    // (measurements: vsm_multi_create takes no options)
     multi_shared_ego = env_int("VSM_MULTI_SHARED_EGO", 0);
+    fused_keys = env_int("VSM_FUSED_KEYS", 1) != 0;  // (likewise)
   }
   bool set(const char *name, int v) {
     if (!strcmp(name, "seq_v2")) seq_v2 = v != 0;
@@ -499,6 +512,7 @@ struct VsmSwitches {
     else if (!strcmp(name, "match_heads")) match_heads = v != 0;
     else if (!strcmp(name, "fused_features")) fused_features = v != 0;
     else if (!strcmp(name, "filter_planes")) filter_planes = v != 0;
+    else if (!strcmp(name, "fused_keys")) fused_keys = v != 0;
     else if (!strcmp(name, "feat_order")) feat_order = v != 0;
     else if (!strcmp(name, "frame_early_xy")) frame_early_xy = v != 0;
     else if (!strcmp(name, "multi_host_pass1")) multi_host_pass1 = v;
@@ -2022,6 +2036,110 @@ int32_t vsm_debug_dc2(const vsm_params *p, const vsm_p_match *list, int32_t n, i
   (void)hipFree(d_ranges);
   B.release();
   return result;
+}
+
+// ---- test hook of the compaction and its key store (k_compact_quad, k_compact_count / k_compact_write) ----
+// P pairs in one launch, pair k with n_query[k] queries whose acceptance flags and raw records the caller gives.  Out per pair:
+// the list (n_query[k] + 1 records), its count, the keys (key_cap[k] + VSM_DEBUG_KEY_GUARD words).  List and key arrays are
+// filled with 0xA5 bytes before the launch, so whatever the kernels do not write - the guard entries behind each array, keys
+// at and beyond the count or the capacity - comes back as that pattern.  old_keys = 1: the compaction without its key
+// store, then k_dc2_keys over the lists (cap = key_cap[k]) - the hand-over the fused store replaces; 2: the fused store
+// with its host-mapped second target, whose content comes back.
+#define VSM_DEBUG_KEY_GUARD 8
+int32_t vsm_debug_compact_keys(int32_t method, int32_t pass, int32_t P, const int32_t *n_query, const int32_t *const *flag, const vsm_p_match *const *raw,
+                               const int32_t *key_cap, int32_t old_keys, vsm_p_match *const *list_out, int32_t *count_out, uint64_t *const *keys_out) {
+  if (P < 1 || P > 64 || method < 0 || method > 2 || pass < 0 || pass > 1 || !n_query || !flag || !raw || !key_cap || !list_out || !count_out || !keys_out)
+    return VSM_EARG;
+  int max_nq = 0;
+  for (int32_t k = 0; k < P; k++) {
+    if (n_query[k] < 0 || n_query[k] > (1 << 20) || key_cap[k] < 0 || key_cap[k] > (1 << 20)) return VSM_EARG;
+    max_nq = std::max(max_nq, n_query[k]);
+  }
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    const size_t o = off;
+    off += al256(bytes);
+    return o;
+  };
+  struct Off {
+    size_t raw, flag, bc, list, keys, cnt;
+  };
+  std::vector<Off> po(P);
+  for (int32_t k = 0; k < P; k++) {
+    const size_t nq = (size_t)n_query[k];
+    po[k].raw = take((nq + 1) * sizeof(vsm_p_match));
+    po[k].flag = take((nq + 4) * 4);
+    po[k].bc = take((nq / 256 + 2) * 4);
+    po[k].list = take((nq + 1) * sizeof(vsm_p_match));
+    po[k].keys = take(((size_t)key_cap[k] + VSM_DEBUG_KEY_GUARD) * 8);
+    po[k].cnt = take(4 * sizeof(int32_t));
+  }
+  const size_t o_pairs = take((size_t)P * sizeof(VsmPair)), o_jobs = take((size_t)P * sizeof(VsmJob)), o_dc = take((size_t)P * sizeof(VsmDc2Job));
+  uint8_t *block = nullptr;
+  if (hipMalloc((void **)&block, off) != hipSuccess) return VSM_EHIP;
+  std::vector<VsmPair> pairs(P);
+  std::vector<VsmJob> jobs(P);
+  std::vector<VsmDc2Job> dc(P);
+  bool ok = hipMemset(block, 0, off) == hipSuccess;
+  for (int32_t k = 0; k < P && ok; k++) {
+    VsmPair &pr = pairs[k];
+    memset(&pr, 0, sizeof(pr));
+    memset(&jobs[k], 0, sizeof(VsmJob));
+    memset(&dc[k], 0, sizeof(VsmDc2Job));
+    pr.raw = (vsm_p_match *)(block + po[k].raw);
+    pr.flag = (int32_t *)(block + po[k].flag);
+    pr.blockcnt = (int32_t *)(block + po[k].bc);
+    pr.list1 = pr.list2 = (vsm_p_match *)(block + po[k].list);
+    pr.count = (int32_t *)(block + po[k].cnt);
+    pr.hcount = pr.count + 2;  // (no host-mapped twin here)
+    pr.keys[0] = pr.keys[1] = (uint64_t *)(block + po[k].keys);
+    pr.key_cap[0] = pr.key_cap[1] = key_cap[k];
+    jobs[k].nq[pass] = n_query[k];
+    dc[k].list = pr.list1;
+    dc[k].count = pr.count + pass;
+    dc[k].cap = key_cap[k];
+    dc[k].keys_in = pr.keys[0];
+    const size_t nq = (size_t)n_query[k];
+    ok = hipMemset(pr.list1, 0xA5, (nq + 1) * sizeof(vsm_p_match)) == hipSuccess &&
+         hipMemset(pr.keys[0], 0xA5, ((size_t)key_cap[k] + VSM_DEBUG_KEY_GUARD) * 8) == hipSuccess &&
+         (nq == 0 || (hipMemcpy(pr.flag, flag[k], nq * 4, hipMemcpyHostToDevice) == hipSuccess &&
+                      hipMemcpy(pr.raw, raw[k], nq * sizeof(vsm_p_match), hipMemcpyHostToDevice) == hipSuccess));
+  }
+  VsmPair *d_pairs = (VsmPair *)(block + o_pairs);
+  VsmJob *d_jobs = (VsmJob *)(block + o_jobs);
+  VsmDc2Job *d_dc = (VsmDc2Job *)(block + o_dc);
+  ok = ok && hipMemcpy(d_pairs, pairs.data(), (size_t)P * sizeof(VsmPair), hipMemcpyHostToDevice) == hipSuccess &&
+       hipMemcpy(d_jobs, jobs.data(), (size_t)P * sizeof(VsmJob), hipMemcpyHostToDevice) == hipSuccess &&
+       hipMemcpy(d_dc, dc.data(), (size_t)P * sizeof(VsmDc2Job), hipMemcpyHostToDevice) == hipSuccess;
+  // (old_keys = 2: the key store's second target, a host-mapped array per pair, is what comes back)
+  uint8_t *hk = nullptr;
+  uint64_t *hk_dev = nullptr;
+  int32_t max_cap = 0;
+  for (int32_t k = 0; k < P; k++) max_cap = std::max(max_cap, key_cap[k]);
+  const size_t hk_stride = al256(((size_t)max_cap + VSM_DEBUG_KEY_GUARD) * 8);
+  if (ok && old_keys == 2) {
+    ok = hipHostMalloc((void **)&hk, hk_stride * P, hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer((void **)&hk_dev, hk, 0) == hipSuccess;
+    if (ok) memset(hk, 0xA5, hk_stride * P);
+  }
+  if (ok) {
+    VsmJob dummy;
+    memset(&dummy, 0, sizeof(dummy));
+    const VsmKeyOut ko = {hk_dev, hk_stride, max_cap};
+    vsm_launch_compact(nullptr, d_pairs, d_jobs, dummy, P, method, pass, max_nq, old_keys == 1 ? nullptr : &ko);
+    if (old_keys == 1) vsm_dc2_launch_keys(nullptr, d_dc, P, max_nq);
+    ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+  }
+  for (int32_t k = 0; k < P && ok; k++) {
+    int32_t cnt[4] = {0, 0, 0, 0};
+    ok = hipMemcpy(cnt, pairs[k].count, sizeof(cnt), hipMemcpyDeviceToHost) == hipSuccess && cnt[pass] == cnt[2 + pass] &&
+         hipMemcpy(list_out[k], pairs[k].list1, ((size_t)n_query[k] + 1) * sizeof(vsm_p_match), hipMemcpyDeviceToHost) == hipSuccess &&
+         hipMemcpy(keys_out[k], pairs[k].keys[0], ((size_t)key_cap[k] + VSM_DEBUG_KEY_GUARD) * 8, hipMemcpyDeviceToHost) == hipSuccess;
+    if (ok && old_keys == 2) memcpy(keys_out[k], hk + hk_stride * k, ((size_t)key_cap[k] + VSM_DEBUG_KEY_GUARD) * 8);
+    count_out[k] = cnt[pass];
+  }
+  if (hk) (void)hipHostFree(hk);
+  (void)hipFree(block);
+  return ok ? VSM_OK : VSM_EHIP;
 }
 
 // ---- test hooks of the refinement kernels (k_refine<TILED>, k_parabolic_costs, k_parabolic_apply) on lists of the caller ----

@@ -960,8 +960,7 @@ __global__ void __launch_bounds__(256) k_dc2_keys(const VsmDc2Job *__restrict__ 
   const uint64_t k = ((uint64_t)(uint32_t)(int32_t)a.u1c << 34) | ((uint64_t)(uint32_t)(int32_t)a.v1c << 20) | (uint32_t)i;
   jb.keys_in[i] = k;
   if (jb.h_keys) jb.h_keys[i] = k;
-  jb.remap[i] = i;
-  jb.support[i] = 0;
+  // (remap[] / support[] start in k_dc2_flows: chains whose keys the matching pass's compaction wrote do not come through here)
 }
 
 // one stable LSD pass (7 bits at `sh`) over n 64-bit keys; thread t < KD_CHUNKS owns a contiguous chunk and its own
@@ -2024,7 +2023,12 @@ __global__ void __launch_bounds__(256) k_dc2_flows(const VsmDc2Job *__restrict__
   const VsmDc2Job jb = jobs[blockIdx.y];
   const int n = jb.mn[1];
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n || jb.mn[0] < 2) return;
+  if (i >= n) return;
+  // the per-match state of the chain's end, in the slab (the only kernel in front of the tie patches and the votes that
+  // touches every match whoever made the keys; lists the votes skip - mn[0] < 2 - are still compacted by support)
+  jb.remap[i] = i;
+  jb.support[i] = 0;
+  if (jb.mn[0] < 2) return;
   const vsm_p_match a = jb.list[i];
   float *fu = (float *)jb.kd_scratch, *fv = fu + jb.kd_stride, *dp = fv + jb.kd_stride;
   fu[i] = a.u1c - a.u1p;

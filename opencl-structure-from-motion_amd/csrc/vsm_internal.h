@@ -87,6 +87,11 @@ struct VsmPair {
   int32_t *hcount;               // [2] host-mapped list sizes
   float *ranges;       // [ub*vb][16]
   int32_t *pf;         // refinement==2 scratch: [cap][3][12] {status,du,dv,c0..c8}
+  // the Delaunay chains' keys of the two lists, u1c << 34 | v1c << 20 | list position, written by the compaction that
+  // writes the list (vsm_launch_match with_keys); entries at and beyond key_cap are not written.  They belong to the
+  // pair, not to a chain slab: whatever guards the reuse of list1 / list2 guards them
+  uint64_t *keys[2];
+  int32_t key_cap[2];
 };
 
 // Optional per-kernel timing with HIP events recorded on the handle's own stream (bench.py's
@@ -178,13 +183,25 @@ int vsm_launch_features(hipStream_t s, VsmProf &pf, const VsmImage *d_imgs, int 
                         int16_t *f1, int16_t *f2, size_t f_stride, int nms_tau, int multi_stage, int half_res,
                         int binsize, const VsmImage *h_imgs, int front_done = 0, int fused = 1);
 
+// where the keys a compaction writes go beside VsmPair::keys[pass]: pair y of the launch has room for host_cap keys at
+// host + y * host_stride (bytes; host-mapped memory), or host = null: nowhere else
+struct VsmKeyOut {
+  uint64_t *host;
+  size_t host_stride;
+  int32_t host_cap;
+};
+
 // ---- launchers of the pair side (vsm_match.hip) ----
 // small table in pinned (hipHostMalloc) memory -> HBM by a kernel on stream s (see k_upload)
 hipError_t vsm_upload(hipStream_t s, void *dst_device, const void *src_pinned, size_t bytes);
 // fuse_export (quad matching only; the return value says whether it happened): 1 - the compacted list also goes to its host-mapped
 // copy (what vsm_launch_export does), 2 - pair 0's pixels go to xy_dst (what vsm_launch_export_xy does)
 bool vsm_launch_match(hipStream_t s, VsmProf &pf, const VsmImage *d_imgs, const VsmPair *d_pairs, const VsmJob *d_jobs,
-                      const VsmJob &job0, int npairs, const VsmDims &d, const VsmMatchCfg &cfg, int max_nq, int fuse_export = 0, uint32_t *xy_dst = nullptr);
+                      const VsmJob &job0, int npairs, const VsmDims &d, const VsmMatchCfg &cfg, int max_nq, int fuse_export = 0, uint32_t *xy_dst = nullptr,
+                      const VsmKeyOut *keys = nullptr);  // keys: the compaction also writes VsmPair::keys[pass] (not together with fuse_export)
+// the compaction of a pass, on flag[] / raw[] that are in place: vsm_launch_match ends with it, vsm_debug_compact_keys runs it alone
+bool vsm_launch_compact(hipStream_t s, const VsmPair *d_pairs, const VsmJob *d_jobs, const VsmJob &job0, int npairs, int method, int pass, int max_nq,
+                        const VsmKeyOut *keys, int fuse_export = 0, uint32_t *xy_dst = nullptr);
 void vsm_launch_export(hipStream_t s, VsmProf &pf, const VsmPair *d_pairs, int npairs, int pass, int n_upper);
 void vsm_launch_export_xy(hipStream_t s, const VsmPair *d_pairs, uint32_t *dst_host_mapped, int n_upper);  // pair 0's pass-2 pixels, x | y << 16
 #define VSM_PARA_MAX_LIST 16384  // matches per pair the batched tail of refinement==2 takes

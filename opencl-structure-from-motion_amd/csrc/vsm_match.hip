@@ -502,6 +502,11 @@ __global__ void __launch_bounds__(VSM_MATCH_BLOCK, VSM_MATCH_WAVES)
   MT_END(mtph);
 }
 
+// key of list entry `pos` for the exact Delaunay chain (VsmDc2Job::keys_in; the casts are k_dc2_keys')
+__device__ __forceinline__ uint64_t vsm_chain_key(float u1c, float v1c, int pos) {
+  return ((uint64_t)(uint32_t)(int32_t)u1c << 34) | ((uint64_t)(uint32_t)(int32_t)v1c << 20) | (uint32_t)pos;
+}
+
 // ordered compaction of the accepted queries (push_back order = ascending query index) with the
 // first-come pixel de-dup of flow / stereo (M[] in viso/matcher.cpp:1036-1039, :1078-1081):
 // features sharing a pixel come from one NMS cell, hence are at most 3 indices apart.
@@ -532,8 +537,9 @@ __global__ void __launch_bounds__(256)
   if (threadIdx.x == 0) pair.blockcnt[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
 }
 
+// (keys: the Delaunay chain's key of every list entry goes out with it, see k_compact_quad)
 __global__ void __launch_bounds__(256)
-    k_compact_write(const VsmPair *__restrict__ pairs, const VsmJob *__restrict__ jobs, VsmJob job0, int method, int pass) {
+    k_compact_write(const VsmPair *__restrict__ pairs, const VsmJob *__restrict__ jobs, VsmJob job0, int method, int pass, int keys, VsmKeyOut ko) {
   __shared__ int s_red[4];
   __shared__ int s_cnt[4];
   const VsmPair &pair = pairs[blockIdx.y];
@@ -558,7 +564,20 @@ __global__ void __launch_bounds__(256)
   int pos = s_red[0] + s_red[1] + s_red[2] + s_red[3];
   for (int w = 0; w < wv; w++) pos += s_cnt[w];
   pos += __popcll(bal & ((1ull << lane) - 1ull));
-  if (keep) list[pos] = pair.raw[i];
+  if (keep) {
+    // the record as its three 16-byte pieces, read once: piece 1 holds (u1c, v1c), as in k_compact_quad
+    const uint4 *src = (const uint4 *)(pair.raw + i);
+    uint4 *dst = (uint4 *)(list + pos);
+    const uint4 r0 = src[0], r1 = src[1], r2 = src[2];
+    dst[0] = r0;
+    dst[1] = r1;
+    dst[2] = r2;
+    if (keys && pos < pair.key_cap[pass]) {
+      const uint64_t key = vsm_chain_key(__uint_as_float(r1.z), __uint_as_float(r1.w), pos);
+      pair.keys[pass][pos] = key;
+      if (ko.host && pos < ko.host_cap) ((uint64_t *)((uint8_t *)ko.host + blockIdx.y * ko.host_stride))[pos] = key;
+    }
+  }
   if ((int)blockIdx.x == nblk - 1 && threadIdx.x == 255) {
     const int total = pos + (keep ? 1 : 0);
     pair.count[pass] = total;
@@ -577,10 +596,15 @@ __global__ void __launch_bounds__(256)
 // EXPORT (the per-frame path, where a launch of its own for the copy is 8 us of a 0.5 ms frame): 1 - every piece goes to the
 // list's host-mapped copy as well (k_export_list's work), 2 - the pixel (u1c, v1c) of every match as x | y << 16 to xy_dst
 // (k_export_xy's).
+// EXPORT 3 (the batched forms): the Delaunay chain's key of every match - its pixel and its place in the list - to the pair's
+// keys[pass], made from the two words of piece 1 that EXPORT 2 packs; the chain starts on its sort without a pass of its own
+// over the list (k_dc2_keys: 48 bytes read per match for 8 written).  Places at and beyond key_cap[pass] get no key.
+// EXPORT 4: the same, and every key to the host-mapped array ko names as well (the forms whose single stream has nothing
+// beside it to hold up: the pool's vertex sorts read them there).
 #define QUAD_SPAN 1024
 template <int EXPORT>
 __global__ void __launch_bounds__(256)
-    k_compact_quad(const VsmPair *__restrict__ pairs, const VsmJob *__restrict__ jobs, VsmJob job0, int pass, uint32_t *__restrict__ xy_dst) {
+    k_compact_quad(const VsmPair *__restrict__ pairs, const VsmJob *__restrict__ jobs, VsmJob job0, int pass, uint32_t *__restrict__ xy_dst, VsmKeyOut ko) {
   __shared__ int s_w[5];
   __shared__ int s_base[4];
   __shared__ int s_dst[QUAD_SPAN];  // place of every query of the span in the list, -1 = not accepted
@@ -641,6 +665,9 @@ __global__ void __launch_bounds__(256)
     const uint4 *src = (const uint4 *)(pair.raw + q0);
     uint4 *dst = (uint4 *)list;
     uint4 *hdst = EXPORT == 1 ? (uint4 *)(pass ? pair.hlist2 : pair.hlist1) : nullptr;
+    uint64_t *__restrict__ keys = EXPORT >= 3 ? pair.keys[pass] : nullptr;
+    uint64_t *__restrict__ hkeys = EXPORT == 4 ? (uint64_t *)((uint8_t *)ko.host + blockIdx.y * ko.host_stride) : nullptr;
+    const int key_cap = EXPORT >= 3 ? pair.key_cap[pass] : 0;
     const int pieces = 3 * (q1 - q0);
     for (int p0 = t; p0 < pieces; p0 += 4 * 256) {
       uint4 v[4];
@@ -651,7 +678,7 @@ __global__ void __launch_bounds__(256)
         const int e = p / 3;
         part[k] = p - 3 * e;
         d[k] = p < pieces ? s_dst[e] : -1;
-        if (d[k] >= 0) v[k] = src[p];
+        v[k] = d[k] >= 0 ? src[p] : make_uint4(0u, 0u, 0u, 0u);
       }
 #pragma unroll
       for (int k = 0; k < 4; k++)
@@ -660,6 +687,11 @@ __global__ void __launch_bounds__(256)
           if (EXPORT == 1) hdst[3 * (size_t)d[k] + part[k]] = v[k];
           if (EXPORT == 2 && part[k] == 1)  // (piece 1 of a record: v2p, i2p, u1c, v1c)
             xy_dst[d[k]] = (uint32_t)(int32_t)__uint_as_float(v[k].z) | ((uint32_t)(int32_t)__uint_as_float(v[k].w) << 16);
+          if (EXPORT >= 3 && part[k] == 1 && d[k] < key_cap) {
+            const uint64_t key = vsm_chain_key(__uint_as_float(v[k].z), __uint_as_float(v[k].w), d[k]);
+            keys[d[k]] = key;
+            if (EXPORT == 4 && d[k] < ko.host_cap) hkeys[d[k]] = key;
+          }
         }
     }
   }
@@ -1130,7 +1162,7 @@ hipError_t vsm_upload(hipStream_t s, void *dst_device, const void *src_pinned, s
 // One launch serves `npairs` frame pairs (blockIdx.y); jobs == nullptr: the single pair job0.
 // pass: 0 = sparse lists (list1/hlist1/count[0]), 1 = dense lists.  max_nq bounds nq[pass].
 bool vsm_launch_match(hipStream_t s, VsmProf &pf, const VsmImage *d_imgs, const VsmPair *d_pairs, const VsmJob *d_jobs,
-                      const VsmJob &job0, int npairs, const VsmDims &d, const VsmMatchCfg &cfg, int max_nq, int fuse_export, uint32_t *xy_dst) {
+                      const VsmJob &job0, int npairs, const VsmDims &d, const VsmMatchCfg &cfg, int max_nq, int fuse_export, uint32_t *xy_dst, const VsmKeyOut *keys) {
   // lanes per query: the chain is latency-bound per wavefront, so big batches want many
   // queries per wave (G = 2..4) and a lone frame pair wants more lanes per query (G = 8).
   const long total_q = (long)npairs * max_nq;
@@ -1162,24 +1194,35 @@ bool vsm_launch_match(hipStream_t s, VsmProf &pf, const VsmImage *d_imgs, const 
       VSM_MATCH_LAUNCH(8);
     pf.end(s);
   }
-  const int nblk = max(cdiv(max_nq, 256), 1);
   pf.begin(cfg.sparse ? VSM_K_COMPACT1 : VSM_K_COMPACT2, s);
-  bool fused = false;
-  if (cfg.method == 2) {
-    const dim3 grid(std::max(1, cdiv(max_nq, QUAD_SPAN)), npairs);
-    if (fuse_export == 1)
-      hipLaunchKernelGGL(k_compact_quad<1>, grid, dim3(256), 0, s, d_pairs, d_jobs, job0, pass, nullptr);
-    else if (fuse_export == 2 && xy_dst && npairs == 1)
-      hipLaunchKernelGGL(k_compact_quad<2>, grid, dim3(256), 0, s, d_pairs, d_jobs, job0, pass, xy_dst);
-    else
-      hipLaunchKernelGGL(k_compact_quad<0>, grid, dim3(256), 0, s, d_pairs, d_jobs, job0, pass, nullptr);
-    fused = fuse_export == 1 || (fuse_export == 2 && xy_dst && npairs == 1);
-  } else {
-    hipLaunchKernelGGL(k_compact_count, dim3(nblk, npairs), dim3(256), 0, s, d_pairs, d_jobs, job0, cfg.method, pass);
-    hipLaunchKernelGGL(k_compact_write, dim3(nblk, npairs), dim3(256), 0, s, d_pairs, d_jobs, job0, cfg.method, pass);
-  }
+  const bool fused = vsm_launch_compact(s, d_pairs, d_jobs, job0, npairs, cfg.method, pass, max_nq, keys, fuse_export, xy_dst);
   pf.end(s);
   return fused;  // the export asked for went along with the compaction (quad matching): no launch of its own
+}
+
+// the ordered compaction of a matching pass: which kernel form takes it (the one place that decides; the return value as above)
+bool vsm_launch_compact(hipStream_t s, const VsmPair *d_pairs, const VsmJob *d_jobs, const VsmJob &job0, int npairs, int method, int pass, int max_nq,
+                        const VsmKeyOut *keys, int fuse_export, uint32_t *xy_dst) {
+  const VsmKeyOut ko = keys ? *keys : VsmKeyOut{nullptr, 0, 0};
+  if (method == 2) {
+    const dim3 grid(std::max(1, cdiv(max_nq, QUAD_SPAN)), npairs);
+    const bool fused = fuse_export == 1 || (fuse_export == 2 && xy_dst && npairs == 1);
+    if (keys && !fuse_export && ko.host)
+      hipLaunchKernelGGL(k_compact_quad<4>, grid, dim3(256), 0, s, d_pairs, d_jobs, job0, pass, nullptr, ko);
+    else if (keys && !fuse_export)
+      hipLaunchKernelGGL(k_compact_quad<3>, grid, dim3(256), 0, s, d_pairs, d_jobs, job0, pass, nullptr, ko);
+    else if (fuse_export == 1)
+      hipLaunchKernelGGL(k_compact_quad<1>, grid, dim3(256), 0, s, d_pairs, d_jobs, job0, pass, nullptr, ko);
+    else if (fused)
+      hipLaunchKernelGGL(k_compact_quad<2>, grid, dim3(256), 0, s, d_pairs, d_jobs, job0, pass, xy_dst, ko);
+    else
+      hipLaunchKernelGGL(k_compact_quad<0>, grid, dim3(256), 0, s, d_pairs, d_jobs, job0, pass, nullptr, ko);
+    return fused;
+  }
+  const int nblk = max(cdiv(max_nq, 256), 1);
+  hipLaunchKernelGGL(k_compact_count, dim3(nblk, npairs), dim3(256), 0, s, d_pairs, d_jobs, job0, method, pass);
+  hipLaunchKernelGGL(k_compact_write, dim3(nblk, npairs), dim3(256), 0, s, d_pairs, d_jobs, job0, method, pass, keys && !fuse_export ? 1 : 0, ko);
+  return false;
 }
 
 void vsm_launch_export(hipStream_t s, VsmProf &pf, const VsmPair *d_pairs, int npairs, int pass, int n_upper) {

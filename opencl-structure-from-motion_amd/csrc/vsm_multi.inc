@@ -178,6 +178,11 @@ int vsm_multi_process(vsm_multi *m, const uint8_t *left, const uint8_t *right, i
     VsmJob *d_jobs = c.d_jobs;
     VSM_CHK(vsm_upload(h->stream, d_jobs, h_jobs, sizeof(VsmJob) * K));
     VsmMatchCfg cfg = make_cfg(p, method, h->sw.match_heads && c.has_heads);
+    // option fused_keys: the chains' job tables go up in front of the matching launches and the compactions write the chains'
+    // keys - into the pair bank and, the single stream having nothing beside it that a store across PCIe could hold up, into
+    // the host-mapped arrays the pool sorts from; no k_upload + k_dc2_keys between a compaction and its chain's sort kernel.
+    // (refinement = 2 shortens the lists behind the compaction: keys by k_dc2_keys behind it, as before)
+    const bool fused_keys = h->sw.fused_keys && p.refinement != 2;
     VsmJob dummy;
     memset(&dummy, 0, sizeof(dummy));
     // Few sequences: the first-pass lists (0.7 k matches) go to the host pool, a list per thread - the device chain is a row
@@ -199,11 +204,18 @@ int vsm_multi_process(vsm_multi *m, const uint8_t *left, const uint8_t *right, i
       // ---- pass 1 and its chain: removeOutliers + computePriorStatistics on the device (viso/matcher.cpp:222-226) ----
       cfg.sparse = 1;
       cfg.use_prior = 0;
-      vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, K, c.dims, cfg, max_nq[0]);
       Dc2Bank &B = m->bank1;
-      for (int i = 0; i < K; i++) B.fill_job(i, c.h_pairs[i].list1, c.h_pairs[i].count, false, nullptr, nullptr, c.h_pairs[i].ranges);
-      VSM_CHK(vsm_upload(h->stream, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * K));
-      vsm_dc2_launch_keys(h->stream, B.d_jobs, K, max_nq[0]);  // (also into host-mapped memory)
+      for (int i = 0; i < K; i++)
+        B.fill_job(i, c.h_pairs[i].list1, c.h_pairs[i].count, false, nullptr, nullptr, c.h_pairs[i].ranges, nullptr, false, fused_keys ? c.h_pairs[i].keys[0] : nullptr, c.hm_lcount + 2 * i);
+      if (fused_keys) {  // the chain's job table first, the keys from the compaction - also into host-mapped memory (see above)
+        VSM_CHK(vsm_upload(h->stream, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * K));
+        const VsmKeyOut ko = {B.dev_of(B.host_keys(0)), Dc2Bank::al((size_t)B.cap * 8), B.cap};
+        vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, K, c.dims, cfg, max_nq[0], 0, nullptr, &ko);
+      } else {
+        vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, K, c.dims, cfg, max_nq[0]);
+        VSM_CHK(vsm_upload(h->stream, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * K));
+        vsm_dc2_launch_keys(h->stream, B.d_jobs, K, max_nq[0]);  // (also into host-mapped memory)
+      }
       VSM_CHK(hipEventRecord(m->ev_a, h->stream));
       dc2_enqueue_mesh(h->stream, B, K, max_nq[0]);
       // Triangle's vertex sort of the K short lists on the pool (a few microseconds each) while the device triangulates: the
@@ -211,7 +223,7 @@ int vsm_multi_process(vsm_multi *m, const uint8_t *left, const uint8_t *right, i
       VSM_CHK(hipEventSynchronize(m->ev_a));
       h->pool->run(K, [&](int i) {
         static thread_local ExactDelaunay sorter;
-        const int32_t n = B.h_n[i];
+        const int32_t n = B.list_n(i);
         int32_t *out = B.host_ties_of(i);
         out[0] = (n > 3 && n <= B.cap) ? sorter.sort_ties(B.host_keys(i), n, out + 1, (B.ties_stride - 1) / 2) : 0;
       });
@@ -221,16 +233,23 @@ int vsm_multi_process(vsm_multi *m, const uint8_t *left, const uint8_t *right, i
     // ---- pass 2, refinement, final removeOutliers (viso/matcher.cpp:229-232) ----
     cfg.sparse = 0;
     cfg.use_prior = p.multi_stage ? 1 : 0;
-    vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, K, c.dims, cfg, max_nq[1]);
     Dc2Bank &B = m->bank2;
     for (int i = 0; i < K; i++)
-      B.fill_job(i, c.h_pairs[i].list2, c.h_pairs[i].count + 1, false, (vsm_p_match *)(m->arena.res_dev + m->arena.slot * i), m->arena.res_cnt_dev + i, nullptr);
-    VSM_CHK(vsm_upload(h->stream, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * K));
+      B.fill_job(i, c.h_pairs[i].list2, c.h_pairs[i].count + 1, false, (vsm_p_match *)(m->arena.res_dev + m->arena.slot * i), m->arena.res_cnt_dev + i, nullptr, nullptr, false,
+                 fused_keys ? c.h_pairs[i].keys[1] : nullptr, c.hm_lcount + 2 * i + 1);
+    if (fused_keys) {
+      VSM_CHK(vsm_upload(h->stream, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * K));
+      const VsmKeyOut ko = {B.dev_of(B.host_keys(0)), Dc2Bank::al((size_t)B.cap * 8), B.cap};
+      vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, K, c.dims, cfg, max_nq[1], 0, nullptr, &ko);
+    } else {
+      vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, K, c.dims, cfg, max_nq[1]);
+      VSM_CHK(vsm_upload(h->stream, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * K));
+    }
     if (p.refinement == 2) {  // sub-pixel fits drop matches: they come before the keys of what is left (section 6b of DESIGN.md)
       vsm_launch_refine(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, K, c.dims, c.dims, method, p.refinement, max_nq[1]);
       vsm_launch_parabolic_apply(h->stream, h->prof, d_pairs, K);
     }
-    vsm_dc2_launch_keys(h->stream, B.d_jobs, K, max_nq[1]);  // (also into host-mapped memory: the pool sorts them)
+    if (!fused_keys) vsm_dc2_launch_keys(h->stream, B.d_jobs, K, max_nq[1]);  // (also into host-mapped memory: the pool sorts them)
     VSM_CHK(hipEventRecord(m->ev_keys, h->stream));
     dc2_enqueue_mesh(h->stream, B, K, max_nq[1]);
     if (p.refinement == 1) vsm_launch_refine(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, K, c.dims, c.dims, method, p.refinement, max_nq[1]);
@@ -241,7 +260,7 @@ int vsm_multi_process(vsm_multi *m, const uint8_t *left, const uint8_t *right, i
     h->pool->run(K, [&](int i) {
       static thread_local ExactDelaunay sorter;
       static thread_local std::vector<uint64_t> keys;
-      const int32_t n = B.h_n[i];
+      const int32_t n = B.list_n(i);
       int32_t *out = B.host_ties_of(i);
       if (n > 3 && n <= B.cap) {
         keys.assign(B.host_keys(i), B.host_keys(i) + n);

@@ -236,6 +236,11 @@ int vsm_pairs_run(vsm_handle *h, const uint8_t *left, const uint8_t *right, int6
       if ((p.multi_stage && !P.bank1.reserve(C, std::max(max_nq[0], 64), true)) || !P.bank2.reserve(C, std::max(max_nq[1], 64), true)) return fail(VSM_EHIP);
       VSM_CHK(vsm_upload(h->stream, d_jobs, h_jobs, sizeof(VsmJob) * n));
       VsmMatchCfg cfg = make_cfg(p, method, h->sw.match_heads && c.has_heads);
+      // option fused_keys: the chains' job tables go up in front of the matching launches and the compactions write the chains'
+      // keys - into the pair bank and, the single stream having nothing beside it that a store across PCIe could hold up, into
+      // the host-mapped arrays the pool sorts from; no k_upload + k_dc2_keys between a compaction and its chain's sort kernel.
+      // (refinement = 2 shortens the lists behind the compaction: keys by k_dc2_keys behind it, as before)
+      const bool fused_keys = h->sw.fused_keys && p.refinement != 2;
       // few pairs: the first-pass lists go to the host pool, a list per thread; else the device chain (vsm_multi.inc has the measurements)
       const bool host_p1 = p.multi_stage && (h->sw.multi_host_pass1 >= 0 ? h->sw.multi_host_pass1 != 0 : n <= h->pool->size());
       if (host_p1) {
@@ -252,17 +257,24 @@ int vsm_pairs_run(vsm_handle *h, const uint8_t *left, const uint8_t *right, int6
         // ---- pass 1 and its chain: removeOutliers + computePriorStatistics on the device ----
         cfg.sparse = 1;
         cfg.use_prior = 0;
-        vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, n, c.dims, cfg, max_nq[0]);
         Dc2Bank &B = P.bank1;
-        for (int i = 0; i < n; i++) B.fill_job(i, c.h_pairs[i].list1, c.h_pairs[i].count, false, nullptr, nullptr, c.h_pairs[i].ranges);
-        VSM_CHK(vsm_upload(h->stream, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * n));
-        vsm_dc2_launch_keys(h->stream, B.d_jobs, n, max_nq[0]);  // (also into host-mapped memory)
+        for (int i = 0; i < n; i++)
+          B.fill_job(i, c.h_pairs[i].list1, c.h_pairs[i].count, false, nullptr, nullptr, c.h_pairs[i].ranges, nullptr, false, fused_keys ? c.h_pairs[i].keys[0] : nullptr, c.hm_lcount + 2 * i);
+        if (fused_keys) {  // the chain's job table first, the keys from the compaction - also into host-mapped memory (see above)
+          VSM_CHK(vsm_upload(h->stream, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * n));
+          const VsmKeyOut ko = {B.dev_of(B.host_keys(0)), Dc2Bank::al((size_t)B.cap * 8), B.cap};
+          vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, n, c.dims, cfg, max_nq[0], 0, nullptr, &ko);
+        } else {
+          vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, n, c.dims, cfg, max_nq[0]);
+          VSM_CHK(vsm_upload(h->stream, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * n));
+          vsm_dc2_launch_keys(h->stream, B.d_jobs, n, max_nq[0]);  // (also into host-mapped memory)
+        }
         VSM_CHK(hipEventRecord(P.ev_a, h->stream));
         dc2_enqueue_mesh(h->stream, B, n, max_nq[0]);
         VSM_CHK(hipEventSynchronize(P.ev_a));
         h->pool->run(n, [&](int i) {  // Triangle's vertex sort of the short lists on the pool while the device triangulates
           static thread_local ExactDelaunay sorter;
-          const int32_t nl = B.h_n[i];
+          const int32_t nl = B.list_n(i);
           int32_t *out = B.host_ties_of(i);
           out[0] = (nl > 3 && nl <= B.cap) ? sorter.sort_ties(B.host_keys(i), nl, out + 1, (B.ties_stride - 1) / 2) : 0;
         });
@@ -272,16 +284,23 @@ int vsm_pairs_run(vsm_handle *h, const uint8_t *left, const uint8_t *right, int6
       // ---- pass 2, refinement, final removeOutliers (viso/matcher.cpp:229-232) ----
       cfg.sparse = 0;
       cfg.use_prior = p.multi_stage ? 1 : 0;
-      vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, n, c.dims, cfg, max_nq[1]);
       Dc2Bank &B = P.bank2;
       for (int i = 0; i < n; i++)
-        B.fill_job(i, c.h_pairs[i].list2, c.h_pairs[i].count + 1, false, (vsm_p_match *)(P.arena.res_dev + P.arena.slot * i), P.arena.res_cnt_dev + i, nullptr);
-      VSM_CHK(vsm_upload(h->stream, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * n));
+        B.fill_job(i, c.h_pairs[i].list2, c.h_pairs[i].count + 1, false, (vsm_p_match *)(P.arena.res_dev + P.arena.slot * i), P.arena.res_cnt_dev + i, nullptr, nullptr, false,
+                   fused_keys ? c.h_pairs[i].keys[1] : nullptr, c.hm_lcount + 2 * i + 1);
+      if (fused_keys) {
+        VSM_CHK(vsm_upload(h->stream, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * n));
+        const VsmKeyOut ko = {B.dev_of(B.host_keys(0)), Dc2Bank::al((size_t)B.cap * 8), B.cap};
+        vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, n, c.dims, cfg, max_nq[1], 0, nullptr, &ko);
+      } else {
+        vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, n, c.dims, cfg, max_nq[1]);
+        VSM_CHK(vsm_upload(h->stream, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * n));
+      }
       if (p.refinement == 2) {  // sub-pixel fits drop matches: they come before the keys of what is left
         vsm_launch_refine(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, n, c.dims, c.dims, method, p.refinement, max_nq[1]);
         vsm_launch_parabolic_apply(h->stream, h->prof, d_pairs, n);
       }
-      vsm_dc2_launch_keys(h->stream, B.d_jobs, n, max_nq[1]);  // (also into host-mapped memory: the pool sorts them)
+      if (!fused_keys) vsm_dc2_launch_keys(h->stream, B.d_jobs, n, max_nq[1]);  // (also into host-mapped memory: the pool sorts them)
       VSM_CHK(hipEventRecord(P.ev_keys, h->stream));
       dc2_enqueue_mesh(h->stream, B, n, max_nq[1]);
       if (p.refinement == 1) vsm_launch_refine(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, n, c.dims, c.dims, method, p.refinement, max_nq[1]);
@@ -291,7 +310,7 @@ int vsm_pairs_run(vsm_handle *h, const uint8_t *left, const uint8_t *right, int6
       h->pool->run(n, [&](int i) {  // Triangle's vertex sort of every list on the pool while the device triangulates
         static thread_local ExactDelaunay sorter;
         static thread_local std::vector<uint64_t> keys;
-        const int32_t nl = B.h_n[i];
+        const int32_t nl = B.list_n(i);
         int32_t *out = B.host_ties_of(i);
         if (nl > 3 && nl <= B.cap) {
           keys.assign(B.host_keys(i), B.host_keys(i) + nl);

@@ -66,6 +66,7 @@ struct Dc2Bank {
     }
     memset(h_block, 0, h_bytes);
     pp.resize(npairs);
+    n_src.assign(npairs, nullptr);
     uint8_t *b = d_block;
     auto take = [&](size_t bytes) {
       uint8_t *r = b;
@@ -101,6 +102,12 @@ struct Dc2Bank {
     }
     return true;
   }
+  // list length of job i as the host sees it: the word k_dc2_keys writes (min(count, cap)), or - jobs whose keys the
+  // compaction wrote, no key kernel - the count the compaction itself put into host-mapped memory (fill_job's host_count, the
+  // pair's hcount[pass]).  That count is NOT clamped at cap: every reader checks n <= cap or takes the minimum itself, and the
+  // device side declines a list beyond cap (k_dc2_prepare) whoever made its keys.
+  std::vector<const int32_t *> n_src;  // per job; set by every fill_job
+  int32_t list_n(int i) const { return n_src[i] ? *n_src[i] : h_n[i]; }
   uint64_t *host_keys(int i) const { return (uint64_t *)((uint8_t *)h_keys + al((size_t)cap * 8) * i); }
   int32_t *host_ties_of(int i) const { return (int32_t *)((uint8_t *)h_ties + al((size_t)ties_stride * 4) * i); }
   template <typename T>
@@ -108,18 +115,23 @@ struct Dc2Bank {
     return (T *)(h_block_dev + ((uint8_t *)host_ptr - h_block));
   }
   // job i: the chain of list `list` / `count`; gpu_ties: the verdicts come from k_dc2_ties, else from the host
+  // pair_keys: the list's keys are where the matching pass's compaction wrote them (VsmPair::keys, fused_keys) - no key
+  // kernel runs for this job, the keys the pool sorts leave by a DMA copy out of the pair bank or by the compaction's own
+  // stores, and host_count is the host view of the count that compaction writes (list_n)
   void fill_job(int i, const vsm_p_match *list, const int32_t *count, bool gpu_ties, vsm_p_match *out, int32_t *h_out_count,
-                float *ranges, uint32_t *h_keep = nullptr, bool keys_by_dma = false) {
+                float *ranges, uint32_t *h_keep = nullptr, bool keys_by_dma = false, uint64_t *pair_keys = nullptr,
+                const int32_t *host_count = nullptr) {
     const PairPtr &q = pp[i];
+    n_src[i] = pair_keys ? host_count : nullptr;
     VsmDc2Job &jb = h_jobs[i];
     memset(&jb, 0, sizeof(jb));
     jb.list = list;
     jb.count = count;
     jb.cap = cap;
     jb.kd_stride = cap;
-    jb.keys_in = q.keys_in;
+    jb.keys_in = pair_keys ? pair_keys : q.keys_in;
     // (keys_by_dma: the keys the pool sorts leave by a DMA copy of keys_in, not by stores of the key kernel)
-    jb.h_keys = (!gpu_ties && host_ties && !keys_by_dma) ? dev_of(host_keys(i)) : nullptr;
+    jb.h_keys = (!gpu_ties && host_ties && !keys_by_dma && !pair_keys) ? dev_of(host_keys(i)) : nullptr;
     jb.h_n = dev_of(h_n + i);
     jb.key_sorted = q.key_sorted;
     jb.key = q.key;
@@ -426,7 +438,7 @@ static void seq2_destroy(vsm_handle *h) {
 static void seq2_close_gaps(Seq2Chunk *ch, vsm_handle *h, int i) {
   Seq2 &S = *h->seq2;
   const int32_t f = ch->f0 + i;
-  const int32_t cnt = std::max(S.res_cnt[f], 0), n_all = std::max(0, std::min(ch->B->h_n[i], ch->B->cap));
+  const int32_t cnt = std::max(S.res_cnt[f], 0), n_all = std::max(0, std::min(ch->B->list_n(i), ch->B->cap));
   vsm_p_match *rec = (vsm_p_match *)(S.res + S.res_off[f]);
   const uint32_t *keep = S.keep + S.keep_words * (size_t)f;
   // runs of consecutive survivors move in one piece each (a list loses a match in twelve or so: runs of a few hundred bytes)
@@ -561,7 +573,7 @@ static void seq2_keys_ready(Seq2Chunk *ch, int first, int last) {
     const int i = first + t;
     if (i < last) {
       static thread_local ExactDelaunay sorter;
-      const int32_t n = B.h_n[i];
+      const int32_t n = B.list_n(i);
       int32_t *out = B.host_ties_of(i);
       if (n > 3 && n <= B.cap) {  // (sort_ties works on a copy of its own: one pass over the DMA'd keys, then cache-resident work)
         out[0] = sorter.sort_ties(B.host_keys(i), n, out + 1, (B.ties_stride - 1) / 2);
@@ -582,7 +594,7 @@ static void seq2_keys_ready(Seq2Chunk *ch, int first, int last) {
           if (!ch->warm_claim[j].load(std::memory_order_acquire)) {  // (a list whose gaps are being closed already needs no warming)
             Seq2 &S = *h2->seq2;
             const int32_t f = ch->f0 + j;
-            const int32_t n_all = std::max(0, std::min(ch->B->h_n[j], ch->B->cap));
+            const int32_t n_all = std::max(0, std::min(ch->B->list_n(j), ch->B->cap));
             const volatile uint64_t *p = (const volatile uint64_t *)(S.res + S.res_off[f]);
             uint64_t acc = 0;
             for (size_t w = 0, nw = (size_t)n_all * sizeof(vsm_p_match) / 8; w < nw; w += 8) acc += p[w];  // (one word per 64-byte line)
@@ -763,7 +775,8 @@ struct Seq2Call {
   const int sides = right ? 2 : 1;
   // --- the plan: const once the set-up is through
   const bool host_in = !on_device;
-  const int keys_dma = sw.seq_keys_dma >= 0 ? sw.seq_keys_dma : (h->pool->size() >= 10 ? 2 : 1);  // (vsm_api.cpp: VsmSwitches)
+  // (vsm_api.cpp: VsmSwitches; 0 = stores of k_dc2_keys, which fused_keys does not run: 1 then)
+  const int keys_dma = sw.seq_keys_dma >= 0 ? ((sw.seq_keys_dma == 0 && sw.fused_keys && p.refinement != 2) ? 1 : sw.seq_keys_dma) : (h->pool->size() >= 10 ? 2 : 1);
   const Seq2Plan plan = seq2_plan(n_frames, h->pool->size(), host_in, sw.seq_chunk, sw.seq_first_chunk, getenv("VSM_SEQ_PLAN"));
   const int C = plan.C;
   const std::vector<int32_t> &chunk_start = plan.start;
@@ -779,6 +792,13 @@ struct Seq2Call {
   // enqueued, so each kernel's HIP-event time is its time with the GPU to itself (bench.py's "alone" figures).  Same
   // kernels, same data, same results.
   const bool serial = sw.seq_serial;
+  // Option fused_keys: a chain's keys are written by the compaction of the matching pass in front of it, into the PAIR bank
+  // (VsmPair::keys), and its job table is uploaded before that pass is launched - behind the compaction's event the chain
+  // starts on its first real work.  Who guards the key arrays: the rule of the lists they lie beside - a pair bank comes round
+  // after kPairBanks chunks and run_ahead / the in-order loop wait for the chunk that used it last (wait_for_chunk); a chain
+  // slab (bank1[k & 1]) would not do, the first pass of chunk k runs while chunk k - 2's pass-1 chain may still read its slab.
+  // (refinement = 2 shortens the lists behind the compaction: its chains make their keys themselves, k_dc2_keys behind ev_ref)
+  const bool fused = sw.fused_keys && p.refinement != 2;
   const int gpu_sorts_default = h->pool->size() <= 2 ? 67 : (h->pool->size() == 3 ? 50 : (h->pool->size() == 4 ? 33 : 0));  // (four threads: 7.0 ms without a share, 8.3 with one)
   const bool split_sorts = nchunks == 2 && sw.seq_gpu_sorts < 0 && gpu_sorts_default > 0 && !serial;
   const bool p2_first = sw.seq_p2_first >= 0 ? sw.seq_p2_first != 0 : (h->pool->size() >= 5 && h->pool->size() < 10 && (sw.seq_gpu_sorts >= 0 ? sw.seq_gpu_sorts : gpu_sorts_default) == 0);
@@ -1062,12 +1082,17 @@ struct Seq2Call {
     }
     HIPCHK(vsm_upload(h->stream, d_jobs, h_jobs, sizeof(VsmJob) * n));
     if (p.multi_stage) {
+      if (fused) {  // (the pass-1 chain's job table: everything in it is known now)
+        const int rc = upload_chain1_jobs(k);
+        if (rc != VSM_OK) return rc;
+      }
       VsmMatchCfg cfg = make_cfg(p, method, h->sw.match_heads && c.has_heads);
       VsmJob dummy;
       memset(&dummy, 0, sizeof(dummy));
       cfg.sparse = 1;
       cfg.use_prior = 0;
-      vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, n, c.dims, cfg, q.max_nq[0]);
+      const VsmKeyOut ko = {nullptr, 0, 0};  // (the keys the pool sorts leave by a DMA copy, start_chain1)
+      vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, n, c.dims, cfg, q.max_nq[0], 0, nullptr, fused ? &ko : nullptr);
       q.ev_p1 = S.get_event();
       q.ev_prior = S.get_event();
       if (!q.ev_p1 || !q.ev_prior) return VSM_EHIP;
@@ -1077,6 +1102,32 @@ struct Seq2Call {
   }
   // ... and the chain of its pass-1 lists (outlier removal + prior boxes) on a stream of its own: a dozen and a half enqueue
   // calls that the caller makes AFTER it has given the main stream its next kernels - the boxes are wanted two chunks later
+  // fused_keys: the job table of chunk k's pass-1 chain, filled and sent on the chain's own stream BEFORE the first pass is
+  // launched (start_chunk): nothing in it comes from the matching - list, count and key pointers of the pair bank, slab
+  // pointers, the capacity.  The three waits for the slab bank1[k & 1] come along: the copy of its last job table out of the
+  // pinned twin (bank1_copied: the caller's thread waits here, a copy enqueued two chunks ago), the slab's last chain
+  // (ev_prior of chunk k - 2: the chain's stream waits in front of the upload; recorded by now - start_chunk has been
+  // through finish_chain1 of every chunk in front) and, should the slab have to grow, the same event on the host.
+  int upload_chain1_jobs(int k) {
+    Ck &q = ck[k];
+    const int n = q.n, first_pair = q.first_pair;
+    Dc2Bank &B = S.bank1[k & 1];
+    const int want = std::max(q.max_nq[0], 64);
+    hipEvent_t last_chain = k > 1 ? ck[k - 2].ev_prior : nullptr;
+    if (last_chain && (C > B.npairs || want > B.cap || (ties1_host && !B.host_ties))) HIPCHK(hipEventSynchronize(last_chain));
+    if (!B.reserve(C, want, ties1_host)) return VSM_EHIP;
+    if (S.bank1_copied[k & 1]) HIPCHK(hipEventSynchronize(S.bank1_copied[k & 1]));
+    for (int i = 0; i < n; i++)
+      B.fill_job(i, c.h_pairs[first_pair + i].list1, c.h_pairs[first_pair + i].count, !ties1_host, nullptr, nullptr, c.h_pairs[first_pair + i].ranges,
+                 nullptr, false, c.h_pairs[first_pair + i].keys[0], c.hm_lcount + 2 * (first_pair + i));
+    hipStream_t c1 = S.cs(k);
+    if (last_chain) HIPCHK(hipStreamWaitEvent(c1, last_chain, 0));
+    HIPCHK(vsm_upload(c1, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * n));
+    S.bank1_copied[k & 1] = S.get_event();
+    if (!S.bank1_copied[k & 1]) return VSM_EHIP;
+    HIPCHK(hipEventRecord(S.bank1_copied[k & 1], c1));
+    return VSM_OK;
+  }
   int start_chain1(int k) {
     Ck &q = ck[k];
     if (!p.multi_stage) return VSM_OK;
@@ -1085,26 +1136,42 @@ struct Seq2Call {
       // (two slabs: a chunk's pass-1 chain takes half a millisecond, the first passes of the call's last chunks follow each other
       // faster than that - and the last chunk's boxes are what the main stream ends up waiting for)
       Dc2Bank &B = S.bank1[k & 1];
-      if (!B.reserve(C, std::max(q.max_nq[0], 64), ties1_host)) return VSM_EHIP;
-      if (S.bank1_copied[k & 1]) HIPCHK(hipEventSynchronize(S.bank1_copied[k & 1]));  // (the slab's last use: its copy of the job table)
-      for (int i = 0; i < n; i++)
-        B.fill_job(i, c.h_pairs[first_pair + i].list1, c.h_pairs[first_pair + i].count, !ties1_host, nullptr, nullptr,
-                   c.h_pairs[first_pair + i].ranges);
       hipStream_t c1 = S.cs(k);
-      if (k > 1 && ck[k - 2].ev_prior) HIPCHK(hipStreamWaitEvent(c1, ck[k - 2].ev_prior, 0));  // (the slab's last chain is through)
-      HIPCHK(hipStreamWaitEvent(c1, q.ev_p1, 0));
-      HIPCHK(vsm_upload(c1, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * n));
-      S.bank1_copied[k & 1] = S.get_event();
-      if (!S.bank1_copied[k & 1]) return VSM_EHIP;
-      HIPCHK(hipEventRecord(S.bank1_copied[k & 1], c1));
-      // keys, then the vertex sort (one wave per pair, a third of a millisecond) on a stream of its own beside kd order
-      // and triangulation; the support votes wait for both
-      h->prof.begin(VSM_K_DC_KEYS, c1);
-      vsm_dc2_launch_keys(c1, B.d_jobs, n, q.max_nq[0]);
-      h->prof.end(c1);
       hipEvent_t ev_keys = S.get_event(), ev_ties = S.get_event();
       if (!ev_keys || !ev_ties) return VSM_EHIP;
-      HIPCHK(hipEventRecord(ev_keys, c1));
+      if (fused) {
+        // the job table is in place (upload_chain1_jobs) and the first pass's compaction has written the keys: behind its event
+        // the chain starts on sort + kd order.  The keys the pool sorts cross by a strided DMA copy out of the pair bank, on the
+        // null stream beside the mesh (host-resident inputs keep that stream's engine busy with frames: the chain's own stream)
+        HIPCHK(hipStreamWaitEvent(c1, q.ev_p1, 0));
+        if (ties1_host) {
+          hipStream_t ks = host_in ? c1 : S.ns;
+          if (ks != c1) HIPCHK(hipStreamWaitEvent(ks, q.ev_p1, 0));
+          HIPCHK(hipMemcpy2DAsync(B.host_keys(0), Dc2Bank::al((size_t)B.cap * 8), c.h_pairs[first_pair].keys[0], c.pair_stride,
+                                  (size_t)std::min(std::max(q.max_nq[0], 1), B.cap) * 8, (size_t)n, hipMemcpyDeviceToHost, ks));
+          HIPCHK(hipEventRecord(ev_keys, ks));
+        } else {
+          HIPCHK(hipEventRecord(ev_keys, c1));
+        }
+      } else {
+          if (!B.reserve(C, std::max(q.max_nq[0], 64), ties1_host)) return VSM_EHIP;
+        if (S.bank1_copied[k & 1]) HIPCHK(hipEventSynchronize(S.bank1_copied[k & 1]));  // (the slab's last use: its copy of the job table)
+        for (int i = 0; i < n; i++)
+          B.fill_job(i, c.h_pairs[first_pair + i].list1, c.h_pairs[first_pair + i].count, !ties1_host, nullptr, nullptr,
+                     c.h_pairs[first_pair + i].ranges);
+        if (k > 1 && ck[k - 2].ev_prior) HIPCHK(hipStreamWaitEvent(c1, ck[k - 2].ev_prior, 0));  // (the slab's last chain is through)
+        HIPCHK(hipStreamWaitEvent(c1, q.ev_p1, 0));
+        HIPCHK(vsm_upload(c1, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * n));
+        S.bank1_copied[k & 1] = S.get_event();
+        if (!S.bank1_copied[k & 1]) return VSM_EHIP;
+        HIPCHK(hipEventRecord(S.bank1_copied[k & 1], c1));
+        // keys, then the vertex sort (one wave per pair, a third of a millisecond) on a stream of its own beside kd order
+        // and triangulation; the support votes wait for both
+        h->prof.begin(VSM_K_DC_KEYS, c1);
+        vsm_dc2_launch_keys(c1, B.d_jobs, n, q.max_nq[0]);
+        h->prof.end(c1);
+        HIPCHK(hipEventRecord(ev_keys, c1));
+      }
       if (ties1_host) {
         // The vertex sorts of these lists on the POOL, which has nothing to do before the call's first final keys: the key
         // kernel has written keys and counts into host-mapped memory; the mesh goes in now, the second part (tie patches,
@@ -1148,7 +1215,7 @@ struct Seq2Call {
     HIPCHK(hipEventSynchronize(q.ev_k1));
     h->pool->run(n, [&](int i) {
       static thread_local ExactDelaunay sorter;
-      const int32_t nl = B.h_n[i];
+      const int32_t nl = B.list_n(i);
       int32_t *out = B.host_ties_of(i);
       out[0] = (nl > 3 && nl <= B.cap) ? sorter.sort_ties(B.host_keys(i), nl, out + 1, (B.ties_stride - 1) / 2) : 0;
     });
@@ -1394,9 +1461,17 @@ struct Seq2Call {
       if (rc != VSM_OK) return rc;
       HIPCHK(hipStreamWaitEvent(h->stream, q.ev_prior, 0));
     }
+    if (fused) {
+      // the final chain's job table in front of the second pass's launch, on the chain's stream: its slab and the pinned twin
+      // of the table were last used by chunk k - kBanks, which is through (wait_for_chunk above) - no event to wait for
+      fill_chain_jobs(k);
+      std::lock_guard<std::mutex> lk(S.enq_mu);
+      HIPCHK(vsm_upload(ch->stream, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * n));
+    }
     cfg.sparse = 0;
     cfg.use_prior = p.multi_stage ? 1 : 0;
-    vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, n, c.dims, cfg, q.max_nq[1]);
+    const VsmKeyOut ko = {nullptr, 0, 0};  // (the final keys leave by DMA, enqueue_chain_head)
+    vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, n, c.dims, cfg, q.max_nq[1], 0, nullptr, fused ? &ko : nullptr);
     ch->ev_c2 = S.get_event();
     if (!ch->ev_c2) return VSM_EHIP;
     HIPCHK(hipEventRecord(ch->ev_c2, h->stream));
@@ -1421,12 +1496,13 @@ struct Seq2Call {
   }
   // The chain comes in two steps as well.  Its HEAD - jobs, keys, the keys' DMA copy and the pool task that waits for it - goes in
   // right behind the chunk's main-stream work: the vertex sorts are 25 ms of pool work per call and want their keys early.
-  int enqueue_chain_head(int k) {
+  // the final chain's job table on the host: who sorts which list, where everything lies (fused_keys: filled in front of the
+  // second pass, enqueue_main; else with the head)
+  void fill_chain_jobs(int k) {
     const Ck &q = ck[k];
     const int n = q.n, first_pair = q.first_pair;
     Seq2Chunk *ch = S.chunks[k].get();
     Dc2Bank &B = *ch->B;
-    hipEvent_t ev_c2 = ch->ev_c2;
     // Who sorts: the pool does a 7.4 k list in 125 us per thread, the device needs 3.2 ms for one (one wave, all dependent
     // scalar work) but does any number of lists side by side.  With six host threads or more the pool keeps up; below that it
     // is the longest pole (200 lists / 2 threads = 12.5 ms), so the device takes a share of every chunk (seq_gpu_sorts =
@@ -1445,19 +1521,31 @@ struct Seq2Call {
     for (int i = 0; i < n; i++) {
       const int32_t f = q.f0 + i;
       B.fill_job(i, c.h_pairs[first_pair + i].list2, c.h_pairs[first_pair + i].count + 1, i < ch->gpu_sorts,
-                 (vsm_p_match *)(S.res_stage + S.res_off[f]), S.res_cnt_dev + f, nullptr, S.res_early ? S.keep_dev + S.keep_words * (size_t)f : nullptr, keys_dma != 0);
+                 (vsm_p_match *)(S.res_stage + S.res_off[f]), S.res_cnt_dev + f, nullptr, S.res_early ? S.keep_dev + S.keep_words * (size_t)f : nullptr, keys_dma != 0,
+                 fused ? c.h_pairs[first_pair + i].keys[1] : nullptr, c.hm_lcount + 2 * (first_pair + i) + 1);
     }
+  }
+  int enqueue_chain_head(int k) {
+    const Ck &q = ck[k];
+    const int n = q.n, first_pair = q.first_pair;
+    Seq2Chunk *ch = S.chunks[k].get();
+    Dc2Bank &B = *ch->B;
+    hipEvent_t ev_c2 = ch->ev_c2;
+    if (!fused) fill_chain_jobs(k);
     hipStream_t s2 = ch->stream;
     hipEvent_t ev_jobs = nullptr;
     {
       // (the pool enqueues second parts on these streams too: what the caller puts on s2 here stays in one piece)
       std::lock_guard<std::mutex> lk(S.enq_mu);
       // jobs, keys (the chain itself only needs (u1c, v1c), which the refinement leaves alone)
+      // (fused_keys: both are there when the second pass's compaction is through - the head is this wait and the keys' copies)
       HIPCHK(hipStreamWaitEvent(s2, p.refinement == 2 ? ch->ev_ref : ev_c2, 0));
-      HIPCHK(vsm_upload(s2, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * n));
-      h->prof.begin(VSM_K_DC_KEYS, s2);
-      vsm_dc2_launch_keys(s2, B.d_jobs, n, q.max_nq[1]);
-      h->prof.end(s2);
+      if (!fused) {
+        HIPCHK(vsm_upload(s2, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * n));
+        h->prof.begin(VSM_K_DC_KEYS, s2);
+        vsm_dc2_launch_keys(s2, B.d_jobs, n, q.max_nq[1]);
+        h->prof.end(s2);
+      }
       ev_jobs = S.get_event();
       if (!ev_jobs) return VSM_EHIP;
       HIPCHK(hipEventRecord(ev_jobs, s2));
@@ -1496,7 +1584,8 @@ struct Seq2Call {
         for (int pc = 0; pc < pieces; pc++) {
           const int r0 = ch->gpu_sorts + (int)((int64_t)lists * pc / pieces), r1 = ch->gpu_sorts + (int)((int64_t)lists * (pc + 1) / pieces);
           if (r1 > r0 && keys_dma)
-            HIPCHK(hipMemcpy2DAsync(B.host_keys(r0), Dc2Bank::al((size_t)B.cap * 8), B.pp[r0].keys_in, B.pair_stride,
+            HIPCHK(hipMemcpy2DAsync(B.host_keys(r0), Dc2Bank::al((size_t)B.cap * 8), fused ? c.h_pairs[first_pair + r0].keys[1] : B.pp[r0].keys_in,
+                                    fused ? c.pair_stride : B.pair_stride,
                                     (size_t)std::min(std::max(q.max_nq[1], 1), B.cap) * 8, (size_t)(r1 - r0), hipMemcpyDeviceToHost, ks));
           hipEvent_t ev = S.get_event();
           if (!ev) {

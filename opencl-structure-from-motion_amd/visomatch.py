@@ -37,7 +37,7 @@ EXPORTS = ["vsm_default_params", "vsm_create", "vsm_destroy", "vsm_set_intrinsic
            "vsm_num_features", "vsm_get_features", "vsm_set_stage_capture", "vsm_stage_size", "vsm_stage_get",
            "vsm_num_ranges", "vsm_get_ranges", "vsm_get_gradients", "vsm_get_filter_responses", "vsm_get_counters",
            "vsm_get_timings", "vsm_set_profiling", "vsm_num_kernels", "vsm_kernel_name", "vsm_get_kernel_stats",
-           "vsm_host_delaunay", "vsm_host_delaunay_split", "vsm_debug_delaunay_gpu", "vsm_debug_dc_bench", "vsm_host_ties", "vsm_debug_ties_gpu", "vsm_host_outliers_and_prior", "vsm_host_outliers_and_prior_threads", "vsm_debug_dc2", "vsm_debug_dc2_band_factor", "vsm_debug_predicates", "vsm_debug_seq_plan", "vsm_debug_chunk_jobs", "vsm_debug_pair_jobs", "vsm_debug_refine", "vsm_debug_refine_check", "vsm_debug_parabolic_apply", "vsm_host_parabolic_fits", "vsm_local_cpus", "vsm_forkjoin_cpus", "vsm_device_pool_stats", "vsm_device_pool_trim", "vsm_sequence_run", "vsm_sequence_num_matches", "vsm_sequence_get_matches",
+           "vsm_host_delaunay", "vsm_host_delaunay_split", "vsm_debug_delaunay_gpu", "vsm_debug_dc_bench", "vsm_host_ties", "vsm_debug_ties_gpu", "vsm_host_outliers_and_prior", "vsm_host_outliers_and_prior_threads", "vsm_debug_dc2", "vsm_debug_dc2_band_factor", "vsm_debug_predicates", "vsm_debug_seq_plan", "vsm_debug_chunk_jobs", "vsm_debug_pair_jobs", "vsm_debug_refine", "vsm_debug_refine_check", "vsm_debug_parabolic_apply", "vsm_host_parabolic_fits", "vsm_debug_compact_keys", "vsm_local_cpus", "vsm_forkjoin_cpus", "vsm_device_pool_stats", "vsm_device_pool_trim", "vsm_sequence_run", "vsm_sequence_num_matches", "vsm_sequence_get_matches",
            "vsm_sequence_get_timings", "vsm_sequence_path", "vsm_pairs_run", "vsm_pairs_num_matches", "vsm_pairs_get_matches", "vsm_pairs_get_timings",
            "vsm_tracks_run", "vsm_pairs_tracks", "vsm_tracks_count", "vsm_tracks_num_obs", "vsm_tracks_get", "vsm_tracks_of_matches",
            "vsm_tracks_get_stats", "vsm_tracks_get_timings", "vsm_host_tracks",
@@ -191,6 +191,7 @@ def lib():
         L.vsm_debug_refine_check.argtypes = [i32, i32, vp, vp, i32]
         L.vsm_debug_parabolic_apply.argtypes = [vp, vp, vp, i32, vp, vp]
         L.vsm_host_parabolic_fits.argtypes = [vp, i32, vp, vp]
+        L.vsm_debug_compact_keys.argtypes = [i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp]
         L.vsm_pairs_run.argtypes = [vp, vp, vp, C.c_int64, C.c_int, i32, i32, i32, i32, i32, vp, i32, vp, vp]
         L.vsm_pairs_num_matches.argtypes = [vp, i32]
         L.vsm_pairs_get_matches.argtypes = [vp, i32, vp, i32]
@@ -840,6 +841,28 @@ def host_parabolic_fits(records, uv):
     ok = np.zeros(len(r), dtype=np.int32)
     _check(lib().vsm_host_parabolic_fits(_ptr(r), len(r), _ptr(out), _ptr(ok)), "vsm_host_parabolic_fits")
     return out, ok
+
+
+COMPACT_KEY_GUARD = 8
+
+
+def device_compact_keys(flags, raws, key_caps, method=2, pass_=1, old_keys=False):
+    """test hook: the matching passes' compaction over len(flags) pairs in one launch.  flags[k]: int32 [n_k] acceptance flags,
+    raws[k]: [n_k] per-query records, key_caps[k]: capacity of pair k's key array -> per pair (list with one guard record,
+    count, keys with COMPACT_KEY_GUARD guard words); what the kernels did not write holds 0xA5 bytes.  old_keys 1: the keys by
+    k_dc2_keys behind the plain compaction; 2: the keys as the fused store leaves them in its host-mapped second target."""
+    fs = [np.ascontiguousarray(f, dtype=np.int32) for f in flags]
+    rs = [np.ascontiguousarray(r, dtype=P_MATCH) for r in raws]
+    assert len(fs) == len(rs) == len(key_caps) and all(len(f) == len(r) for f, r in zip(fs, rs))
+    nq = np.array([len(f) for f in fs], dtype=np.int32)
+    caps = np.ascontiguousarray(key_caps, dtype=np.int32)
+    lists = [np.zeros(len(f) + 1, dtype=P_MATCH) for f in fs]
+    keys = [np.zeros(int(c) + COMPACT_KEY_GUARD, dtype=np.uint64) for c in caps]
+    counts = np.full(len(fs), -1, dtype=np.int32)
+    tab = lambda arrs: (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+    _check(lib().vsm_debug_compact_keys(int(method), int(pass_), len(fs), _ptr(nq), tab(fs), tab(rs), _ptr(caps), int(old_keys), tab(lists),
+                                        _ptr(counts), tab(keys)), "vsm_debug_compact_keys")
+    return [(l, int(n), k) for l, n, k in zip(lists, counts, keys)]
 
 
 def local_cpus():

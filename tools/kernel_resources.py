@@ -30,6 +30,7 @@ with tempfile.TemporaryDirectory() as td:
         meta = yaml.safe_load(doc)
         for k in meta.get("amdhsa.kernels", []):
             name = subprocess.run(["c++filt", k[".name"]], capture_output=True, text=True).stdout.strip()
+            name = name.replace("(anonymous namespace)::", "")  # (else the cut below takes the whole name)
             name = re.sub(r"\(.*", "", name).replace("void ", "")
             rows.append((name, k[".vgpr_count"], k.get(".agpr_count", 0), k[".sgpr_count"], k[".group_segment_fixed_size"],
                          k[".private_segment_fixed_size"], k[".max_flat_workgroup_size"], bool(k.get(".uses_dynamic_stack"))))
