@@ -1425,6 +1425,7 @@ static int seq_ingest_host_frames(vsm_handle *h, VsmCtx &c, int first_img, const
 }  // extern "C"
 #include "vsm_seq2.inc"
 #include "vsm_seq1.inc"
+#include "vsm_step.inc"
 #include "vsm_multi.inc"
 #include "vsm_pairs.inc"
 #include "vsm_tracks.inc"
@@ -1965,12 +1966,7 @@ int32_t vsm_debug_dc2(const vsm_params *p, const vsm_p_match *list, int32_t n, i
     dc2_enqueue_triangulation(nullptr, B, copies, n, gpu_ties != 0);
     if (!gpu_ties) {  // the host's verdicts (the look-ahead path computes them while the device triangulates)
       ok = hipDeviceSynchronize() == hipSuccess;
-      ExactDelaunay sorter;
-      for (int i = 0; i < copies && ok; i++) {
-        int32_t *o = B.host_ties_of(i);
-        const int32_t nn = B.h_n[i];
-        o[0] = nn > 3 ? sorter.sort_ties(B.host_keys(i), nn, o + 1, (B.ties_stride - 1) / 2) : 0;
-      }
+      for (int i = 0; i < copies && ok; i++) B.sort_ties_of(i);
     }
     // (VSM_DC2_EXPECT_LONG=0, tests: a list of 8193..16384 matches through the narrow form inside the LDS kernel, as in a handle
     // that has not met a long list yet)

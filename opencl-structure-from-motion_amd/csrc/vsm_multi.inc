@@ -13,9 +13,7 @@ struct vsm_multi {
   int K = 0;
   int64_t step = 0;
   int32_t w = 0, hh = 0;
-  Dc2Bank bank1, bank2;
-  hipEvent_t ev_feat = nullptr, ev_keys = nullptr, ev_a = nullptr, ev_b = nullptr;
-  VsmResArena arena;  // host-mapped survivors, one slot per sequence
+  VsmStep st;  // the step's banks, events and survivors (vsm_step.inc): one arena slot per sequence
   struct Seq {
     VsmEgoSeq *ego = nullptr;
     double T[16];
@@ -36,11 +34,7 @@ static void multi_release(vsm_multi *m) {
     (void)hipSetDevice(m->h->device);
     (void)hipStreamSynchronize(m->h->stream);
   }
-  for (hipEvent_t e : {m->ev_feat, m->ev_keys, m->ev_a, m->ev_b})
-    if (e) (void)hipEventDestroy(e);
-  m->bank1.release();
-  m->bank2.release();
-  m->arena.free();
+  m->st.release();
   for (auto &s : m->seq) vsm_ego_seq_destroy(s.ego);
   if (m->h) vsm_destroy(m->h);
   delete m;
@@ -62,9 +56,7 @@ vsm_multi *vsm_multi_create(const vsm_vo_stereo_params *p, int32_t n_sequences) 
     s.ego = vsm_ego_seq_create(p);
     for (int i = 0; i < 16; i++) s.T[i] = (i % 5 == 0) ? 1.0 : 0.0;
   }
-  bool ok = true;
-  for (hipEvent_t *e : {&m->ev_feat, &m->ev_keys, &m->ev_a, &m->ev_b}) ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
-  if (!ok) {
+  if (!m->st.create_events()) {
     multi_release(m);
     return nullptr;
   }
@@ -97,7 +89,7 @@ int vsm_multi_process(vsm_multi *m, const uint8_t *left, const uint8_t *right, i
     h->seq_chunk = K;
     m->step = 0;
     for (auto &s : m->seq) s.have_prev = false;
-    if (!m->arena.alloc(al256((size_t)c.cap_set[1] * sizeof(vsm_p_match)), (size_t)K)) {
+    if (!m->st.arena.alloc(al256((size_t)c.cap_set[1] * sizeof(vsm_p_match)), (size_t)K)) {
       c.ready = false;  // (the next call sets the context up again instead of running with half of it)
       return VSM_EHIP;
     }
@@ -106,13 +98,7 @@ int vsm_multi_process(vsm_multi *m, const uint8_t *left, const uint8_t *right, i
   }
   if ((size_t)c.dims.ub * c.dims.vb > 1024) return VSM_EARG;  // (k_dc2_prior keeps the bins' minima and maxima in LDS)
   // a step that fails after something was enqueued: drain the device, report, commit nothing
-  auto fail = [&](int rc) {
-    (void)hipStreamSynchronize(h->stream);
-    (void)hipGetLastError();
-    if (m->bank1.h_error) *m->bank1.h_error = 0;
-    if (m->bank2.h_error) *m->bank2.h_error = 0;
-    return rc;
-  };
+  auto fail = [&](int rc) { return m->st.fail(h->stream, rc); };
   const double t0 = now_us();
   const int bank = (int)(m->step & 1), first_img = 2 * bank * K, prev_img = 2 * (bank ^ 1) * K;
   // ---- pushBack of K frames: one launch per kernel over 2 K images ----
@@ -123,8 +109,8 @@ int vsm_multi_process(vsm_multi *m, const uint8_t *left, const uint8_t *right, i
     if (rc != VSM_OK) return fail(rc);
   }
   enqueue_features(h, c, first_img, 2 * K);
-  VSM_CHK(hipEventRecord(m->ev_feat, h->stream));
-  VSM_CHK(hipEventSynchronize(m->ev_feat));  // the feature counts are in host-mapped memory
+  VSM_CHK(hipEventRecord(m->st.ev_feat, h->stream));
+  VSM_CHK(hipEventSynchronize(m->st.ev_feat));  // the feature counts are in host-mapped memory
   VSM_CHK(hipGetLastError());
   const double t1 = now_us();
   // ---- one job per sequence ----
@@ -166,114 +152,13 @@ int vsm_multi_process(vsm_multi *m, const uint8_t *left, const uint8_t *right, i
   bool any = false;
   for (int i = 0; i < K; i++) any = any || valid[i];
   if (any) {
-    // every size limit of the step before anything of it is enqueued (the first-pass lists are sorted on the pool here: only
-    // the triangulation's own limits apply to them)
-    if (max_nq[0] > VSM_DC_KD_MAX_POINTS || max_nq[1] > VSM_DC_KD_MAX_POINTS || vsm_dc2_depth(std::max(max_nq[0], max_nq[1])) > VSM_DC2_MAX_DEPTH ||
-        (p.refinement == 2 && max_nq[1] > VSM_PARA_MAX_LIST)) {
+    if (!vsm_step_fits(p, max_nq)) {
       fprintf(stderr, "visomatch: vsm_multi_process: a match list of %d / %d entries is beyond the device chain\n", max_nq[0], max_nq[1]);
       return fail(VSM_EARG);
     }
-    if ((p.multi_stage && !m->bank1.reserve(K, std::max(max_nq[0], 64), true)) || !m->bank2.reserve(K, std::max(max_nq[1], 64), true)) return fail(VSM_EHIP);
-    const VsmPair *d_pairs = c.d_pairs;
-    VsmJob *d_jobs = c.d_jobs;
-    VSM_CHK(vsm_upload(h->stream, d_jobs, h_jobs, sizeof(VsmJob) * K));
-    VsmMatchCfg cfg = make_cfg(p, method, h->sw.match_heads && c.has_heads);
-    // option fused_keys: the chains' job tables go up in front of the matching launches and the compactions write the chains'
-    // keys - into the pair bank and, the single stream having nothing beside it that a store across PCIe could hold up, into
-    // the host-mapped arrays the pool sorts from; no k_upload + k_dc2_keys between a compaction and its chain's sort kernel.
-    // (refinement = 2 shortens the lists behind the compaction: keys by k_dc2_keys behind it, as before)
-    const bool fused_keys = h->sw.fused_keys && p.refinement != 2;
-    VsmJob dummy;
-    memset(&dummy, 0, sizeof(dummy));
-    // Few sequences: the first-pass lists (0.7 k matches) go to the host pool, a list per thread - the device chain is a row
-    // of latencies whatever the number of lists (0.4 ms for K = 8: keys, sort, sub-trees, two merge levels, votes, boxes),
-    // one thread triangulates such a list in 50-60 us.  (Option multi_host_pass1: -1 = up to as many sequences as pool threads.)
-    const bool host_p1 = p.multi_stage && (h->sw.multi_host_pass1 >= 0 ? h->sw.multi_host_pass1 != 0 : K <= h->pool->size());
-    if (host_p1) {
-      // ---- pass 1; removeOutliers + computePriorStatistics on the pool (viso/matcher.cpp:222-226) ----
-      cfg.sparse = 1;
-      cfg.use_prior = 0;
-      if (!vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, K, c.dims, cfg, max_nq[0], 1))
-        vsm_launch_export(h->stream, h->prof, d_pairs, K, 0, max_nq[0]);
-      VSM_CHK(hipEventRecord(m->ev_a, h->stream));
-      VSM_CHK(hipEventSynchronize(m->ev_a));  // the lists are in host-mapped memory
-      VSM_CHK(hipGetLastError());
-      const int32_t dims_c[3] = {w, hh, c.dims.bpl};
-      VSM_CHK(host_pass1_boxes(h, c, 0, K, valid.data(), method, dims_c));
-    } else if (p.multi_stage) {
-      // ---- pass 1 and its chain: removeOutliers + computePriorStatistics on the device (viso/matcher.cpp:222-226) ----
-      cfg.sparse = 1;
-      cfg.use_prior = 0;
-      Dc2Bank &B = m->bank1;
-      for (int i = 0; i < K; i++)
-        B.fill_job(i, c.h_pairs[i].list1, c.h_pairs[i].count, false, nullptr, nullptr, c.h_pairs[i].ranges, nullptr, false, fused_keys ? c.h_pairs[i].keys[0] : nullptr, c.hm_lcount + 2 * i);
-      if (fused_keys) {  // the chain's job table first, the keys from the compaction - also into host-mapped memory (see above)
-        VSM_CHK(vsm_upload(h->stream, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * K));
-        const VsmKeyOut ko = {B.dev_of(B.host_keys(0)), Dc2Bank::al((size_t)B.cap * 8), B.cap};
-        vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, K, c.dims, cfg, max_nq[0], 0, nullptr, &ko);
-      } else {
-        vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, K, c.dims, cfg, max_nq[0]);
-        VSM_CHK(vsm_upload(h->stream, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * K));
-        vsm_dc2_launch_keys(h->stream, B.d_jobs, K, max_nq[0]);  // (also into host-mapped memory)
-      }
-      VSM_CHK(hipEventRecord(m->ev_a, h->stream));
-      dc2_enqueue_mesh(h->stream, B, K, max_nq[0]);
-      // Triangle's vertex sort of the K short lists on the pool (a few microseconds each) while the device triangulates: the
-      // device's own sort of such a list is one wave for 0.36 ms, longer than the triangulation beside it
-      VSM_CHK(hipEventSynchronize(m->ev_a));
-      h->pool->run(K, [&](int i) {
-        static thread_local ExactDelaunay sorter;
-        const int32_t n = B.list_n(i);
-        int32_t *out = B.host_ties_of(i);
-        out[0] = (n > 3 && n <= B.cap) ? sorter.sort_ties(B.host_keys(i), n, out + 1, (B.ties_stride - 1) / 2) : 0;
-      });
-      dc2_enqueue_votes(h->stream, B, K, max_nq[0], method, (float)p.outlier_flow_tolerance, (float)p.outlier_disp_tolerance);
-      vsm_dc2_launch_prior(h->stream, B.d_jobs, K, method, p.match_binsize, p.match_radius, w, hh, c.dims.ub, c.dims.vb);
-    }
-    // ---- pass 2, refinement, final removeOutliers (viso/matcher.cpp:229-232) ----
-    cfg.sparse = 0;
-    cfg.use_prior = p.multi_stage ? 1 : 0;
-    Dc2Bank &B = m->bank2;
-    for (int i = 0; i < K; i++)
-      B.fill_job(i, c.h_pairs[i].list2, c.h_pairs[i].count + 1, false, (vsm_p_match *)(m->arena.res_dev + m->arena.slot * i), m->arena.res_cnt_dev + i, nullptr, nullptr, false,
-                 fused_keys ? c.h_pairs[i].keys[1] : nullptr, c.hm_lcount + 2 * i + 1);
-    if (fused_keys) {
-      VSM_CHK(vsm_upload(h->stream, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * K));
-      const VsmKeyOut ko = {B.dev_of(B.host_keys(0)), Dc2Bank::al((size_t)B.cap * 8), B.cap};
-      vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, K, c.dims, cfg, max_nq[1], 0, nullptr, &ko);
-    } else {
-      vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, K, c.dims, cfg, max_nq[1]);
-      VSM_CHK(vsm_upload(h->stream, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * K));
-    }
-    if (p.refinement == 2) {  // sub-pixel fits drop matches: they come before the keys of what is left (section 6b of DESIGN.md)
-      vsm_launch_refine(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, K, c.dims, c.dims, method, p.refinement, max_nq[1]);
-      vsm_launch_parabolic_apply(h->stream, h->prof, d_pairs, K);
-    }
-    if (!fused_keys) vsm_dc2_launch_keys(h->stream, B.d_jobs, K, max_nq[1]);  // (also into host-mapped memory: the pool sorts them)
-    VSM_CHK(hipEventRecord(m->ev_keys, h->stream));
-    dc2_enqueue_mesh(h->stream, B, K, max_nq[1]);
-    if (p.refinement == 1) vsm_launch_refine(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, K, c.dims, c.dims, method, p.refinement, max_nq[1]);
-    VSM_CHK(hipGetLastError());
-    VSM_CHK(hipEventSynchronize(m->ev_keys));
-    t2 = now_us();
-    // Triangle's vertex sort of every list on the pool while the device triangulates (which match stands for a shared pixel)
-    h->pool->run(K, [&](int i) {
-      static thread_local ExactDelaunay sorter;
-      static thread_local std::vector<uint64_t> keys;
-      const int32_t n = B.list_n(i);
-      int32_t *out = B.host_ties_of(i);
-      if (n > 3 && n <= B.cap) {
-        keys.assign(B.host_keys(i), B.host_keys(i) + n);
-        out[0] = sorter.sort_ties(keys.data(), n, out + 1, (B.ties_stride - 1) / 2);
-      } else {
-        out[0] = 0;
-      }
-    });
-    dc2_enqueue_votes(h->stream, B, K, max_nq[1], method, (float)p.outlier_flow_tolerance, (float)p.outlier_disp_tolerance);
-    VSM_CHK(hipGetLastError());
-    VSM_CHK(hipStreamSynchronize(h->stream));
-    int declined = m->bank2.h_error ? *m->bank2.h_error : 0;
-    if (m->bank1.h_error) declined |= *m->bank1.h_error;
+    int declined = 0;
+    const int rc = vsm_step_run(h, c, m->st, K, K, valid.data(), method, max_nq, w, hh, &t2, &declined);
+    if (rc != VSM_OK) return rc;
     if (declined) {
       fprintf(stderr, "visomatch: vsm_multi_process: the device chain declined a list (code %d)\n", declined);
       return fail(VSM_EARG);
@@ -292,8 +177,8 @@ int vsm_multi_process(vsm_multi *m, const uint8_t *left, const uint8_t *right, i
     }
     s.have_prev = true;
     if (valid[i]) {
-      const int32_t n = m->arena.res_cnt[i];
-      const vsm_p_match *src = (const vsm_p_match *)(m->arena.res + m->arena.slot * i);
+      const int32_t n = m->st.arena.res_cnt[i];
+      const vsm_p_match *src = (const vsm_p_match *)(m->st.arena.res + m->st.arena.slot * i);
       s.final_list.assign(src, src + std::max(n, 0));
       s.matched = s.final_list;
     } else {

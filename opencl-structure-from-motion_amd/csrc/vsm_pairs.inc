@@ -4,16 +4,14 @@
 // wants other pairs of the same frames: the keyframe kept by pushBack(replace = true) against later frames, (a, b) and
 // (b, a), loop-closure candidates, the frames of several short clips.  vsm_pairs_run takes the frames and a list of
 // (previous, current) pairs: every frame goes through the image side ONCE, whatever number of pairs names it, and stays
-// in HBM; the pairs then go, C at a time, through what a vsm_multi_process step runs for its K sequences - first pass,
-// its outlier removal and prior boxes, second pass, refinement, the final exact-Delaunay chain - from a job table that
-// names the images by slot (pair_jobs, vsm_api.cpp).  No kernel is this form's own.  Per pair the list is, byte for byte,
+// in HBM; the pairs then go, C at a time, through the step a vsm_multi_process call runs for its K sequences (vsm_step_run,
+// vsm_step.inc) - first pass, its outlier removal and prior boxes, second pass, refinement, the final exact-Delaunay chain -
+// from a job table that names the images by slot (pair_jobs, vsm_api.cpp).  No kernel is this form's own.  Per pair the list is, byte for byte,
 // getMatches() of a fresh Matcher after pushBack(a), pushBack(b), matchFeatures(method, Tr of the pair).
 struct VsmPairs {
   VsmCtx ctx;  // every image of the set (frame f: slots sides * f, + 1) and one bank of C pairs
   int chunk = 0;
-  Dc2Bank bank1, bank2;
-  hipEvent_t ev_feat = nullptr, ev_keys = nullptr, ev_a = nullptr;
-  VsmResArena arena;  // the chunk's survivors, host-mapped: one slot per pair of the bank
+  VsmStep st;  // a chunk's banks, events and survivors (vsm_step.inc): one arena slot per pair of the bank
   std::vector<std::vector<vsm_p_match>> lists;  // per pair of the last call
   std::vector<int32_t> pair_list;  // ... its pairs, frame count and method, for vsm_pairs_tracks; done: it ran to its end
   int32_t n_frames = 0, method = -1;
@@ -24,11 +22,7 @@ struct VsmPairs {
 static void pairs_destroy(vsm_handle *h) {
   VsmPairs *P = h->pairs;
   if (!P) return;
-  for (hipEvent_t e : {P->ev_feat, P->ev_keys, P->ev_a})
-    if (e) (void)hipEventDestroy(e);
-  P->bank1.release();
-  P->bank2.release();
-  P->arena.free();
+  P->st.release();
   ctx_destroy(P->ctx);
   delete P;
   h->pairs = nullptr;
@@ -175,21 +169,14 @@ int vsm_pairs_run(vsm_handle *h, const uint8_t *left, const uint8_t *right, int6
     const int rc = ctx_create(c, p, w, hh, slots, C, h->stream, h->sw.match_heads != 0);
     if (rc != VSM_OK) return rc;
     P.chunk = C;
-    if (!P.arena.alloc(al256((size_t)c.cap_set[1] * sizeof(vsm_p_match)), (size_t)C)) {
+    if (!P.st.arena.alloc(al256((size_t)c.cap_set[1] * sizeof(vsm_p_match)), (size_t)C)) {
       c.ready = false;  // (the next call sets the context up again instead of running with half of it)
       return VSM_EHIP;
     }
   }
-  for (hipEvent_t *e : {&P.ev_feat, &P.ev_keys, &P.ev_a})
-    if (!*e) HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+  if (!P.st.create_events()) return VSM_EHIP;
   // a call that fails after something was enqueued: drain the device, report
-  auto fail = [&](int rc) {
-    (void)hipStreamSynchronize(h->stream);
-    (void)hipGetLastError();
-    if (P.bank1.h_error) P.bank1.h_error[0] = P.bank1.h_error[1] = 0;
-    if (P.bank2.h_error) P.bank2.h_error[0] = P.bank2.h_error[1] = 0;
-    return rc;
-  };
+  auto fail = [&](int rc) { return P.st.fail(h->stream, rc); };
   // ---- pushBack of every frame, once: chunks of frames through the front end and the feature kernels ----
   {
     const int Cf = std::min<int>(n_frames, 64);
@@ -208,124 +195,30 @@ int vsm_pairs_run(vsm_handle *h, const uint8_t *left, const uint8_t *right, int6
     h->seq_chunk = seq_chunk_before;
     if (rc != VSM_OK) return fail(rc);
   }
-  VSM_CHK(hipEventRecord(P.ev_feat, h->stream));
-  VSM_CHK(hipEventSynchronize(P.ev_feat));  // every image's feature counts are in host-mapped memory
+  VSM_CHK(hipEventRecord(P.st.ev_feat, h->stream));
+  VSM_CHK(hipEventSynchronize(P.st.ev_feat));  // every image's feature counts are in host-mapped memory
   VSM_CHK(hipGetLastError());
   P.timings[0] = now_us() - t0;
-  // ---- the pairs, C at a time: what a vsm_multi_process step does for its K sequences ----
-  const int32_t dims_c[3] = {w, hh, c.dims.bpl};
-  const VsmPair *d_pairs = c.d_pairs;
-  VsmJob *h_jobs = c.h_jobs, *d_jobs = c.d_jobs;
+  // ---- the pairs, C at a time: the step a vsm_multi_process call runs for its K sequences (vsm_step.inc) ----
   std::vector<char> valid((size_t)C, 0);
-  VsmJob dummy;
-  memset(&dummy, 0, sizeof(dummy));
   for (int32_t k0 = 0; k0 < n_pairs; k0 += C) {
     const int n = std::min<int>(C, n_pairs - k0);
     const double t1 = now_us();
     int max_nq[2];
-    pair_jobs(p, method, sides, c.hm_counts, pairs + 2 * (size_t)k0, n, Tr ? Tr + (size_t)k0 * 12 : nullptr, Tr_valid ? Tr_valid + k0 : nullptr, h_jobs,
+    pair_jobs(p, method, sides, c.hm_counts, pairs + 2 * (size_t)k0, n, Tr ? Tr + (size_t)k0 * 12 : nullptr, Tr_valid ? Tr_valid + k0 : nullptr, c.h_jobs,
               valid.data(), max_nq);
     bool any = false;
     for (int i = 0; i < n; i++) any = any || valid[i];
     if (!any) continue;  // (matchFeatures returns early on every pair of the chunk: empty lists)
-    // every size limit of the device chain before anything of the chunk is enqueued
-    bool chain = !(max_nq[0] > VSM_DC_KD_MAX_POINTS || max_nq[1] > VSM_DC_KD_MAX_POINTS || vsm_dc2_depth(std::max(max_nq[0], max_nq[1])) > VSM_DC2_MAX_DEPTH ||
-                   (p.refinement == 2 && max_nq[1] > VSM_PARA_MAX_LIST));
+    // a chunk with a list beyond the device chain's limits, or with a list the chain declined, goes pair by pair
+    bool chain = vsm_step_fits(p, max_nq);
     double t2 = t1;
     if (chain) {
-      if ((p.multi_stage && !P.bank1.reserve(C, std::max(max_nq[0], 64), true)) || !P.bank2.reserve(C, std::max(max_nq[1], 64), true)) return fail(VSM_EHIP);
-      VSM_CHK(vsm_upload(h->stream, d_jobs, h_jobs, sizeof(VsmJob) * n));
-      VsmMatchCfg cfg = make_cfg(p, method, h->sw.match_heads && c.has_heads);
-      // option fused_keys: the chains' job tables go up in front of the matching launches and the compactions write the chains'
-      // keys - into the pair bank and, the single stream having nothing beside it that a store across PCIe could hold up, into
-      // the host-mapped arrays the pool sorts from; no k_upload + k_dc2_keys between a compaction and its chain's sort kernel.
-      // (refinement = 2 shortens the lists behind the compaction: keys by k_dc2_keys behind it, as before)
-      const bool fused_keys = h->sw.fused_keys && p.refinement != 2;
-      // few pairs: the first-pass lists go to the host pool, a list per thread; else the device chain (vsm_multi.inc has the measurements)
-      const bool host_p1 = p.multi_stage && (h->sw.multi_host_pass1 >= 0 ? h->sw.multi_host_pass1 != 0 : n <= h->pool->size());
-      if (host_p1) {
-        // ---- pass 1; removeOutliers + computePriorStatistics on the pool (viso/matcher.cpp:222-226) ----
-        cfg.sparse = 1;
-        cfg.use_prior = 0;
-        if (!vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, n, c.dims, cfg, max_nq[0], 1))
-          vsm_launch_export(h->stream, h->prof, d_pairs, n, 0, max_nq[0]);
-        VSM_CHK(hipEventRecord(P.ev_a, h->stream));
-        VSM_CHK(hipEventSynchronize(P.ev_a));  // the lists are in host-mapped memory
-        VSM_CHK(hipGetLastError());
-        VSM_CHK(host_pass1_boxes(h, c, 0, n, valid.data(), method, dims_c));
-      } else if (p.multi_stage) {
-        // ---- pass 1 and its chain: removeOutliers + computePriorStatistics on the device ----
-        cfg.sparse = 1;
-        cfg.use_prior = 0;
-        Dc2Bank &B = P.bank1;
-        for (int i = 0; i < n; i++)
-          B.fill_job(i, c.h_pairs[i].list1, c.h_pairs[i].count, false, nullptr, nullptr, c.h_pairs[i].ranges, nullptr, false, fused_keys ? c.h_pairs[i].keys[0] : nullptr, c.hm_lcount + 2 * i);
-        if (fused_keys) {  // the chain's job table first, the keys from the compaction - also into host-mapped memory (see above)
-          VSM_CHK(vsm_upload(h->stream, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * n));
-          const VsmKeyOut ko = {B.dev_of(B.host_keys(0)), Dc2Bank::al((size_t)B.cap * 8), B.cap};
-          vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, n, c.dims, cfg, max_nq[0], 0, nullptr, &ko);
-        } else {
-          vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, n, c.dims, cfg, max_nq[0]);
-          VSM_CHK(vsm_upload(h->stream, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * n));
-          vsm_dc2_launch_keys(h->stream, B.d_jobs, n, max_nq[0]);  // (also into host-mapped memory)
-        }
-        VSM_CHK(hipEventRecord(P.ev_a, h->stream));
-        dc2_enqueue_mesh(h->stream, B, n, max_nq[0]);
-        VSM_CHK(hipEventSynchronize(P.ev_a));
-        h->pool->run(n, [&](int i) {  // Triangle's vertex sort of the short lists on the pool while the device triangulates
-          static thread_local ExactDelaunay sorter;
-          const int32_t nl = B.list_n(i);
-          int32_t *out = B.host_ties_of(i);
-          out[0] = (nl > 3 && nl <= B.cap) ? sorter.sort_ties(B.host_keys(i), nl, out + 1, (B.ties_stride - 1) / 2) : 0;
-        });
-        dc2_enqueue_votes(h->stream, B, n, max_nq[0], method, (float)p.outlier_flow_tolerance, (float)p.outlier_disp_tolerance);
-        vsm_dc2_launch_prior(h->stream, B.d_jobs, n, method, p.match_binsize, p.match_radius, w, hh, c.dims.ub, c.dims.vb);
-      }
-      // ---- pass 2, refinement, final removeOutliers (viso/matcher.cpp:229-232) ----
-      cfg.sparse = 0;
-      cfg.use_prior = p.multi_stage ? 1 : 0;
-      Dc2Bank &B = P.bank2;
-      for (int i = 0; i < n; i++)
-        B.fill_job(i, c.h_pairs[i].list2, c.h_pairs[i].count + 1, false, (vsm_p_match *)(P.arena.res_dev + P.arena.slot * i), P.arena.res_cnt_dev + i, nullptr, nullptr, false,
-                   fused_keys ? c.h_pairs[i].keys[1] : nullptr, c.hm_lcount + 2 * i + 1);
-      if (fused_keys) {
-        VSM_CHK(vsm_upload(h->stream, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * n));
-        const VsmKeyOut ko = {B.dev_of(B.host_keys(0)), Dc2Bank::al((size_t)B.cap * 8), B.cap};
-        vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, n, c.dims, cfg, max_nq[1], 0, nullptr, &ko);
-      } else {
-        vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, n, c.dims, cfg, max_nq[1]);
-        VSM_CHK(vsm_upload(h->stream, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * n));
-      }
-      if (p.refinement == 2) {  // sub-pixel fits drop matches: they come before the keys of what is left
-        vsm_launch_refine(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, n, c.dims, c.dims, method, p.refinement, max_nq[1]);
-        vsm_launch_parabolic_apply(h->stream, h->prof, d_pairs, n);
-      }
-      if (!fused_keys) vsm_dc2_launch_keys(h->stream, B.d_jobs, n, max_nq[1]);  // (also into host-mapped memory: the pool sorts them)
-      VSM_CHK(hipEventRecord(P.ev_keys, h->stream));
-      dc2_enqueue_mesh(h->stream, B, n, max_nq[1]);
-      if (p.refinement == 1) vsm_launch_refine(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, n, c.dims, c.dims, method, p.refinement, max_nq[1]);
-      VSM_CHK(hipGetLastError());
-      VSM_CHK(hipEventSynchronize(P.ev_keys));
-      t2 = now_us();
-      h->pool->run(n, [&](int i) {  // Triangle's vertex sort of every list on the pool while the device triangulates
-        static thread_local ExactDelaunay sorter;
-        static thread_local std::vector<uint64_t> keys;
-        const int32_t nl = B.list_n(i);
-        int32_t *out = B.host_ties_of(i);
-        if (nl > 3 && nl <= B.cap) {
-          keys.assign(B.host_keys(i), B.host_keys(i) + nl);
-          out[0] = sorter.sort_ties(keys.data(), nl, out + 1, (B.ties_stride - 1) / 2);
-        } else {
-          out[0] = 0;
-        }
-      });
-      dc2_enqueue_votes(h->stream, B, n, max_nq[1], method, (float)p.outlier_flow_tolerance, (float)p.outlier_disp_tolerance);
-      VSM_CHK(hipGetLastError());
-      VSM_CHK(hipStreamSynchronize(h->stream));
-      int declined = P.bank2.h_error ? P.bank2.h_error[0] : 0;
-      if (P.bank1.h_error) declined |= P.bank1.h_error[0];
+      int declined = 0;
+      const int rc = vsm_step_run(h, c, P.st, C, n, valid.data(), method, max_nq, w, hh, &t2, &declined);
+      if (rc != VSM_OK) return rc;
       if (declined) {
-        (void)fail(VSM_OK);  // (clears the banks' flag words)
+        P.st.clear_flags();
         chain = false;
       }
     }
@@ -333,8 +226,8 @@ int vsm_pairs_run(vsm_handle *h, const uint8_t *left, const uint8_t *right, int6
       // the survivors out of the chunk's arena into the pairs' own lists: host memory grows with the matches found
       h->pool->run(n, [&](int i) {
         if (!valid[i]) return;
-        const vsm_p_match *src = (const vsm_p_match *)(P.arena.res + P.arena.slot * i);
-        P.lists[(size_t)k0 + i].assign(src, src + std::max(P.arena.res_cnt[i], 0));
+        const vsm_p_match *src = (const vsm_p_match *)(P.st.arena.res + P.st.arena.slot * i);
+        P.lists[(size_t)k0 + i].assign(src, src + std::max(P.st.arena.res_cnt[i], 0));
       });
     } else {
       const int rc = pairs_fallback(h, P, save, left, right, frame_stride, on_device, w, hh, bpl, method, pairs, k0, n, Tr, Tr_valid);

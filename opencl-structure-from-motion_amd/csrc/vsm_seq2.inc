@@ -110,6 +110,15 @@ struct Dc2Bank {
   int32_t list_n(int i) const { return n_src[i] ? *n_src[i] : h_n[i]; }
   uint64_t *host_keys(int i) const { return (uint64_t *)((uint8_t *)h_keys + al((size_t)cap * 8) * i); }
   int32_t *host_ties_of(int i) const { return (int32_t *)((uint8_t *)h_ties + al((size_t)ties_stride * 4) * i); }
+  // a pool task: Triangle's vertex sort of list i from its keys in host-mapped memory - the number of (carried, right) index
+  // patches and the patches into host_ties_of(i); none for a list the chain leaves alone or declines.  (sort_ties works on a
+  // copy of its own: one pass over the keys, then cache-resident work)
+  void sort_ties_of(int i) const {
+    static thread_local ExactDelaunay sorter;
+    const int32_t n = list_n(i);
+    int32_t *out = host_ties_of(i);
+    out[0] = (n > 3 && n <= cap) ? sorter.sort_ties(host_keys(i), n, out + 1, (ties_stride - 1) / 2) : 0;
+  }
   template <typename T>
   T *dev_of(T *host_ptr) const {  // device address of something inside the host-mapped block
     return (T *)(h_block_dev + ((uint8_t *)host_ptr - h_block));
@@ -571,16 +580,7 @@ static void seq2_keys_ready(Seq2Chunk *ch, int first, int last) {
     const double t0 = vsm_now_us();
     Dc2Bank &B = *ch->B;
     const int i = first + t;
-    if (i < last) {
-      static thread_local ExactDelaunay sorter;
-      const int32_t n = B.list_n(i);
-      int32_t *out = B.host_ties_of(i);
-      if (n > 3 && n <= B.cap) {  // (sort_ties works on a copy of its own: one pass over the DMA'd keys, then cache-resident work)
-        out[0] = sorter.sort_ties(B.host_keys(i), n, out + 1, (B.ties_stride - 1) / 2);
-      } else {
-        out[0] = 0;
-      }
-    }
+    if (i < last) B.sort_ties_of(i);
     ch->sort_ns.fetch_add((long long)((vsm_now_us() - t0) * 1e3), std::memory_order_relaxed);
     if (ch->sort_tasks_left.fetch_sub(1, std::memory_order_acq_rel) == 1) {
       ch->sorts_left.fetch_sub(1, std::memory_order_acq_rel);
@@ -1213,12 +1213,7 @@ struct Seq2Call {
     const int n = q.n;
     const double t0 = now_us();
     HIPCHK(hipEventSynchronize(q.ev_k1));
-    h->pool->run(n, [&](int i) {
-      static thread_local ExactDelaunay sorter;
-      const int32_t nl = B.list_n(i);
-      int32_t *out = B.host_ties_of(i);
-      out[0] = (nl > 3 && nl <= B.cap) ? sorter.sort_ties(B.host_keys(i), nl, out + 1, (B.ties_stride - 1) / 2) : 0;
-    });
+    h->pool->run(n, [&](int i) { B.sort_ties_of(i); });
     tg += now_us() - t0;
     hipStream_t c1 = S.cs(k);
     std::lock_guard<std::mutex> lk(S.enq_mu);

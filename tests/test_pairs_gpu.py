@@ -244,6 +244,52 @@ def test_fallback_beyond_1024_statistics_bins(vm, B, frames):
     m.close()
 
 
+BIG_W, BIG_H = 1344, 720
+BIG_PAIRS = [(2, 1), (0, 1), (2, 0)]
+BIG_SIZES = {2: (7418, 14984, 8637), 0: (7668, 15224, 8911)}  # the oracle's list sizes, per method and pair
+
+
+@pytest.fixture(scope="module")
+def big_frames(synth):
+    """three stereo frames of 1344 x 720; the right half of frame 2 is blank, which halves its features"""
+    cv = synth.canvas(5, BIG_W, BIG_H)
+    seq = [synth.stereo_frame(cv, f, BIG_W, BIG_H) for f in range(3)]
+    for img in seq[2]:
+        img[:, BIG_W // 2:] = 96
+    return CT.stack(seq)
+
+
+@pytest.mark.parametrize("chunk", (1, 3))
+@pytest.mark.parametrize("method", (2, 0))
+def test_fallback_of_a_chunk_beyond_the_refinement_limit(vm, B, big_frames, method, chunk):
+    """refinement = 2 batches lists of up to 16384 entries (VSM_PARA_MAX_LIST); the second-pass list of a pair is as long as
+    the dense set of its previous frame.  Frames 0 and 1 have 18051 and 18040 dense features, the half-blanked frame 2 has
+    9077 (the oracle's counts): a chunk that holds pair (0, 1) goes pair by pair, the others through the device chain.
+    pairs_chunk = 1: chain, fall-back, chain - a chain chunk after the ring was set aside; 3: one long list sends the
+    whole chunk through the fall-back."""
+    left, right = big_frames
+    want = oracle_pairs(B, "big", left, right, BIG_PAIRS, method, refinement=2)
+    sizes = tuple(len(x) for x in want)
+    print("oracle list sizes, method", method, sizes)
+    assert sizes == BIG_SIZES[method] and min(sizes) > 1000
+    m = vm.Matcher(options={"pairs_chunk": chunk}, refinement=2)
+    # the caller's own pushes: they also show the precondition that forces the path
+    assert m.push_back(left[0], right[0]) == 0
+    dense0 = len(m.features("1c2"))
+    assert m.push_back(left[2], right[2]) == 0
+    dense2 = len(m.features("1c2"))
+    print("dense features of frames 0 and 2", dense0, dense2)
+    assert dense0 > 16384 > dense2
+    assert m.match(method)
+    ring = m.get_matches()
+    assert len(ring) > 1000
+    got = m.match_pairs(left, right, BIG_PAIRS, method)
+    assert_same_lists(got, want, (method, chunk))
+    assert min(len(x) for x in got) > 1000
+    assert m.get_matches().tobytes() == ring.tobytes()  # the caller's ring was set aside and put back
+    m.close()
+
+
 # ---- 9: bad arguments ------------------------------------------------------------------------------------------------------------
 
 def test_bad_arguments(vm, B, frames):
