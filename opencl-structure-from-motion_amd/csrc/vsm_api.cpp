@@ -26,6 +26,7 @@
 #include "vsm_host.h"
 #include "vsm_dc_gpu.h"
 #include "vsm_internal.h"
+#include "vsm_jobs.h"
 #include "vsm_stage.h"
 #include "vsm_tracks.h"
 #include "vsm_points.h"
@@ -889,232 +890,12 @@ int vsm_push_back_device(vsm_handle *h, const uint8_t *dI1, const uint8_t *dI2, 
   return push_common(h, dI1, dI2, w, hh, bpl, replace, true);
 }
 
-// sanity checks of viso/matcher.cpp:190-212 on feature counts n[image 1p,2p,1c,2c][set]
-// (a NULL set and an empty set are both "count 0" here)
-static bool match_ready(const vsm_params &p, int method, const int32_t n[4][2]) {
-  if (method == 0) {
-    if (n[0][1] == 0 || n[2][1] == 0) return false;
-    if (p.multi_stage && (n[0][0] == 0 || n[2][0] == 0)) return false;
-  } else if (method == 1) {
-    if (n[2][1] == 0 || n[3][1] == 0) return false;
-    if (p.multi_stage && (n[2][0] == 0 || n[3][0] == 0)) return false;
-  } else {
-    if (n[0][1] == 0 || n[1][1] == 0 || n[2][1] == 0 || n[3][1] == 0) return false;
-    if (p.multi_stage && (n[0][0] == 0 || n[1][0] == 0 || n[2][0] == 0 || n[3][0] == 0)) return false;
-  }
-  return true;
-}
-
-static VsmMatchCfg make_cfg(const vsm_params &p, int method, int heads) {
-  VsmMatchCfg cfg;
-  memset(&cfg, 0, sizeof(cfg));
-  cfg.method = method;
-  cfg.heads = heads;
-  cfg.binsize = p.match_binsize;
-  cfg.bin_magic = p.match_binsize >= 2 ? (uint32_t)(((1ull << 32) + (uint64_t)p.match_binsize - 1) / (uint64_t)p.match_binsize) : 0u;
-  cfg.radius = p.match_radius;
-  cfg.disp_tol = p.match_disp_tolerance;
-  cfg.f = p.f;
-  cfg.cu = p.cu;
-  cfg.cv = p.cv;
-  cfg.base = p.base;
-  return cfg;
-}
-
-// The job table of one chunk of a batched form: frames f0 .. f0 + n - 1, whose images stand in slots first_img, first_img +
-// sides, ... (sides: images per frame) and whose feature counts the device has written into `counts` ([image][set], the
-// layout of VsmCtx::hm_counts); img_before: the slot of frame f0 - 1, the last one of the previous chunk's bank.  That
-// bank's counts may be gone by now: nprev[side][set] carries the counts of frame f0 - 1 in, and those of the chunk's last
-// frame out.  Per frame: the job (image slots; query counts and Tr only where matchFeatures would run, match_ready),
-// valid (may be NULL), and seq_src (vsm_handle::seq_src: a frame that is not matched keeps the list of the one before).
-// Pure arithmetic - no HIP call, nothing of a handle - so the CPU suite pins it through vsm_debug_chunk_jobs
-// (tests/test_chunk_jobs.py).
-static void seq_chunk_jobs(const vsm_params &p, int method, int sides, int32_t f0, int n, int first_img, int img_before, const int32_t *counts,
-                           int32_t nprev[2][2], const double *Tr, const uint8_t *Tr_valid, VsmJob *jobs, char *valid, int max_nq[2],
-                           int32_t *seq_src) {
-  max_nq[0] = max_nq[1] = 0;
-  for (int i = 0; i < n; i++) {
-    const int32_t f = f0 + i;
-    VsmJob &jb = jobs[i];
-    memset(&jb, 0, sizeof(jb));
-    const int img_c = first_img + sides * i;
-    int img_p;
-    int32_t cnt[4][2];
-    for (int s = 0; s < 2; s++) {
-      cnt[2][s] = counts[img_c * 2 + s];
-      cnt[3][s] = sides == 2 ? counts[(img_c + 1) * 2 + s] : 0;
-    }
-    if (method == 1) {
-      img_p = img_c;
-      for (int s = 0; s < 2; s++) cnt[0][s] = cnt[1][s] = 0;
-    } else if (i > 0) {
-      img_p = img_c - sides;
-      for (int s = 0; s < 2; s++) {
-        cnt[0][s] = counts[img_p * 2 + s];
-        cnt[1][s] = sides == 2 ? counts[(img_p + 1) * 2 + s] : 0;
-      }
-    } else {  // the previous frame is the last one of the previous chunk's bank
-      img_p = img_before;
-      for (int s = 0; s < 2; s++) {
-        cnt[0][s] = f > 0 ? nprev[0][s] : 0;
-        cnt[1][s] = f > 0 ? nprev[1][s] : 0;
-      }
-    }
-    jb.img_prev = img_p;
-    jb.img_curr = img_c;
-    const bool ready = match_ready(p, method, cnt);
-    if (ready) {
-      const int qimg = method == 2 ? 0 : 2;
-      jb.nq[0] = p.multi_stage ? cnt[qimg][0] : 0;
-      jb.nq[1] = cnt[qimg][1];
-      if (Tr && (!Tr_valid || Tr_valid[f])) {
-        jb.use_tr = 1;
-        memcpy(jb.t, Tr + (size_t)f * 12, 12 * sizeof(double));
-      }
-    }
-    if (valid) valid[i] = ready ? 1 : 0;
-    seq_src[f] = ready ? f : (f > 0 ? seq_src[f - 1] : -1);
-    max_nq[0] = std::max(max_nq[0], jb.nq[0]);
-    max_nq[1] = std::max(max_nq[1], jb.nq[1]);
-  }
-  for (int s = 0; s < 2; s++) {  // remember the last frame's counts for the next chunk
-    nprev[0][s] = counts[(first_img + sides * (n - 1)) * 2 + s];
-    nprev[1][s] = sides == 2 ? counts[(first_img + sides * (n - 1) + 1) * 2 + s] : 0;
-  }
-}
-// the slot of the frame in front of chunk k's first one: the last frame of chunk k - 1, in the bank before chunk k's
-static int seq_slot_before(const std::vector<int32_t> &chunk_start, int k, int sides, int banks, int C) {
-  return sides * ((k + banks - 1) % banks) * C + sides * ((k > 0 ? chunk_start[k] - chunk_start[k - 1] : 1) - 1);
-}
-
-// (debug entry, include/visomatch.h)
-int32_t vsm_debug_chunk_jobs(int32_t method, int32_t multi_stage, int32_t sides, int32_t banks, int32_t chunk, const int32_t *starts,
-                             int32_t n_chunks, const int32_t *counts, const uint8_t *tr_valid, int32_t *frames_out, int32_t *max_nq_out) {
-  if (method < 0 || method > 2 || sides < 1 || sides > 2 || banks < 2 || chunk < 1 || n_chunks < 1 || !starts || !counts || !frames_out ||
-      !max_nq_out || starts[0] != 0)
-    return -1;
-  for (int k = 0; k < n_chunks; k++)
-    if (starts[k + 1] <= starts[k] || starts[k + 1] - starts[k] > chunk) return -1;
-  const std::vector<int32_t> chunk_start(starts, starts + n_chunks + 1);
-  const int32_t n_frames = chunk_start[n_chunks];
-  vsm_params p;
-  vsm_default_params(&p);
-  p.multi_stage = multi_stage;
-  std::vector<int32_t> hm_counts((size_t)banks * chunk * sides * 2, 0), seq_src(n_frames, 0);
-  const std::vector<double> Tr((size_t)n_frames * 12, 0.0);
-  std::vector<VsmJob> jobs(chunk);
-  std::vector<char> valid(chunk);
-  int32_t nprev[2][2] = {{0, 0}, {0, 0}};
-  for (int k = 0; k < n_chunks; k++) {
-    const int32_t f0 = chunk_start[k];
-    const int n = chunk_start[k + 1] - f0, first_img = sides * (k % banks) * chunk;
-    for (int i = 0; i < n; i++)  // what the feature kernels of the chunk leave in its bank (an older chunk's counts are gone)
-      for (int side = 0; side < sides; side++)
-        for (int s = 0; s < 2; s++) hm_counts[(size_t)(first_img + sides * i + side) * 2 + s] = counts[((size_t)(f0 + i) * 2 + side) * 2 + s];
-    int max_nq[2];
-    seq_chunk_jobs(p, method, sides, f0, n, first_img, seq_slot_before(chunk_start, k, sides, banks, chunk), hm_counts.data(), nprev, Tr.data(), tr_valid,
-                   jobs.data(), valid.data(), max_nq, seq_src.data());
-    for (int i = 0; i < n; i++) {
-      int32_t *o = frames_out + (size_t)(f0 + i) * 7;
-      o[0] = jobs[i].img_prev;
-      o[1] = jobs[i].img_curr;
-      o[2] = jobs[i].nq[0];
-      o[3] = jobs[i].nq[1];
-      o[4] = jobs[i].use_tr;
-      o[5] = valid[i];
-      o[6] = seq_src[f0 + i];
-    }
-    max_nq_out[2 * k] = max_nq[0];
-    max_nq_out[2 * k + 1] = max_nq[1];
-  }
-  return 0;
-}
-
-// The job table of a list of arbitrary frame pairs (vsm_pairs_run): pair k = pairs[2 k], pairs[2 k + 1] = (previous frame,
-// current frame) of a frame set whose images all stand in one context, frame f's at slots sides * f (+ 1: its right image),
-// with the feature counts the device has written into `counts` ([image][set], the layout of VsmCtx::hm_counts).  Per pair
-// what a fresh matcher does after pushBack(previous), pushBack(current), matchFeatures(method, Tr of the pair): the job
-// (query counts and Tr only where matchFeatures would run, match_ready; queries come from the previous left image for quad
-// matching, from the current one otherwise), valid, and the longest query lists.  Stereo matching does not read the previous
-// frame: its slot is the current one's, whatever the pair names.  Tr / Tr_valid: per PAIR (NULL: none / all valid).
-// Pure arithmetic like seq_chunk_jobs: pinned through vsm_debug_pair_jobs (tests/test_pair_jobs.py).
-static void pair_jobs(const vsm_params &p, int method, int sides, const int32_t *counts, const int32_t *pairs, int n, const double *Tr,
-                      const uint8_t *Tr_valid, VsmJob *jobs, char *valid, int max_nq[2]) {
-  max_nq[0] = max_nq[1] = 0;
-  for (int k = 0; k < n; k++) {
-    VsmJob &jb = jobs[k];
-    memset(&jb, 0, sizeof(jb));
-    const int img_c = sides * pairs[2 * k + 1], img_p = method == 1 ? img_c : sides * pairs[2 * k];
-    int32_t cnt[4][2];
-    for (int s = 0; s < 2; s++) {
-      cnt[0][s] = method == 1 ? 0 : counts[img_p * 2 + s];
-      cnt[1][s] = method == 1 || sides != 2 ? 0 : counts[(img_p + 1) * 2 + s];
-      cnt[2][s] = counts[img_c * 2 + s];
-      cnt[3][s] = sides == 2 ? counts[(img_c + 1) * 2 + s] : 0;
-    }
-    jb.img_prev = img_p;
-    jb.img_curr = img_c;
-    const bool ready = match_ready(p, method, cnt);
-    if (ready) {
-      const int qimg = method == 2 ? 0 : 2;
-      jb.nq[0] = p.multi_stage ? cnt[qimg][0] : 0;
-      jb.nq[1] = cnt[qimg][1];
-      if (Tr && (!Tr_valid || Tr_valid[k])) {
-        jb.use_tr = 1;
-        memcpy(jb.t, Tr + (size_t)k * 12, 12 * sizeof(double));
-      }
-    }
-    if (valid) valid[k] = ready ? 1 : 0;
-    max_nq[0] = std::max(max_nq[0], jb.nq[0]);
-    max_nq[1] = std::max(max_nq[1], jb.nq[1]);
-  }
-}
-// the argument checks of vsm_pairs_run on its pair list: every current frame inside the set, every previous one too - or,
-// with stereo matching (which does not read it), -1
-static bool pair_list_ok(int method, int32_t n_frames, const int32_t *pairs, int32_t n_pairs) {
-  if (method < 0 || method > 2 || n_frames <= 0 || !pairs || n_pairs <= 0) return false;
-  for (int32_t k = 0; k < n_pairs; k++) {
-    const int32_t a = pairs[2 * k], b = pairs[2 * k + 1];
-    if (b < 0 || b >= n_frames || a >= n_frames || a < (method == 1 ? -1 : 0)) return false;
-  }
-  return true;
-}
-
-// (debug entry, include/visomatch.h)
-int32_t vsm_debug_pair_jobs(int32_t method, int32_t multi_stage, int32_t sides, int32_t n_frames, const int32_t *counts, const int32_t *pairs,
-                            int32_t n_pairs, int32_t chunk, const uint8_t *tr_valid, int32_t *pairs_out, int32_t *max_nq_out) {
-  if (sides < 1 || sides > 2 || chunk < 1 || !counts || !pairs_out || !max_nq_out || !pair_list_ok(method, n_frames, pairs, n_pairs)) return -1;
-  vsm_params p;
-  vsm_default_params(&p);
-  p.multi_stage = multi_stage;
-  std::vector<int32_t> img_counts((size_t)n_frames * sides * 2, 0);  // [frame][2 sides][set] -> [image][set]
-  for (int32_t f = 0; f < n_frames; f++)
-    for (int side = 0; side < sides; side++)
-      for (int s = 0; s < 2; s++) img_counts[((size_t)f * sides + side) * 2 + s] = counts[((size_t)f * 2 + side) * 2 + s];
-  std::vector<double> Tr((size_t)n_pairs * 12, 0.0);
-  for (int32_t k = 0; k < n_pairs; k++) Tr[(size_t)k * 12] = (double)(k + 1);  // (says which pair's Tr a job took)
-  std::vector<VsmJob> jobs(chunk);
-  std::vector<char> valid(chunk);
-  int32_t nchunks = 0;
-  for (int32_t k0 = 0; k0 < n_pairs; k0 += chunk, nchunks++) {
-    const int n = std::min(chunk, n_pairs - k0);
-    int max_nq[2];
-    pair_jobs(p, method, sides, img_counts.data(), pairs + 2 * (size_t)k0, n, Tr.data() + (size_t)k0 * 12, tr_valid ? tr_valid + k0 : nullptr, jobs.data(),
-              valid.data(), max_nq);
-    for (int i = 0; i < n; i++) {
-      int32_t *o = pairs_out + (size_t)(k0 + i) * 7;
-      o[0] = jobs[i].img_prev;
-      o[1] = jobs[i].img_curr;
-      o[2] = jobs[i].nq[0];
-      o[3] = jobs[i].nq[1];
-      o[4] = jobs[i].use_tr;
-      o[5] = valid[i];
-      o[6] = (int32_t)jobs[i].t[0];
-    }
-    max_nq_out[2 * nchunks] = max_nq[0];
-    max_nq_out[2 * nchunks + 1] = max_nq[1];
-  }
-  return nchunks;
+// a job with the ring's image slots: the previous frame's and the current one's left image (stereo matching only needs the
+// current pair: "prev" then aliases the current slot)
+static VsmJob ring_job(const vsm_handle *h, int method) {
+  VsmJob jb;
+  vsm_job_slots(jb, (method == 1 ? h->cur : h->cur ^ 1) * 2, h->cur * 2);
+  return jb;
 }
 
 // The pass-1 host stage of n pairs, first_pair onwards, on the pool (viso/matcher.cpp:222-226): a pair's pass-1 list out of
@@ -1162,23 +943,14 @@ int vsm_match(vsm_handle *h, int32_t method, const double *Tr) {
     n[2][s] = h->have[sc] ? h->n_feat[sc][0][s] : 0;
     n[3][s] = h->have[sc] ? h->n_feat[sc][1][s] : 0;
   }
-  if (!match_ready(p, method, n)) return VSM_ENOTREADY;
+  VsmJob job = ring_job(h, method);
+  if (!vsm_job_fill(p, method, n, job.img_prev, job.img_curr, Tr, job, nullptr)) return VSM_ENOTREADY;
   const double t0 = now_us();
   for (int s = 0; s < 5; s++) h->stage[s].clear();
   h->matched.clear();
   memset(h->counters, 0, sizeof(h->counters));
 
   VsmMatchCfg cfg = make_cfg(p, method, h->sw.match_heads && c.has_heads);
-  VsmJob job;
-  memset(&job, 0, sizeof(job));
-  // stereo matching only needs the current pair: "prev" then aliases the current slot
-  job.img_prev = (method == 1 ? sc : sp) * 2;
-  job.img_curr = sc * 2;
-  const int qimg = method == 2 ? 0 : 2;  // quad iterates the previous left features, flow/stereo the current
-  job.nq[0] = p.multi_stage ? n[qimg][0] : 0;
-  job.nq[1] = n[qimg][1];
-  job.use_tr = Tr ? 1 : 0;
-  if (Tr) memcpy(job.t, Tr, 12 * sizeof(double));
   const int stages = method == 2 ? 4 : 2;
   const VsmDims dp = c.dims, dc = c.dims;  // one size per handle
 
@@ -1665,650 +1437,8 @@ void vsm_get_kernel_stats(vsm_handle *h, double *total_ms, int64_t *launches) {
   memcpy(launches, h->prof.launches, sizeof(h->prof.launches));
 }
 
-int32_t vsm_host_delaunay(const int32_t *x, const int32_t *y, int32_t n, int32_t *tris, int32_t cap, int32_t threads) {
-  ExactDelaunay d;
-  VsmForkJoin pool(threads);
-  VsmPool side(2);  // with more than one thread the emulated vertex sort runs next to the triangulation (as in a handle)
-  d.run(x, y, n, threads > 1 ? &pool : nullptr, threads > 1 ? &side : nullptr);
-  const int32_t nt = d.num_triangles();
-  for (int32_t i = 0; i < nt && i < cap; i++)
-    for (int k = 0; k < 3; k++) tris[i * 3 + k] = d.triangles()[i * 3 + k];
-  return nt;
-}
-
-int32_t vsm_host_delaunay_split(const int32_t *x, const int32_t *y, int32_t n, int32_t *tris, int32_t cap,
-                                int32_t max_task_points, int32_t device_top_points) {
-  ExactDelaunay d;
-  // (device_top_points < 0: additionally with the emulated vertex sort set apart, see ExactDelaunay::prepare)
-  if (d.prepare(x, y, n, max_task_points, nullptr, std::max(device_top_points, 0), false, device_top_points < 0)) {
-    d.solve_tasks();
-    d.solve_merges();
-    d.finish();
-    d.resolve_ties();
-    d.apply_ties();
-  }
-  const int32_t nt = d.num_triangles();
-  for (int32_t i = 0; i < nt && i < cap; i++)
-    for (int k = 0; k < 3; k++) tris[i * 3 + k] = d.triangles()[i * 3 + k];
-  return nt;
-}
-
-// One prepared triangulation on the device, `copies` times (test hook and micro-benchmark below)
-namespace {
-struct DcDeviceCopy {
-  std::vector<VsmDcJob> jobs;
-  VsmDcTask *d_tasks = nullptr;
-  VsmDcMerge *d_merges = nullptr;
-  VsmDcJob *d_jobs = nullptr;
-  int nt = 0, nn = 0, m = 0, nlev = 0, lev_nodes[VSM_DC_MAX_LEVELS] = {0};
-  size_t tri_bytes = 0;
-  bool device_kd = false;  // the keys arrive in (x,y) order and k_dc_kd_order runs first
-  bool block = false;      // k_dc_block instead of k_dc_subtrees + k_dc_merge_level
-  bool create(ExactDelaunay &d, int copies) {
-    static_assert(sizeof(VsmDcTask) == sizeof(ExactDelaunay::Task), "task layout");
-    static_assert(sizeof(VsmDcMerge) == sizeof(ExactDelaunay::Merge), "merge layout");
-    m = d.points();
-    nt = (int)d.tasks().size();
-    nn = d.num_nodes();
-    const int ng = (int)d.device_merges().size();
-    nlev = (int)d.device_levels().size();
-    if (nlev > VSM_DC_MAX_LEVELS) return false;
-    tri_bytes = (size_t)m * 2 * 8 * sizeof(int32_t);
-    jobs.assign(copies, VsmDcJob());
-    if (hipMalloc((void **)&d_tasks, sizeof(VsmDcTask) * nt) != hipSuccess ||
-        hipMalloc((void **)&d_merges, sizeof(VsmDcMerge) * std::max(ng, 1)) != hipSuccess ||
-        hipMalloc((void **)&d_jobs, sizeof(VsmDcJob) * copies) != hipSuccess)
-      return false;
-    (void)hipMemcpy(d_tasks, d.tasks().data(), sizeof(VsmDcTask) * nt, hipMemcpyHostToDevice);
-    (void)hipMemcpy(d_merges, d.device_merges().data(), sizeof(VsmDcMerge) * ng, hipMemcpyHostToDevice);
-    for (VsmDcJob &job : jobs) {
-      if (hipMalloc((void **)&job.key, (size_t)m * 8) != hipSuccess || hipMalloc((void **)&job.pt, (size_t)m * 4) != hipSuccess ||
-          hipMalloc((void **)&job.id, (size_t)m * 4) != hipSuccess || hipMalloc((void **)&job.tri, tri_bytes) != hipSuccess ||
-          hipMalloc((void **)&job.hulls, sizeof(VsmDcHull) * nn) != hipSuccess)
-        return false;
-      if (device_kd && (hipMalloc((void **)&job.key_sorted, (size_t)m * 8) != hipSuccess ||
-                        hipMalloc((void **)&job.kd_scratch, (size_t)m * 4 * VSM_DC_KD_SCRATCH) != hipSuccess))
-        return false;
-      job.kd_stride = m;
-      job.tasks = d_tasks;
-      job.merges = d_merges;
-      job.ntasks = nt;
-      job.m = m;
-      job.nlevels = nlev;
-      job.level_off[0] = 0;
-      for (int l = 0; l < nlev; l++) {
-        job.level_off[l + 1] = job.level_off[l] + d.device_levels()[l];
-        lev_nodes[l] = d.device_levels()[l];
-      }
-    }
-    return hipMemcpy(d_jobs, jobs.data(), sizeof(VsmDcJob) * copies, hipMemcpyHostToDevice) == hipSuccess;
-  }
-  void load(const DcMesh &mesh, hipStream_t s) {
-    for (VsmDcJob &job : jobs) {
-      (void)hipMemcpyAsync(device_kd ? (void *)job.key_sorted : (void *)job.key, mesh.key, (size_t)m * 8, hipMemcpyHostToDevice, s);
-      (void)hipMemsetAsync(job.tri, 0xff, tri_bytes, s);
-    }
-  }
-  void launch(hipStream_t s) {
-    if (device_kd) vsm_dc_launch_kd_order(s, d_jobs, (int)jobs.size());
-    if (block) {
-      vsm_dc_launch_blocks(s, d_jobs, (int)jobs.size(), nt);
-      return;
-    }
-    vsm_dc_launch_subtrees(s, d_jobs, (int)jobs.size(), nt);
-    for (int l = 0; l < nlev; l++) vsm_dc_launch_merge_level(s, d_jobs, (int)jobs.size(), l, lev_nodes[l]);
-  }
-  ~DcDeviceCopy() {
-    for (VsmDcJob &job : jobs) {
-      (void)hipFree(job.key);
-      (void)hipFree(job.pt);
-      (void)hipFree(job.id);
-      (void)hipFree(job.tri);
-      (void)hipFree(job.hulls);
-      (void)hipFree((void *)job.key_sorted);
-      (void)hipFree(job.kd_scratch);
-    }
-    (void)hipFree(d_tasks);
-    (void)hipFree(d_merges);
-    (void)hipFree(d_jobs);
-  }
-};
-}  // namespace
-
-// test hook: prepare on the host; sub-trees and the merge nodes of at most device_top_points points on
-// the GPU (vsm_dc.hip); the merges above them on the host
-int32_t vsm_debug_delaunay_gpu(const int32_t *x, const int32_t *y, int32_t n, int32_t *tris, int32_t cap,
-                               int32_t max_task_points, int32_t device_top_points, int32_t device_kd) {
-  ExactDelaunay d;
-  if (d.prepare(x, y, n, max_task_points, nullptr, std::max(device_top_points, 0), device_kd != 0)) {
-    if (d.points() > VSM_DC_KD_MAX_POINTS) return -1;
-    const DcMesh mesh = d.mesh();
-    DcDeviceCopy dev;
-    dev.device_kd = device_kd != 0;
-    dev.block = device_top_points < 0;
-    if (!dev.create(d, 1)) return -1;
-    dev.load(mesh, nullptr);
-    dev.launch(nullptr);
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    std::vector<VsmDcHull> hulls(dev.nn);
-    (void)hipMemcpy(mesh.tri, dev.jobs[0].tri, dev.tri_bytes, hipMemcpyDeviceToHost);
-    (void)hipMemcpy(mesh.pt, dev.jobs[0].pt, (size_t)dev.m * 4, hipMemcpyDeviceToHost);
-    (void)hipMemcpy(mesh.id, dev.jobs[0].id, (size_t)dev.m * 4, hipMemcpyDeviceToHost);
-    (void)hipMemcpy(hulls.data(), dev.jobs[0].hulls, sizeof(VsmDcHull) * dev.nn, hipMemcpyDeviceToHost);
-    auto take = [&](int32_t q) {
-      d.set_node_hull(q, ExactDelaunay::OTri{hulls[q].fl_t, hulls[q].fl_o}, ExactDelaunay::OTri{hulls[q].fr_t, hulls[q].fr_o});
-    };
-    for (const ExactDelaunay::Task &tk : d.tasks()) take(tk.node);
-    for (const ExactDelaunay::Merge &mg : d.device_merges()) take(mg.node);
-    d.finish();
-  }
-  const int32_t ntri = d.num_triangles();
-  for (int32_t i = 0; i < ntri && i < cap; i++)
-    for (int k = 0; k < 3; k++) tris[i * 3 + k] = d.triangles()[i * 3 + k];
-  return ntri;
-}
-
-// micro-benchmark of the GPU side of the Delaunay stage: `njobs` copies of one prepared triangulation per
-// launch sequence (sub-trees, then the merge levels up to device_top_points); returns microseconds per
-// sequence (kernels only, HIP events), -1 on error
-double vsm_debug_dc_bench(const int32_t *x, const int32_t *y, int32_t n, int32_t max_task_points, int32_t device_top_points,
-                          int32_t device_kd, int32_t njobs, int32_t reps) {
-  ExactDelaunay d;
-  if (!d.prepare(x, y, n, max_task_points, nullptr, std::max(device_top_points, 0), device_kd != 0)) return -1;
-  const DcMesh mesh = d.mesh();
-  DcDeviceCopy dev;
-  dev.device_kd = device_kd != 0;
-  dev.block = device_top_points < 0;
-  if (!dev.create(d, njobs)) return -1;
-  hipEvent_t e0, e1;
-  (void)hipEventCreate(&e0);
-  (void)hipEventCreate(&e1);
-  double total = 0;
-  for (int r = 0; r < reps + 1; r++) {
-    dev.load(mesh, nullptr);
-    (void)hipEventRecord(e0, nullptr);
-    dev.launch(nullptr);
-    (void)hipEventRecord(e1, nullptr);
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    if (r > 0) total += ms * 1e3;
-  }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  return total / reps;
-}
-
-// test hooks: which matches at shared pixels stand for their points, (index the radix-sorted keys carry, index
-// Triangle's randomised vertex sort puts first) pairs - from the host emulation and from k_dc_ties; -1: not done
-int32_t vsm_host_ties(const int32_t *x, const int32_t *y, int32_t n, int32_t *pairs, int32_t cap) {
-  ExactDelaunay d;
-  d.prepare(x, y, n, n, nullptr, 0, true, true);
-  d.resolve_ties();
-  const auto &t = d.ties();
-  for (size_t k = 0; k < t.size() && (int32_t)k < cap; k++) {
-    pairs[2 * k] = t[k].first;
-    pairs[2 * k + 1] = t[k].second;
-  }
-  return (int32_t)t.size();
-}
-
-int32_t vsm_debug_ties_gpu(const int32_t *x, const int32_t *y, int32_t n, int32_t *pairs, int32_t cap, double *kernel_us) {
-  ExactDelaunay d;
-  d.prepare(x, y, n, n, nullptr, 0, true, true);
-  VsmDcJob job;
-  memset(&job, 0, sizeof(job));
-  VsmDcJob *d_job = nullptr;
-  uint64_t *d_keys = nullptr;
-  int32_t *d_out = nullptr;
-  std::vector<int32_t> out(1 + 2 * VSM_DC_TIE_PATCHES, 0);
-  if (hipMalloc((void **)&d_keys, (size_t)std::max(n, 1) * 8) != hipSuccess || hipMalloc((void **)&d_out, out.size() * 4) != hipSuccess ||
-      hipMalloc((void **)&d_job, sizeof(job)) != hipSuccess)
-    return -2;
-  (void)hipMemcpy(d_keys, d.tie_keys(), (size_t)n * 8, hipMemcpyHostToDevice);
-  (void)hipMemset(d_out, 0, out.size() * 4);
-  job.tie_keys = d_keys;
-  job.tie_out = d_out;
-  job.n_in = n;
-  (void)hipMemcpy(d_job, &job, sizeof(job), hipMemcpyHostToDevice);
-  hipEvent_t e0, e1;
-  (void)hipEventCreate(&e0);
-  (void)hipEventCreate(&e1);
-  (void)hipEventRecord(e0, nullptr);
-  vsm_dc_launch_ties(nullptr, d_job, 1);
-  (void)hipEventRecord(e1, nullptr);
-  const bool ok = hipDeviceSynchronize() == hipSuccess;
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  if (kernel_us) *kernel_us = ms * 1e3;
-  (void)hipMemcpy(out.data(), d_out, out.size() * 4, hipMemcpyDeviceToHost);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  (void)hipFree(d_keys);
-  (void)hipFree(d_out);
-  (void)hipFree(d_job);
-  if (!ok) return -2;
-  for (int32_t k = 0; k < out[0] && k < cap; k++) {
-    pairs[2 * k] = out[1 + 2 * k];
-    pairs[2 * k + 1] = out[2 + 2 * k];
-  }
-  return out[0];
-}
-
-int32_t vsm_host_outliers_and_prior(const vsm_params *p, const vsm_p_match *list, int32_t n, int32_t method, vsm_p_match *out,
-                                    int32_t cap, float *ranges, int32_t w, int32_t hh) {
-  VsmHostWork wk;
-  std::vector<vsm_p_match> m(list, list + std::max(n, 0));
-  vsm_host_remove_outliers(wk, *p, m, method);
-  if (ranges) {
-    const int32_t dims[3] = {w, hh, w};
-    std::vector<float> rg;
-    vsm_host_prior_statistics(*p, dims, m, method, rg);
-    ranges_to_device_layout(ranges, rg.data(), rg.size());
-  }
-  for (size_t i = 0; i < m.size() && (int32_t)i < cap; i++) out[i] = m[i];
-  return (int32_t)m.size();
-}
-
-int32_t vsm_host_outliers_and_prior_threads(const vsm_params *p, const vsm_p_match *list, int32_t n, int32_t method, vsm_p_match *out,
-                                            int32_t cap, float *ranges, int32_t w, int32_t hh, int32_t threads) {
-  if (threads <= 1) return vsm_host_outliers_and_prior(p, list, n, method, out, cap, ranges, w, hh);
-  VsmForkJoin fj(std::min(threads, 64));
-  VsmPool apart(2);  // (as in a handle: Triangle's emulated vertex sort runs beside the triangulation of lists from 1024 matches)
-  VsmHostWork wk;
-  wk.pool = &fj;
-  wk.async = &apart;
-  std::vector<vsm_p_match> m;
-  if (n > 3) {  // vsm_match's final stage (early_xy): pixels first, then flows, votes, survivors
-    std::vector<uint32_t> xy((size_t)n);
-    for (int32_t i = 0; i < n; i++) xy[i] = (uint32_t)(int32_t)list[i].u1c | ((uint32_t)(int32_t)list[i].v1c << 16);
-    vsm_host_outliers_begin_xy(wk, xy.data(), n);
-    wk.del.run(wk.x.data(), wk.y.data(), n, wk.pool, wk.async);
-    vsm_host_outliers_begin_flows(wk, list, n, method);
-    vsm_host_outliers_end(wk, *p, list, n, method, m);
-  } else {
-    m.assign(list, list + std::max(n, 0));  // the reference leaves short lists alone (viso/matcher.cpp:1210)
-  }
-  if (ranges) {
-    const int32_t dims[3] = {w, hh, w};
-    std::vector<float> rg;
-    vsm_host_prior_statistics(*p, dims, m, method, rg);
-    ranges_to_device_layout(ranges, rg.data(), rg.size());
-  }
-  for (size_t i = 0; i < m.size() && (int32_t)i < cap; i++) out[i] = m[i];
-  return (int32_t)m.size();
-}
-
-int32_t vsm_debug_dc2(const vsm_params *p, const vsm_p_match *list, int32_t n, int32_t method, int32_t gpu_ties, int32_t copies,
-                      vsm_p_match *out, int32_t cap, float *ranges, int32_t w, int32_t hh, double *kernel_us) {
-  if (copies < 1) copies = 1;
-  const int ub = (int)ceilf((float)w / (float)p->match_binsize), vb = (int)ceilf((float)hh / (float)p->match_binsize);
-  if (ranges && ub * vb > 1024) return -2;
-  Dc2Bank B;
-  if (!B.reserve(copies, std::max(n, 64), true)) return -1;
-  vsm_p_match *d_list = nullptr, *d_out = nullptr;
-  int32_t *d_cnt = nullptr;
-  float *d_ranges = nullptr;
-  const size_t lb = (size_t)std::max(n, 1) * sizeof(vsm_p_match), rb = (size_t)ub * vb * 16 * 4;
-  bool ok = hipMalloc((void **)&d_list, lb) == hipSuccess && hipMalloc((void **)&d_out, lb * copies) == hipSuccess &&
-            hipMalloc((void **)&d_cnt, 4) == hipSuccess && hipMalloc((void **)&d_ranges, rb * copies) == hipSuccess;
-  int32_t result = -1;
-  if (ok) {
-    (void)hipMemcpy(d_list, list, (size_t)n * sizeof(vsm_p_match), hipMemcpyHostToDevice);
-    (void)hipMemcpy(d_cnt, &n, 4, hipMemcpyHostToDevice);
-    for (int i = 0; i < copies; i++)
-      B.fill_job(i, d_list, d_cnt, gpu_ties != 0, d_out + (size_t)i * std::max(n, 1), nullptr, d_ranges + (size_t)i * ub * vb * 16);
-    (void)hipMemcpy(B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * copies, hipMemcpyHostToDevice);
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0);
-    (void)hipEventCreate(&e1);
-    (void)hipEventRecord(e0, nullptr);
-    dc2_enqueue_triangulation(nullptr, B, copies, n, gpu_ties != 0);
-    if (!gpu_ties) {  // the host's verdicts (the look-ahead path computes them while the device triangulates)
-      ok = hipDeviceSynchronize() == hipSuccess;
-      for (int i = 0; i < copies && ok; i++) B.sort_ties_of(i);
-    }
-    // (VSM_DC2_EXPECT_LONG=0, tests: a list of 8193..16384 matches through the narrow form inside the LDS kernel, as in a handle
-    // that has not met a long list yet)
-    const char *xl = getenv("VSM_DC2_EXPECT_LONG");
-    dc2_enqueue_mesh(nullptr, B, copies, n, g_no_prof, false, nullptr, xl ? atoi(xl) != 0 : true);
-    dc2_enqueue_votes(nullptr, B, copies, n, method, (float)p->outlier_flow_tolerance, (float)p->outlier_disp_tolerance);
-    if (ranges) vsm_dc2_launch_prior(nullptr, B.d_jobs, copies, method, p->match_binsize, p->match_radius, w, hh, ub, vb);
-    (void)hipEventRecord(e1, nullptr);
-    ok = ok && hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess;
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    if (kernel_us) *kernel_us = ms * 1e3;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-#ifdef VSM_DC2_DUMP_FILE  // debugging aid (tools/dc2_dump.py on a -DVSM_DC2_DUMP_FILE=\"path\" build): the first job's triangulation as the device left it
-    {
-      const char *dump = VSM_DC2_DUMP_FILE;  // debugging aid: the first job's triangulation as the device left it
-      int32_t mn[2] = {0, 0};
-      (void)hipMemcpy(mn, B.pp[0].mn, 8, hipMemcpyDeviceToHost);
-      const int32_t mm = std::max(mn[0], 0);
-      std::vector<int32_t> tri((size_t)mm * 16), idv(mm);
-      std::vector<uint32_t> ptv(mm);
-      (void)hipMemcpy(tri.data(), B.pp[0].tri, tri.size() * 4, hipMemcpyDeviceToHost);
-      (void)hipMemcpy(ptv.data(), B.pp[0].pt, ptv.size() * 4, hipMemcpyDeviceToHost);
-      (void)hipMemcpy(idv.data(), B.pp[0].id, idv.size() * 4, hipMemcpyDeviceToHost);
-      if (FILE *f = fopen(dump, "wb")) {
-        fwrite(mn, 4, 2, f);
-        fwrite(tri.data(), 4, tri.size(), f);
-        fwrite(ptv.data(), 4, ptv.size(), f);
-        fwrite(idv.data(), 4, idv.size(), f);
-        fclose(f);
-      }
-    }
-#endif
-    if (ok && *B.h_error) {
-      result = -2;
-    } else if (ok) {
-      // every copy must have produced the same survivors
-      std::vector<int32_t> cnt(copies);
-      std::vector<vsm_p_match> first, other;
-      bool same = true;
-      for (int i = 0; i < copies && same; i++) {
-        (void)hipMemcpy(&cnt[i], B.pp[i].out_count, 4, hipMemcpyDeviceToHost);
-        same = cnt[i] == cnt[0] && cnt[i] >= 0 && cnt[i] <= n;
-        if (!same) break;
-        std::vector<vsm_p_match> &dst = i == 0 ? first : other;
-        dst.resize(cnt[i]);
-        if (cnt[i]) (void)hipMemcpy(dst.data(), d_out + (size_t)i * std::max(n, 1), (size_t)cnt[i] * sizeof(vsm_p_match), hipMemcpyDeviceToHost);
-        if (i > 0) same = memcmp(first.data(), other.data(), (size_t)cnt[0] * sizeof(vsm_p_match)) == 0;
-      }
-      if (same) {
-        result = cnt[0];
-        for (int32_t i = 0; i < result && i < cap; i++) out[i] = first[i];
-        if (ranges) (void)hipMemcpy(ranges, d_ranges + (size_t)(copies - 1) * ub * vb * 16, rb, hipMemcpyDeviceToHost);
-      } else {
-        result = -3;
-      }
-    }
-  }
-  (void)hipFree(d_list);
-  (void)hipFree(d_out);
-  (void)hipFree(d_cnt);
-  (void)hipFree(d_ranges);
-  B.release();
-  return result;
-}
-
-// ---- test hook of the compaction and its key store (k_compact_quad, k_compact_count / k_compact_write) ----
-// P pairs in one launch, pair k with n_query[k] queries whose acceptance flags and raw records the caller gives.  Out per pair:
-// the list (n_query[k] + 1 records), its count, the keys (key_cap[k] + VSM_DEBUG_KEY_GUARD words).  List and key arrays are
-// filled with 0xA5 bytes before the launch, so whatever the kernels do not write - the guard entries behind each array, keys
-// at and beyond the count or the capacity - comes back as that pattern.  old_keys = 1: the compaction without its key
-// store, then k_dc2_keys over the lists (cap = key_cap[k]) - the hand-over the fused store replaces; 2: the fused store
-// with its host-mapped second target, whose content comes back.
-#define VSM_DEBUG_KEY_GUARD 8
-int32_t vsm_debug_compact_keys(int32_t method, int32_t pass, int32_t P, const int32_t *n_query, const int32_t *const *flag, const vsm_p_match *const *raw,
-                               const int32_t *key_cap, int32_t old_keys, vsm_p_match *const *list_out, int32_t *count_out, uint64_t *const *keys_out) {
-  if (P < 1 || P > 64 || method < 0 || method > 2 || pass < 0 || pass > 1 || !n_query || !flag || !raw || !key_cap || !list_out || !count_out || !keys_out)
-    return VSM_EARG;
-  int max_nq = 0;
-  for (int32_t k = 0; k < P; k++) {
-    if (n_query[k] < 0 || n_query[k] > (1 << 20) || key_cap[k] < 0 || key_cap[k] > (1 << 20)) return VSM_EARG;
-    max_nq = std::max(max_nq, n_query[k]);
-  }
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = off;
-    off += al256(bytes);
-    return o;
-  };
-  struct Off {
-    size_t raw, flag, bc, list, keys, cnt;
-  };
-  std::vector<Off> po(P);
-  for (int32_t k = 0; k < P; k++) {
-    const size_t nq = (size_t)n_query[k];
-    po[k].raw = take((nq + 1) * sizeof(vsm_p_match));
-    po[k].flag = take((nq + 4) * 4);
-    po[k].bc = take((nq / 256 + 2) * 4);
-    po[k].list = take((nq + 1) * sizeof(vsm_p_match));
-    po[k].keys = take(((size_t)key_cap[k] + VSM_DEBUG_KEY_GUARD) * 8);
-    po[k].cnt = take(4 * sizeof(int32_t));
-  }
-  const size_t o_pairs = take((size_t)P * sizeof(VsmPair)), o_jobs = take((size_t)P * sizeof(VsmJob)), o_dc = take((size_t)P * sizeof(VsmDc2Job));
-  uint8_t *block = nullptr;
-  if (hipMalloc((void **)&block, off) != hipSuccess) return VSM_EHIP;
-  std::vector<VsmPair> pairs(P);
-  std::vector<VsmJob> jobs(P);
-  std::vector<VsmDc2Job> dc(P);
-  bool ok = hipMemset(block, 0, off) == hipSuccess;
-  for (int32_t k = 0; k < P && ok; k++) {
-    VsmPair &pr = pairs[k];
-    memset(&pr, 0, sizeof(pr));
-    memset(&jobs[k], 0, sizeof(VsmJob));
-    memset(&dc[k], 0, sizeof(VsmDc2Job));
-    pr.raw = (vsm_p_match *)(block + po[k].raw);
-    pr.flag = (int32_t *)(block + po[k].flag);
-    pr.blockcnt = (int32_t *)(block + po[k].bc);
-    pr.list1 = pr.list2 = (vsm_p_match *)(block + po[k].list);
-    pr.count = (int32_t *)(block + po[k].cnt);
-    pr.hcount = pr.count + 2;  // (no host-mapped twin here)
-    pr.keys[0] = pr.keys[1] = (uint64_t *)(block + po[k].keys);
-    pr.key_cap[0] = pr.key_cap[1] = key_cap[k];
-    jobs[k].nq[pass] = n_query[k];
-    dc[k].list = pr.list1;
-    dc[k].count = pr.count + pass;
-    dc[k].cap = key_cap[k];
-    dc[k].keys_in = pr.keys[0];
-    const size_t nq = (size_t)n_query[k];
-    ok = hipMemset(pr.list1, 0xA5, (nq + 1) * sizeof(vsm_p_match)) == hipSuccess &&
-         hipMemset(pr.keys[0], 0xA5, ((size_t)key_cap[k] + VSM_DEBUG_KEY_GUARD) * 8) == hipSuccess &&
-         (nq == 0 || (hipMemcpy(pr.flag, flag[k], nq * 4, hipMemcpyHostToDevice) == hipSuccess &&
-                      hipMemcpy(pr.raw, raw[k], nq * sizeof(vsm_p_match), hipMemcpyHostToDevice) == hipSuccess));
-  }
-  VsmPair *d_pairs = (VsmPair *)(block + o_pairs);
-  VsmJob *d_jobs = (VsmJob *)(block + o_jobs);
-  VsmDc2Job *d_dc = (VsmDc2Job *)(block + o_dc);
-  ok = ok && hipMemcpy(d_pairs, pairs.data(), (size_t)P * sizeof(VsmPair), hipMemcpyHostToDevice) == hipSuccess &&
-       hipMemcpy(d_jobs, jobs.data(), (size_t)P * sizeof(VsmJob), hipMemcpyHostToDevice) == hipSuccess &&
-       hipMemcpy(d_dc, dc.data(), (size_t)P * sizeof(VsmDc2Job), hipMemcpyHostToDevice) == hipSuccess;
-  // (old_keys = 2: the key store's second target, a host-mapped array per pair, is what comes back)
-  uint8_t *hk = nullptr;
-  uint64_t *hk_dev = nullptr;
-  int32_t max_cap = 0;
-  for (int32_t k = 0; k < P; k++) max_cap = std::max(max_cap, key_cap[k]);
-  const size_t hk_stride = al256(((size_t)max_cap + VSM_DEBUG_KEY_GUARD) * 8);
-  if (ok && old_keys == 2) {
-    ok = hipHostMalloc((void **)&hk, hk_stride * P, hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer((void **)&hk_dev, hk, 0) == hipSuccess;
-    if (ok) memset(hk, 0xA5, hk_stride * P);
-  }
-  if (ok) {
-    VsmJob dummy;
-    memset(&dummy, 0, sizeof(dummy));
-    const VsmKeyOut ko = {hk_dev, hk_stride, max_cap};
-    vsm_launch_compact(nullptr, d_pairs, d_jobs, dummy, P, method, pass, max_nq, old_keys == 1 ? nullptr : &ko);
-    if (old_keys == 1) vsm_dc2_launch_keys(nullptr, d_dc, P, max_nq);
-    ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
-  }
-  for (int32_t k = 0; k < P && ok; k++) {
-    int32_t cnt[4] = {0, 0, 0, 0};
-    ok = hipMemcpy(cnt, pairs[k].count, sizeof(cnt), hipMemcpyDeviceToHost) == hipSuccess && cnt[pass] == cnt[2 + pass] &&
-         hipMemcpy(list_out[k], pairs[k].list1, ((size_t)n_query[k] + 1) * sizeof(vsm_p_match), hipMemcpyDeviceToHost) == hipSuccess &&
-         hipMemcpy(keys_out[k], pairs[k].keys[0], ((size_t)key_cap[k] + VSM_DEBUG_KEY_GUARD) * 8, hipMemcpyDeviceToHost) == hipSuccess;
-    if (ok && old_keys == 2) memcpy(keys_out[k], hk + hk_stride * k, ((size_t)key_cap[k] + VSM_DEBUG_KEY_GUARD) * 8);
-    count_out[k] = cnt[pass];
-  }
-  if (hk) (void)hipHostFree(hk);
-  (void)hipFree(block);
-  return ok ? VSM_OK : VSM_EHIP;
-}
-
-// ---- test hooks of the refinement kernels (k_refine<TILED>, k_parabolic_costs, k_parabolic_apply) on lists of the caller ----
-#define VSM_DEBUG_REFINE_MAX_PAIRS 64
-
-// The refinement reads 5 x 5 bytes around (u1c, v1c) unguarded and converts the point to int: every reference point must be a
-// pixel inside the margin.  The targets only have to be finite (the kernels' own margin tests guard them; the conversion of
-// a float they let through is defined).  Pure arithmetic: the CPU suite calls it (vsm_debug_refine_check).
-static int refine_lists_check(int32_t w, int32_t hh, const vsm_p_match *const *lists, const int32_t *counts, int32_t P) {
-  if (P < 1 || P > VSM_DEBUG_REFINE_MAX_PAIRS || !lists || !counts) return VSM_EARG;
-  if (w < 2 * VSM_MARGIN + 1 || hh < 2 * VSM_MARGIN + 1) return VSM_EARG;
-  const float u_lo = (float)VSM_MARGIN, u_hi = (float)(w - 1 - VSM_MARGIN), v_hi = (float)(hh - 1 - VSM_MARGIN);
-  for (int32_t k = 0; k < P; k++) {
-    if (counts[k] < 0 || counts[k] > VSM_PARA_MAX_LIST || (counts[k] > 0 && !lists[k])) return VSM_EARG;
-    for (int32_t i = 0; i < counts[k]; i++) {
-      const vsm_p_match &m = lists[k][i];
-      const float xy[8] = {m.u1p, m.v1p, m.u2p, m.v2p, m.u1c, m.v1c, m.u2c, m.v2c};
-      for (float x : xy)
-        if (!std::isfinite(x)) return VSM_EARG;
-      if (!(m.u1c >= u_lo && m.u1c <= u_hi && m.v1c >= u_lo && m.v1c <= v_hi)) return VSM_EARG;
-      if (m.u1c != floorf(m.u1c) || m.v1c != floorf(m.v1c)) return VSM_EARG;
-    }
-  }
-  return VSM_OK;
-}
-
-// P caller-given pass-2 lists as the P pairs of one launch: per pair list2, raw, (records) and the counts in one device
-// block, the pair table, and a job table whose entries all name the same frames
-struct DebugPairs {
-  uint8_t *block = nullptr;
-  VsmPair *d_pairs = nullptr;
-  VsmJob *d_jobs = nullptr;
-  std::vector<VsmPair> pairs;
-  ~DebugPairs() {
-    if (block) (void)hipFree(block);
-  }
-  hipError_t create(hipStream_t s, const vsm_p_match *const *lists, const int32_t *const *records, const int32_t *counts, int32_t P, bool with_pf,
-                    const VsmJob &job) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-      const size_t o = off;
-      off += al256(bytes);
-      return o;
-    };
-    struct Off {
-      size_t l2, raw, pf, cnt;
-    };
-    std::vector<Off> po(P);
-    for (int32_t k = 0; k < P; k++) {
-      const size_t cap = (size_t)std::max(counts[k], 1);
-      po[k].l2 = take(cap * sizeof(vsm_p_match));
-      po[k].raw = take(cap * sizeof(vsm_p_match));
-      po[k].pf = with_pf ? take(cap * 36 * sizeof(int32_t)) : 0;
-      po[k].cnt = take(4 * sizeof(int32_t));
-    }
-    const size_t o_pairs = take((size_t)P * sizeof(VsmPair)), o_jobs = take((size_t)P * sizeof(VsmJob));
-    hipError_t e = hipMalloc((void **)&block, off);
-    if (e != hipSuccess) return e;
-    if ((e = hipMemsetAsync(block, 0, off, s)) != hipSuccess) return e;
-    pairs.assign(P, VsmPair());
-    std::vector<VsmJob> jobs(P, job);
-    std::vector<int32_t> cnt((size_t)P * 2, 0);  // (sources of asynchronous copies: alive until the synchronisation below)
-    for (int32_t k = 0; k < P; k++) {
-      VsmPair &pr = pairs[k];
-      memset(&pr, 0, sizeof(pr));
-      pr.list2 = (vsm_p_match *)(block + po[k].l2);
-      pr.raw = (vsm_p_match *)(block + po[k].raw);
-      pr.pf = with_pf ? (int32_t *)(block + po[k].pf) : nullptr;
-      pr.count = (int32_t *)(block + po[k].cnt);
-      pr.hcount = pr.count + 2;  // (no host-mapped twin here: the tail's second count goes beside the first)
-      cnt[2 * k + 1] = counts[k];
-      if ((e = hipMemcpyAsync(pr.count, &cnt[2 * k], 2 * sizeof(int32_t), hipMemcpyHostToDevice, s)) != hipSuccess) return e;
-      if (counts[k] > 0 && (e = hipMemcpyAsync(pr.list2, lists[k], (size_t)counts[k] * sizeof(vsm_p_match), hipMemcpyHostToDevice, s)) != hipSuccess)
-        return e;
-      if (counts[k] > 0 && records &&
-          (e = hipMemcpyAsync(pr.pf, records[k], (size_t)counts[k] * 36 * sizeof(int32_t), hipMemcpyHostToDevice, s)) != hipSuccess)
-        return e;
-    }
-    d_pairs = (VsmPair *)(block + o_pairs);
-    d_jobs = (VsmJob *)(block + o_jobs);
-    if ((e = hipMemcpyAsync(d_pairs, pairs.data(), (size_t)P * sizeof(VsmPair), hipMemcpyHostToDevice, s)) != hipSuccess) return e;
-    if ((e = hipMemcpyAsync(d_jobs, jobs.data(), (size_t)P * sizeof(VsmJob), hipMemcpyHostToDevice, s)) != hipSuccess) return e;
-    return hipStreamSynchronize(s);  // (the sources are the caller's and this function's pageable memory)
-  }
-  // the lists as the kernels left them; shorter: the tail of refinement == 2 has rewritten the counts
-  hipError_t fetch(const int32_t *counts, int32_t P, bool shorter, vsm_p_match *const *out, int32_t *out_counts) {
-    for (int32_t k = 0; k < P; k++) {
-      int32_t n = counts[k];
-      if (shorter) {
-        int32_t cnt[4] = {0, 0, 0, 0};
-        const hipError_t e = hipMemcpy(cnt, pairs[k].count, sizeof(cnt), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return e;
-        if (cnt[1] < 0 || cnt[1] > counts[k] || cnt[3] != cnt[1]) return hipErrorUnknown;
-        n = cnt[1];
-      }
-      out_counts[k] = n;
-      if (n > 0) {
-        const hipError_t e = hipMemcpy(out[k], pairs[k].list2, (size_t)n * sizeof(vsm_p_match), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return e;
-      }
-    }
-    return hipSuccess;
-  }
-};
-
-int32_t vsm_debug_refine_check(int32_t w, int32_t hh, const vsm_p_match *const *lists, const int32_t *counts, int32_t P) {
-  return refine_lists_check(w, hh, lists, counts, P);
-}
-
-int32_t vsm_debug_refine(vsm_handle *h, int32_t method, const vsm_p_match *const *lists, const int32_t *counts, int32_t P,
-                         vsm_p_match *const *out, int32_t *out_counts) {
-  if (!h || method < 0 || method > 2 || !out || !out_counts) return VSM_EARG;
-  VsmCtx &c = h->ring;
-  if (!c.ready) return VSM_ENOTREADY;
-  const vsm_params &p = h->param;
-  if (p.refinement != 1 && p.refinement != 2) return VSM_EARG;
-  {
-    const int rc = refine_lists_check(c.dims.w, c.dims.h, lists, counts, P);
-    if (rc != VSM_OK) return rc;
-  }
-  HIPCHK(hipSetDevice(h->device));
-  {
-    const int rc = settle(h);
-    if (rc != VSM_OK) return rc;
-  }
-  const int sc = h->cur, sp = h->cur ^ 1;
-  if (!h->have[sc] || (method != 1 && !h->have[sp]) || (method != 0 && !h->right[sc]) || (method == 2 && !h->right[sp])) return VSM_ENOTREADY;
-  for (int s = 0; s < 5; s++) h->stage[s].clear();
-  h->stage3_in_hm = false;
-  h->matched.clear();
-  VsmJob job;
-  memset(&job, 0, sizeof(job));
-  job.img_prev = (method == 1 ? sc : sp) * 2;  // (as in vsm_match)
-  job.img_curr = sc * 2;
-  int32_t n_upper = 0;
-  for (int32_t k = 0; k < P; k++) n_upper = std::max(n_upper, counts[k]);
-  DebugPairs D;
-  HIPCHK(D.create(h->stream, lists, nullptr, counts, P, p.refinement == 2, job));
-  vsm_launch_refine(h->stream, h->prof, c.d_imgs, D.d_pairs, D.d_jobs, job, P, c.dims, c.dims, method, p.refinement, n_upper);
-  if (p.refinement == 2) vsm_launch_parabolic_apply(h->stream, h->prof, D.d_pairs, P);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(h->stream));
-  h->prof.resolve();
-  HIPCHK(D.fetch(counts, P, p.refinement == 2, out, out_counts));
-  return VSM_OK;
-}
-
-int32_t vsm_debug_parabolic_apply(const vsm_p_match *const *lists, const int32_t *const *records, const int32_t *counts, int32_t P,
-                                  vsm_p_match *const *out, int32_t *out_counts) {
-  if (P < 1 || P > VSM_DEBUG_REFINE_MAX_PAIRS || !lists || !records || !counts || !out || !out_counts) return VSM_EARG;
-  for (int32_t k = 0; k < P; k++)
-    if (counts[k] < 0 || counts[k] > VSM_PARA_MAX_LIST || (counts[k] > 0 && (!lists[k] || !records[k]))) return VSM_EARG;
-  VsmJob job;
-  memset(&job, 0, sizeof(job));
-  DebugPairs D;
-  HIPCHK(D.create(nullptr, lists, records, counts, P, true, job));
-  vsm_launch_parabolic_apply(nullptr, g_no_prof, D.d_pairs, P);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(D.fetch(counts, P, true, out, out_counts));
-  return VSM_OK;
-}
-
-int32_t vsm_host_parabolic_fits(const int32_t *records, int32_t n, float *uv, int32_t *ok) {
-  if (n < 0 || (n > 0 && (!records || !uv || !ok))) return VSM_EARG;
-  for (int32_t i = 0; i < n; i++) {
-    const int32_t *r = records + (size_t)i * 12;
-    ok[i] = vsm_host_parabolic_update(r + 3, r[1], r[2], uv[2 * i], uv[2 * i + 1]) ? 1 : 0;
-  }
-  return n;
-}
-
 void vsm_get_counters(vsm_handle *h, int64_t *out5) { memcpy(out5, h->counters, sizeof(h->counters)); }
 void vsm_get_timings(vsm_handle *h, double *out5) { memcpy(out5, h->timings, sizeof(h->timings)); }
 
 }  // extern "C"
+#include "vsm_debug.inc"

@@ -120,11 +120,7 @@ int vsm_multi_process(vsm_multi *m, const uint8_t *left, const uint8_t *right, i
   int max_nq[2] = {0, 0};
   for (int i = 0; i < K; i++) {
     vsm_multi::Seq &s = m->seq[i];
-    VsmJob &jb = h_jobs[i];
-    memset(&jb, 0, sizeof(jb));
-    const int img_c = first_img + 2 * i;
-    jb.img_prev = prev_img + 2 * i;
-    jb.img_curr = img_c;
+    const int img_c = first_img + 2 * i, img_p = prev_img + 2 * i;
     int32_t cnt[4][2];
     for (int q = 0; q < 2; q++) {
       cnt[0][q] = s.have_prev ? s.nfeat[0][q] : 0;
@@ -132,17 +128,10 @@ int vsm_multi_process(vsm_multi *m, const uint8_t *left, const uint8_t *right, i
       cnt[2][q] = c.hm_counts[img_c * 2 + q];
       cnt[3][q] = c.hm_counts[(img_c + 1) * 2 + q];
     }
-    if (s.have_prev && match_ready(p, method, cnt)) {
-      valid[i] = 1;
-      jb.nq[0] = p.multi_stage ? cnt[0][0] : 0;
-      jb.nq[1] = cnt[0][1];
-      if (s.valid) {  // matchFeatures(2, Tr_valid ? &Tr_delta : 0), viso/viso_stereo.cpp:35
-        jb.use_tr = 1;
-        memcpy(jb.t, s.T, 12 * sizeof(double));
-      }
-    }
-    max_nq[0] = std::max(max_nq[0], jb.nq[0]);
-    max_nq[1] = std::max(max_nq[1], jb.nq[1]);
+    if (s.have_prev)  // matchFeatures(2, Tr_valid ? &Tr_delta : 0), viso/viso_stereo.cpp:35
+      valid[i] = vsm_job_fill(p, method, cnt, img_p, img_c, s.valid ? s.T : nullptr, h_jobs[i], max_nq) ? 1 : 0;
+    else  // (a sequence's first frame: nothing to match it with)
+      vsm_job_slots(h_jobs[i], img_p, img_c);
     for (int q = 0; q < 2; q++) {  // (this frame is the next step's previous one - once the step has succeeded)
       nfeat_new[(size_t)i * 4 + q] = cnt[2][q];
       nfeat_new[(size_t)i * 4 + 2 + q] = cnt[3][q];

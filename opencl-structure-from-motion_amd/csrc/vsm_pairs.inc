@@ -6,7 +6,7 @@
 // (previous, current) pairs: every frame goes through the image side ONCE, whatever number of pairs names it, and stays
 // in HBM; the pairs then go, C at a time, through the step a vsm_multi_process call runs for its K sequences (vsm_step_run,
 // vsm_step.inc) - first pass, its outlier removal and prior boxes, second pass, refinement, the final exact-Delaunay chain -
-// from a job table that names the images by slot (pair_jobs, vsm_api.cpp).  No kernel is this form's own.  Per pair the list is, byte for byte,
+// from a job table that names the images by slot (pair_jobs, vsm_jobs.h).  No kernel is this form's own.  Per pair the list is, byte for byte,
 // getMatches() of a fresh Matcher after pushBack(a), pushBack(b), matchFeatures(method, Tr of the pair).
 struct VsmPairs {
   VsmCtx ctx;  // every image of the set (frame f: slots sides * f, + 1) and one bank of C pairs

@@ -465,30 +465,7 @@ static int sequence_run_v1(vsm_handle *h, const uint8_t *left, const uint8_t *ri
   double tg = 0, thost = 0;
   std::atomic<long long> mid_ns[2] = {};  // VSM_DEBUG_TIMING: pass-1 outlier removal, prior statistics (task time)
   const double tstart = now_us();
-  // Chunk boundaries: chunks of C frames; a sequence of at least three chunks starts (and ends) with a half chunk - the
-  // host pool has nothing to do until the first chunk's lists exist, and nothing overlaps the last chunk's final stage
-  std::vector<int32_t> chunk_start;
-  {
-    const bool taper = true;
-    const int32_t half = C / 2;
-    int32_t f = 0;
-    if (taper && half >= 8 && n_frames >= 3 * C) {
-      chunk_start.push_back(0);
-      f = half;
-      while (n_frames - f > C + half) {
-        chunk_start.push_back(f);
-        f += C;
-      }
-      if (n_frames - f > C) {  // between C and 3C/2 frames left: a full chunk and a short one
-        chunk_start.push_back(f);
-        f = n_frames - std::min<int32_t>(half, n_frames - f - 1);
-      }
-      chunk_start.push_back(f);
-    } else {
-      for (; f < n_frames; f += C) chunk_start.push_back(f);
-    }
-    chunk_start.push_back(n_frames);
-  }
+  const std::vector<int32_t> chunk_start = seq1_plan(n_frames, C);  // (vsm_jobs.h)
   const int nchunks = (int)chunk_start.size() - 1;
   auto launch_features_of = [&](int k) -> hipError_t {  // ingest + all feature kernels of chunk k, then the marker
     const int32_t f0 = chunk_start[k];

@@ -624,71 +624,6 @@ static bool seq2_wait_chunk(Seq2Chunk *ch, double timeout_us, VsmPool *helper = 
   return true;
 }
 
-// The chunk plan of a look-ahead call: the chunk size C (the frame and pair banks' stride) and the frame every chunk starts
-// at (start[nchunks] = n_frames).  Pure arithmetic - no HIP call, nothing of a handle - so the CPU suite pins it through
-// vsm_debug_seq_plan (tests/test_seq_plan.py).  `plan`: the call passes getenv("VSM_SEQ_PLAN").
-struct Seq2Plan {
-  int C = 0;
-  std::vector<int32_t> start;
-};
-static Seq2Plan seq2_plan(int32_t n_frames, int pool_threads, bool host_in, int seq_chunk, int seq_first_chunk, const char *plan) {
-  // Chunk size.  A final chain is a row of latency-bound kernels and takes about as long for 50 lists as for 80, so fewer,
-  // larger chunks pay as long as the host keeps up with their vertex sorts.  Measured (200 frames 1242x375, ms per sequence,
-  // 14 pool threads, round 4's five-queue layout): 6.0 / 5.15 / 4.65 / 4.55 / 4.56 / 4.61 / 4.97 with chunks of 40 / 50 / 67 /
-  // 80 / 84 / 90 / 100 (80: 80 + 80 + 40 - the last, short chain is the call's tail).  With the copy engine's order planned
-  // (export_some) and the last chunk's sort + kd order in front of its predecessor's block kernel, TWO chunks beat three for
-  // ranks with ten pool threads or more - 4.60 / 4.76 / 4.34 / 4.28 / 4.30 / 4.33 / 4.40 with 80 / 90 / 100 / 105 / 110 / 115 / 120
-  // / 134 (110: 110 + 90) -; with eight threads the pool's vertex sorts bound the call either way (5.3 ms), with four 50 wins.
-  // Host-resident inputs: the first chunk's upload is the one transfer nothing hides, so the first chunk is HALF a chunk
-  // (and the chunks a little larger, so that 200 frames still make three): 40 + 80 + 80.
-  // (three host threads or fewer: the device sorts a share of the final lists in one launch behind the call's last keys, and
-  // every chunk's survivors cross PCIe behind that - two chunks of 100: 7.6 ms against 8.3 with four of 50)
-  int C = seq_chunk > 0 ? seq_chunk : (pool_threads >= 10 && !host_in ? 110 : (pool_threads >= 6 ? 80 : (pool_threads <= 4 && !host_in ? 100 : 50)));
-  if (C > n_frames) C = n_frames;
-  if (seq_chunk <= 0 && n_frames > C && n_frames % C != 0 && n_frames % C < C / 2) {
-    // (a short last chunk costs a whole chain's latency at the end of the call: 1000 frames are ten chunks of 100, not nine
-    // of 110 and one of 10; 200 stay 110 + 90)
-    const int nch = (n_frames + C - 1) / C;
-    C = (n_frames + nch - 1) / nch;
-  }
-  Seq2Plan P;
-  P.C = C;
-  std::vector<int32_t> &chunk_start = P.start;
-  if (host_in && plan) {  // (experiments: the chunks' sizes, "40,80,60,20")
-    chunk_start.push_back(0);
-    for (const char *q = plan; *q && chunk_start.back() < n_frames;) {
-      const int v = std::min(std::max(atoi(q), 2), C);
-      chunk_start.push_back(std::min(n_frames, chunk_start.back() + v));
-      while (*q && *q != ',') q++;
-      if (*q == ',') q++;
-    }
-    while (chunk_start.back() < n_frames) chunk_start.push_back(std::min(n_frames, chunk_start.back() + C));
-    chunk_start.pop_back();
-  } else if (host_in && n_frames > C && C >= 2) {
-    chunk_start.push_back(0);
-    for (int32_t f = C / 2; f < n_frames; f += C) chunk_start.push_back(f);
-    // (the frames arrive at the link's rate and the GPU keeps up with them: what the call waits for at its end is everything
-    // that follows the LAST frames' arrival - features, both passes, two chain latencies - so the last chunk is a short one)
-    if (n_frames - chunk_start.back() > 30) chunk_start.push_back(n_frames - 20);
-  } else if (seq_first_chunk > 0 && seq_first_chunk < C && n_frames > C) {
-    chunk_start.push_back(0);
-    for (int32_t f = seq_first_chunk; f < n_frames; f += C) chunk_start.push_back(f);
-  } else {
-    for (int32_t f = 0; f < n_frames; f += C) chunk_start.push_back(f);
-  }
-  chunk_start.push_back(n_frames);
-  return P;
-}
-// (debug entry, include/visomatch.h)
-extern "C" int32_t vsm_debug_seq_plan(int32_t n_frames, int32_t pool_threads, int32_t host_in, int32_t seq_chunk, int32_t seq_first_chunk,
-                                      const char *plan, int32_t *chunk, int32_t *starts, int32_t cap) {
-  if (n_frames <= 0 || pool_threads <= 0 || !chunk || !starts) return -1;
-  const Seq2Plan P = seq2_plan(n_frames, pool_threads, host_in != 0, seq_chunk, seq_first_chunk, plan);
-  if ((int32_t)P.start.size() > cap) return -1;
-  *chunk = P.C;
-  std::copy(P.start.begin(), P.start.end(), starts);
-  return (int32_t)P.start.size() - 1;
-}
 // Whatever way a look-ahead call is left, nothing of it may still be running: the last data member of Seq2Call, so that it
 // waits - for the pool's tasks, the poller's, the streams - BEFORE anything else of the call is destroyed.
 struct Seq2Drain {
@@ -1076,8 +1011,7 @@ struct Seq2Call {
     dbg_counts.push_back(now_us());
     seq_chunk_jobs(p, method, sides, q.f0, n, first_img, seq_slot_before(chunk_start, k, sides, kFrameBanks, C), c.hm_counts, nprev, Tr, Tr_valid, h_jobs,
                    nullptr, q.max_nq, h->seq_src.data());
-    if (q.max_nq[0] > VSM_DC_TIE_POINTS || q.max_nq[1] > VSM_DC_KD_MAX_POINTS || (p.refinement == 2 && q.max_nq[1] > VSM_PARA_MAX_LIST) ||
-        vsm_dc2_depth(std::max(q.max_nq[0], q.max_nq[1])) > VSM_DC2_MAX_DEPTH) {
+    if (!vsm_chain_fits(p, q.max_nq, VSM_DC_TIE_POINTS)) {
       return VSM_SEQ2_DECLINED;  // (a pass-1 list longer than the device's vertex sort takes: the first form does this run)
     }
     HIPCHK(vsm_upload(h->stream, d_jobs, h_jobs, sizeof(VsmJob) * n));

@@ -37,11 +37,8 @@ struct VsmStep {
 
 // every size limit of the device chain, asked before anything of the step is enqueued (max_nq: the longest first-pass and
 // second-pass list the jobs can give; the first-pass lists are sorted on the pool here: only the triangulation's own
-// limits apply to them)
-static bool vsm_step_fits(const vsm_params &p, const int max_nq[2]) {
-  return max_nq[0] <= VSM_DC_KD_MAX_POINTS && max_nq[1] <= VSM_DC_KD_MAX_POINTS && vsm_dc2_depth(std::max(max_nq[0], max_nq[1])) <= VSM_DC2_MAX_DEPTH &&
-         !(p.refinement == 2 && max_nq[1] > VSM_PARA_MAX_LIST);
-}
+// limits apply to them - vsm_chain_fits, vsm_jobs.h)
+static bool vsm_step_fits(const vsm_params &p, const int max_nq[2]) { return vsm_chain_fits(p, max_nq, VSM_DC_KD_MAX_POINTS); }
 
 // Jobs 0 .. n - 1 of c.h_jobs (filled by the caller, uploaded here; valid[i]: job i has lists at all; their lists fit:
 // vsm_step_fits) from the reservation of the banks, for `reserve` jobs, to the drained stream.  t_keys: when the final

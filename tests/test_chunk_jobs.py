@@ -1,4 +1,4 @@
-"""CPU suite: the per-chunk job table of the batched look-ahead forms (csrc/vsm_api.cpp: seq_chunk_jobs, through the debug
+"""CPU suite: the per-chunk job table of the batched look-ahead forms (csrc/vsm_jobs.h: seq_chunk_jobs, through the debug
 entry vsm_debug_chunk_jobs - pure arithmetic, no GPU).  Both forms' start_chunk build their jobs with it: the host-shared
 form with two images per frame and three frame banks, the GPU-resident one with one or two and five.
 

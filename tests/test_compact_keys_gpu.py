@@ -120,6 +120,19 @@ def test_quad_capacity_below_the_count(vm):
         assert (keys[cap:] == guard).all() and (cap == 0 or keys[cap - 1] != guard)
 
 
+def test_quad_sixty_four_pairs_with_empty_blocks_and_the_last_slot(vm):
+    """the hook's maximum of pairs in one launch: empty pairs, pairs of one query, pairs on either side of the 256-query
+    block, key arrays of capacity 0 (no room but the guard) among them - the first and the last pair's slots included"""
+    rng = np.random.default_rng(15)
+    sizes = [[0, 1, 255, 256, 257][k % 5] for k in range(63)] + [257]
+    caps = [0 if k % 3 == 0 else max(n, 1) for k, n in enumerate(sizes)]
+    assert len(sizes) == 64 and caps[0] == 0 and caps[63] == 0 and {(n, c == 0) for n, c in zip(sizes, caps)} >= {(n, z) for n in (0, 1, 255, 256, 257) for z in (False, True)}
+    raws = [records(vm, rng, n) for n in sizes]
+    flags = [flags_of("random", n, rng) for n in sizes]
+    want = check(vm, flags, raws, caps, 2)
+    assert [w[1] for w in want[:2]] == [0, int(flags[1][0] != 0)] and want[63][1] > 100
+
+
 @pytest.mark.parametrize("method", [0, 1])
 @pytest.mark.parametrize("pattern", ["all", "alternating", "random"])
 def test_flow_and_stereo_with_the_pixel_dedup(vm, method, pattern):

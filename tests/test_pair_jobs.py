@@ -1,4 +1,4 @@
-"""CPU suite: the job table of Matcher.match_pairs / vsm_pairs_run (csrc/vsm_api.cpp: pair_jobs, through the debug entry
+"""CPU suite: the job table of Matcher.match_pairs / vsm_pairs_run (csrc/vsm_jobs.h: pair_jobs, through the debug entry
 vsm_debug_pair_jobs - pure arithmetic, no GPU).
 
 The expected values do not come from the function: they restate the call's contract - for pair (a, b) a fresh matcher after

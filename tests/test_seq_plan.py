@@ -1,4 +1,4 @@
-"""CPU suite: the chunk plan of the look-ahead call's GPU-resident form (csrc/vsm_seq2.inc: seq2_plan, through the debug
+"""CPU suite: the chunk plan of the look-ahead call's GPU-resident form (csrc/vsm_jobs.h: seq2_plan, through the debug
 entry vsm_debug_seq_plan - pure arithmetic, no GPU).  The expected plans were worked out from the arithmetic of the commit
 before the planner was lifted out of sequence_run_v2 (110 + 90, 40 + 80 + 60 + 20, ten chunks of
 100 for 1000 frames): they pin what that commit did, not what the function returns today."""
