@@ -283,6 +283,77 @@ int32_t vsm_host_triangulate(int32_t n_frames, const double *poses, const uint8_
                              int32_t n_tracks, const int32_t *offsets, const int32_t *obs_frames, const float *uv, const uint8_t *flags,
                              const vsm_triangulate_params *params, int32_t *status, double *xyz, int32_t *type, int32_t *updates,
                              double *dist, double *angle);
+/* ---- refinement of camera poses against triangulated points ----
+ * The other half of the alternation: the triangulation refines points with the poses fixed, this refines every frame's pose
+ * with the points fixed - motion-only bundle adjustment, a Gauss-Newton resection per frame.  No counterpart in the
+ * reference.  csrc/vsm_resect.h is the one statement of the arithmetic (every product, every sum and its order); what
+ * follows is the contract.
+ * Input: n_frames poses, camera to world, 12 doubles each (rows 0..2 of [R | c]); pose_valid, a byte per frame (NULL: all
+ * valid); refine, a byte per frame (NULL: all) - a frame with 0 is left alone, which is how a caller pins the root; the
+ * intrinsics f, cu, cv; the tracks exactly as vsm_triangulate_run takes them (offsets[T + 1], obs_frames, uv); xyz[T][3],
+ * the tracks' points; use[T] bytes (NULL: all).
+ * The ROWS of frame g are the observations (t, i) with obs_frames == g and use[t] != 0, in ascending (t, i); a row is
+ * {track, u, v}.  The state is world to camera, [Rw | tw], the rigid inverse [R^T | -R^T c] of the input pose as the
+ * triangulation forms it.  One UPDATE evaluates every row at the state: Xc = Rw X + tw; the row is USED if zc > min_depth
+ * and ru^2 + rv^2 < max_residual^2 (max_residual = 0: below infinity), with ru = u - (f xc / zc + cu), rv = v - (f yc / zc
+ * + cv) - so rows behind the camera, NaN pixels, NaN points and overflowing residuals are never used.  Over the used rows
+ * it forms the 21 upper entries of J^T J, the 6 of J^T r (J the derivative of the prediction for Xc' = Xc + w x Xc + tau,
+ * parameters (w, tau)) and the sum of ru^2 + rv^2: 28 double sums and a count.  Every sum is taken in one fixed order:
+ * partial[l], l = 0..255, adds the terms of the frame's rows i with i mod 256 == l in ascending order starting from 0.0 (a
+ * skipped row adds nothing); then for s = 128, 64, .., 1: partial[l] += partial[l + s] for l < s; the sum is partial[0].
+ * The 6x6 system is solved by Gauss-Jordan with full pivoting (eps 1e-20, the stereo egomotion's Matrix::solve) and the
+ * state moves by the Cayley rotation of a = w / 2, Rd = ((1 - a.a) I + 2 a a^T + 2 [a]x) / (1 + a.a): Rw <- Rd Rw, tw <- Rd
+ * tw + tau.  Only + - * / on doubles: the device equals the host view bit for bit.  Converged when all six |delta| <= eps.
+ * Per frame, the first status that applies wins:
+ *   1  no valid input pose
+ *   2  not asked for (refine == 0)
+ *   3  fewer than min_observations rows
+ *   4  an update found fewer than min_observations used rows
+ *   5  an update's system had no pivot
+ *   6  not converged after max_updates updates: the estimate as it stands
+ *   0  refined
+ * Results per frame: status; pose[12], camera to world, the rigid inverse of the final state (status 0, 6) or the input
+ * pose's bytes (1..5); updates, the number of updates applied to the state; rows; used, the rows used at the last
+ * evaluation (0 for 1..3); ss_before, the sum of ru^2 + rv^2 over the rows used at the input pose (0 for 1..3); ss_after,
+ * the same at the final state from one more evaluation (status 0, 6; else 0); rms_before / rms_after, libm's sqrt(ss /
+ * rows used at that evaluation) applied by the host (0 where nothing was used). */
+typedef struct vsm_resect_params {
+  int32_t min_observations; /* 10 */
+  int32_t max_updates;      /* 20 */
+  double eps;               /* 1e-8 */
+  double max_residual;      /* 0 = no gate (pixels) */
+  double min_depth;         /* 1e-10 */
+} vsm_resect_params;
+void vsm_resect_default_params(vsm_resect_params *p);
+/* The general form, on the caller's arrays.  Runs on the handle's device and stream: the host groups the rows by frame (a
+ * stable counting sort, timed), one copy up (102 bytes per frame, 12 per row, 24 per track), the kernel (a 256-thread
+ * workgroup per frame, the update loop inside), one copy back (128 bytes per frame).  It has no CPU path.  VSM_EARG,
+ * nothing enqueued and the last result kept: what vsm_triangulate_run rejects (with params NULL), min_observations < 6,
+ * max_updates < 1, eps not positive or not finite, xyz NULL with n_tracks > 0.  Nothing else of the handle is touched. */
+int vsm_resect_run(vsm_handle *h, int32_t n_frames, const double *poses, const uint8_t *pose_valid, const uint8_t *refine, double f, double cu,
+                   double cv, int32_t n_tracks, const int32_t *offsets, const int32_t *obs_frames, const float *uv, const double *xyz,
+                   const uint8_t *use, const vsm_resect_params *params);
+/* The same on the handle's last track and point results: use = the point's status is 0, xyz the points, the pixels read
+ * from the match lists as vsm_tracks_triangulate reads them (lists, counts: as there).  VSM_ENOTREADY: no track result or
+ * no point result, or their track counts differ; lists == NULL as there.  VSM_EARG: as there, and params as above.  Both
+ * results stay as they are. */
+int vsm_points_resect(vsm_handle *h, const vsm_p_match *const *lists, const int32_t *counts, const double *poses, const uint8_t *pose_valid,
+                      const uint8_t *refine, double f, double cu, double cv, const vsm_resect_params *params);
+/* the handle's last resection result: the number of frames; the arrays (any may be NULL; returns the number of frames):
+ * status[F], poses[F][12], updates[F], rows[F], used[F], ss_before[F], ss_after[F], rms_before[F], rms_after[F] */
+int32_t vsm_resect_count(vsm_handle *h);
+int32_t vsm_resect_get(vsm_handle *h, int32_t *status, double *poses, int32_t *updates, int32_t *rows, int32_t *used, double *ss_before,
+                       double *ss_after, double *rms_before, double *rms_after);
+/* frames per status value 0..6 */
+void vsm_resect_get_stats(vsm_handle *h, int64_t *out7);
+/* wall-clock split of the last call, microseconds: {gather + grouping + packing, upload, kernel, download + host part} */
+void vsm_resect_get_timings(vsm_handle *h, double *out4);
+/* The same definition on one host thread: no GPU, no handle (the CPU suite's subject and the device path's second opinion -
+ * not a fallback).  Returns n_frames, or VSM_EARG with the output arrays untouched.  Outputs may be NULL. */
+int32_t vsm_host_resect(int32_t n_frames, const double *poses, const uint8_t *pose_valid, const uint8_t *refine, double f, double cu, double cv,
+                        int32_t n_tracks, const int32_t *offsets, const int32_t *obs_frames, const float *uv, const double *xyz,
+                        const uint8_t *use, const vsm_resect_params *params, int32_t *status, double *out_poses, int32_t *updates,
+                        int32_t *rows, int32_t *used, double *ss_before, double *ss_after, double *rms_before, double *rms_after);
 /* Measurement / test switches of a handle.  They are read from the environment once, by vsm_create (VSM_SEQ_V2,
  * VSM_SEQ_CHUNK, VSM_SEQ_DC_STREAMS, VSM_SEQ_SERIAL, VSM_SEQ_GPU_SORTS, VSM_SEQ_EARLY_EXPORT, VSM_FUSED_KEYS); this call changes one
  * afterwards: name = the variable's name without the VSM_ prefix, in lower case ("seq_serial", "seq_chunk", ...).

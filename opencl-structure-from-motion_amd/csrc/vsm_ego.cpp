@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "vsm_host.h"
+#include "vsm_linalg.h"
 
 namespace {
 
@@ -82,40 +83,9 @@ struct Pose {
   }
 };
 
-// Matrix::solve (viso/matrix.cpp:424-513) for 6 unknowns and one right-hand side
-bool solve6(double (&a)[6][6], double (&b)[6]) {
-  int taken[6] = {0, 0, 0, 0, 0, 0};
-  for (int round = 0; round < 6; round++) {
-    double big = 0.0;
-    int row = 0, col = 0;
-    for (int j = 0; j < 6; j++)
-      if (taken[j] != 1)
-        for (int k = 0; k < 6; k++)
-          if (taken[k] == 0 && fabs(a[j][k]) >= big) {
-            big = fabs(a[j][k]);
-            row = j;
-            col = k;
-          }
-    ++taken[col];
-    if (row != col) {
-      for (int l = 0; l < 6; l++) std::swap(a[row][l], a[col][l]);
-      std::swap(b[row], b[col]);
-    }
-    if (fabs(a[col][col]) < 1e-20) return false;
-    const double scale = 1.0 / a[col][col];
-    a[col][col] = 1.0;
-    for (int l = 0; l < 6; l++) a[col][l] *= scale;
-    b[col] *= scale;
-    for (int other = 0; other < 6; other++) {
-      if (other == col) continue;
-      const double m = a[other][col];
-      a[other][col] = 0.0;
-      for (int l = 0; l < 6; l++) a[other][l] -= a[col][l] * m;
-      b[other] -= b[col] * m;
-    }
-  }
-  return true;
-}
+// Matrix::solve (viso/matrix.cpp:424-513) for 6 unknowns and one right-hand side: vsm_linalg.h has it, for the pose
+// refinement's kernel as well
+bool solve6(double (&a)[6][6], double (&b)[6]) { return vsm_la::solve6(&a[0][0], &b[0]); }
 
 enum Step { UPDATED, FAILED, CONVERGED };
 

@@ -113,6 +113,8 @@ enum VsmKernelId {
   VSM_K_TRK_FILL, VSM_K_TRK_ORDER_WAVE, VSM_K_TRK_ORDER_BLOCK,
   // track triangulation (vsm_points.hip)
   VSM_K_PTS_TRIANGULATE,
+  // pose refinement against the points (vsm_resect.hip)
+  VSM_K_RS_RESECT,
   VSM_K_COUNT
 };
 struct VsmProf {

@@ -377,4 +377,50 @@ VSM_HD inline void rank2_3x3(const double *F, double *out) {
   mul(UD, Vt, out, 3, 3, 3);
 }
 
+// Matrix::solve (viso/matrix.cpp:424-513) for 6 unknowns and one right-hand side: Gauss-Jordan with full pivoting, eps =
+// 1e-20, on the row-major 6x6 `a` and `b`, both overwritten; on success b holds the solution.  false: no pivot.  The
+// pivot counters are six 4-bit fields of one word (a counter passes 1 only where no candidate compares, i.e. with NaNs,
+// and six rounds cannot take it past 6), so that a kernel keeps them in a register.  The stereo egomotion
+// (vsm_ego.cpp) and the pose refinement (vsm_resect.h; its kernel runs this on a system in LDS) both call it.
+template <class A, class B>
+VSM_HD inline bool solve6(A a, B b) {
+  uint32_t taken = 0;
+  for (int round = 0; round < 6; round++) {
+    double big = 0.0;
+    int row = 0, col = 0;
+    for (int j = 0; j < 6; j++)
+      if (((taken >> (4 * j)) & 15u) != 1u)
+        for (int k = 0; k < 6; k++)
+          if (((taken >> (4 * k)) & 15u) == 0u && fabs(a[j * 6 + k]) >= big) {
+            big = fabs(a[j * 6 + k]);
+            row = j;
+            col = k;
+          }
+    taken += 1u << (4 * col);
+    if (row != col) {
+      for (int l = 0; l < 6; l++) {
+        const double t = a[row * 6 + l];
+        a[row * 6 + l] = a[col * 6 + l];
+        a[col * 6 + l] = t;
+      }
+      const double t = b[row];
+      b[row] = b[col];
+      b[col] = t;
+    }
+    if (fabs(a[col * 6 + col]) < 1e-20) return false;
+    const double scale = 1.0 / a[col * 6 + col];
+    a[col * 6 + col] = 1.0;
+    for (int l = 0; l < 6; l++) a[col * 6 + l] = a[col * 6 + l] * scale;
+    b[col] = b[col] * scale;
+    for (int other = 0; other < 6; other++) {
+      if (other == col) continue;
+      const double m = a[other * 6 + col];
+      a[other * 6 + col] = 0.0;
+      for (int l = 0; l < 6; l++) a[other * 6 + l] = a[other * 6 + l] - a[col * 6 + l] * m;
+      b[other] = b[other] - b[col] * m;
+    }
+  }
+  return true;
+}
+
 }  // namespace vsm_la

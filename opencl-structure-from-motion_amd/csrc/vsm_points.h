@@ -33,15 +33,20 @@ struct PtsFrame {
 
 // pose: rows 0..2 of the camera-to-world [R | c], row-major.  inv is the RIGID inverse (the reference calls the general
 // Matrix::inv on its 4x4); every entry of -R^T c and of K * inv is a sum over k ascending that starts from the k = 0 product.
-VSM_HD inline void pts_frame(const double *pose, double f, double cu, double cv, PtsFrame *F) {
+// the rigid inverse alone, [R | c] -> [R^T | -R^T c] (the pose refinement, vsm_resect.h, goes both ways with it)
+template <class In, class Out>
+VSM_HD inline void pts_rigid_inverse(In pose, Out inv) {
   for (int i = 0; i < 3; i++) {
-    for (int j = 0; j < 3; j++) F->inv[i * 4 + j] = pose[j * 4 + i];
+    for (int j = 0; j < 3; j++) inv[i * 4 + j] = pose[j * 4 + i];
     double s = pose[0 * 4 + i] * pose[3];
     s += pose[1 * 4 + i] * pose[7];
     s += pose[2 * 4 + i] * pose[11];
-    F->inv[i * 4 + 3] = -s;
-    F->c[i] = pose[i * 4 + 3];
+    inv[i * 4 + 3] = -s;
   }
+}
+VSM_HD inline void pts_frame(const double *pose, double f, double cu, double cv, PtsFrame *F) {
+  pts_rigid_inverse(pose, F->inv);
+  for (int i = 0; i < 3; i++) F->c[i] = pose[i * 4 + 3];
   const double K[9] = {f, 0, cu, 0, f, cv, 0, 0, 1};
   for (int i = 0; i < 3; i++)
     for (int j = 0; j < 4; j++) {

@@ -124,6 +124,54 @@ static int points_run(vsm_handle *h, double t0, int32_t n_frames, const double *
 
 static const VsmPoints *points_result(vsm_handle *h) { return (h && h->points && h->points->have) ? h->points : nullptr; }
 
+// The match lists the observations of the track result T name (vsm_tracks_triangulate, vsm_points_resect): the caller's,
+// checked against the result's counts, or - lists == NULL - those of the last vsm_pairs_run, if the tracks came from them
+// (own / own_counts keep them).  VSM_OK, VSM_ENOTREADY or VSM_EARG.
+static int tracks_lists(vsm_handle *h, const VsmTracks &T, const vsm_p_match *const *&lists, const int32_t *counts, std::vector<const vsm_p_match *> &own,
+                        std::vector<int32_t> &own_counts) {
+  const int32_t n_pairs = (int32_t)T.pair_base.size() - 1;
+  if (!lists) {
+    if (!T.from_pairs || !pairs_last_lists(h, own, own_counts) || (int32_t)own.size() != n_pairs) return VSM_ENOTREADY;
+    for (int32_t k = 0; k < n_pairs; k++)
+      if (own_counts[k] != T.pair_base[k + 1] - T.pair_base[k]) return VSM_ENOTREADY;  // (a later vsm_pairs_run has replaced them)
+    lists = own.data();
+  } else {
+    if (n_pairs > 0 && !counts) return VSM_EARG;
+    for (int32_t k = 0; k < n_pairs; k++)
+      if (counts[k] != T.pair_base[k + 1] - T.pair_base[k] || (counts[k] > 0 && !lists[k])) return VSM_EARG;
+  }
+  return VSM_OK;
+}
+
+// the pixel of an observation {frame, feature, pair, 2 * match + end}, read from the match it names: end 0 = previous, 1 =
+// current
+static inline void tracks_pixel(const int32_t *row, const vsm_p_match *const *lists, int32_t side, float *u, float *v) {
+  const vsm_p_match &m = lists[row[2]][row[3] >> 1];
+  if (row[3] & 1) {
+    *u = side ? m.u2c : m.u1c;
+    *v = side ? m.v2c : m.v1c;
+  } else {
+    *u = side ? m.u2p : m.u1p;
+    *v = side ? m.v2p : m.v1p;
+  }
+}
+
+// every observation's frame and pixel
+static void tracks_gather(vsm_handle *h, const VsmTracks &T, const vsm_p_match *const *lists, int32_t *fr, float *px) {
+  const int32_t *obs = T.obs.data();
+  const int32_t side = T.side;
+  const int64_t n_obs = (int64_t)T.obs.size() / 4;
+  const int chunks = (int)std::min<int64_t>(64, (n_obs + 4095) / 4096);
+  if (chunks > 0)
+    h->pool->run(chunks, [&](int c) {
+      const int64_t a = n_obs * c / chunks, b = n_obs * (c + 1) / chunks;
+      for (int64_t i = a; i < b; i++) {
+        fr[i] = obs[4 * i];
+        tracks_pixel(obs + 4 * i, lists, side, px + 2 * i, px + 2 * i + 1);
+      }
+    });
+}
+
 extern "C" {
 
 int vsm_triangulate_run(vsm_handle *h, int32_t n_frames, const double *poses, const uint8_t *pose_valid, double f, double cu, double cv, int32_t n_tracks,
@@ -149,42 +197,15 @@ int vsm_tracks_triangulate(vsm_handle *h, const vsm_p_match *const *lists, const
   const VsmTracks *Tp = h->tracks;
   if (!Tp || !Tp->have) return VSM_ENOTREADY;
   const VsmTracks &T = *Tp;
-  const int32_t n_pairs = (int32_t)T.pair_base.size() - 1;
   std::vector<const vsm_p_match *> own;
   std::vector<int32_t> own_counts;
-  if (!lists) {  // the lists of the last vsm_pairs_run, if the tracks came from them
-    if (!T.from_pairs || !pairs_last_lists(h, own, own_counts) || (int32_t)own.size() != n_pairs) return VSM_ENOTREADY;
-    for (int32_t k = 0; k < n_pairs; k++)
-      if (own_counts[k] != T.pair_base[k + 1] - T.pair_base[k]) return VSM_ENOTREADY;  // (a later vsm_pairs_run has replaced them)
-    lists = own.data();
-  } else {
-    if (n_pairs > 0 && !counts) return VSM_EARG;
-    for (int32_t k = 0; k < n_pairs; k++)
-      if (counts[k] != T.pair_base[k + 1] - T.pair_base[k] || (counts[k] > 0 && !lists[k])) return VSM_EARG;
-  }
-  const int32_t n_tracks = (int32_t)T.flags.size(), n_frames = T.n_frames, side = T.side;
+  const int rc = tracks_lists(h, T, lists, counts, own, own_counts);
+  if (rc != VSM_OK) return rc;
+  const int32_t n_tracks = (int32_t)T.flags.size(), n_frames = T.n_frames;
   const int64_t n_obs = (int64_t)T.obs.size() / 4;
   if (!params || params->min_track_length < 1 || (n_frames > 0 && !poses)) return VSM_EARG;
   return points_run(h, t0, n_frames, poses, pose_valid, f, cu, cv, n_tracks, n_obs, T.offsets.data(), T.flags.data(), *params, [&](int32_t *fr, float *px) {
-    // every observation's pixel is read from the match it names: (pair, 2 * match + end), end 0 = previous, 1 = current
-    const int32_t *obs = T.obs.data();
-    const int chunks = (int)std::min<int64_t>(64, (n_obs + 4095) / 4096);
-    if (chunks > 0)
-      h->pool->run(chunks, [&](int c) {
-        const int64_t a = n_obs * c / chunks, b = n_obs * (c + 1) / chunks;
-        for (int64_t i = a; i < b; i++) {
-          const int32_t *row = obs + 4 * i;
-          const vsm_p_match &m = lists[row[2]][row[3] >> 1];
-          fr[i] = row[0];
-          if (row[3] & 1) {
-            px[2 * i] = side ? m.u2c : m.u1c;
-            px[2 * i + 1] = side ? m.v2c : m.v1c;
-          } else {
-            px[2 * i] = side ? m.u2p : m.u1p;
-            px[2 * i + 1] = side ? m.v2p : m.v1p;
-          }
-        }
-      });
+    tracks_gather(h, T, lists, fr, px);
     return true;
   });
 }

@@ -42,7 +42,9 @@ EXPORTS = ["vsm_default_params", "vsm_create", "vsm_destroy", "vsm_set_intrinsic
            "vsm_tracks_run", "vsm_pairs_tracks", "vsm_tracks_count", "vsm_tracks_num_obs", "vsm_tracks_get", "vsm_tracks_of_matches",
            "vsm_tracks_get_stats", "vsm_tracks_get_timings", "vsm_host_tracks",
            "vsm_triangulate_default_params", "vsm_triangulate_run", "vsm_tracks_triangulate", "vsm_points_count", "vsm_points_get",
-           "vsm_points_get_stats", "vsm_points_get_timings", "vsm_host_triangulate", "vsm_set_option", "vsm_version", "vsm_host_register", "vsm_host_unregister",
+           "vsm_points_get_stats", "vsm_points_get_timings", "vsm_host_triangulate",
+           "vsm_resect_default_params", "vsm_resect_run", "vsm_points_resect", "vsm_resect_count", "vsm_resect_get", "vsm_resect_get_stats",
+           "vsm_resect_get_timings", "vsm_host_resect", "vsm_set_option", "vsm_version", "vsm_host_register", "vsm_host_unregister",
            "vsm_multi_create", "vsm_multi_destroy", "vsm_multi_process", "vsm_multi_num_sequences", "vsm_multi_get_motion",
            "vsm_multi_motion_valid", "vsm_multi_num_matches", "vsm_multi_get_matches", "vsm_multi_num_inliers", "vsm_multi_get_inliers",
            "vsm_multi_get_timings",
@@ -83,6 +85,10 @@ class VsmVoMonoParams(C.Structure):
 class VsmTriangulateParams(C.Structure):
     _fields_ = [("point_type", C.c_int32), ("min_track_length", C.c_int32), ("max_dist", C.c_double), ("min_angle", C.c_double),
                 ("cam_pitch", C.c_double), ("cam_height", C.c_double)]
+
+
+class VsmResectParams(C.Structure):
+    _fields_ = [("min_observations", C.c_int32), ("max_updates", C.c_int32), ("eps", C.c_double), ("max_residual", C.c_double), ("min_depth", C.c_double)]
 
 
 def host_register(arr):
@@ -222,6 +228,18 @@ def lib():
         L.vsm_points_get_timings.restype = None
         L.vsm_host_triangulate.restype = i32
         L.vsm_host_triangulate.argtypes = [i32, vp, vp, f64, f64, f64, i32, vp, vp, vp, vp, C.POINTER(VsmTriangulateParams)] + [vp] * 6
+        L.vsm_resect_default_params.argtypes = [C.POINTER(VsmResectParams)]
+        L.vsm_resect_default_params.restype = None
+        L.vsm_resect_run.argtypes = [vp, i32, vp, vp, vp, f64, f64, f64, i32, vp, vp, vp, vp, vp, C.POINTER(VsmResectParams)]
+        L.vsm_points_resect.argtypes = [vp, vp, vp, vp, vp, vp, f64, f64, f64, C.POINTER(VsmResectParams)]
+        L.vsm_resect_count.argtypes = [vp]
+        L.vsm_resect_get.argtypes = [vp] + [vp] * 9
+        L.vsm_resect_get_stats.argtypes = [vp, vp]
+        L.vsm_resect_get_stats.restype = None
+        L.vsm_resect_get_timings.argtypes = [vp, vp]
+        L.vsm_resect_get_timings.restype = None
+        L.vsm_host_resect.restype = i32
+        L.vsm_host_resect.argtypes = [i32, vp, vp, vp, f64, f64, f64, i32, vp, vp, vp, vp, vp, C.POINTER(VsmResectParams)] + [vp] * 9
         L.vsm_local_cpus.argtypes = [vp, i32]
         L.vsm_forkjoin_cpus.argtypes = [vp, i32]
         L.vsm_debug_dc2_band_factor.restype = None
@@ -769,6 +787,71 @@ def host_triangulate(poses, f, cu, cv, offsets, obs_frames, uv, flags=None, pose
     return Points(*out)
 
 
+RESECT_STATUS = ("refined", "no_pose", "not_asked", "too_few_rows", "too_few_used", "no_pivot", "not_converged")
+RESECT_TIMINGS = ("group_us", "upload_us", "kernels_us", "download_host_us")
+
+
+class Resection:
+    """refined poses (include/visomatch.h, vsm_resect_run): per frame status [F] int32 (0 = refined, RESECT_STATUS names the
+    values), poses [F, 12] float64 camera to world, updates, rows, used [F] int32, ss_before, ss_after, rms_before, rms_after [F]
+    float64; stats: frames per status name, timings: dict (both empty for the host view)."""
+
+    def __init__(self, status, poses, updates, rows, used, ss_before, ss_after, rms_before, rms_after, stats=None, timings=None):
+        self.status, self.poses, self.updates, self.rows, self.used = status, poses, updates, rows, used
+        self.ss_before, self.ss_after, self.rms_before, self.rms_after = ss_before, ss_after, rms_before, rms_after
+        self.stats, self.timings = stats or {}, timings or {}
+
+    def __len__(self):
+        return len(self.status)
+
+    @property
+    def refined(self):
+        return self.status == 0
+
+
+def resect_params(**kw):
+    """vsm_resect_default_params with fields overridden by keyword"""
+    p = VsmResectParams()
+    lib().vsm_resect_default_params(C.byref(p))
+    for k, v in kw.items():
+        assert hasattr(p, k), k
+        setattr(p, k, v)
+    return p
+
+
+def _as_resect_params(params):
+    if isinstance(params, VsmResectParams):
+        return params
+    return resect_params(**(params or {}))
+
+
+def _resect_arrays(F):
+    return (np.zeros(F, np.int32), np.zeros((F, 12), np.float64), np.zeros(F, np.int32), np.zeros(F, np.int32), np.zeros(F, np.int32),
+            np.zeros(F, np.float64), np.zeros(F, np.float64), np.zeros(F, np.float64), np.zeros(F, np.float64))
+
+
+def _resect_inputs(poses, pose_valid, refine, offsets, obs_frames, uv, xyz, use):
+    po, pv, off, fr, px, us = _triangulate_inputs(poses, pose_valid, offsets, obs_frames, uv, use)
+    rf = None if refine is None else np.ascontiguousarray(np.asarray(refine).astype(np.uint8))
+    assert rf is None or rf.shape == (len(po),)
+    pt = None if xyz is None else np.ascontiguousarray(np.asarray(xyz, dtype=np.float64).reshape(-1, 3))
+    assert pt is None or len(pt) >= len(off) - 1
+    assert us is None or len(us) >= len(off) - 1
+    return po, pv, rf, off, fr, px, pt, us
+
+
+def host_resect(poses, f, cu, cv, offsets, obs_frames, uv, xyz, use=None, refine=None, pose_valid=None, params=None, n_tracks=None):
+    """vsm_host_resect: every frame's pose refined against the points on one host thread - no GPU.  n_tracks: override
+    len(offsets) - 1 (argument tests).  Returns a Resection object; raises VisoMatchError on VSM_EARG."""
+    po, pv, rf, off, fr, px, pt, us = _resect_inputs(poses, pose_valid, refine, offsets, obs_frames, uv, xyz, use)
+    T = max(len(off) - 1, 0) if n_tracks is None else int(n_tracks)
+    out = _resect_arrays(len(po))
+    got = _check(lib().vsm_host_resect(len(po), _ptr(po), _ptr(pv), _ptr(rf), float(f), float(cu), float(cv), T, _ptr(off), _ptr(fr), _ptr(px), _ptr(pt),
+                                       _ptr(us), C.byref(_as_resect_params(params)), *[_ptr(a) for a in out]), "vsm_host_resect")
+    assert got == len(po)
+    return Resection(*out)
+
+
 def remove_outliers(matches, method, w, h, gpu=False, gpu_ties=False, copies=1, threads=1, **params):
     """Matcher::removeOutliers + computePriorStatistics on a match list: host code of the per-frame path (gpu=False; threads > 1:
     split over fork-join threads the way vsm_match runs a frame's final list) or the GPU-resident chain of the look-ahead path;
@@ -1209,6 +1292,48 @@ class Matcher:
             ls, ptrs, cnt = _list_inputs(lists, counts)
         rc = lib().vsm_tracks_triangulate(self.h, ptrs, _ptr(cnt), _ptr(po), _ptr(pv), float(f), float(cu), float(cv), C.byref(_as_params(params)))
         return self._points_result(rc, "vsm_tracks_triangulate")
+
+    # --- poses refined against the points ---------------------------------------------------------
+    def _resect_result(self, rc, what):
+        L = lib()
+        _check(rc, what)
+        out = _resect_arrays(L.vsm_resect_count(self.h))
+        L.vsm_resect_get(self.h, *[_ptr(a) for a in out])
+        return Resection(*out, *_stage_dicts(self.h, L.vsm_resect_get_stats, RESECT_STATUS, L.vsm_resect_get_timings, RESECT_TIMINGS))
+
+    def resect(self, poses, f, cu, cv, offsets, obs_frames, uv, xyz, use=None, refine=None, pose_valid=None, params=None, n_tracks=None):
+        """vsm_resect_run: every frame's pose refined against the points it sees, on the device.  poses [F, 12] (or [F, 3, 4] /
+        [F, 4, 4]) camera to world; the tracks as for triangulate; xyz [T, 3]; use [T] and refine [F]: masks (None: all);
+        params: a dict of vsm_resect_params fields or the struct.  Returns a Resection object."""
+        po, pv, rf, off, fr, px, pt, us = _resect_inputs(poses, pose_valid, refine, offsets, obs_frames, uv, xyz, use)
+        T = max(len(off) - 1, 0) if n_tracks is None else int(n_tracks)
+        rc = lib().vsm_resect_run(self.h, len(po), _ptr(po), _ptr(pv), _ptr(rf), float(f), float(cu), float(cv), T, _ptr(off), _ptr(fr), _ptr(px), _ptr(pt),
+                                  _ptr(us), C.byref(_as_resect_params(params)))
+        return self._resect_result(rc, "vsm_resect_run")
+
+    def resect_points(self, poses, f, cu, cv, lists=None, refine=None, pose_valid=None, params=None, counts=None):
+        """vsm_points_resect: the same on the handle's last track and point results (the kept points; lists as for
+        track_points)."""
+        po, pv = _pose_inputs(poses, pose_valid, self._track_frames)
+        rf = None if refine is None else np.ascontiguousarray(np.asarray(refine).astype(np.uint8))
+        assert rf is None or rf.shape == (len(po),)
+        ptrs = cnt = None
+        if lists is not None:
+            ls, ptrs, cnt = _list_inputs(lists, counts)
+        rc = lib().vsm_points_resect(self.h, ptrs, _ptr(cnt), _ptr(po), _ptr(pv), _ptr(rf), float(f), float(cu), float(cv),
+                                     C.byref(_as_resect_params(params)))
+        return self._resect_result(rc, "vsm_points_resect")
+
+    def alternate(self, poses, f, cu, cv, rounds, refine=None, point_params=None, resect_params=None, pose_valid=None, lists=None):
+        """block-coordinate bundle adjustment from the two batched calls: `rounds` times track_points, then resect_points on its
+        poses.  Returns (the last poses, the last Points, [(sum of ss_before, sum of ss_after) per round])."""
+        points, history = None, []
+        for _ in range(int(rounds)):
+            points = self.track_points(poses, f, cu, cv, lists=lists, pose_valid=pose_valid, params=point_params)
+            res = self.resect_points(poses, f, cu, cv, lists=lists, refine=refine, pose_valid=pose_valid, params=resect_params)
+            poses = res.poses
+            history.append((float(res.ss_before.sum()), float(res.ss_after.sum())))
+        return poses, points, history
 
     # --- monocular motions of a pair set ---------------------------------------------------------
     def _motions_result(self, rc, what):
