@@ -354,6 +354,83 @@ int32_t vsm_host_resect(int32_t n_frames, const double *poses, const uint8_t *po
                         int32_t n_tracks, const int32_t *offsets, const int32_t *obs_frames, const float *uv, const double *xyz,
                         const uint8_t *use, const vsm_resect_params *params, int32_t *status, double *out_poses, int32_t *updates,
                         int32_t *rows, int32_t *used, double *ss_before, double *ss_after, double *rms_before, double *rms_after);
+/* ---- vetting of observations by reprojection error, and the pruned track set ----
+ * The step between rounds of adjustment: the residual of every observation at the given poses and points, a verdict per
+ * observation, per track and per frame, and the track set with the outliers taken out.  No counterpart in the reference.
+ * csrc/vsm_vet.h is the one statement of the arithmetic; what follows is the contract.
+ * Input: as vsm_resect_run takes it, without refine - n_frames poses (camera to world, 12 doubles each), pose_valid (NULL:
+ * all valid), f, cu, cv, the tracks (offsets[T + 1], obs_frames, uv), xyz[T][3], use[T] bytes (NULL: all).
+ * A frame's state is [Rw | tw], the rigid inverse of its pose as the resection forms it; observation i of track t in frame g
+ * is a row of the resection: Xc = Rw X + tw, ru = u - (f xc / zc + cu), rv = v - (f yc / zc + cv).  Its CODE, the first that
+ * applies:
+ *   1  the track is not in use (use[t] == 0)
+ *   2  frame g has no valid pose
+ *   3  behind the camera: not zc > min_depth (a NaN point lands here: its depth is NaN)
+ *   4  gated: not ru^2 + rv^2 < max_residual^2 (max_residual = 0: below infinity) - NaN and infinite pixels, and
+ *      infinite residuals of whatever origin, land here by the comparison alone
+ *   0  inlier: exactly the rows the resection uses at these poses with the same max_residual and min_depth
+ * and r2, the float of the double ru^2 + rv^2 for codes 0 and 4, 0 for 1..3 (a NaN's sign and payload are not defined).
+ * Per track: n_in, the number of inliers; frame_lo / frame_hi, the smallest / largest frame among them (-1, -1 without
+ * any); worst, the largest double ru^2 + rv^2 among them (0 without any); ss, their sum in one fixed order: partial[l], l =
+ * 0..15, adds the inliers whose position in the track i - offsets[t] is l mod 16, ascending, from +0.0 (a non-inlier is
+ * passed over); then partial[l] += partial[l + s] for l < s, s = 8, 4, 2, 1; ss = partial[0].  The track's STATUS, the first
+ * that applies:
+ *   1  not in use
+ *   2  n_in < min_observations
+ *   3  all inliers in one frame (frame_lo == frame_hi): observations are match ends, a feature appears once per pair it
+ *      takes part in, so two inliers need not be two views
+ *   0  kept
+ * Per frame three int32 counts of its observations: {inliers, behind (code 3), gated (code 4)}.
+ * The pruned track set, over the same T tracks (so xyz and every per-track array stay aligned): kept_offsets[T + 1] - a
+ * kept track has length n_in, every other track length 0 -, and kept_index[n_kept], the original indices of the kept
+ * tracks' inliers, ascending. */
+typedef struct vsm_vet_params {
+  double max_residual;      /* 2.0 pixels; 0 = no gate, as in the resection */
+  double min_depth;         /* 1e-10 */
+  int32_t min_observations; /* 2: the inliers a track needs */
+} vsm_vet_params;
+void vsm_vet_default_params(vsm_vet_params *p);
+/* The general form, on the caller's arrays.  Runs on the handle's device and stream: one copy up (97 bytes per frame, 12 per
+ * observation, 29 per track), the kernels (a 16-lane group per track for the verdicts, the tracks' multi-level scan over
+ * the kept lengths, the groups once more for kept_index), one copy back at the results' upper bounds - the call waits once,
+ * at its end.  It has no CPU path.  VSM_EARG, nothing enqueued and the last result kept: what vsm_resect_run rejects for
+ * these arrays, params NULL, min_observations < 1, max_residual negative or NaN, min_depth NaN.  VSM_EHIP after a HIP error
+ * (nothing further is launched; there is then no result).  Nothing else of the handle is touched: not the streaming ring,
+ * the pairs lists, the track, point, resect or motions results. */
+int vsm_vet_run(vsm_handle *h, int32_t n_frames, const double *poses, const uint8_t *pose_valid, double f, double cu, double cv, int32_t n_tracks,
+                const int32_t *offsets, const int32_t *obs_frames, const float *uv, const double *xyz, const uint8_t *use,
+                const vsm_vet_params *params);
+/* The same on the handle's last track and point results: use = the point's status is 0, xyz the points, the pixels read from
+ * the match lists exactly as vsm_points_resect reads them (lists, counts: as there).  VSM_ENOTREADY and VSM_EARG as there,
+ * with params as above.  Both results stay as they are. */
+int vsm_points_vet(vsm_handle *h, const vsm_p_match *const *lists, const int32_t *counts, const double *poses, const uint8_t *pose_valid,
+                   double f, double cu, double cv, const vsm_vet_params *params);
+/* the handle's last vetting result (zeros / nothing written without one); any output may be NULL.
+ * count: T, n_obs, n_kept.  get_obs: code[n_obs] (bytes), r2[n_obs]; returns n_obs.  get_tracks: status[T], n_in[T],
+ * frame_lo[T], frame_hi[T], ss[T], worst[T]; returns T.  get_frames: counts[F][3]; returns F.  get_kept: kept_offsets[T + 1],
+ * kept_index[n_kept]; returns n_kept. */
+void vsm_vet_count(vsm_handle *h, int32_t *n_tracks, int32_t *n_obs, int32_t *n_kept);
+int32_t vsm_vet_get_obs(vsm_handle *h, uint8_t *code, float *r2);
+int32_t vsm_vet_get_tracks(vsm_handle *h, int32_t *status, int32_t *n_in, int32_t *frame_lo, int32_t *frame_hi, double *ss, double *worst);
+int32_t vsm_vet_get_frames(vsm_handle *h, int32_t *counts3);
+int32_t vsm_vet_get_kept(vsm_handle *h, int32_t *kept_offsets, int32_t *kept_index);
+/* observations per code 0..4, then tracks per status 0..3 */
+void vsm_vet_get_stats(vsm_handle *h, int64_t *out9);
+/* wall-clock split of the last call, microseconds: {gather / packing, upload, kernels, download + host part} */
+void vsm_vet_get_timings(vsm_handle *h, double *out4);
+/* The same definition on one host thread: no GPU, no handle (the CPU suite's subject and the device path's second opinion -
+ * not a fallback).  frame_counts[F][3], kept_offsets[T + 1], kept_index[n_obs] (room for the upper bound), *n_kept.  Returns
+ * T, or VSM_EARG with the outputs untouched.  Outputs may be NULL. */
+int32_t vsm_host_vet(int32_t n_frames, const double *poses, const uint8_t *pose_valid, double f, double cu, double cv, int32_t n_tracks,
+                     const int32_t *offsets, const int32_t *obs_frames, const float *uv, const double *xyz, const uint8_t *use,
+                     const vsm_vet_params *params, uint8_t *code, float *r2, int32_t *status, int32_t *n_in, int32_t *frame_lo,
+                     int32_t *frame_hi, double *ss, double *worst, int32_t *frame_counts, int32_t *kept_offsets, int32_t *kept_index,
+                     int32_t *n_kept);
+/* The frame and the pixel of every observation of the handle's last track result, as vsm_tracks_triangulate gathers them
+ * (host only; lists, counts: as there): what a caller of the handle forms needs to build the pruned arrays.  obs_frames_out[n_obs],
+ * uv_out[n_obs][2], either may be NULL.  Returns n_obs, or VSM_ENOTREADY / VSM_EARG as vsm_tracks_triangulate does for the
+ * lists. */
+int32_t vsm_tracks_pixels(vsm_handle *h, const vsm_p_match *const *lists, const int32_t *counts, int32_t *obs_frames_out, float *uv_out);
 /* Measurement / test switches of a handle.  They are read from the environment once, by vsm_create (VSM_SEQ_V2,
  * VSM_SEQ_CHUNK, VSM_SEQ_DC_STREAMS, VSM_SEQ_SERIAL, VSM_SEQ_GPU_SORTS, VSM_SEQ_EARLY_EXPORT, VSM_FUSED_KEYS); this call changes one
  * afterwards: name = the variable's name without the VSM_ prefix, in lower case ("seq_serial", "seq_chunk", ...).

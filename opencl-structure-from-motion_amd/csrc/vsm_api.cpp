@@ -31,6 +31,7 @@
 #include "vsm_tracks.h"
 #include "vsm_points.h"
 #include "vsm_resect.h"
+#include "vsm_vet.h"
 #include "vsm_motions.h"
 
 #define HIPCHK(expr)                                                                              \
@@ -589,6 +590,7 @@ struct vsm_handle {
   struct VsmPairs *pairs = nullptr;  // arbitrary frame pairs in one call (vsm_pairs.inc): its own context, banks and result lists
   struct VsmPoints *points = nullptr;  // track triangulation (vsm_points.inc): staging, device block, last result
   struct VsmResect *resect = nullptr;  // pose refinement against the points (vsm_resect.inc): staging, device block, last result
+  struct VsmVet *vet = nullptr;        // vetting of observations (vsm_vet.inc): staging, device block, last result
   struct VsmMotions *motions = nullptr;  // monocular pair motions (vsm_motions_api.inc): staging, device block, last result
   struct VsmTracks *tracks = nullptr;  // feature tracks from pair match lists (vsm_tracks.inc): staging, device block, last result
 
@@ -623,6 +625,7 @@ static void pairs_destroy(vsm_handle *h);  // vsm_pairs.inc
 static void tracks_destroy(vsm_handle *h);  // vsm_tracks.inc
 static void points_destroy(vsm_handle *h);  // vsm_points.inc
 static void resect_destroy(vsm_handle *h);  // vsm_resect.inc
+static void vet_destroy(vsm_handle *h);     // vsm_vet.inc
 static void motions_destroy(vsm_handle *h);  // vsm_motions_api.inc
 
 extern "C" {
@@ -717,6 +720,7 @@ void vsm_destroy(vsm_handle *h) {
   tracks_destroy(h);
   points_destroy(h);
   resect_destroy(h);
+  vet_destroy(h);
   motions_destroy(h);
   ctx_destroy(h->ring);
   ctx_destroy(h->seq);
@@ -1207,6 +1211,7 @@ static int seq_ingest_host_frames(vsm_handle *h, VsmCtx &c, int first_img, const
 #include "vsm_tracks.inc"
 #include "vsm_points.inc"
 #include "vsm_resect.inc"
+#include "vsm_vet.inc"
 #include "vsm_motions_api.inc"
 extern "C" {
 
@@ -1421,7 +1426,7 @@ static const char *kKernelNames[VSM_K_COUNT] = {
     "k_dc_keys", "k_dc_vertex_sort", "k_dc_prepare_kd_order", "k_dc_block", "k_dc_merge", "k_dc_support", "k_dc_compact", "k_dc_prior",
     "k_feat_dense", "k_feat_sparse", "k_feat_scan", "k_feat_order", "k_parabolic_apply",
     "k_trk_init", "k_trk_hook", "k_trk_flatten", "k_trk_keep", "k_trk_scan_reduce", "k_trk_scan_top", "k_trk_scan_apply", "k_trk_match_tracks", "k_trk_fill",
-    "k_trk_order_wave", "k_trk_order_block", "k_pts_triangulate", "k_rs_resect"};
+    "k_trk_order_wave", "k_trk_order_block", "k_pts_triangulate", "k_rs_resect", "k_vet_obs", "k_vet_emit"};
 
 void vsm_set_profiling(vsm_handle *h, int on) {
   h->prof.on = on != 0;

@@ -115,6 +115,8 @@ enum VsmKernelId {
   VSM_K_PTS_TRIANGULATE,
   // pose refinement against the points (vsm_resect.hip)
   VSM_K_RS_RESECT,
+  // vetting of observations (vsm_vet.hip)
+  VSM_K_VET_OBS, VSM_K_VET_EMIT,
   VSM_K_COUNT
 };
 struct VsmProf {

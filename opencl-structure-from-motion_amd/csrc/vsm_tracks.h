@@ -5,6 +5,7 @@
 // kernels, the host view and a stand-alone host program share: the union-find steps, written once for both sides, the
 // packing of a match list, and the launch interface of the device path.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include "visomatch.h"
@@ -88,6 +89,16 @@ TRK_HD inline int32_t trk_owner(const int32_t *base, int32_t n, int32_t e) {
   return lo;
 }
 
+// the int2 items the levels above level 0 of a scan over n items need
+inline size_t trk_scan_part_items(int64_t n) {
+  size_t items = 0;
+  while (n > TRK_SCAN_BLOCK) {
+    n = (n + TRK_SCAN_BLOCK - 1) / TRK_SCAN_BLOCK;
+    items += (size_t)n;
+  }
+  return items;
+}
+
 // ---- host side (vsm_tracks_host.cpp; no HIP) ----
 // the argument checks that need no list: returns the number of edges, or -1
 int64_t trk_check_args(int32_t n_frames, const int32_t *pairs, int32_t n_pairs, const vsm_p_match *const *lists, const int32_t *counts, int32_t side,
@@ -120,6 +131,9 @@ struct TrkDevice {
 };
 // init, hook, flatten + sizes, kept roots, the scan: everything up to the totals (2 words, device memory)
 void vsm_tracks_launch_link(hipStream_t s, VsmProf &pf, const TrkDevice &d);
+// The scan alone, for a further stage (vsm_vet.hip): the exclusive prefix of n_items int2 items in place, their sum into
+// totals (2 words); scan_part holds the partial sums of every level above (trk_scan_part_items int2 items).
+void vsm_tracks_launch_scan(hipStream_t s, VsmProf &pf, int32_t *scan, int32_t n_items, int32_t *scan_part, int32_t *totals);
 // track of every match, observations, their order and the flags, for the totals the host has read back
 void vsm_tracks_launch_emit(hipStream_t s, VsmProf &pf, const TrkDevice &d, int32_t n_tracks, int32_t n_obs);
 #endif

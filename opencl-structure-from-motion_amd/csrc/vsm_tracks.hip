@@ -218,6 +218,26 @@ inline int trk_grid(int64_t items) { return (int)std::max<int64_t>(1, std::min<i
     pf.end(s);                                                             \
   } while (0)
 
+void vsm_tracks_launch_scan(hipStream_t s, VsmProf &pf, int32_t *scan, int32_t n_items, int32_t *scan_part, int32_t *totals) {
+  // the levels of the scan: level 0 is the items, level l + 1 the workgroup sums of level l
+  int2 *lev[8];
+  int32_t n[8];
+  int top = 0;
+  lev[0] = (int2 *)scan;
+  n[0] = n_items;
+  int2 *next = (int2 *)scan_part;
+  while (n[top] > kB) {
+    n[top + 1] = (int32_t)(((int64_t)n[top] + kB - 1) / kB);
+    lev[top + 1] = next;
+    next += n[top + 1];
+    TRK_LAUNCH(VSM_K_TRK_SCAN_REDUCE, k_trk_scan_reduce, std::min(n[top + 1], 2048), (const int2 *)lev[top], n[top], lev[top + 1], n[top + 1]);
+    top++;
+  }
+  TRK_LAUNCH(VSM_K_TRK_SCAN_TOP, k_trk_scan_top, 1, lev[top], n[top], (int2 *)totals);
+  for (int l = top - 1; l >= 0; l--)
+    TRK_LAUNCH(VSM_K_TRK_SCAN_APPLY, k_trk_scan_apply, std::min(n[l + 1], 2048), lev[l], n[l], (const int2 *)lev[l + 1], n[l + 1]);
+}
+
 void vsm_tracks_launch_link(hipStream_t s, VsmProf &pf, const TrkDevice &d) {
   const bool lds = d.n_pairs <= kLdsBase;
   const int gn = trk_grid(d.n_nodes), ge = trk_grid(d.n_edges);
@@ -228,23 +248,7 @@ void vsm_tracks_launch_link(hipStream_t s, VsmProf &pf, const TrkDevice &d) {
     TRK_LAUNCH(VSM_K_TRK_HOOK, k_trk_hook<false>, ge, d);
   TRK_LAUNCH(VSM_K_TRK_FLATTEN, k_trk_flatten, gn, d);
   TRK_LAUNCH(VSM_K_TRK_KEEP, k_trk_keep, gn, d);
-  // the levels of the scan: level 0 is the nodes, level l + 1 the workgroup sums of level l
-  int2 *lev[8];
-  int32_t n[8];
-  int top = 0;
-  lev[0] = (int2 *)d.scan;
-  n[0] = d.n_nodes;
-  int2 *next = (int2 *)d.scan_part;
-  while (n[top] > kB) {
-    n[top + 1] = (int32_t)(((int64_t)n[top] + kB - 1) / kB);
-    lev[top + 1] = next;
-    next += n[top + 1];
-    TRK_LAUNCH(VSM_K_TRK_SCAN_REDUCE, k_trk_scan_reduce, std::min(n[top + 1], 2048), (const int2 *)lev[top], n[top], lev[top + 1], n[top + 1]);
-    top++;
-  }
-  TRK_LAUNCH(VSM_K_TRK_SCAN_TOP, k_trk_scan_top, 1, lev[top], n[top], (int2 *)d.totals);
-  for (int l = top - 1; l >= 0; l--)
-    TRK_LAUNCH(VSM_K_TRK_SCAN_APPLY, k_trk_scan_apply, std::min(n[l + 1], 2048), lev[l], n[l], (const int2 *)lev[l + 1], n[l + 1]);
+  vsm_tracks_launch_scan(s, pf, d.scan, d.n_nodes, d.scan_part, d.totals);
 }
 
 void vsm_tracks_launch_emit(hipStream_t s, VsmProf &pf, const TrkDevice &d, int32_t n_tracks, int32_t n_obs) {

@@ -79,11 +79,7 @@ static int tracks_run(vsm_handle *h, int32_t n_frames, const int32_t *pairs, int
     return VSM_OK;
   }
   // ---- device memory: the uploaded block, the working set per node, the results (at their upper bounds) ----
-  size_t scan_part_items = 0;
-  for (int64_t n = n_nodes; n > TRK_SCAN_BLOCK;) {
-    n = (n + TRK_SCAN_BLOCK - 1) / TRK_SCAN_BLOCK;
-    scan_part_items += (size_t)n;
-  }
+  const size_t scan_part_items = trk_scan_part_items(n_nodes);
   VsmLayout dl = in;
   const size_t N = (size_t)n_nodes;
   const size_t o_parent = dl.take(N * 4), o_first = dl.take(N * 4), o_size = dl.take(N * 4), o_cursor = dl.take(N * 4), o_scan = dl.take(N * 8),

@@ -44,7 +44,9 @@ EXPORTS = ["vsm_default_params", "vsm_create", "vsm_destroy", "vsm_set_intrinsic
            "vsm_triangulate_default_params", "vsm_triangulate_run", "vsm_tracks_triangulate", "vsm_points_count", "vsm_points_get",
            "vsm_points_get_stats", "vsm_points_get_timings", "vsm_host_triangulate",
            "vsm_resect_default_params", "vsm_resect_run", "vsm_points_resect", "vsm_resect_count", "vsm_resect_get", "vsm_resect_get_stats",
-           "vsm_resect_get_timings", "vsm_host_resect", "vsm_set_option", "vsm_version", "vsm_host_register", "vsm_host_unregister",
+           "vsm_resect_get_timings", "vsm_host_resect",
+           "vsm_vet_default_params", "vsm_vet_run", "vsm_points_vet", "vsm_vet_count", "vsm_vet_get_obs", "vsm_vet_get_tracks", "vsm_vet_get_frames",
+           "vsm_vet_get_kept", "vsm_vet_get_stats", "vsm_vet_get_timings", "vsm_host_vet", "vsm_tracks_pixels", "vsm_set_option", "vsm_version", "vsm_host_register", "vsm_host_unregister",
            "vsm_multi_create", "vsm_multi_destroy", "vsm_multi_process", "vsm_multi_num_sequences", "vsm_multi_get_motion",
            "vsm_multi_motion_valid", "vsm_multi_num_matches", "vsm_multi_get_matches", "vsm_multi_num_inliers", "vsm_multi_get_inliers",
            "vsm_multi_get_timings",
@@ -89,6 +91,10 @@ class VsmTriangulateParams(C.Structure):
 
 class VsmResectParams(C.Structure):
     _fields_ = [("min_observations", C.c_int32), ("max_updates", C.c_int32), ("eps", C.c_double), ("max_residual", C.c_double), ("min_depth", C.c_double)]
+
+
+class VsmVetParams(C.Structure):
+    _fields_ = [("max_residual", C.c_double), ("min_depth", C.c_double), ("min_observations", C.c_int32)]
 
 
 def host_register(arr):
@@ -240,6 +246,26 @@ def lib():
         L.vsm_resect_get_timings.restype = None
         L.vsm_host_resect.restype = i32
         L.vsm_host_resect.argtypes = [i32, vp, vp, vp, f64, f64, f64, i32, vp, vp, vp, vp, vp, C.POINTER(VsmResectParams)] + [vp] * 9
+        L.vsm_vet_default_params.argtypes = [C.POINTER(VsmVetParams)]
+        L.vsm_vet_default_params.restype = None
+        L.vsm_vet_run.argtypes = [vp, i32, vp, vp, f64, f64, f64, i32, vp, vp, vp, vp, vp, C.POINTER(VsmVetParams)]
+        L.vsm_points_vet.argtypes = [vp, vp, vp, vp, vp, f64, f64, f64, C.POINTER(VsmVetParams)]
+        L.vsm_vet_count.argtypes = [vp, vp, vp, vp]
+        L.vsm_vet_count.restype = None
+        L.vsm_vet_get_obs.argtypes = [vp] + [vp] * 2
+        L.vsm_vet_get_tracks.argtypes = [vp] + [vp] * 6
+        L.vsm_vet_get_frames.argtypes = [vp, vp]
+        L.vsm_vet_get_kept.argtypes = [vp, vp, vp]
+        for fn in (L.vsm_vet_get_obs, L.vsm_vet_get_tracks, L.vsm_vet_get_frames, L.vsm_vet_get_kept):
+            fn.restype = i32
+        L.vsm_vet_get_stats.argtypes = [vp, vp]
+        L.vsm_vet_get_stats.restype = None
+        L.vsm_vet_get_timings.argtypes = [vp, vp]
+        L.vsm_vet_get_timings.restype = None
+        L.vsm_host_vet.restype = i32
+        L.vsm_host_vet.argtypes = [i32, vp, vp, f64, f64, f64, i32, vp, vp, vp, vp, vp, C.POINTER(VsmVetParams)] + [vp] * 12
+        L.vsm_tracks_pixels.restype = i32
+        L.vsm_tracks_pixels.argtypes = [vp, vp, vp, vp, vp]
         L.vsm_local_cpus.argtypes = [vp, i32]
         L.vsm_forkjoin_cpus.argtypes = [vp, i32]
         L.vsm_debug_dc2_band_factor.restype = None
@@ -852,6 +878,88 @@ def host_resect(poses, f, cu, cv, offsets, obs_frames, uv, xyz, use=None, refine
     return Resection(*out)
 
 
+VET_CODES = ("inlier", "unused", "no_pose", "behind", "gated")
+VET_STATUS = ("kept", "unused", "too_few_inliers", "one_frame")
+VET_STATS = tuple("obs_" + c for c in VET_CODES) + tuple("tracks_" + s for s in VET_STATUS)
+VET_TIMINGS = ("gather_us", "upload_us", "kernels_us", "download_host_us")
+
+
+class Vetting:
+    """vetted observations (include/visomatch.h, vsm_vet_run): per observation code [n_obs] uint8 (0 = inlier, VET_CODES names the
+    values) and r2 [n_obs] float32; per track status [T] int32 (0 = kept, VET_STATUS names the values), n_in, frame_lo, frame_hi
+    [T] int32, ss, worst [T] float64; per frame frame_counts [F, 3] int32 (inliers, behind, gated); the pruned set kept_offsets
+    [T + 1], kept_index [n_kept] int32; stats: observations per code and tracks per status by name, timings: dict (empty for the
+    host view)."""
+
+    def __init__(self, code, r2, status, n_in, frame_lo, frame_hi, ss, worst, frame_counts, kept_offsets, kept_index, stats=None, timings=None):
+        self.code, self.r2 = code, r2
+        self.status, self.n_in, self.frame_lo, self.frame_hi, self.ss, self.worst = status, n_in, frame_lo, frame_hi, ss, worst
+        self.frame_counts, self.kept_offsets, self.kept_index = frame_counts, kept_offsets, kept_index
+        if stats is None:
+            stats = dict(zip(VET_STATS, np.bincount(code, minlength=5).tolist() + np.bincount(status, minlength=4).tolist()))
+        self.stats, self.timings = stats, timings or {}
+
+    def __len__(self):
+        return len(self.status)
+
+    @property
+    def kept(self):
+        return self.status == 0
+
+    @property
+    def inlier(self):
+        return self.code == 0
+
+    def prune(self, obs_frames, uv):
+        """the track set without the outliers, over the same T tracks: (kept_offsets, obs_frames[kept_index], uv[kept_index])"""
+        fr = np.asarray(obs_frames, dtype=np.int32)
+        px = np.asarray(uv, dtype=np.float32).reshape(-1, 2)
+        assert len(fr) == len(self.code) and len(px) == len(self.code)
+        return self.kept_offsets.copy(), np.ascontiguousarray(fr[self.kept_index]), np.ascontiguousarray(px[self.kept_index])
+
+
+def vet_params(**kw):
+    """vsm_vet_default_params with fields overridden by keyword"""
+    p = VsmVetParams()
+    lib().vsm_vet_default_params(C.byref(p))
+    for k, v in kw.items():
+        assert hasattr(p, k), k
+        setattr(p, k, v)
+    return p
+
+
+def _as_vet_params(params):
+    if isinstance(params, VsmVetParams):
+        return params
+    return vet_params(**(params or {}))
+
+
+def _vet_arrays(T, n_obs, F, n_kept):
+    return (np.zeros(n_obs, np.uint8), np.zeros(n_obs, np.float32), np.zeros(T, np.int32), np.zeros(T, np.int32), np.zeros(T, np.int32), np.zeros(T, np.int32),
+            np.zeros(T, np.float64), np.zeros(T, np.float64), np.zeros((F, 3), np.int32), np.zeros(T + 1, np.int32), np.zeros(n_kept, np.int32))
+
+
+def _vet_inputs(poses, pose_valid, offsets, obs_frames, uv, xyz, use):
+    po, pv, _, off, fr, px, pt, us = _resect_inputs(poses, pose_valid, None, offsets, obs_frames, uv, xyz, use)
+    return po, pv, off, fr, px, pt, us
+
+
+def host_vet(poses, f, cu, cv, offsets, obs_frames, uv, xyz, use=None, pose_valid=None, params=None, n_tracks=None):
+    """vsm_host_vet: every observation vetted on one host thread - no GPU.  n_tracks: override len(offsets) - 1 (argument
+    tests).  Returns a Vetting object; raises VisoMatchError on VSM_EARG."""
+    po, pv, off, fr, px, pt, us = _vet_inputs(poses, pose_valid, offsets, obs_frames, uv, xyz, use)
+    T = max(len(off) - 1, 0) if n_tracks is None else int(n_tracks)
+    out = _vet_arrays(max(T, 0), len(fr), len(po), len(fr))
+    n_kept = C.c_int32(0)
+    got = _check(lib().vsm_host_vet(len(po), _ptr(po), _ptr(pv), float(f), float(cu), float(cv), T, _ptr(off), _ptr(fr), _ptr(px), _ptr(pt), _ptr(us),
+                                    None if params is _NO_PARAMS else C.byref(_as_vet_params(params)), *[_ptr(a) for a in out], C.byref(n_kept)), "vsm_host_vet")
+    assert got == T
+    return Vetting(*out[:-1], out[-1][:n_kept.value].copy())
+
+
+_NO_PARAMS = object()  # params=_NO_PARAMS: a NULL params pointer (argument tests)
+
+
 def remove_outliers(matches, method, w, h, gpu=False, gpu_ties=False, copies=1, threads=1, **params):
     """Matcher::removeOutliers + computePriorStatistics on a match list: host code of the per-frame path (gpu=False; threads > 1:
     split over fork-join threads the way vsm_match runs a frame's final list) or the GPU-resident chain of the look-ahead path;
@@ -1323,6 +1431,50 @@ class Matcher:
         rc = lib().vsm_points_resect(self.h, ptrs, _ptr(cnt), _ptr(po), _ptr(pv), _ptr(rf), float(f), float(cu), float(cv),
                                      C.byref(_as_resect_params(params)))
         return self._resect_result(rc, "vsm_points_resect")
+
+    # --- observations vetted by reprojection error -----------------------------------------------
+    def _vet_result(self, rc, what):
+        L = lib()
+        _check(rc, what)
+        T, n_obs, n_kept = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        L.vsm_vet_count(self.h, C.byref(T), C.byref(n_obs), C.byref(n_kept))
+        out = _vet_arrays(T.value, n_obs.value, L.vsm_vet_get_frames(self.h, None), n_kept.value)
+        L.vsm_vet_get_obs(self.h, _ptr(out[0]), _ptr(out[1]))
+        L.vsm_vet_get_tracks(self.h, *[_ptr(a) for a in out[2:8]])
+        L.vsm_vet_get_frames(self.h, _ptr(out[8]))
+        L.vsm_vet_get_kept(self.h, _ptr(out[9]), _ptr(out[10]))
+        return Vetting(*out, *_stage_dicts(self.h, L.vsm_vet_get_stats, VET_STATS, L.vsm_vet_get_timings, VET_TIMINGS))
+
+    def vet(self, poses, f, cu, cv, offsets, obs_frames, uv, xyz, use=None, pose_valid=None, params=None, n_tracks=None):
+        """vsm_vet_run: every observation's reprojection residual at the poses and points, the verdicts per observation, track
+        and frame, and the pruned track set, on the device.  Arguments as for resect, without refine; params: a dict of
+        vsm_vet_params fields or the struct.  Returns a Vetting object."""
+        po, pv, off, fr, px, pt, us = _vet_inputs(poses, pose_valid, offsets, obs_frames, uv, xyz, use)
+        T = max(len(off) - 1, 0) if n_tracks is None else int(n_tracks)
+        rc = lib().vsm_vet_run(self.h, len(po), _ptr(po), _ptr(pv), float(f), float(cu), float(cv), T, _ptr(off), _ptr(fr), _ptr(px), _ptr(pt), _ptr(us),
+                               None if params is _NO_PARAMS else C.byref(_as_vet_params(params)))
+        return self._vet_result(rc, "vsm_vet_run")
+
+    def vet_points(self, poses, f, cu, cv, lists=None, pose_valid=None, params=None, counts=None):
+        """vsm_points_vet: the same on the handle's last track and point results (the kept points; lists as for track_points)"""
+        po, pv = _pose_inputs(poses, pose_valid, self._track_frames)
+        ptrs = cnt = None
+        if lists is not None:
+            ls, ptrs, cnt = _list_inputs(lists, counts)
+        rc = lib().vsm_points_vet(self.h, ptrs, _ptr(cnt), _ptr(po), _ptr(pv), float(f), float(cu), float(cv),
+                                  None if params is _NO_PARAMS else C.byref(_as_vet_params(params)))
+        return self._vet_result(rc, "vsm_points_vet")
+
+    def track_pixels(self, lists=None, counts=None):
+        """vsm_tracks_pixels: (obs_frames [n_obs] int32, uv [n_obs, 2] float32) of the handle's last track result, the pixels
+        read from the match lists as track_points reads them (lists: as there)"""
+        ptrs = cnt = None
+        if lists is not None:
+            ls, ptrs, cnt = _list_inputs(lists, counts)
+        n = _check(lib().vsm_tracks_pixels(self.h, ptrs, _ptr(cnt), None, None), "vsm_tracks_pixels")
+        fr, px = np.zeros(n, np.int32), np.zeros((n, 2), np.float32)
+        _check(lib().vsm_tracks_pixels(self.h, ptrs, _ptr(cnt), _ptr(fr), _ptr(px)), "vsm_tracks_pixels")
+        return fr, px
 
     def alternate(self, poses, f, cu, cv, rounds, refine=None, point_params=None, resect_params=None, pose_valid=None, lists=None):
         """block-coordinate bundle adjustment from the two batched calls: `rounds` times track_points, then resect_points on its
