@@ -28,6 +28,7 @@
 #include "vsm_internal.h"
 #include "vsm_jobs.h"
 #include "vsm_stage.h"
+#include "vsm_layouts.h"
 #include "vsm_tracks.h"
 #include "vsm_points.h"
 #include "vsm_resect.h"

@@ -1,0 +1,87 @@
+// The blocks of the staged calls: per stage one struct that declares every array once - its element
+// type - and places it once - its count and the spare bytes behind it -, as a pure function of the call's counts.  No HIP
+// call is made here, so tools/stage_host_check.cpp checks the offsets on the CPU.  vsm_stage.h has the arrays' views.
+#pragma once
+
+#include "vsm_stage.h"
+#include "vsm_tracks.h"
+#include "vsm_points.h"
+#include "vsm_resect.h"
+#include "vsm_vet.h"
+
+// vsm_points.inc: F frames, T tracks, N observations
+struct PtsBlocks : VsmBlocks {
+  VsmIn<PtsFrame> frames;
+  VsmIn<uint8_t> valid, flags;
+  VsmIn<int32_t> offsets, obs_frames;
+  VsmIn<float> uv;
+  VsmOut<int32_t> status, type, updates;
+  VsmOut<double> xyz, dist, ray;
+  PtsBlocks(size_t F, size_t T, size_t N) {
+    frames.place(in, F, 8); valid.place(in, F, 1); offsets.place(in, T + 1, 0); obs_frames.place(in, N, 4); uv.place(in, 2 * N, 8); flags.place(in, T, 1);
+    status.place(out, T, 4); type.place(out, T, 4); updates.place(out, T, 4); xyz.place(out, 3 * T, 8); dist.place(out, T, 8); ray.place(out, T, 8);
+    out_behind_in(out.at);
+  }
+};
+
+// vsm_resect.inc: F frames, T tracks, R rows (the observations of the tracks in use)
+struct RsBlocks : VsmBlocks {
+  VsmIn<double> poses, xyz;
+  VsmIn<uint8_t> valid, refine;
+  VsmIn<int32_t> row_off;
+  VsmIn<RsRow> rows;
+  VsmOut<int32_t> status, updates, used_before, used;
+  VsmOut<double> out_poses, ss_before, ss_after;
+  RsBlocks(size_t F, size_t T, size_t R) {
+    poses.place(in, 12 * F, 8); valid.place(in, F, 1); refine.place(in, F, 1); row_off.place(in, F + 1, 0); rows.place(in, R, 4); xyz.place(in, 3 * T, 8);
+    status.place(out, F, 4); updates.place(out, F, 4); used_before.place(out, F, 4); used.place(out, F, 4); out_poses.place(out, 12 * F, 8);
+    ss_before.place(out, F, 8); ss_after.place(out, F, 8);
+    out_behind_in(out.at);
+  }
+};
+
+// vsm_vet.inc: F frames, T tracks, N observations; the scan's working set lies behind the results and is not copied back
+struct VetBlocks : VsmBlocks {
+  VsmIn<double> states, xyz;
+  VsmIn<uint8_t> valid, use;
+  VsmIn<int32_t> offsets, obs_frames;
+  VsmIn<float> uv;
+  VsmOut<uint8_t> code;
+  VsmOut<float> r2;
+  VsmOut<int32_t> status, n_in, frame_lo, frame_hi, frame_counts, kept_offsets, kept_index, totals, scan, scan_part;
+  VsmOut<double> ss, worst;
+  VetBlocks(size_t F, size_t T, size_t N) {
+    states.place(in, 12 * F, 8); valid.place(in, F, 1); offsets.place(in, T + 1, 0); obs_frames.place(in, N, 4); uv.place(in, 2 * N, 8); xyz.place(in, 3 * T, 8);
+    use.place(in, T, 1);
+    code.place(out, N, 1); r2.place(out, N, 4); status.place(out, T, 4); n_in.place(out, T, 4); frame_lo.place(out, T, 4); frame_hi.place(out, T, 4);
+    ss.place(out, T, 8); worst.place(out, T, 8); frame_counts.place(out, 3 * F, 4); kept_offsets.place(out, T + 1, 0); kept_index.place(out, N, 4);
+    totals.place(out, 2, 0);
+    VsmLayout work = out;
+    scan.place(work, 2 * T, 8); scan_part.place(work, 2 * trk_scan_part_items((int64_t)T), 8);
+    out_behind_in(work.at);
+  }
+};
+
+// vsm_tracks.inc, in the three steps of the call: the uploaded block from the arguments' counts; the working set per node
+// behind it and the results' upper bounds (every node an observation, every node a track) once the packing has counted the
+// nodes; the results themselves once the totals are back.
+struct TrkBlocks : VsmBlocks {
+  VsmIn<int32_t> pair_base, pairs, feat_base, edges;
+  VsmDev<int32_t> parent, first, size, cursor, scan, scan_part, totals, mid_list;
+  VsmOut<int32_t> counters, offsets, obs, track_of_match;
+  VsmOut<uint8_t> flags;
+  size_t n_edges;
+  TrkBlocks(size_t P, size_t F, size_t E) : n_edges(E) { pair_base.place(in, P + 1, 0); pairs.place(in, 2 * P, 4); feat_base.place(in, F + 1, 0); edges.place(in, 2 * E, 4); }
+  void nodes(size_t N) {
+    VsmLayout dl = in;
+    parent.place(dl, N, 0); first.place(dl, N, 0); size.place(dl, N, 0); cursor.place(dl, N, 0); scan.place(dl, 2 * N, 0);
+    scan_part.place(dl, 2 * trk_scan_part_items((int64_t)N), 8); totals.place(dl, 2, 0); mid_list.place(dl, N / (VSM_TRACKS_WAVE_MAX + 1) + 1, 0);
+    out_at = dl.at;
+    dev_bytes = out_at + al256(16) + al256((N + 1) * 4) + al256(N * 16) + al256(n_edges * 4) + al256(N);
+    results(0, 0);  // (the counters are in place for the first launch; the rest moves when the totals are back)
+  }
+  void results(size_t n_tracks, size_t n_obs) {
+    out = VsmLayout();
+    counters.place(out, 4, 0); offsets.place(out, n_tracks + 1, 0); obs.place(out, 4 * n_obs, 0); track_of_match.place(out, n_edges, 0); flags.place(out, n_tracks, 0);
+  }
+};

@@ -263,11 +263,7 @@ int vsm_motions_device(VsmMotionsDev &D, hipStream_t stream, VsmPool *pool, cons
   chunk = std::min(chunk, (int)n_pairs);
   std::vector<MotPair> pairs((size_t)chunk);
   std::vector<int32_t> running;  // chunk-local indices of the pairs still in the estimate
-  auto fail = [&](int rc) {
-    (void)hipStreamSynchronize(stream);
-    (void)hipGetLastError();
-    return rc;
-  };
+  const VsmDrain fail{stream};  // (vsm_stage.h)
   auto run_pairs = [&](const std::vector<int32_t> &which, const std::function<void(int)> &fn) {
     if (which.empty()) return;
     pool->run((int)which.size(), [&](int t) { fn(which[t]); });

@@ -5,143 +5,115 @@
 // matrices (27 doubles per frame), one pinned block with them, the offsets, a frame index and a pixel per observation (12
 // bytes per observation) and the flags; one copy up, one kernel, one copy back (52 bytes per track); then libm's acos on the
 // ray values, which decides status 9.  vsm_tracks_triangulate fills the same block from the handle's last track result,
-// reading every observation's pixel from the match it names.
-struct VsmPoints {
-  VsmStage st;  // pinned input and output, the device block, the events (vsm_stage.h)
-  bool have = false;
+// reading every observation's pixel from the match it names.  Blocks: PtsBlocks (vsm_layouts.h); round trip, result record,
+// keep and getters' copies: vsm_stage.h.  The handle forms' prologue (TracksInput) and the pixels' gathering live here.
+struct VsmPoints : VsmResult<10> {  // the staging and the last result's stats and timings (vsm_stage.h)
   std::vector<int32_t> status, type, updates;
   std::vector<double> xyz, dist, angle;
-  int64_t stats[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  double timings[4] = {0, 0, 0, 0};
 };
 
-static void points_destroy(vsm_handle *h) {
-  VsmPoints *P = h->points;
-  if (!P) return;
-  P->st.release();
-  delete P;
-  h->points = nullptr;
-}
+static void points_destroy(vsm_handle *h) { vsm_result_destroy(h->points); }
 
-// The arguments have been checked.  fill(obs_frames, uv) writes the n_obs frame indices and pixels into the pinned block and
-// returns false for an argument error it finds on the way (nothing is enqueued before it has returned true).
+// The arguments have been checked.  fill(obs_frames, uv) writes the n_obs frame indices and pixels into the pinned block.
+template <class Fill>
 static int points_run(vsm_handle *h, double t0, int32_t n_frames, const double *poses, const uint8_t *pose_valid, double f, double cu, double cv, int32_t n_tracks,
-                      int64_t n_obs, const int32_t *offsets, const uint8_t *flags, const vsm_triangulate_params &prm,
-                      const std::function<bool(int32_t *, float *)> &fill) {
+                      int64_t n_obs, const int32_t *offsets, const uint8_t *flags, const vsm_triangulate_params &prm, Fill fill) {
   HIPCHK(hipSetDevice(h->device));
   if (!h->points) h->points = new VsmPoints();
   VsmPoints &P = *h->points;
   VsmStage &S = P.st;
   const size_t T = (size_t)n_tracks;
-  VsmLayout in;
-  const size_t o_frames = in.take((size_t)n_frames * sizeof(PtsFrame) + 8), o_valid = in.take((size_t)n_frames + 1), o_offsets = in.take((T + 1) * 4),
-               o_fr = in.take((size_t)n_obs * 4 + 4), o_uv = in.take((size_t)n_obs * 8 + 8), o_flags = in.take(T + 1);
-  VsmLayout out;
-  const size_t r_status = out.take(T * 4 + 4), r_type = out.take(T * 4 + 4), r_updates = out.take(T * 4 + 4), r_xyz = out.take(T * 24 + 8), r_dist = out.take(T * 8 + 8),
-               r_ray = out.take(T * 8 + 8);
-  HIPCHK(S.grow_in(in.at, h->stream));
-  HIPCHK(S.grow_out(out.at, h->stream));
+  const PtsBlocks L((size_t)n_frames, T, (size_t)n_obs);
+  HIPCHK(S.grow_in(L.in.at, h->stream));
+  HIPCHK(S.grow_out(L.out.at, h->stream));
   // ---- pack ----
-  PtsFrame *p_frames = (PtsFrame *)(S.pin_in + o_frames);
-  uint8_t *p_valid = S.pin_in + o_valid;
   for (int32_t k = 0; k < n_frames; k++) {
-    pts_frame(poses + 12 * (size_t)k, f, cu, cv, p_frames + k);
-    p_valid[k] = (!pose_valid || pose_valid[k]) ? 1 : 0;
+    pts_frame(poses + 12 * (size_t)k, f, cu, cv, L.frames.host(S) + k);
+    L.valid.host(S)[k] = (!pose_valid || pose_valid[k]) ? 1 : 0;
   }
-  memcpy(S.pin_in + o_offsets, offsets, (T + 1) * 4);
+  memcpy(L.offsets.host(S), offsets, (T + 1) * 4);
   if (flags)
-    memcpy(S.pin_in + o_flags, flags, T);
+    memcpy(L.flags.host(S), flags, T);
   else
-    memset(S.pin_in + o_flags, 0, T);
-  if (!fill((int32_t *)(S.pin_in + o_fr), (float *)(S.pin_in + o_uv))) return VSM_EARG;
+    memset(L.flags.host(S), 0, T);
+  fill(L.obs_frames.host(S), L.uv.host(S));
   // ---- from here on the call replaces the last result ----
-  P.have = false;
-  memset(P.stats, 0, sizeof(P.stats));
-  memset(P.timings, 0, sizeof(P.timings));
-  HIPCHK(S.grow_dev(al256(in.at) + out.at, h->stream));
-  HIPCHK(S.events());
-  const double t1 = now_us();
-  P.timings[0] = t1 - t0;
-  auto fail = [&](int rc) {
-    (void)hipStreamSynchronize(h->stream);
-    (void)hipGetLastError();
-    return rc;
-  };
-  uint8_t *dout = S.dev + al256(in.at);
+  HIPCHK(P.replace(L, h->stream, t0));
   PtsDevice d;
   memset(&d, 0, sizeof(d));
-  d.frames = (const PtsFrame *)(S.dev + o_frames);
-  d.valid = S.dev + o_valid;
-  d.offsets = (const int32_t *)(S.dev + o_offsets);
-  d.obs_frames = (const int32_t *)(S.dev + o_fr);
-  d.uv = (const float *)(S.dev + o_uv);
-  d.flags = S.dev + o_flags;
-  d.status = (int32_t *)(dout + r_status);
-  d.type = (int32_t *)(dout + r_type);
-  d.updates = (int32_t *)(dout + r_updates);
-  d.xyz = (double *)(dout + r_xyz);
-  d.dist = (double *)(dout + r_dist);
-  d.ray = (double *)(dout + r_ray);
+  d.frames = L.frames.dev(S);
+  d.valid = L.valid.dev(S);
+  d.offsets = L.offsets.dev(S);
+  d.obs_frames = L.obs_frames.dev(S);
+  d.uv = L.uv.dev(S);
+  d.flags = L.flags.dev(S);
+  d.status = L.status.dev(S, L.out_at);
+  d.type = L.type.dev(S, L.out_at);
+  d.updates = L.updates.dev(S, L.out_at);
+  d.xyz = L.xyz.dev(S, L.out_at);
+  d.dist = L.dist.dev(S, L.out_at);
+  d.ray = L.ray.dev(S, L.out_at);
   pts_road(prm.cam_pitch, prm.cam_height, d.road);
   d.max_dist = prm.max_dist;
   d.n_tracks = n_tracks;
   d.point_type = prm.point_type;
   d.min_track_length = prm.min_track_length;
-  float ms_up = 0, ms_k = 0;
   if (n_tracks > 0) {
-    VSM_CHK(hipEventRecord(S.ev[0], h->stream));
-    VSM_CHK(hipMemcpyAsync(S.dev, S.pin_in, in.at, hipMemcpyHostToDevice, h->stream));
-    VSM_CHK(hipEventRecord(S.ev[1], h->stream));
-    vsm_points_launch(h->stream, h->prof, d);
-    VSM_CHK(hipGetLastError());
-    VSM_CHK(hipEventRecord(S.ev[2], h->stream));
-    VSM_CHK(hipMemcpyAsync(S.pin_out, dout, out.at, hipMemcpyDeviceToHost, h->stream));
-    VSM_CHK(hipStreamSynchronize(h->stream));
-    VSM_CHK(hipGetLastError());
-    if (h->prof.on) h->prof.resolve();
-    (void)hipEventElapsedTime(&ms_up, S.ev[0], S.ev[1]);
-    (void)hipEventElapsedTime(&ms_k, S.ev[1], S.ev[2]);
+    const int rc = S.round_trip(h->stream, h->prof, L, vsm_no_pre, [&] { vsm_points_launch(h->stream, h->prof, d); });
+    if (rc != VSM_OK) return rc;
   }
   // ---- into the handle's vectors; the angle and status 9 need libm ----
-  const int32_t *o_st = (const int32_t *)(S.pin_out + r_status), *o_ty = (const int32_t *)(S.pin_out + r_type), *o_up = (const int32_t *)(S.pin_out + r_updates);
-  const double *o_xyz = (const double *)(S.pin_out + r_xyz), *o_di = (const double *)(S.pin_out + r_dist), *o_ray = (const double *)(S.pin_out + r_ray);
-  P.status.assign(o_st, o_st + T);
-  P.type.assign(o_ty, o_ty + T);
-  P.updates.assign(o_up, o_up + T);
-  P.xyz.assign(o_xyz, o_xyz + 3 * T);
-  P.dist.assign(o_di, o_di + T);
+  VsmKeep K;
+  L.status.keep(K, S, P.status);
+  L.type.keep(K, S, P.type);
+  L.updates.keep(K, S, P.updates);
+  L.xyz.keep(K, S, P.xyz);
+  L.dist.keep(K, S, P.dist);
   P.angle.assign(T, 0.0);
-  pts_finish(n_tracks, prm.min_angle, P.status.data(), o_ray, P.angle.data());
+  pts_finish(n_tracks, prm.min_angle, P.status.data(), L.ray.host(S), P.angle.data());
   for (size_t t = 0; t < T; t++)
     if (P.status[t] >= 0 && P.status[t] < 10) P.stats[P.status[t]]++;
-  const double t2 = now_us();
-  P.timings[1] = ms_up * 1e3;
-  P.timings[2] = ms_k * 1e3;
-  P.timings[3] = std::max(0.0, (t2 - t1) - P.timings[1] - P.timings[2]);
-  P.have = true;
+  P.close();
   return VSM_OK;
 }
 
 static const VsmPoints *points_result(vsm_handle *h) { return (h && h->points && h->points->have) ? h->points : nullptr; }
 
-// The match lists the observations of the track result T name (vsm_tracks_triangulate, vsm_points_resect): the caller's,
-// checked against the result's counts, or - lists == NULL - those of the last vsm_pairs_run, if the tracks came from them
-// (own / own_counts keep them).  VSM_OK, VSM_ENOTREADY or VSM_EARG.
-static int tracks_lists(vsm_handle *h, const VsmTracks &T, const vsm_p_match *const *&lists, const int32_t *counts, std::vector<const vsm_p_match *> &own,
-                        std::vector<int32_t> &own_counts) {
-  const int32_t n_pairs = (int32_t)T.pair_base.size() - 1;
-  if (!lists) {
-    if (!T.from_pairs || !pairs_last_lists(h, own, own_counts) || (int32_t)own.size() != n_pairs) return VSM_ENOTREADY;
-    for (int32_t k = 0; k < n_pairs; k++)
-      if (own_counts[k] != T.pair_base[k + 1] - T.pair_base[k]) return VSM_ENOTREADY;  // (a later vsm_pairs_run has replaced them)
-    lists = own.data();
-  } else {
-    if (n_pairs > 0 && !counts) return VSM_EARG;
-    for (int32_t k = 0; k < n_pairs; k++)
-      if (counts[k] != T.pair_base[k + 1] - T.pair_base[k] || (counts[k] > 0 && !lists[k])) return VSM_EARG;
+// What a handle form works on (vsm_tracks_triangulate, vsm_points_resect, vsm_points_vet, vsm_tracks_pixels).  take() tests
+// in the order the callers see: the track result and - with_points - the point result of the same tracks, else
+// VSM_ENOTREADY; then the match lists the observations name: the caller's, checked against the result's counts (VSM_EARG),
+// or - lists == NULL - those of the last vsm_pairs_run, if the tracks came from them and they still stand (VSM_ENOTREADY).
+// The form's own parameters come after it.
+struct TracksInput {
+  const VsmTracks *T = nullptr;
+  const VsmPoints *P = nullptr;
+  const vsm_p_match *const *lists = nullptr;
+  int32_t n_tracks = 0, n_frames = 0;
+  int64_t n_obs = 0;
+  std::vector<const vsm_p_match *> own;  // the pairs run's lists
+  std::vector<int32_t> own_counts;
+  int take(vsm_handle *h, bool with_points, const vsm_p_match *const *caller_lists, const int32_t *counts) {
+    T = tracks_result(h);
+    P = with_points ? points_result(h) : nullptr;
+    if (!T || (with_points && (!P || P->status.size() != T->flags.size()))) return VSM_ENOTREADY;
+    const int32_t n_pairs = (int32_t)T->pair_base.size() - 1;
+    lists = caller_lists;
+    if (!lists) {
+      if (!T->from_pairs || !pairs_last_lists(h, own, own_counts) || (int32_t)own.size() != n_pairs) return VSM_ENOTREADY;
+      for (int32_t k = 0; k < n_pairs; k++)
+        if (own_counts[k] != T->pair_base[k + 1] - T->pair_base[k]) return VSM_ENOTREADY;  // (a later vsm_pairs_run has replaced them)
+      lists = own.data();
+    } else {
+      if (n_pairs > 0 && !counts) return VSM_EARG;
+      for (int32_t k = 0; k < n_pairs; k++)
+        if (counts[k] != T->pair_base[k + 1] - T->pair_base[k] || (counts[k] > 0 && !lists[k])) return VSM_EARG;
+    }
+    n_tracks = (int32_t)T->flags.size();
+    n_frames = T->n_frames;
+    n_obs = (int64_t)T->obs.size() / 4;
+    return VSM_OK;
   }
-  return VSM_OK;
-}
+};
 
 // the pixel of an observation {frame, feature, pair, 2 * match + end}, read from the match it names: end 0 = previous, 1 =
 // current
@@ -172,6 +144,19 @@ static void tracks_gather(vsm_handle *h, const VsmTracks &T, const vsm_p_match *
     });
 }
 
+// the fill of the general forms (vsm_triangulate_run, vsm_vet_run): the caller's arrays as they are
+struct ObsCopy {
+  int64_t n_obs;
+  const int32_t *obs_frames;
+  const float *uv;
+  void operator()(int32_t *fr, float *px) const {
+    if (n_obs > 0) {
+      memcpy(fr, obs_frames, (size_t)n_obs * 4);
+      memcpy(px, uv, (size_t)n_obs * 8);
+    }
+  }
+};
+
 extern "C" {
 
 int vsm_triangulate_run(vsm_handle *h, int32_t n_frames, const double *poses, const uint8_t *pose_valid, double f, double cu, double cv, int32_t n_tracks,
@@ -181,57 +166,34 @@ int vsm_triangulate_run(vsm_handle *h, int32_t n_frames, const double *poses, co
   const int64_t n_obs = pts_check_args(n_frames, poses, n_tracks, offsets, obs_frames, uv, params);
   if (n_obs < 0) return VSM_EARG;
   const int32_t zero = 0;
-  return points_run(h, t0, n_frames, poses, pose_valid, f, cu, cv, n_tracks, n_obs, n_tracks > 0 ? offsets : &zero, flags, *params, [&](int32_t *fr, float *px) {
-    if (n_obs > 0) {
-      memcpy(fr, obs_frames, (size_t)n_obs * 4);
-      memcpy(px, uv, (size_t)n_obs * 8);
-    }
-    return true;
-  });
+  return points_run(h, t0, n_frames, poses, pose_valid, f, cu, cv, n_tracks, n_obs, n_tracks > 0 ? offsets : &zero, flags, *params, ObsCopy{n_obs, obs_frames, uv});
 }
 
 int vsm_tracks_triangulate(vsm_handle *h, const vsm_p_match *const *lists, const int32_t *counts, const double *poses, const uint8_t *pose_valid, double f,
                            double cu, double cv, const vsm_triangulate_params *params) {
   if (!h) return VSM_EARG;
   const double t0 = now_us();
-  const VsmTracks *Tp = h->tracks;
-  if (!Tp || !Tp->have) return VSM_ENOTREADY;
-  const VsmTracks &T = *Tp;
-  std::vector<const vsm_p_match *> own;
-  std::vector<int32_t> own_counts;
-  const int rc = tracks_lists(h, T, lists, counts, own, own_counts);
+  TracksInput in;
+  const int rc = in.take(h, false, lists, counts);
   if (rc != VSM_OK) return rc;
-  const int32_t n_tracks = (int32_t)T.flags.size(), n_frames = T.n_frames;
-  const int64_t n_obs = (int64_t)T.obs.size() / 4;
-  if (!params || params->min_track_length < 1 || (n_frames > 0 && !poses)) return VSM_EARG;
-  return points_run(h, t0, n_frames, poses, pose_valid, f, cu, cv, n_tracks, n_obs, T.offsets.data(), T.flags.data(), *params, [&](int32_t *fr, float *px) {
-    tracks_gather(h, T, lists, fr, px);
-    return true;
-  });
+  if (!params || params->min_track_length < 1 || (in.n_frames > 0 && !poses)) return VSM_EARG;
+  return points_run(h, t0, in.n_frames, poses, pose_valid, f, cu, cv, in.n_tracks, in.n_obs, in.T->offsets.data(), in.T->flags.data(), *params,
+                    [&](int32_t *fr, float *px) { tracks_gather(h, *in.T, in.lists, fr, px); });
 }
 
-int32_t vsm_points_count(vsm_handle *h) { return (h && h->points && h->points->have) ? (int32_t)h->points->status.size() : 0; }
+int32_t vsm_points_count(vsm_handle *h) { return points_result(h) ? (int32_t)h->points->status.size() : 0; }
 int32_t vsm_points_get(vsm_handle *h, int32_t *status, double *xyz, int32_t *type, int32_t *updates, double *dist, double *angle) {
-  if (!h || !h->points || !h->points->have) return 0;
-  const VsmPoints &P = *h->points;
-  const size_t T = P.status.size();
-  if (T > 0) {
-    if (status) memcpy(status, P.status.data(), T * 4);
-    if (xyz) memcpy(xyz, P.xyz.data(), T * 24);
-    if (type) memcpy(type, P.type.data(), T * 4);
-    if (updates) memcpy(updates, P.updates.data(), T * 4);
-    if (dist) memcpy(dist, P.dist.data(), T * 8);
-    if (angle) memcpy(angle, P.angle.data(), T * 8);
-  }
-  return (int32_t)T;
-}
-void vsm_points_get_stats(vsm_handle *h, int64_t *out10) {
   const VsmPoints *P = points_result(h);
-  vsm_copy_or_zero(P ? &P->stats : nullptr, out10);
+  if (!P) return 0;
+  vsm_copy_wanted(P->status, status);
+  vsm_copy_wanted(P->xyz, xyz);
+  vsm_copy_wanted(P->type, type);
+  vsm_copy_wanted(P->updates, updates);
+  vsm_copy_wanted(P->dist, dist);
+  vsm_copy_wanted(P->angle, angle);
+  return (int32_t)P->status.size();
 }
-void vsm_points_get_timings(vsm_handle *h, double *out4) {
-  const VsmPoints *P = points_result(h);
-  vsm_copy_or_zero(P ? &P->timings : nullptr, out4);
-}
+void vsm_points_get_stats(vsm_handle *h, int64_t *out10) { vsm_result_get(points_result(h), &VsmPoints::stats, out10); }
+void vsm_points_get_timings(vsm_handle *h, double *out4) { vsm_result_get(points_result(h), &VsmPoints::timings, out4); }
 
 }  // extern "C"

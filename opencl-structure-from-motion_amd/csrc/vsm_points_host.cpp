@@ -10,7 +10,12 @@
 
 int64_t pts_check_args(int32_t n_frames, const double *poses, int32_t n_tracks, const int32_t *offsets, const int32_t *obs_frames, const float *uv,
                        const vsm_triangulate_params *params) {
-  if (!params || params->min_track_length < 1 || n_frames < 0 || n_tracks < 0) return -1;
+  if (!params || params->min_track_length < 1) return -1;
+  return pts_check_obs(n_frames, poses, n_tracks, offsets, obs_frames, uv);
+}
+
+int64_t pts_check_obs(int32_t n_frames, const double *poses, int32_t n_tracks, const int32_t *offsets, const int32_t *obs_frames, const float *uv) {
+  if (n_frames < 0 || n_tracks < 0) return -1;
   if (n_frames > 0 && !poses) return -1;
   if (n_tracks == 0) return 0;
   if (!offsets || offsets[0] != 0) return -1;

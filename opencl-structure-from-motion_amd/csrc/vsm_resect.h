@@ -177,6 +177,7 @@ inline void rs_frame(Eval evaluate, W ab, M S, const vsm_resect_params &prm, RsR
 // the argument checks of vsm_resect_run / vsm_host_resect: the number of observations, or -1
 int64_t rs_check_args(int32_t n_frames, const double *poses, int32_t n_tracks, const int32_t *offsets, const int32_t *obs_frames, const float *uv,
                       const double *xyz, const vsm_resect_params *params);
+bool rs_params_ok(const vsm_resect_params *params);  // its test of the parameters
 // The rows by frame, a stable counting sort in two passes over the tracks t0 .. t1 - 1, so that chunks of tracks can go to
 // threads: the counts per frame (added to cnt[n_frames]), then - with at[g] where the chunk's first row of frame g belongs:
 // the frame's start plus the counts of the chunks in front - the rows themselves.  frame_of(i) is observation i's frame,

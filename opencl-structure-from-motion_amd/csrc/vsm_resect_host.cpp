@@ -10,12 +10,11 @@
 
 int64_t rs_check_args(int32_t n_frames, const double *poses, int32_t n_tracks, const int32_t *offsets, const int32_t *obs_frames, const float *uv,
                       const double *xyz, const vsm_resect_params *params) {
-  if (!params || params->min_observations < 6 || params->max_updates < 1 || !(params->eps > 0) || !(params->eps < HUGE_VAL)) return -1;
-  if (n_tracks > 0 && !xyz) return -1;
-  vsm_triangulate_params tp;
-  vsm_triangulate_default_params(&tp);
-  return pts_check_args(n_frames, poses, n_tracks, offsets, obs_frames, uv, &tp);
+  if (!rs_params_ok(params) || (n_tracks > 0 && !xyz)) return -1;
+  return pts_check_obs(n_frames, poses, n_tracks, offsets, obs_frames, uv);
 }
+
+bool rs_params_ok(const vsm_resect_params *p) { return p && p->min_observations >= 6 && p->max_updates >= 1 && p->eps > 0 && p->eps < HUGE_VAL; }
 
 double rs_rms(double ss, int32_t used) { return used > 0 ? sqrt(ss / (double)used) : 0.0; }
 

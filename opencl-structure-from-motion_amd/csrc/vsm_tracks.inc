@@ -7,13 +7,11 @@
 // device (vsm_tracks.hip) from lists in host memory.  The host's part: the pool packs the lists' index pairs into one
 // pinned block (8 bytes per match) and finds each frame's node count on the way, one copy takes the block up, one brings
 // offsets, observations, flags and the track of every match back.  Segments longer than a workgroup orders are sorted here.
-struct VsmTracks {
-  VsmStage st;  // pinned input and output, the device block, the events (vsm_stage.h)
-  bool have = false;
+// The blocks are TrkBlocks (vsm_layouts.h), placed in the call's three steps; the call waits twice, so it keeps its own
+// sequence of copies and launches and takes the drain, the keep and the timings' close of vsm_stage.h.
+struct VsmTracks : VsmResult<8> {  // the staging and the last result's stats and timings (vsm_stage.h)
   std::vector<int32_t> offsets, obs, track_of_match, pair_base;
   std::vector<uint8_t> flags;
-  int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  double timings[4] = {0, 0, 0, 0};
   std::vector<int32_t> max_p, max_c;
   std::vector<uint8_t> bad;
   // what vsm_tracks_triangulate needs to find the observations' pixels (vsm_points.inc)
@@ -21,13 +19,7 @@ struct VsmTracks {
   bool from_pairs = false;  // the lists were those of vsm_pairs_run (vsm_pairs_tracks)
 };
 
-static void tracks_destroy(vsm_handle *h) {
-  VsmTracks *T = h->tracks;
-  if (!T) return;
-  T->st.release();
-  delete T;
-  h->tracks = nullptr;
-}
+static void tracks_destroy(vsm_handle *h) { vsm_result_destroy(h->tracks); }
 
 static int tracks_run(vsm_handle *h, int32_t n_frames, const int32_t *pairs, int32_t n_pairs, const vsm_p_match *const *lists, const int32_t *counts,
                       int32_t side, int32_t min_length) {
@@ -40,12 +32,9 @@ static int tracks_run(vsm_handle *h, int32_t n_frames, const int32_t *pairs, int
   VsmTracks &T = *h->tracks;
   VsmStage &S = T.st;
   // ---- pack: (ip, ic) of every match, behind the three tables, in one pinned block ----
-  VsmLayout in;
-  const size_t o_pair_base = in.take(((size_t)n_pairs + 1) * 4), o_pairs = in.take((size_t)n_pairs * 8 + 4), o_feat_base = in.take(((size_t)n_frames + 1) * 4),
-               o_edges = in.take((size_t)n_edges * 8 + 4);
-  HIPCHK(S.grow_in(in.at, h->stream));
-  int32_t *p_pair_base = (int32_t *)(S.pin_in + o_pair_base), *p_pairs = (int32_t *)(S.pin_in + o_pairs), *p_feat_base = (int32_t *)(S.pin_in + o_feat_base),
-          *p_edges = (int32_t *)(S.pin_in + o_edges);
+  TrkBlocks L((size_t)n_pairs, (size_t)n_frames, (size_t)n_edges);
+  HIPCHK(S.grow_in(L.in.at, h->stream));
+  int32_t *p_pair_base = L.pair_base.host(S), *p_pairs = L.pairs.host(S), *p_feat_base = L.feat_base.host(S), *p_edges = L.edges.host(S);
   T.max_p.assign((size_t)n_pairs, -1);
   T.max_c.assign((size_t)n_pairs, -1);
   T.bad.assign((size_t)n_pairs, 0);
@@ -72,51 +61,39 @@ static int tracks_run(vsm_handle *h, int32_t n_frames, const int32_t *pairs, int
   T.offsets.assign(1, 0);
   T.obs.clear();
   T.flags.clear();
-  const double t1 = now_us();
-  T.timings[0] = t1 - t0;
+  T.t1 = now_us();
+  T.timings[0] = T.t1 - t0;
   if (n_edges == 0) {  // no pair with a match: no tracks
     T.have = true;
     return VSM_OK;
   }
   // ---- device memory: the uploaded block, the working set per node, the results (at their upper bounds) ----
-  const size_t scan_part_items = trk_scan_part_items(n_nodes);
-  VsmLayout dl = in;
-  const size_t N = (size_t)n_nodes;
-  const size_t o_parent = dl.take(N * 4), o_first = dl.take(N * 4), o_size = dl.take(N * 4), o_cursor = dl.take(N * 4), o_scan = dl.take(N * 8),
-               o_part = dl.take(scan_part_items * 8 + 8), o_totals = dl.take(8), o_mid = dl.take((N / (VSM_TRACKS_WAVE_MAX + 1) + 1) * 4), o_out = dl.take(0);
-  // the results' upper bounds: every node an observation, every node a track
-  const size_t out_cap = al256(16) + al256((N + 1) * 4) + al256(N * 16) + al256((size_t)n_edges * 4) + al256(N);
-  HIPCHK(S.grow_dev(o_out + out_cap, h->stream));
-  HIPCHK(S.events());
+  L.nodes((size_t)n_nodes);
+  HIPCHK(S.fit_dev(L, h->stream));
   HIPCHK(S.grow_out(8, h->stream, 4096));  // (the totals; the first block is a page)
-  // a call that fails after something was enqueued: drain the device, report
-  auto fail = [&](int rc) {
-    (void)hipStreamSynchronize(h->stream);
-    (void)hipGetLastError();
-    return rc;
-  };
+  const VsmDrain fail{h->stream};          // a call that fails after something was enqueued: drain the device, report
   TrkDevice d;
   memset(&d, 0, sizeof(d));
-  d.pair_base = (const int32_t *)(S.dev + o_pair_base);
-  d.pairs = (const int32_t *)(S.dev + o_pairs);
-  d.feat_base = (const int32_t *)(S.dev + o_feat_base);
-  d.edges = (const int32_t *)(S.dev + o_edges);
-  d.parent = (int32_t *)(S.dev + o_parent);
-  d.first = (int32_t *)(S.dev + o_first);
-  d.size = (int32_t *)(S.dev + o_size);
-  d.cursor = (int32_t *)(S.dev + o_cursor);
-  d.scan = (int32_t *)(S.dev + o_scan);
-  d.scan_part = (int32_t *)(S.dev + o_part);
-  d.totals = (int32_t *)(S.dev + o_totals);
-  d.mid_list = (int32_t *)(S.dev + o_mid);
-  d.counters = (int32_t *)(S.dev + o_out);
+  d.pair_base = L.pair_base.dev(S);
+  d.pairs = L.pairs.dev(S);
+  d.feat_base = L.feat_base.dev(S);
+  d.edges = L.edges.dev(S);
+  d.parent = L.parent.dev(S);
+  d.first = L.first.dev(S);
+  d.size = L.size.dev(S);
+  d.cursor = L.cursor.dev(S);
+  d.scan = L.scan.dev(S);
+  d.scan_part = L.scan_part.dev(S);
+  d.totals = L.totals.dev(S);
+  d.mid_list = L.mid_list.dev(S);
+  d.counters = L.counters.dev(S, L.out_at);
   d.n_nodes = n_nodes;
   d.n_edges = n_edges;
   d.n_pairs = n_pairs;
   d.n_frames = n_frames;
   d.min_length = min_length;
   VSM_CHK(hipEventRecord(S.ev[0], h->stream));
-  VSM_CHK(hipMemcpyAsync(S.dev, S.pin_in, in.at, hipMemcpyHostToDevice, h->stream));
+  VSM_CHK(hipMemcpyAsync(S.dev, S.pin_in, L.in.at, hipMemcpyHostToDevice, h->stream));
   VSM_CHK(hipEventRecord(S.ev[1], h->stream));
   vsm_tracks_launch_link(h->stream, h->prof, d);
   VSM_CHK(hipGetLastError());
@@ -125,32 +102,25 @@ static int tracks_run(vsm_handle *h, int32_t n_frames, const int32_t *pairs, int
   VSM_CHK(hipStreamSynchronize(h->stream));
   const int32_t n_tracks = ((int32_t *)S.pin_out)[0], n_obs = ((int32_t *)S.pin_out)[1];
   if (n_tracks < 0 || n_tracks > n_nodes || n_obs < 0 || n_obs > n_nodes) return fail(VSM_EHIP);  // (cannot be: nothing is sized by it then)
-  VsmLayout ol;
-  ol.at = o_out;
-  const size_t r_counters = ol.take(16), r_offsets = ol.take(((size_t)n_tracks + 1) * 4), r_obs = ol.take((size_t)n_obs * 16),
-               r_tom = ol.take((size_t)n_edges * 4), r_flags = ol.take((size_t)n_tracks);
-  d.offsets = (int32_t *)(S.dev + r_offsets);
-  d.obs = (int32_t *)(S.dev + r_obs);
-  d.track_of_match = (int32_t *)(S.dev + r_tom);
-  d.flags = (uint8_t *)(S.dev + r_flags);
-  const size_t out_bytes = ol.at - o_out;
-  VSM_CHK(S.grow_out(out_bytes, h->stream));
+  L.results((size_t)n_tracks, (size_t)n_obs);
+  d.offsets = L.offsets.dev(S, L.out_at);
+  d.obs = L.obs.dev(S, L.out_at);
+  d.track_of_match = L.track_of_match.dev(S, L.out_at);
+  d.flags = L.flags.dev(S, L.out_at);
+  VSM_CHK(S.grow_out(L.out.at, h->stream));
   vsm_tracks_launch_emit(h->stream, h->prof, d, n_tracks, n_obs);
   VSM_CHK(hipGetLastError());
   VSM_CHK(hipEventRecord(S.ev[2], h->stream));
-  VSM_CHK(hipMemcpyAsync(S.pin_out, S.dev + o_out, out_bytes, hipMemcpyDeviceToHost, h->stream));
+  VSM_CHK(hipMemcpyAsync(S.pin_out, S.dev + L.out_at, L.out.at, hipMemcpyDeviceToHost, h->stream));
   VSM_CHK(hipStreamSynchronize(h->stream));
   VSM_CHK(hipGetLastError());
   if (h->prof.on) h->prof.resolve();
   // ---- into the handle's vectors; the segments no workgroup took are ordered here ----
-  const uint8_t *out = S.pin_out;
-  const int32_t *r_off = (const int32_t *)(out + (r_offsets - o_out));
-  T.offsets.assign(r_off, r_off + n_tracks + 1);
-  const int32_t *r_rows = (const int32_t *)(out + (r_obs - o_out));
-  T.obs.assign(r_rows, r_rows + 4 * (size_t)n_obs);
-  const int32_t *r_t = (const int32_t *)(out + (r_tom - o_out));
-  T.track_of_match.assign(r_t, r_t + n_edges);
-  T.flags.assign(out + (r_flags - o_out), out + (r_flags - o_out) + n_tracks);
+  VsmKeep K;
+  L.offsets.keep(K, S, T.offsets);
+  L.obs.keep(K, S, T.obs);
+  L.track_of_match.keep(K, S, T.track_of_match);
+  L.flags.keep(K, S, T.flags);
   int64_t by_host = 0, inconsistent = 0;
   for (int32_t t = 0; t < n_tracks; t++) {
     const int32_t len = T.offsets[t + 1] - T.offsets[t];
@@ -160,7 +130,7 @@ static int tracks_run(vsm_handle *h, int32_t n_frames, const int32_t *pairs, int
     }
     inconsistent += T.flags[t] & 1;
   }
-  const int64_t by_block = ((const int32_t *)(out + (r_counters - o_out)))[0];
+  const int64_t by_block = L.counters.host(S)[0];
   T.stats[0] = n_nodes;
   T.stats[1] = n_edges;
   T.stats[2] = n_tracks;
@@ -168,14 +138,8 @@ static int tracks_run(vsm_handle *h, int32_t n_frames, const int32_t *pairs, int
   T.stats[4] = n_tracks - by_block - by_host;
   T.stats[5] = by_block;
   T.stats[6] = by_host;
-  float ms_up = 0, ms_k = 0;
-  (void)hipEventElapsedTime(&ms_up, S.ev[0], S.ev[1]);
-  (void)hipEventElapsedTime(&ms_k, S.ev[1], S.ev[2]);
-  const double t2 = now_us();
-  T.timings[1] = ms_up * 1e3;
-  T.timings[2] = ms_k * 1e3;
-  T.timings[3] = std::max(0.0, (t2 - t1) - T.timings[1] - T.timings[2]);
-  T.have = true;
+  S.elapsed();
+  T.close();
   return VSM_OK;
 }
 
@@ -220,13 +184,7 @@ int32_t vsm_tracks_of_matches(vsm_handle *h, int32_t pair, int32_t *out, int32_t
   if (out && m > 0) memcpy(out, T.track_of_match.data() + T.pair_base[pair], (size_t)m * 4);
   return n;
 }
-void vsm_tracks_get_stats(vsm_handle *h, int64_t *out8) {
-  const VsmTracks *T = tracks_result(h);
-  vsm_copy_or_zero(T ? &T->stats : nullptr, out8);
-}
-void vsm_tracks_get_timings(vsm_handle *h, double *out4) {
-  const VsmTracks *T = tracks_result(h);
-  vsm_copy_or_zero(T ? &T->timings : nullptr, out4);
-}
+void vsm_tracks_get_stats(vsm_handle *h, int64_t *out8) { vsm_result_get(tracks_result(h), &VsmTracks::stats, out8); }
+void vsm_tracks_get_timings(vsm_handle *h, double *out4) { vsm_result_get(tracks_result(h), &VsmTracks::timings, out4); }
 
 }  // extern "C"

@@ -9,11 +9,8 @@
 
 int64_t vet_check_args(int32_t n_frames, const double *poses, int32_t n_tracks, const int32_t *offsets, const int32_t *obs_frames, const float *uv,
                        const double *xyz, const vsm_vet_params *params) {
-  if (!vet_params_ok(params)) return -1;
-  if (n_tracks > 0 && !xyz) return -1;
-  vsm_triangulate_params tp;
-  vsm_triangulate_default_params(&tp);
-  return pts_check_args(n_frames, poses, n_tracks, offsets, obs_frames, uv, &tp);
+  if (!vet_params_ok(params) || (n_tracks > 0 && !xyz)) return -1;
+  return pts_check_obs(n_frames, poses, n_tracks, offsets, obs_frames, uv);
 }
 
 extern "C" {

@@ -649,6 +649,11 @@ def _list_inputs(lists, counts=None):
     return ls, ptrs, np.ascontiguousarray(counts, dtype=np.int32)
 
 
+def _optional_lists(lists, counts=None):
+    """_list_inputs for a handle form's lists, or - None: the lists of the last match_pairs call - three times None"""
+    return (None, None, None) if lists is None else _list_inputs(lists, counts)
+
+
 def _track_inputs(pairs, lists, counts=None):
     """(pairs [P,2] int32, then what _list_inputs gives for the pairs' lists)"""
     pa = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
@@ -756,20 +761,39 @@ def chain_poses(n_frames, pairs, T, rc, root=0):
     return poses, valid, got
 
 
-def triangulate_params(**kw):
-    """vsm_triangulate_default_params with fields overridden by keyword"""
-    p = VsmTriangulateParams()
-    lib().vsm_triangulate_default_params(C.byref(p))
+def _default_params(struct, defaults, kw):
+    """a parameter struct filled by the library's function `defaults`, with fields overridden by keyword"""
+    p = struct()
+    getattr(lib(), defaults)(C.byref(p))
     for k, v in kw.items():
         assert hasattr(p, k), k
         setattr(p, k, v)
     return p
 
 
-def _as_params(params):
-    if isinstance(params, VsmTriangulateParams):
-        return params
-    return triangulate_params(**(params or {}))
+def _params_ref(struct, make, params):
+    """a call's params argument by reference: a `struct` itself, or make(**params) for a dict of its fields (None: the
+    defaults); _NO_PARAMS: a NULL pointer"""
+    if params is _NO_PARAMS:
+        return None
+    return C.byref(params if isinstance(params, struct) else make(**(params or {})))
+
+
+def triangulate_params(**kw):
+    """vsm_triangulate_default_params with fields overridden by keyword"""
+    return _default_params(VsmTriangulateParams, "vsm_triangulate_default_params", kw)
+
+
+def _n_tracks(offsets, n_tracks=None):
+    """T = len(offsets) - 1, unless overridden (argument tests)"""
+    return max(len(offsets) - 1, 0) if n_tracks is None else int(n_tracks)
+
+
+def _mask(mask, n):
+    """a per-frame mask as n bytes, or None"""
+    m = None if mask is None else np.ascontiguousarray(np.asarray(mask).astype(np.uint8))
+    assert m is None or m.shape == (n,)
+    return m
 
 
 def _pose_inputs(poses, pose_valid, n_frames=None):
@@ -778,9 +802,7 @@ def _pose_inputs(poses, pose_valid, n_frames=None):
     po = np.ascontiguousarray(po.reshape(len(po), -1)[:, :12]) if po.size else np.zeros((0, 12))
     if n_frames is not None:
         assert len(po) == n_frames, (len(po), n_frames)
-    pv = None if pose_valid is None else np.ascontiguousarray(np.asarray(pose_valid).astype(np.uint8))
-    assert pv is None or pv.shape == (len(po),)
-    return po, pv
+    return po, _mask(pose_valid, len(po))
 
 
 def _triangulate_inputs(poses, pose_valid, offsets, obs_frames, uv, flags):
@@ -805,10 +827,10 @@ def host_triangulate(poses, f, cu, cv, offsets, obs_frames, uv, flags=None, pose
     """vsm_host_triangulate: the tracks' 3-D points on one host thread - no GPU.  n_tracks: override len(offsets) - 1 (argument
     tests).  Returns a Points object; raises VisoMatchError on VSM_EARG."""
     po, pv, off, fr, px, fl = _triangulate_inputs(poses, pose_valid, offsets, obs_frames, uv, flags)
-    T = max(len(off) - 1, 0) if n_tracks is None else int(n_tracks)
+    T = _n_tracks(off, n_tracks)
     out = _points_arrays(max(T, 0))
     got = _check(lib().vsm_host_triangulate(len(po), _ptr(po), _ptr(pv), float(f), float(cu), float(cv), T, _ptr(off), _ptr(fr), _ptr(px), _ptr(fl),
-                                            C.byref(_as_params(params)), *[_ptr(a) for a in out]), "vsm_host_triangulate")
+                                            _params_ref(VsmTriangulateParams, triangulate_params, params), *[_ptr(a) for a in out]), "vsm_host_triangulate")
     assert got == T
     return Points(*out)
 
@@ -837,18 +859,7 @@ class Resection:
 
 def resect_params(**kw):
     """vsm_resect_default_params with fields overridden by keyword"""
-    p = VsmResectParams()
-    lib().vsm_resect_default_params(C.byref(p))
-    for k, v in kw.items():
-        assert hasattr(p, k), k
-        setattr(p, k, v)
-    return p
-
-
-def _as_resect_params(params):
-    if isinstance(params, VsmResectParams):
-        return params
-    return resect_params(**(params or {}))
+    return _default_params(VsmResectParams, "vsm_resect_default_params", kw)
 
 
 def _resect_arrays(F):
@@ -858,8 +869,7 @@ def _resect_arrays(F):
 
 def _resect_inputs(poses, pose_valid, refine, offsets, obs_frames, uv, xyz, use):
     po, pv, off, fr, px, us = _triangulate_inputs(poses, pose_valid, offsets, obs_frames, uv, use)
-    rf = None if refine is None else np.ascontiguousarray(np.asarray(refine).astype(np.uint8))
-    assert rf is None or rf.shape == (len(po),)
+    rf = _mask(refine, len(po))
     pt = None if xyz is None else np.ascontiguousarray(np.asarray(xyz, dtype=np.float64).reshape(-1, 3))
     assert pt is None or len(pt) >= len(off) - 1
     assert us is None or len(us) >= len(off) - 1
@@ -870,10 +880,10 @@ def host_resect(poses, f, cu, cv, offsets, obs_frames, uv, xyz, use=None, refine
     """vsm_host_resect: every frame's pose refined against the points on one host thread - no GPU.  n_tracks: override
     len(offsets) - 1 (argument tests).  Returns a Resection object; raises VisoMatchError on VSM_EARG."""
     po, pv, rf, off, fr, px, pt, us = _resect_inputs(poses, pose_valid, refine, offsets, obs_frames, uv, xyz, use)
-    T = max(len(off) - 1, 0) if n_tracks is None else int(n_tracks)
+    T = _n_tracks(off, n_tracks)
     out = _resect_arrays(len(po))
     got = _check(lib().vsm_host_resect(len(po), _ptr(po), _ptr(pv), _ptr(rf), float(f), float(cu), float(cv), T, _ptr(off), _ptr(fr), _ptr(px), _ptr(pt),
-                                       _ptr(us), C.byref(_as_resect_params(params)), *[_ptr(a) for a in out]), "vsm_host_resect")
+                                       _ptr(us), _params_ref(VsmResectParams, resect_params, params), *[_ptr(a) for a in out]), "vsm_host_resect")
     assert got == len(po)
     return Resection(*out)
 
@@ -920,18 +930,7 @@ class Vetting:
 
 def vet_params(**kw):
     """vsm_vet_default_params with fields overridden by keyword"""
-    p = VsmVetParams()
-    lib().vsm_vet_default_params(C.byref(p))
-    for k, v in kw.items():
-        assert hasattr(p, k), k
-        setattr(p, k, v)
-    return p
-
-
-def _as_vet_params(params):
-    if isinstance(params, VsmVetParams):
-        return params
-    return vet_params(**(params or {}))
+    return _default_params(VsmVetParams, "vsm_vet_default_params", kw)
 
 
 def _vet_arrays(T, n_obs, F, n_kept):
@@ -948,11 +947,11 @@ def host_vet(poses, f, cu, cv, offsets, obs_frames, uv, xyz, use=None, pose_vali
     """vsm_host_vet: every observation vetted on one host thread - no GPU.  n_tracks: override len(offsets) - 1 (argument
     tests).  Returns a Vetting object; raises VisoMatchError on VSM_EARG."""
     po, pv, off, fr, px, pt, us = _vet_inputs(poses, pose_valid, offsets, obs_frames, uv, xyz, use)
-    T = max(len(off) - 1, 0) if n_tracks is None else int(n_tracks)
+    T = _n_tracks(off, n_tracks)
     out = _vet_arrays(max(T, 0), len(fr), len(po), len(fr))
     n_kept = C.c_int32(0)
     got = _check(lib().vsm_host_vet(len(po), _ptr(po), _ptr(pv), float(f), float(cu), float(cv), T, _ptr(off), _ptr(fr), _ptr(px), _ptr(pt), _ptr(us),
-                                    None if params is _NO_PARAMS else C.byref(_as_vet_params(params)), *[_ptr(a) for a in out], C.byref(n_kept)), "vsm_host_vet")
+                                    _params_ref(VsmVetParams, vet_params, params), *[_ptr(a) for a in out], C.byref(n_kept)), "vsm_host_vet")
     assert got == T
     return Vetting(*out[:-1], out[-1][:n_kept.value].copy())
 
@@ -1385,9 +1384,9 @@ class Matcher:
         world; offsets [T + 1], obs_frames [n_obs], uv [n_obs, 2]; params: a dict of vsm_triangulate_params fields or the
         struct.  Returns a Points object."""
         po, pv, off, fr, px, fl = _triangulate_inputs(poses, pose_valid, offsets, obs_frames, uv, flags)
-        T = max(len(off) - 1, 0) if n_tracks is None else int(n_tracks)
+        T = _n_tracks(off, n_tracks)
         rc = lib().vsm_triangulate_run(self.h, len(po), _ptr(po), _ptr(pv), float(f), float(cu), float(cv), T, _ptr(off), _ptr(fr), _ptr(px), _ptr(fl),
-                                       C.byref(_as_params(params)))
+                                       _params_ref(VsmTriangulateParams, triangulate_params, params))
         return self._points_result(rc, "vsm_triangulate_run")
 
     def track_points(self, poses, f, cu, cv, lists=None, pose_valid=None, params=None, counts=None):
@@ -1395,10 +1394,9 @@ class Matcher:
         built from (None: those of the last match_pairs call, for tracks from pair_tracks).  counts: override the lists' lengths
         (argument tests)."""
         po, pv = _pose_inputs(poses, pose_valid, self._track_frames)  # (the library reads one pose per frame of the track call)
-        ptrs = cnt = None
-        if lists is not None:
-            ls, ptrs, cnt = _list_inputs(lists, counts)
-        rc = lib().vsm_tracks_triangulate(self.h, ptrs, _ptr(cnt), _ptr(po), _ptr(pv), float(f), float(cu), float(cv), C.byref(_as_params(params)))
+        ls, ptrs, cnt = _optional_lists(lists, counts)
+        rc = lib().vsm_tracks_triangulate(self.h, ptrs, _ptr(cnt), _ptr(po), _ptr(pv), float(f), float(cu), float(cv),
+                                          _params_ref(VsmTriangulateParams, triangulate_params, params))
         return self._points_result(rc, "vsm_tracks_triangulate")
 
     # --- poses refined against the points ---------------------------------------------------------
@@ -1414,22 +1412,19 @@ class Matcher:
         [F, 4, 4]) camera to world; the tracks as for triangulate; xyz [T, 3]; use [T] and refine [F]: masks (None: all);
         params: a dict of vsm_resect_params fields or the struct.  Returns a Resection object."""
         po, pv, rf, off, fr, px, pt, us = _resect_inputs(poses, pose_valid, refine, offsets, obs_frames, uv, xyz, use)
-        T = max(len(off) - 1, 0) if n_tracks is None else int(n_tracks)
+        T = _n_tracks(off, n_tracks)
         rc = lib().vsm_resect_run(self.h, len(po), _ptr(po), _ptr(pv), _ptr(rf), float(f), float(cu), float(cv), T, _ptr(off), _ptr(fr), _ptr(px), _ptr(pt),
-                                  _ptr(us), C.byref(_as_resect_params(params)))
+                                  _ptr(us), _params_ref(VsmResectParams, resect_params, params))
         return self._resect_result(rc, "vsm_resect_run")
 
     def resect_points(self, poses, f, cu, cv, lists=None, refine=None, pose_valid=None, params=None, counts=None):
         """vsm_points_resect: the same on the handle's last track and point results (the kept points; lists as for
         track_points)."""
         po, pv = _pose_inputs(poses, pose_valid, self._track_frames)
-        rf = None if refine is None else np.ascontiguousarray(np.asarray(refine).astype(np.uint8))
-        assert rf is None or rf.shape == (len(po),)
-        ptrs = cnt = None
-        if lists is not None:
-            ls, ptrs, cnt = _list_inputs(lists, counts)
+        rf = _mask(refine, len(po))
+        ls, ptrs, cnt = _optional_lists(lists, counts)
         rc = lib().vsm_points_resect(self.h, ptrs, _ptr(cnt), _ptr(po), _ptr(pv), _ptr(rf), float(f), float(cu), float(cv),
-                                     C.byref(_as_resect_params(params)))
+                                     _params_ref(VsmResectParams, resect_params, params))
         return self._resect_result(rc, "vsm_points_resect")
 
     # --- observations vetted by reprojection error -----------------------------------------------
@@ -1450,27 +1445,23 @@ class Matcher:
         and frame, and the pruned track set, on the device.  Arguments as for resect, without refine; params: a dict of
         vsm_vet_params fields or the struct.  Returns a Vetting object."""
         po, pv, off, fr, px, pt, us = _vet_inputs(poses, pose_valid, offsets, obs_frames, uv, xyz, use)
-        T = max(len(off) - 1, 0) if n_tracks is None else int(n_tracks)
+        T = _n_tracks(off, n_tracks)
         rc = lib().vsm_vet_run(self.h, len(po), _ptr(po), _ptr(pv), float(f), float(cu), float(cv), T, _ptr(off), _ptr(fr), _ptr(px), _ptr(pt), _ptr(us),
-                               None if params is _NO_PARAMS else C.byref(_as_vet_params(params)))
+                               _params_ref(VsmVetParams, vet_params, params))
         return self._vet_result(rc, "vsm_vet_run")
 
     def vet_points(self, poses, f, cu, cv, lists=None, pose_valid=None, params=None, counts=None):
         """vsm_points_vet: the same on the handle's last track and point results (the kept points; lists as for track_points)"""
         po, pv = _pose_inputs(poses, pose_valid, self._track_frames)
-        ptrs = cnt = None
-        if lists is not None:
-            ls, ptrs, cnt = _list_inputs(lists, counts)
+        ls, ptrs, cnt = _optional_lists(lists, counts)
         rc = lib().vsm_points_vet(self.h, ptrs, _ptr(cnt), _ptr(po), _ptr(pv), float(f), float(cu), float(cv),
-                                  None if params is _NO_PARAMS else C.byref(_as_vet_params(params)))
+                                  _params_ref(VsmVetParams, vet_params, params))
         return self._vet_result(rc, "vsm_points_vet")
 
     def track_pixels(self, lists=None, counts=None):
         """vsm_tracks_pixels: (obs_frames [n_obs] int32, uv [n_obs, 2] float32) of the handle's last track result, the pixels
         read from the match lists as track_points reads them (lists: as there)"""
-        ptrs = cnt = None
-        if lists is not None:
-            ls, ptrs, cnt = _list_inputs(lists, counts)
+        ls, ptrs, cnt = _optional_lists(lists, counts)
         n = _check(lib().vsm_tracks_pixels(self.h, ptrs, _ptr(cnt), None, None), "vsm_tracks_pixels")
         fr, px = np.zeros(n, np.int32), np.zeros((n, 2), np.float32)
         _check(lib().vsm_tracks_pixels(self.h, ptrs, _ptr(cnt), _ptr(fr), _ptr(px)), "vsm_tracks_pixels")

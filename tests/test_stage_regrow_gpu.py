@@ -1,8 +1,10 @@
-"""GPU suite (run with -m gpu on an MI355X): the staging of the tracks, points and motions calls (csrc/vsm_stage.h) when it grows
-and is then reused.  On one fresh handle every stage runs a tiny input, then one more than 1.25 times larger in every block
-(pinned input, pinned output, device), then the tiny one again; the three stages then run interleaved, and an argument error after
-the growth leaves the last result readable.  Every result is compared with the stage's host view by the comparison of the
-stage's own suite (tracks_ref, points_ref, motions_cases); the generators are theirs too."""
+"""GPU suite (run with -m gpu on an MI355X): the staging of the tracks, points, resection and motions calls (csrc/vsm_stage.h)
+when it grows and is then reused (the vetting's is in test_vet_gpu.test_regrow).  On one fresh handle every stage runs a tiny
+input, then one more than 1.25 times larger in every block (pinned input, pinned output, device), then the tiny one again; the
+stages then run interleaved, an argument error after the growth leaves the last result readable, and the calls that share one
+round trip (points, resection, vetting) take their empty call on the grown blocks.  Every result is compared with the stage's
+host view by the comparison of the stage's own suite (tracks_ref, points_ref, resect_ref, vet_ref, motions_cases); the
+generators are theirs too."""
 import functools
 
 import numpy as np
@@ -11,7 +13,11 @@ import pytest
 import motions_cases as MO
 import points_cases as PC
 import points_ref as PR
+import resect_cases as RC
+import resect_ref as RR
 import tracks_ref as TR
+import vet_cases as VC
+import vet_ref as V
 from conftest import pkg
 
 pytestmark = pytest.mark.gpu
@@ -58,6 +64,30 @@ def motion_inputs():
     return ([MO.one("scene12")], MO.params(50)), ([MO.one("scene299"), MO.one("scene300"), MO.one("scene301")], MO.params(200))
 
 
+@functools.lru_cache(maxsize=None)
+def large_scene():
+    """the scene of test_vet_gpu.test_regrow: six frames, 600 points, tracks of 0 to 39 observations, every fifth 50 px off ->
+    (true poses, tracks, points)"""
+    rng = np.random.default_rng(50)
+    true = PC.camera_path(6)
+    pts = VC.RC.visible_points(600, rng)
+    return true, [VC.noisy_track(true, X, [j % 6 for j in range(int(rng.integers(0, 40)))], rng, every=5) for X in pts], pts
+
+
+@functools.lru_cache(maxsize=None)
+def resect_inputs():
+    """resect_cases' one refined frame of 30 rows; the large scene from poses a little off, behind a gate of 8 px"""
+    true, tracks, pts = large_scene()
+    return RC.cases()["frames_1"], RC.Case(RC.perturb(true, np.random.default_rng(51)), tracks, pts, params=dict(max_residual=8.0), true_poses=true)
+
+
+@functools.lru_cache(maxsize=None)
+def vet_inputs():
+    """vet_cases' five tracks; the large scene at its true poses"""
+    true, tracks, pts = large_scene()
+    return VC.cases()["counts_5"], VC.Case(true, tracks, pts)
+
+
 def run_tracks(vm, m, args, what):
     got = m.tracks(*args)
     TR.assert_same(vm.host_tracks(*args), got, (what, "host view against the device"))
@@ -68,6 +98,20 @@ def run_points(vm, m, case, what):
     a, kw = case.args()
     got = m.triangulate(*a, **kw)
     PR.assert_same(vm.host_triangulate(*a, **kw), got, (what, "host view against the device"))
+    return got
+
+
+def run_resect(vm, m, case, what):
+    a, kw = case.args()
+    got = m.resect(*a, **kw)
+    RR.assert_same(vm.host_resect(*a, **kw), got, (what, "host view against the device"))
+    return got
+
+
+def run_vet(vm, m, case, what):
+    a, kw = case.args()
+    got = m.vet(*a, **kw)
+    V.assert_same(vm.host_vet(*a, **kw), got, (what, "host view against the device"))
     return got
 
 
@@ -103,6 +147,15 @@ def test_points_regrow(vm, matcher):
     seg = np.diff(large.offsets)
     assert len(big) > 2500 and seg.min() >= 2 and seg.max() <= 6 and big.kept.any() and not big.kept.all()
     PR.assert_same(run_points(vm, matcher, small, "small again"), first, "the third result equals the first")
+
+
+def test_resect_regrow(vm, matcher):
+    small, large = resect_inputs()
+    first = run_resect(vm, matcher, small, "small")
+    assert len(first) == 1 and first.refined.all() and first.rows[0] == 30
+    big = run_resect(vm, matcher, large, "large")
+    assert len(big) == 6 and big.rows.min() > 1000 and big.refined.all() and (big.used < big.rows).all() and len(large.xyz) == 600
+    RR.assert_same(run_resect(vm, matcher, small, "small again"), first, "the third result equals the first")
 
 
 def test_motions_regrow(vm, matcher):
@@ -141,3 +194,46 @@ def test_interleaved_and_errors(vm, matcher):
     with pytest.raises(vm.VisoMatchError, match="VSM_EARG"):
         matcher.motions(m_small[0], None)
     motions_bytes_equal(matcher.last_motions(), mo, "the last good motions")
+
+
+# ---- the calls that share one round trip: interleaved, and their empty call on grown blocks -------------------------------------------
+
+def last_three(m):
+    return m._points_result(0, "the last result"), m._resect_result(0, "the last result"), m._vet_result(0, "the last result")
+
+
+def test_points_resect_vet_interleaved(vm, matcher):
+    (p_small, p_large), (r_small, r_large), (v_small, v_large) = point_inputs(), resect_inputs(), vet_inputs()
+    pt = run_points(vm, matcher, p_large, "points")
+    rs = run_resect(vm, matcher, r_large, "resection")
+    PR.assert_same(last_three(matcher)[0], pt, "the point result after the resection")
+    ve = run_vet(vm, matcher, v_large, "vetting")
+    assert ve.stats["tracks_kept"] > 256 and ve.stats["obs_gated"] > 1000
+    PR.assert_same(last_three(matcher)[0], pt, "the point result after the vetting")
+    RR.assert_same(last_three(matcher)[1], rs, "the resection result after the vetting")
+    pt2 = run_points(vm, matcher, p_small, "points again")
+    RR.assert_same(last_three(matcher)[1], rs, "the resection result after the second points call")
+    V.assert_same(last_three(matcher)[2], ve, "the vetting result after the second points call")
+    PR.assert_same(last_three(matcher)[0], pt2, "the second point result")
+
+
+def test_empty_calls_on_grown_blocks(vm, matcher):
+    """T = 0 for the points and the vetting, F = 0 for the resection: no round trip, empty arrays, zero stats"""
+    (p_small, p_large), (r_small, r_large), (v_small, v_large) = point_inputs(), resect_inputs(), vet_inputs()
+    poses = PC.camera_path(3)
+    run_points(vm, matcher, p_large, "points, large")
+    got = run_points(vm, matcher, PC.Case(poses, [0], [], np.zeros((0, 2), np.float32)), "points, no track")
+    assert len(got) == 0 and got.xyz.shape == (0, 3) and len(got.angle) == 0 and set(got.stats.values()) == {0}
+    assert got.timings["upload_us"] == 0 and got.timings["kernels_us"] == 0
+    run_resect(vm, matcher, r_large, "resection, large")
+    got = run_resect(vm, matcher, RC.cases()["no_frames"], "resection, no frame")
+    assert len(got) == 0 and got.poses.shape == (0, 12) and len(got.rms_after) == 0 and set(got.stats.values()) == {0}
+    assert got.timings["upload_us"] == 0 and got.timings["kernels_us"] == 0
+    run_vet(vm, matcher, v_large, "vetting, large")
+    got = run_vet(vm, matcher, VC.Case(poses, [], np.zeros((0, 3))), "vetting, no track")
+    assert len(got) == 0 and len(got.code) == 0 and len(got.kept_index) == 0 and got.kept_offsets.tolist() == [0] and set(got.stats.values()) == {0}
+    assert got.frame_counts.shape == (3, 3) and not got.frame_counts.any() and got.timings["upload_us"] == 0 and got.timings["kernels_us"] == 0
+    # and a call with something in it again
+    assert run_points(vm, matcher, p_small, "points, small").kept.all()
+    assert run_resect(vm, matcher, r_small, "resection, small").refined.all()
+    V.assert_same(run_vet(vm, matcher, v_small, "vetting, small"), VC.reference("counts_5"), "vetting after the empty call")

@@ -5,10 +5,10 @@
 // vsm_vo_sampler_seed(71) + vsm_host_estimate_motion_mono; then chains with failed, reversed and self pairs and the
 // argument errors.  Meant to be built with the host sanitizers from the library's own units, e.g.
 //   S="-Xarch_host -fsanitize=address,undefined"; C=opencl-structure-from-motion_amd/csrc
-//   for u in vsm_image vsm_match vsm_mono vsm_dc vsm_tracks vsm_points; do
+//   for u in vsm_image vsm_match vsm_mono vsm_dc vsm_tracks vsm_points vsm_resect vsm_vet; do
 //     hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -ffp-contract=off -Iinclude -I$C $S -x hip -c $C/$u.hip -o $u.o; done
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -ffp-contract=off -Iinclude -I$C $S -x hip -c $C/vsm_api.cpp -o vsm_api.o
-//   for u in vsm_host vsm_ego vsm_tracks_host vsm_points_host; do
+//   for u in vsm_host vsm_ego vsm_tracks_host vsm_points_host vsm_resect_host vsm_vet_host; do
 //     hipcc -O1 -g -std=c++17 -fPIC -ffp-contract=off -Iinclude -I$C -fsanitize=address,undefined -x c++ -c $C/$u.cpp -o $u.o; done
 //   hipcc -O1 -g -std=c++17 -Iinclude -fsanitize=address,undefined -x c++ -c tools/motions_host_check.cpp -o check.o
 //   hipcc --offload-arch=gfx950 -fsanitize=address,undefined *.o -o motions_host_check && ./motions_host_check

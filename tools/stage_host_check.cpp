@@ -1,14 +1,17 @@
 // Stand-alone host check of the block layout the staged calls share (csrc/vsm_stage.h, VsmLayout): the offsets of a handful of
 // take() sequences against the 256-alignment arithmetic written out by hand - sizes 0, 1, 255, 256, 257 and a block of
-// 5 GB, which a 32-bit offset would not survive.  No HIP call is made (the header's staging functions are not instantiated
-// here).  Meant to be built with the sanitizers, e.g.
+// 5 GB, which a 32-bit offset would not survive.  Then the four stages' blocks (csrc/vsm_layouts.h: tracks, points,
+// resection, vetting): every array's offset, in.at, out.at and the device block's size against the sequence of sizes the
+// calls stated by hand before the arrays were typed, for every combination of the counts 0, 1, 5 and 257 and for an
+// observation count whose arrays pass 2^31 bytes.  No HIP call is made (the header's staging functions are not
+// instantiated here).  Meant to be built with the sanitizers, e.g.
 //   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude \
 //       -Iopencl-structure-from-motion_amd/csrc tools/stage_host_check.cpp -o stage_host_check
 // Prints "ok" and returns 0, or says what differed.
 #include <cstdint>
 #include <cstdio>
 
-#include "vsm_stage.h"
+#include "vsm_layouts.h"
 
 static int fails = 0;
 #define CHECK(c)                                             \
@@ -18,6 +21,111 @@ static int fails = 0;
       fails++;                                               \
     }                                                        \
   } while (0)
+
+// an array of a stage's blocks lies where the call's next take() of that many bytes put it
+#define SAME(arr, lay, bytes) CHECK((arr).at == (lay).take(bytes))
+
+static void check_points(size_t F, size_t T, size_t N) {
+  const PtsBlocks L(F, T, N);
+  VsmLayout in, out;
+  SAME(L.frames, in, F * sizeof(PtsFrame) + 8);
+  SAME(L.valid, in, F + 1);
+  SAME(L.offsets, in, (T + 1) * 4);
+  SAME(L.obs_frames, in, N * 4 + 4);
+  SAME(L.uv, in, N * 8 + 8);
+  SAME(L.flags, in, T + 1);
+  SAME(L.status, out, T * 4 + 4);
+  SAME(L.type, out, T * 4 + 4);
+  SAME(L.updates, out, T * 4 + 4);
+  SAME(L.xyz, out, T * 24 + 8);
+  SAME(L.dist, out, T * 8 + 8);
+  SAME(L.ray, out, T * 8 + 8);
+  CHECK(L.in.at == in.at && L.out.at == out.at && L.out_at == al256(in.at) && L.dev_bytes == al256(in.at) + out.at);
+  CHECK(L.frames.n == F && L.uv.n == 2 * N && L.xyz.n == 3 * T && L.status.n == T);
+}
+
+static void check_resect(size_t F, size_t T, size_t R) {
+  const RsBlocks L(F, T, R);
+  VsmLayout in, out;
+  SAME(L.poses, in, F * 96 + 8);
+  SAME(L.valid, in, F + 1);
+  SAME(L.refine, in, F + 1);
+  SAME(L.row_off, in, (F + 1) * 4);
+  SAME(L.rows, in, R * sizeof(RsRow) + 4);
+  SAME(L.xyz, in, T * 24 + 8);
+  SAME(L.status, out, F * 4 + 4);
+  SAME(L.updates, out, F * 4 + 4);
+  SAME(L.used_before, out, F * 4 + 4);
+  SAME(L.used, out, F * 4 + 4);
+  SAME(L.out_poses, out, F * 96 + 8);
+  SAME(L.ss_before, out, F * 8 + 8);
+  SAME(L.ss_after, out, F * 8 + 8);
+  CHECK(L.in.at == in.at && L.out.at == out.at && L.out_at == al256(in.at) && L.dev_bytes == al256(in.at) + out.at);
+  CHECK(L.out_poses.n == 12 * F && L.rows.n == R && L.status.n == F);
+}
+
+static void check_vet(size_t F, size_t T, size_t N) {
+  const VetBlocks L(F, T, N);
+  VsmLayout in, out;
+  SAME(L.states, in, F * 96 + 8);
+  SAME(L.valid, in, F + 1);
+  SAME(L.offsets, in, (T + 1) * 4);
+  SAME(L.obs_frames, in, N * 4 + 4);
+  SAME(L.uv, in, N * 8 + 8);
+  SAME(L.xyz, in, T * 24 + 8);
+  SAME(L.use, in, T + 1);
+  SAME(L.code, out, N + 1);
+  SAME(L.r2, out, N * 4 + 4);
+  SAME(L.status, out, T * 4 + 4);
+  SAME(L.n_in, out, T * 4 + 4);
+  SAME(L.frame_lo, out, T * 4 + 4);
+  SAME(L.frame_hi, out, T * 4 + 4);
+  SAME(L.ss, out, T * 8 + 8);
+  SAME(L.worst, out, T * 8 + 8);
+  SAME(L.frame_counts, out, F * 12 + 4);
+  SAME(L.kept_offsets, out, (T + 1) * 4);
+  SAME(L.kept_index, out, N * 4 + 4);
+  SAME(L.totals, out, 8);
+  VsmLayout work = out;  // behind the results, not copied back
+  SAME(L.scan, work, T * 8 + 8);
+  SAME(L.scan_part, work, trk_scan_part_items((int64_t)T) * 8 + 8);
+  CHECK(L.in.at == in.at && L.out.at == out.at && L.out_at == al256(in.at) && L.dev_bytes == al256(in.at) + work.at);
+  CHECK(L.code.n == N && L.frame_counts.n == 3 * F && L.kept_offsets.n == T + 1 && L.kept_index.n == N);
+}
+
+// P pairs, F frames, E matches; then N nodes; then the totals the device reports
+static void check_tracks(size_t P, size_t F, size_t E, size_t N, size_t n_tracks, size_t n_obs) {
+  TrkBlocks L(P, F, E);
+  VsmLayout in;
+  SAME(L.pair_base, in, (P + 1) * 4);
+  SAME(L.pairs, in, P * 8 + 4);
+  SAME(L.feat_base, in, (F + 1) * 4);
+  SAME(L.edges, in, E * 8 + 4);
+  CHECK(L.in.at == in.at);
+  L.nodes(N);
+  VsmLayout dl = in;
+  SAME(L.parent, dl, N * 4);
+  SAME(L.first, dl, N * 4);
+  SAME(L.size, dl, N * 4);
+  SAME(L.cursor, dl, N * 4);
+  SAME(L.scan, dl, N * 8);
+  SAME(L.scan_part, dl, trk_scan_part_items((int64_t)N) * 8 + 8);
+  SAME(L.totals, dl, 8);
+  SAME(L.mid_list, dl, (N / (VSM_TRACKS_WAVE_MAX + 1) + 1) * 4);
+  const size_t o_out = dl.take(0);
+  CHECK(L.in.at == in.at && L.out_at == o_out);
+  CHECK(L.dev_bytes == o_out + al256(16) + al256((N + 1) * 4) + al256(N * 16) + al256(E * 4) + al256(N));
+  L.results(n_tracks, n_obs);
+  VsmLayout ol;
+  ol.at = o_out;  // (the call placed the results at their device offsets and took o_out off for the pinned block)
+  CHECK(L.counters.at == ol.take(16) - o_out);
+  CHECK(L.offsets.at == ol.take((n_tracks + 1) * 4) - o_out);
+  CHECK(L.obs.at == ol.take(n_obs * 16) - o_out);
+  CHECK(L.track_of_match.at == ol.take(E * 4) - o_out);
+  CHECK(L.flags.at == ol.take(n_tracks) - o_out);
+  CHECK(L.out.at == ol.at - o_out && L.out_at + L.out.at <= L.dev_bytes);
+  CHECK(L.obs.n == 4 * n_obs && L.track_of_match.n == E && L.flags.n == n_tracks);
+}
 
 int main() {
   static_assert(sizeof(size_t) == 8, "offsets are 64-bit");
@@ -56,6 +164,22 @@ int main() {
     CHECK(l.take(big + 1) == 5368709376ull && l.at == 5368709376ull + 5368709120ull + 256);
     CHECK(l.take(0) == 10737418752ull && l.at == 10737418752ull);
     CHECK(al256(big + 1) == big + 256 && al256(big - 1) == big);
+  }
+  {  // the stages' blocks
+    const size_t counts[4] = {0, 1, 5, 257};
+    const size_t big = ((size_t)1 << 29) + 3;  // observations: 4 bytes each pass 2^31, 8 and 16 bytes each pass 2^32
+    for (size_t a : counts)
+      for (size_t b : counts)
+        for (size_t c : counts) {
+          check_points(a, b, c);
+          check_resect(a, b, c);
+          check_vet(a, b, c);
+          for (size_t n : counts) check_tracks(a, b, c, n, std::min(n, b), n);
+        }
+    check_points(5, 257, big);
+    check_resect(5, 257, big);
+    check_vet(5, 257, big);
+    check_tracks(5, 257, big, big, 257, big);
   }
   if (fails) return 1;
   printf("ok\n");
