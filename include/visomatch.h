@@ -431,6 +431,91 @@ int32_t vsm_host_vet(int32_t n_frames, const double *poses, const uint8_t *pose_
  * uv_out[n_obs][2], either may be NULL.  Returns n_obs, or VSM_ENOTREADY / VSM_EARG as vsm_tracks_triangulate does for the
  * lists. */
 int32_t vsm_tracks_pixels(vsm_handle *h, const vsm_p_match *const *lists, const int32_t *counts, int32_t *obs_frames_out, float *uv_out);
+/* ---- joint adjustment of poses and points ----
+ * Poses and points move together: damped Gauss-Newton (Levenberg-Marquardt) rounds on the rows of the resection, the points
+ * eliminated (Schur complement) and the reduced camera system solved by preconditioned conjugate gradients without ever
+ * forming its matrix.  No counterpart in the reference.  csrc/vsm_ba.h is the one statement of the arithmetic (every product,
+ * every sum and its order; only + - * / on doubles, so the device equals the host view bit for bit); what follows is the contract.
+ * Input: exactly what vsm_resect_run takes.  State: per frame [Rw | tw], the rigid inverse of the input pose; per track X.
+ * A ROW is an observation of a track in use in a frame with a valid pose.  One ROUND:
+ *  - linearise: a row is ACTIVE if the resection would use it at the state (zc > min_depth, ru^2 + rv^2 < max_residual^2);
+ *    the active set then stands for the whole round.  Per active row: Jc (2x6, the resection's), Jp (2x3, the derivative of
+ *    the prediction by X), W = Jc^T Jp.  Per frame, over its active rows in the resection's order (256 partial sums, the
+ *    tree): U = Jc^T Jc, gc = Jc^T r and the cost, the resection's 28 sums.  Per track, over its active observations
+ *    ascending: V = Jp^T Jp, gp = Jp^T r.  The diagonals of U and V are multiplied by 1 + lambda.
+ *  - a frame is FREE in the round if it is valid, asked for, has at least min_observations active rows and its damped U has
+ *    a pivot (Gauss-Jordan, full pivoting, eps 1e-20); a track is free if it is in use, has at least min_track_observations
+ *    active observations and its damped V has a pivot.  Everything else is HELD: its update is zero, its rows still count
+ *    in the sums of the other side and in the cost.
+ *  - solve (U - W V^-1 W^T) x = gc - W V^-1 gp over the free frames by conjugate gradients preconditioned with U^-1 per frame,
+ *    from x = 0.  Scalar products: partial[l], l = 0..255, adds the products of the entries 6 g + m with (6 g + m) mod 256 == l
+ *    ascending (held frames are passed over), then the tree.  It ends at the first of: rz <= cg_tol^2 rz0 (end 1); p.q not
+ *    positive and finite, x kept as it stands (end 2); cg_iters iterations (end 3).
+ *  - dX = V^-1 (gp - W^T x); trial poses by the resection's Cayley step of x, trial points X + dX.
+ *  - the trial cost runs over the same active rows; one of them behind the camera (not zc > min_depth) rejects the step.
+ *    Accepted if the trial cost is finite and strictly below the cost: lambda = max(lambda / 10, lambda_min); else the state
+ *    is kept and lambda *= 10.
+ * The call stops after an accepted round with cost - trial <= ftol * cost (stop 1), when lambda > lambda_max (stop 2), or
+ * after max_rounds rounds (stop 3).
+ * Frame status, from the last round: 1 no valid pose, 2 not asked for, 3 fewer than min_observations rows (the resection's
+ * numbers), 7 held in the last round (too few active rows, or no pivot), 0 free in the last round.  Track status, from the
+ * last round: 1 not in use, 2 fewer than min_track_observations active observations, 3 no pivot, 0 free.
+ * Results: per frame status, pose[12] (camera to world: the rigid inverse of the final state if an accepted round moved the
+ * frame, else the input pose's bytes), rows, active (the active rows of the last round); per track status and xyz[3] (the
+ * input point's bytes unless an accepted round moved it); per round run the history: cost before, cost after (the trial
+ * cost if accepted, else the cost before - it never rises), lambda of the round, the CG's iterations, how it ended (1..3),
+ * accepted (0 / 1), active rows. */
+typedef struct vsm_adjust_params {
+  int32_t min_observations;       /* 10: the active rows a free frame needs (at least 6) */
+  int32_t min_track_observations; /* 2: the active observations a free track needs */
+  int32_t max_rounds;             /* 10 */
+  int32_t cg_iters;               /* 40 */
+  double lambda0;                 /* 1e-3 */
+  double lambda_min;              /* 1e-9 */
+  double lambda_max;              /* 1e6 */
+  double cg_tol;                  /* 1e-2 */
+  double ftol;                    /* 1e-6 */
+  double max_residual;            /* 0 = no gate (pixels) */
+  double min_depth;               /* 1e-10 */
+} vsm_adjust_params;
+void vsm_adjust_default_params(vsm_adjust_params *p);
+/* The general form, on the caller's arrays (the argument list of vsm_resect_run).  Runs on the handle's device and stream:
+ * the rows grouped by frame as the resection groups them (16 bytes per row: the observation's index rides along), one copy
+ * up, the rounds' kernels with one wait per round on a control block of the device (launches behind a finished solve or a
+ * finished call do nothing; option "adjust_fixed" = 1: every launch of max_rounds rounds enqueued at once and one wait, the
+ * same bytes), one copy back.  It has no CPU path.  VSM_EARG, nothing enqueued and the last result kept: what
+ * vsm_resect_run rejects for these arrays, params NULL, min_observations < 6, max_rounds < 1, cg_iters < 1, lambda0, cg_tol
+ * or ftol not positive or not finite.  Nothing else of the handle is touched. */
+int vsm_adjust_run(vsm_handle *h, int32_t n_frames, const double *poses, const uint8_t *pose_valid, const uint8_t *refine, double f, double cu,
+                   double cv, int32_t n_tracks, const int32_t *offsets, const int32_t *obs_frames, const float *uv, const double *xyz,
+                   const uint8_t *use, const vsm_adjust_params *params);
+/* The same on the handle's last track and point results, found exactly as vsm_points_resect finds them; VSM_ENOTREADY and
+ * VSM_EARG as there, with params as above.  Both results stay as they are. */
+int vsm_points_adjust(vsm_handle *h, const vsm_p_match *const *lists, const int32_t *counts, const double *poses, const uint8_t *pose_valid,
+                      const uint8_t *refine, double f, double cu, double cv, const vsm_adjust_params *params);
+/* the handle's last adjustment (zeros / nothing written without one); any output may be NULL.  count: F, T, rounds run.
+ * get_frames: status[F], poses[F][12], rows[F], active[F]; returns F.  get_tracks: status[T], xyz[T][3]; returns T.
+ * get_history, per round run: cost_before, cost_after, lambda (doubles), cg_iters, cg_end, accepted, active (int32); returns
+ * the rounds run. */
+void vsm_adjust_count(vsm_handle *h, int32_t *n_frames, int32_t *n_tracks, int32_t *n_rounds);
+int32_t vsm_adjust_get_frames(vsm_handle *h, int32_t *status, double *poses, int32_t *rows, int32_t *active);
+int32_t vsm_adjust_get_tracks(vsm_handle *h, int32_t *status, double *xyz);
+int32_t vsm_adjust_get_history(vsm_handle *h, double *cost_before, double *cost_after, double *lambda, int32_t *cg_iters, int32_t *cg_end,
+                               int32_t *accepted, int32_t *active);
+/* frames per status value 0..7, tracks per status value 0..3, rounds run, rounds accepted, why it stopped (1..3), CG
+ * iterations in all */
+void vsm_adjust_get_stats(vsm_handle *h, int64_t *out16);
+/* wall-clock split of the last call, microseconds: {gather + grouping + packing, upload, kernels (with the waits per round),
+ * download + host part} */
+void vsm_adjust_get_timings(vsm_handle *h, double *out4);
+/* The same definition on one host thread: no GPU, no handle (the CPU suite's subject, the device path's second opinion and
+ * the benchmark's baseline - not a fallback).  history arrays: room for max_rounds entries; *n_rounds the rounds run;
+ * stats16 as vsm_adjust_get_stats.  Returns n_frames, or VSM_EARG with the outputs untouched.  Outputs may be NULL. */
+int32_t vsm_host_adjust(int32_t n_frames, const double *poses, const uint8_t *pose_valid, const uint8_t *refine, double f, double cu, double cv,
+                        int32_t n_tracks, const int32_t *offsets, const int32_t *obs_frames, const float *uv, const double *xyz,
+                        const uint8_t *use, const vsm_adjust_params *params, int32_t *frame_status, double *out_poses, int32_t *rows,
+                        int32_t *active, int32_t *track_status, double *out_xyz, double *cost_before, double *cost_after, double *lambda,
+                        int32_t *cg_iters, int32_t *cg_end, int32_t *accepted, int32_t *round_active, int32_t *n_rounds, int64_t *stats16);
 /* Measurement / test switches of a handle.  They are read from the environment once, by vsm_create (VSM_SEQ_V2,
  * VSM_SEQ_CHUNK, VSM_SEQ_DC_STREAMS, VSM_SEQ_SERIAL, VSM_SEQ_GPU_SORTS, VSM_SEQ_EARLY_EXPORT, VSM_FUSED_KEYS); this call changes one
  * afterwards: name = the variable's name without the VSM_ prefix, in lower case ("seq_serial", "seq_chunk", ...).

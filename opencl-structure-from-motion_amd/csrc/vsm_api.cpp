@@ -32,6 +32,7 @@
 #include "vsm_tracks.h"
 #include "vsm_points.h"
 #include "vsm_resect.h"
+#include "vsm_ba.h"
 #include "vsm_vet.h"
 #include "vsm_motions.h"
 
@@ -471,6 +472,7 @@ struct VsmSwitches {
   int fused_keys = 1;        // VSM_FUSED_KEYS: the batched forms' compactions write the Delaunay chains' keys with the lists and the chains' job tables are uploaded ahead of the
                              // matching launch (1), or every chain starts with
                              // its job table's upload and k_dc2_keys behind the compaction (0); refinement = 2 always takes 0
+  int adjust_fixed = 0;      // vsm_adjust_run / vsm_points_adjust: every launch of max_rounds rounds enqueued at once (1) or a wait per round on the control block (0; profiles/README.md)
   int filter_planes = 0;     // vsm_push_back keeps f1 / f2 in HBM for vsm_get_filter_responses (the fused tiles write them on the side)
   static int env_int(const char *name, int dflt) {
     const char *e = getenv(name);
@@ -523,6 +525,7 @@ struct VsmSwitches {
     else if (!strcmp(name, "multi_shared_ego")) multi_shared_ego = v;
     else if (!strcmp(name, "pairs_chunk")) pairs_chunk = std::max(0, v);
     else if (!strcmp(name, "motions_chunk")) motions_chunk = std::max(0, v);
+    else if (!strcmp(name, "adjust_fixed")) adjust_fixed = v != 0;
     else return false;
     return true;
   }
@@ -592,6 +595,7 @@ struct vsm_handle {
   struct VsmPoints *points = nullptr;  // track triangulation (vsm_points.inc): staging, device block, last result
   struct VsmResect *resect = nullptr;  // pose refinement against the points (vsm_resect.inc): staging, device block, last result
   struct VsmVet *vet = nullptr;        // vetting of observations (vsm_vet.inc): staging, device block, last result
+  struct VsmAdjust *adjust = nullptr;  // joint adjustment of poses and points (vsm_ba.inc): staging, device block, last result
   struct VsmMotions *motions = nullptr;  // monocular pair motions (vsm_motions_api.inc): staging, device block, last result
   struct VsmTracks *tracks = nullptr;  // feature tracks from pair match lists (vsm_tracks.inc): staging, device block, last result
 
@@ -627,6 +631,7 @@ static void tracks_destroy(vsm_handle *h);  // vsm_tracks.inc
 static void points_destroy(vsm_handle *h);  // vsm_points.inc
 static void resect_destroy(vsm_handle *h);  // vsm_resect.inc
 static void vet_destroy(vsm_handle *h);     // vsm_vet.inc
+static void adjust_destroy(vsm_handle *h);  // vsm_ba.inc
 static void motions_destroy(vsm_handle *h);  // vsm_motions_api.inc
 
 extern "C" {
@@ -722,6 +727,7 @@ void vsm_destroy(vsm_handle *h) {
   points_destroy(h);
   resect_destroy(h);
   vet_destroy(h);
+  adjust_destroy(h);
   motions_destroy(h);
   ctx_destroy(h->ring);
   ctx_destroy(h->seq);
@@ -1213,6 +1219,7 @@ static int seq_ingest_host_frames(vsm_handle *h, VsmCtx &c, int first_img, const
 #include "vsm_points.inc"
 #include "vsm_resect.inc"
 #include "vsm_vet.inc"
+#include "vsm_ba.inc"
 #include "vsm_motions_api.inc"
 extern "C" {
 
@@ -1427,7 +1434,9 @@ static const char *kKernelNames[VSM_K_COUNT] = {
     "k_dc_keys", "k_dc_vertex_sort", "k_dc_prepare_kd_order", "k_dc_block", "k_dc_merge", "k_dc_support", "k_dc_compact", "k_dc_prior",
     "k_feat_dense", "k_feat_sparse", "k_feat_scan", "k_feat_order", "k_parabolic_apply",
     "k_trk_init", "k_trk_hook", "k_trk_flatten", "k_trk_keep", "k_trk_scan_reduce", "k_trk_scan_top", "k_trk_scan_apply", "k_trk_match_tracks", "k_trk_fill",
-    "k_trk_order_wave", "k_trk_order_block", "k_pts_triangulate", "k_rs_resect", "k_vet_obs", "k_vet_emit"};
+    "k_trk_order_wave", "k_trk_order_block", "k_pts_triangulate", "k_rs_resect", "k_vet_obs", "k_vet_emit",
+    "k_ba_init", "k_ba_linearise", "k_ba_tracks", "k_ba_frames<rhs>", "k_ba_cg_init", "k_ba_op_tracks", "k_ba_frames<op>", "k_ba_cg_step", "k_ba_back",
+    "k_ba_trial_cost", "k_ba_decide", "k_ba_commit", "k_ba_finish"};
 
 void vsm_set_profiling(vsm_handle *h, int on) {
   h->prof.on = on != 0;

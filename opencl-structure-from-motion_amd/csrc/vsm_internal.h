@@ -117,6 +117,9 @@ enum VsmKernelId {
   VSM_K_RS_RESECT,
   // vetting of observations (vsm_vet.hip)
   VSM_K_VET_OBS, VSM_K_VET_EMIT,
+  // joint adjustment of poses and points (vsm_ba.hip)
+  VSM_K_BA_INIT, VSM_K_BA_LINEARISE, VSM_K_BA_TRACKS, VSM_K_BA_RHS, VSM_K_BA_CG_INIT, VSM_K_BA_OP_TRACKS, VSM_K_BA_OP_FRAMES, VSM_K_BA_CG_STEP, VSM_K_BA_BACK,
+  VSM_K_BA_TRIAL_COST, VSM_K_BA_DECIDE, VSM_K_BA_COMMIT, VSM_K_BA_FINISH,
   VSM_K_COUNT
 };
 struct VsmProf {

@@ -8,6 +8,7 @@
 #include "vsm_points.h"
 #include "vsm_resect.h"
 #include "vsm_vet.h"
+#include "vsm_ba.h"
 
 // vsm_points.inc: F frames, T tracks, N observations
 struct PtsBlocks : VsmBlocks {
@@ -58,6 +59,30 @@ struct VetBlocks : VsmBlocks {
     totals.place(out, 2, 0);
     VsmLayout work = out;
     scan.place(work, 2 * T, 8); scan_part.place(work, 2 * trk_scan_part_items((int64_t)T), 8);
+    out_behind_in(work.at);
+  }
+};
+
+// vsm_ba.inc: F frames, T tracks, R rows, N observations, M rounds at the most; the state, the round's linearisation and the
+// conjugate gradient's vectors lie behind the results and are not copied back
+struct BaBlocks : VsmBlocks {
+  VsmIn<double> poses, xyz;
+  VsmIn<uint8_t> valid, refine, use;
+  VsmIn<int32_t> row_off, offsets, obs_frames;
+  VsmIn<BaRow> rows;
+  VsmOut<int32_t> fstatus, factive, tstatus, hist_i, cnt, tbehind;
+  VsmOut<double> out_poses, out_xyz, hist_d, state, trial_state, trial_X, lin, usum, ud, uinv, vinv, gp, zt, cg, tcost;
+  VsmOut<uint8_t> active, ffree, tfree, moved;
+  VsmOut<BaCtl> ctl;
+  BaBlocks(size_t F, size_t T, size_t R, size_t N, size_t M) {
+    poses.place(in, 12 * F, 8); valid.place(in, F, 1); refine.place(in, F, 1); use.place(in, T, 1); row_off.place(in, F + 1, 0); rows.place(in, R, 16);
+    offsets.place(in, T + 1, 0); obs_frames.place(in, N, 4); xyz.place(in, 3 * T, 8);
+    fstatus.place(out, F, 4); factive.place(out, F, 4); tstatus.place(out, T, 4); out_poses.place(out, 12 * F, 8); out_xyz.place(out, 3 * T, 8);
+    hist_d.place(out, 3 * M, 8); hist_i.place(out, 4 * M, 4); ctl.place(out, 1, 0);
+    VsmLayout work = out;
+    state.place(work, 12 * F, 8); trial_state.place(work, 12 * F, 8); trial_X.place(work, 3 * T, 8); active.place(work, N, 1); lin.place(work, BA_LIN * N, 8);
+    usum.place(work, RS_SUMS * F, 8); cnt.place(work, F, 4); ud.place(work, 36 * F, 8); uinv.place(work, 36 * F, 8); vinv.place(work, 9 * T, 8); gp.place(work, 3 * T, 8); zt.place(work, 3 * T, 8);
+    ffree.place(work, F, 1); tfree.place(work, T, 1); moved.place(work, F, 1); cg.place(work, 36 * F, 8); tcost.place(work, F, 8); tbehind.place(work, F, 4);
     out_behind_in(work.at);
   }
 };

@@ -87,22 +87,11 @@ VSM_HD inline void rs_add_row(Acc acc, const double *ju, const double *jv, const
   acc[27] += t;
 }
 
-// From an evaluation's sums to the next state: the 6x6 system into ab (36 + 6 doubles of work space), vsm_la::solve6,
-// and with delta = (w, tau), a = w / 2: Rd = ((1 - a.a) I + 2 a a^T + 2 [a]x) / (1 + a.a), Rw <- Rd Rw, tw <- Rd tw + tau,
-// every product summed over k ascending from the k = 0 product.  RS_NO_PIVOT: S is untouched.  RS_CONVERGED: all six
-// |delta| <= eps (the state has moved by that last delta).
-template <class Sums, class W, class M>
-VSM_HD inline int rs_step(Sums sums, W ab, M S, double eps) {
-  int k = 0;
-  for (int m = 0; m < 6; m++)
-    for (int c = m; c < 6; c++, k++) {
-      ab[m * 6 + c] = sums[k];
-      ab[c * 6 + m] = sums[k];
-    }
-  for (int m = 0; m < 6; m++) ab[36 + m] = sums[21 + m];
-  if (!vsm_la::solve6(ab, ab + 36)) return RS_NO_PIVOT;
-  double d[6];
-  for (int m = 0; m < 6; m++) d[m] = ab[36 + m];
+// The update half of rs_step, which the joint adjustment (vsm_ba.h) takes its trial poses from: with delta d = (w, tau), a =
+// w / 2: Rd = ((1 - a.a) I + 2 a a^T + 2 [a]x) / (1 + a.a), Rw <- Rd Rw, tw <- Rd tw + tau, every product summed over k
+// ascending from the k = 0 product.
+template <class M>
+VSM_HD inline void rs_move(M S, const double *d) {
   const double a0 = 0.5 * d[0], a1 = 0.5 * d[1], a2 = 0.5 * d[2];
   const double aa = a0 * a0 + a1 * a1 + a2 * a2, den = 1.0 + aa, one = 1.0 - aa;
   double Rd[9];
@@ -126,6 +115,24 @@ VSM_HD inline int rs_step(Sums sums, W ab, M S, double eps) {
     N[i * 4 + 3] = N[i * 4 + 3] + d[3 + i];
   }
   for (int i = 0; i < 12; i++) S[i] = N[i];
+}
+
+// From an evaluation's sums to the next state: the 6x6 system into ab (36 + 6 doubles of work space), vsm_la::solve6,
+// and rs_move by the solution delta.  RS_NO_PIVOT: S is untouched.  RS_CONVERGED: all six |delta| <= eps (the state has
+// moved by that last delta).
+template <class Sums, class W, class M>
+VSM_HD inline int rs_step(Sums sums, W ab, M S, double eps) {
+  int k = 0;
+  for (int m = 0; m < 6; m++)
+    for (int c = m; c < 6; c++, k++) {
+      ab[m * 6 + c] = sums[k];
+      ab[c * 6 + m] = sums[k];
+    }
+  for (int m = 0; m < 6; m++) ab[36 + m] = sums[21 + m];
+  if (!vsm_la::solve6(ab, ab + 36)) return RS_NO_PIVOT;
+  double d[6];
+  for (int m = 0; m < 6; m++) d[m] = ab[36 + m];
+  rs_move(S, d);
   for (int m = 0; m < 6; m++)
     if (!(fabs(d[m]) <= eps)) return RS_UPDATED;
   return RS_CONVERGED;

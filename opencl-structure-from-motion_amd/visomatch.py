@@ -46,7 +46,9 @@ EXPORTS = ["vsm_default_params", "vsm_create", "vsm_destroy", "vsm_set_intrinsic
            "vsm_resect_default_params", "vsm_resect_run", "vsm_points_resect", "vsm_resect_count", "vsm_resect_get", "vsm_resect_get_stats",
            "vsm_resect_get_timings", "vsm_host_resect",
            "vsm_vet_default_params", "vsm_vet_run", "vsm_points_vet", "vsm_vet_count", "vsm_vet_get_obs", "vsm_vet_get_tracks", "vsm_vet_get_frames",
-           "vsm_vet_get_kept", "vsm_vet_get_stats", "vsm_vet_get_timings", "vsm_host_vet", "vsm_tracks_pixels", "vsm_set_option", "vsm_version", "vsm_host_register", "vsm_host_unregister",
+           "vsm_vet_get_kept", "vsm_vet_get_stats", "vsm_vet_get_timings", "vsm_host_vet", "vsm_tracks_pixels",
+           "vsm_adjust_default_params", "vsm_adjust_run", "vsm_points_adjust", "vsm_adjust_count", "vsm_adjust_get_frames", "vsm_adjust_get_tracks",
+           "vsm_adjust_get_history", "vsm_adjust_get_stats", "vsm_adjust_get_timings", "vsm_host_adjust", "vsm_set_option", "vsm_version", "vsm_host_register", "vsm_host_unregister",
            "vsm_multi_create", "vsm_multi_destroy", "vsm_multi_process", "vsm_multi_num_sequences", "vsm_multi_get_motion",
            "vsm_multi_motion_valid", "vsm_multi_num_matches", "vsm_multi_get_matches", "vsm_multi_num_inliers", "vsm_multi_get_inliers",
            "vsm_multi_get_timings",
@@ -95,6 +97,12 @@ class VsmResectParams(C.Structure):
 
 class VsmVetParams(C.Structure):
     _fields_ = [("max_residual", C.c_double), ("min_depth", C.c_double), ("min_observations", C.c_int32)]
+
+
+class VsmAdjustParams(C.Structure):
+    _fields_ = [("min_observations", C.c_int32), ("min_track_observations", C.c_int32), ("max_rounds", C.c_int32), ("cg_iters", C.c_int32),
+                ("lambda0", C.c_double), ("lambda_min", C.c_double), ("lambda_max", C.c_double), ("cg_tol", C.c_double), ("ftol", C.c_double),
+                ("max_residual", C.c_double), ("min_depth", C.c_double)]
 
 
 def host_register(arr):
@@ -244,6 +252,21 @@ def lib():
         L.vsm_resect_get_stats.restype = None
         L.vsm_resect_get_timings.argtypes = [vp, vp]
         L.vsm_resect_get_timings.restype = None
+        L.vsm_adjust_default_params.argtypes = [C.POINTER(VsmAdjustParams)]
+        L.vsm_adjust_default_params.restype = None
+        L.vsm_adjust_run.argtypes = [vp, i32, vp, vp, vp, f64, f64, f64, i32, vp, vp, vp, vp, vp, C.POINTER(VsmAdjustParams)]
+        L.vsm_points_adjust.argtypes = [vp, vp, vp, vp, vp, vp, f64, f64, f64, C.POINTER(VsmAdjustParams)]
+        L.vsm_adjust_count.argtypes = [vp, vp, vp, vp]
+        L.vsm_adjust_count.restype = None
+        L.vsm_adjust_get_frames.argtypes = [vp] + [vp] * 4
+        L.vsm_adjust_get_tracks.argtypes = [vp] + [vp] * 2
+        L.vsm_adjust_get_history.argtypes = [vp] + [vp] * 7
+        L.vsm_adjust_get_stats.argtypes = [vp, vp]
+        L.vsm_adjust_get_stats.restype = None
+        L.vsm_adjust_get_timings.argtypes = [vp, vp]
+        L.vsm_adjust_get_timings.restype = None
+        L.vsm_host_adjust.restype = i32
+        L.vsm_host_adjust.argtypes = [i32, vp, vp, vp, f64, f64, f64, i32, vp, vp, vp, vp, vp, C.POINTER(VsmAdjustParams)] + [vp] * 15
         L.vsm_host_resect.restype = i32
         L.vsm_host_resect.argtypes = [i32, vp, vp, vp, f64, f64, f64, i32, vp, vp, vp, vp, vp, C.POINTER(VsmResectParams)] + [vp] * 9
         L.vsm_vet_default_params.argtypes = [C.POINTER(VsmVetParams)]
@@ -956,6 +979,70 @@ def host_vet(poses, f, cu, cv, offsets, obs_frames, uv, xyz, use=None, pose_vali
     return Vetting(*out[:-1], out[-1][:n_kept.value].copy())
 
 
+ADJUST_FRAME_STATUS = ("free", "no_pose", "not_asked", "too_few_rows", "unused_4", "unused_5", "unused_6", "held")
+ADJUST_TRACK_STATUS = ("free", "unused", "too_few_active", "no_pivot")
+ADJUST_STATS = (tuple("frames_" + s for s in ADJUST_FRAME_STATUS) + tuple("tracks_" + s for s in ADJUST_TRACK_STATUS)
+                + ("rounds", "rounds_accepted", "stop", "cg_iterations"))
+ADJUST_STOP = ("", "ftol", "lambda_max", "max_rounds")
+ADJUST_CG_END = ("", "converged", "breakdown", "cg_iters")
+ADJUST_TIMINGS = ("group_us", "upload_us", "kernels_us", "download_host_us")
+ADJUST_HISTORY = np.dtype([("cost_before", "<f8"), ("cost_after", "<f8"), ("lambda", "<f8"), ("cg_iters", "<i4"), ("cg_end", "<i4"), ("accepted", "<i4"),
+                           ("active", "<i4")])
+
+
+class Adjustment:
+    """jointly adjusted poses and points (include/visomatch.h, vsm_adjust_run): per frame frame_status [F] int32 (0 = free in the
+    last round, ADJUST_FRAME_STATUS names the values), poses [F, 12] float64 camera to world, rows, active [F] int32; per track
+    track_status [T] int32 (ADJUST_TRACK_STATUS) and xyz [T, 3] float64; history: one ADJUST_HISTORY record per round run;
+    stats: dict by ADJUST_STATS; timings: dict (empty for the host view)."""
+
+    def __init__(self, frame_status, poses, rows, active, track_status, xyz, history, stats, timings=None):
+        self.frame_status, self.poses, self.rows, self.active = frame_status, poses, rows, active
+        self.track_status, self.xyz, self.history = track_status, xyz, history
+        self.stats, self.timings = stats, timings or {}
+
+    def __len__(self):
+        return len(self.frame_status)
+
+    @property
+    def cost(self):
+        """the cost after the last round (0.0 without a round)"""
+        return float(self.history["cost_after"][-1]) if len(self.history) else 0.0
+
+
+def adjust_params(**kw):
+    """vsm_adjust_default_params with fields overridden by keyword"""
+    return _default_params(VsmAdjustParams, "vsm_adjust_default_params", kw)
+
+
+def _adjust_arrays(F, T, rounds):
+    return ([np.zeros(F, np.int32), np.zeros((F, 12), np.float64), np.zeros(F, np.int32), np.zeros(F, np.int32)],
+            [np.zeros(T, np.int32), np.zeros((T, 3), np.float64)],
+            [np.zeros(rounds, np.float64) for _ in range(3)] + [np.zeros(rounds, np.int32) for _ in range(4)])
+
+
+def _adjust_history(cols, n):
+    h = np.zeros(n, ADJUST_HISTORY)
+    for name, c in zip(ADJUST_HISTORY.names, cols):
+        h[name] = c[:n]
+    return h
+
+
+def host_adjust(poses, f, cu, cv, offsets, obs_frames, uv, xyz, use=None, refine=None, pose_valid=None, params=None, n_tracks=None):
+    """vsm_host_adjust: poses and points adjusted jointly on one host thread - no GPU.  Arguments as for host_resect; params: a
+    dict of vsm_adjust_params fields or the struct.  Returns an Adjustment object; raises VisoMatchError on VSM_EARG."""
+    po, pv, rf, off, fr, px, pt, us = _resect_inputs(poses, pose_valid, refine, offsets, obs_frames, uv, xyz, use)
+    T = _n_tracks(off, n_tracks)
+    ref = _params_ref(VsmAdjustParams, adjust_params, params)
+    rounds = max(int(ref._obj.max_rounds), 0) if ref is not None else 0
+    fa, ta, ha = _adjust_arrays(len(po), max(T, 0), rounds)
+    n, stats = C.c_int32(0), np.zeros(16, np.int64)
+    got = _check(lib().vsm_host_adjust(len(po), _ptr(po), _ptr(pv), _ptr(rf), float(f), float(cu), float(cv), T, _ptr(off), _ptr(fr), _ptr(px), _ptr(pt),
+                                       _ptr(us), ref, *[_ptr(a) for a in fa + ta + ha], C.byref(n), _ptr(stats)), "vsm_host_adjust")
+    assert got == len(po)
+    return Adjustment(*fa, *ta, _adjust_history(ha, n.value), dict(zip(ADJUST_STATS, stats.tolist())))
+
+
 _NO_PARAMS = object()  # params=_NO_PARAMS: a NULL params pointer (argument tests)
 
 
@@ -1457,6 +1544,37 @@ class Matcher:
         rc = lib().vsm_points_vet(self.h, ptrs, _ptr(cnt), _ptr(po), _ptr(pv), float(f), float(cu), float(cv),
                                   _params_ref(VsmVetParams, vet_params, params))
         return self._vet_result(rc, "vsm_points_vet")
+
+    # --- poses and points adjusted jointly ----------------------------------------------------------
+    def _adjust_result(self, rc, what):
+        L = lib()
+        _check(rc, what)
+        F, T, n = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        L.vsm_adjust_count(self.h, C.byref(F), C.byref(T), C.byref(n))
+        fa, ta, ha = _adjust_arrays(F.value, T.value, n.value)
+        L.vsm_adjust_get_frames(self.h, *[_ptr(a) for a in fa])
+        L.vsm_adjust_get_tracks(self.h, *[_ptr(a) for a in ta])
+        L.vsm_adjust_get_history(self.h, *[_ptr(a) for a in ha])
+        return Adjustment(*fa, *ta, _adjust_history(ha, n.value), *_stage_dicts(self.h, L.vsm_adjust_get_stats, ADJUST_STATS, L.vsm_adjust_get_timings, ADJUST_TIMINGS))
+
+    def adjust(self, poses, f, cu, cv, offsets, obs_frames, uv, xyz, use=None, refine=None, pose_valid=None, params=None, n_tracks=None):
+        """vsm_adjust_run: poses and points adjusted jointly, on the device.  Arguments as for resect; params: a dict of
+        vsm_adjust_params fields or the struct.  Returns an Adjustment object."""
+        po, pv, rf, off, fr, px, pt, us = _resect_inputs(poses, pose_valid, refine, offsets, obs_frames, uv, xyz, use)
+        T = _n_tracks(off, n_tracks)
+        rc = lib().vsm_adjust_run(self.h, len(po), _ptr(po), _ptr(pv), _ptr(rf), float(f), float(cu), float(cv), T, _ptr(off), _ptr(fr), _ptr(px), _ptr(pt),
+                                  _ptr(us), _params_ref(VsmAdjustParams, adjust_params, params))
+        return self._adjust_result(rc, "vsm_adjust_run")
+
+    def adjust_points(self, poses, f, cu, cv, lists=None, refine=None, pose_valid=None, params=None, counts=None):
+        """vsm_points_adjust: the same on the handle's last track and point results (the kept points; lists as for
+        track_points)."""
+        po, pv = _pose_inputs(poses, pose_valid, self._track_frames)
+        rf = _mask(refine, len(po))
+        ls, ptrs, cnt = _optional_lists(lists, counts)
+        rc = lib().vsm_points_adjust(self.h, ptrs, _ptr(cnt), _ptr(po), _ptr(pv), _ptr(rf), float(f), float(cu), float(cv),
+                                     _params_ref(VsmAdjustParams, adjust_params, params))
+        return self._adjust_result(rc, "vsm_points_adjust")
 
     def track_pixels(self, lists=None, counts=None):
         """vsm_tracks_pixels: (obs_frames [n_obs] int32, uv [n_obs, 2] float32) of the handle's last track result, the pixels

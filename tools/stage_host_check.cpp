@@ -1,7 +1,7 @@
 // Stand-alone host check of the block layout the staged calls share (csrc/vsm_stage.h, VsmLayout): the offsets of a handful of
 // take() sequences against the 256-alignment arithmetic written out by hand - sizes 0, 1, 255, 256, 257 and a block of
-// 5 GB, which a 32-bit offset would not survive.  Then the four stages' blocks (csrc/vsm_layouts.h: tracks, points,
-// resection, vetting): every array's offset, in.at, out.at and the device block's size against the sequence of sizes the
+// 5 GB, which a 32-bit offset would not survive.  Then the five stages' blocks (csrc/vsm_layouts.h: tracks, points,
+// resection, vetting, joint adjustment): every array's offset, in.at, out.at and the device block's size against the sequence of sizes the
 // calls stated by hand before the arrays were typed, for every combination of the counts 0, 1, 5 and 257 and for an
 // observation count whose arrays pass 2^31 bytes.  No HIP call is made (the header's staging functions are not
 // instantiated here).  Meant to be built with the sanitizers, e.g.
@@ -93,6 +93,50 @@ static void check_vet(size_t F, size_t T, size_t N) {
   CHECK(L.code.n == N && L.frame_counts.n == 3 * F && L.kept_offsets.n == T + 1 && L.kept_index.n == N);
 }
 
+// F frames, T tracks, R rows, N observations, M rounds
+static void check_adjust(size_t F, size_t T, size_t R, size_t N, size_t M) {
+  const BaBlocks L(F, T, R, N, M);
+  VsmLayout in, out;
+  SAME(L.poses, in, F * 96 + 8);
+  SAME(L.valid, in, F + 1);
+  SAME(L.refine, in, F + 1);
+  SAME(L.use, in, T + 1);
+  SAME(L.row_off, in, (F + 1) * 4);
+  SAME(L.rows, in, R * 16 + 16);
+  SAME(L.offsets, in, (T + 1) * 4);
+  SAME(L.obs_frames, in, N * 4 + 4);
+  SAME(L.xyz, in, T * 24 + 8);
+  SAME(L.fstatus, out, F * 4 + 4);
+  SAME(L.factive, out, F * 4 + 4);
+  SAME(L.tstatus, out, T * 4 + 4);
+  SAME(L.out_poses, out, F * 96 + 8);
+  SAME(L.out_xyz, out, T * 24 + 8);
+  SAME(L.hist_d, out, M * 24 + 8);
+  SAME(L.hist_i, out, M * 16 + 4);
+  SAME(L.ctl, out, sizeof(BaCtl));
+  VsmLayout work = out;  // behind the results, not copied back
+  SAME(L.state, work, F * 96 + 8);
+  SAME(L.trial_state, work, F * 96 + 8);
+  SAME(L.trial_X, work, T * 24 + 8);
+  SAME(L.active, work, N + 1);
+  SAME(L.lin, work, N * 208 + 8);
+  SAME(L.usum, work, F * 224 + 8);
+  SAME(L.cnt, work, F * 4 + 4);
+  SAME(L.ud, work, F * 288 + 8);
+  SAME(L.uinv, work, F * 288 + 8);
+  SAME(L.vinv, work, T * 72 + 8);
+  SAME(L.gp, work, T * 24 + 8);
+  SAME(L.zt, work, T * 24 + 8);
+  SAME(L.ffree, work, F + 1);
+  SAME(L.tfree, work, T + 1);
+  SAME(L.moved, work, F + 1);
+  SAME(L.cg, work, F * 288 + 8);
+  SAME(L.tcost, work, F * 8 + 8);
+  SAME(L.tbehind, work, F * 4 + 4);
+  CHECK(L.in.at == in.at && L.out.at == out.at && L.out_at == al256(in.at) && L.dev_bytes == al256(in.at) + work.at);
+  CHECK(sizeof(BaRow) == 16 && sizeof(BaCtl) == 80 && L.lin.n == 26 * N && L.cg.n == 36 * F && L.hist_d.n == 3 * M && L.ctl.n == 1);
+}
+
 // P pairs, F frames, E matches; then N nodes; then the totals the device reports
 static void check_tracks(size_t P, size_t F, size_t E, size_t N, size_t n_tracks, size_t n_obs) {
   TrkBlocks L(P, F, E);
@@ -174,11 +218,13 @@ int main() {
           check_points(a, b, c);
           check_resect(a, b, c);
           check_vet(a, b, c);
+          for (size_t n : counts) check_adjust(a, b, c, c + n, n + 1);
           for (size_t n : counts) check_tracks(a, b, c, n, std::min(n, b), n);
         }
     check_points(5, 257, big);
     check_resect(5, 257, big);
     check_vet(5, 257, big);
+    check_adjust(5, 257, big / 2, big, 10);
     check_tracks(5, 257, big, big, 257, big);
   }
   if (fails) return 1;
