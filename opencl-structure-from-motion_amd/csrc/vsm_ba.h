@@ -533,23 +533,14 @@ inline void ba_schedule(Ops &o, const vsm_adjust_params &prm) {
 }
 
 // ---- host side (vsm_ba_host.cpp; no HIP) ----
-bool ba_params_ok(const vsm_adjust_params *params);
-int64_t ba_check_args(int32_t n_frames, const double *poses, int32_t n_tracks, const int32_t *offsets, const int32_t *obs_frames, const float *uv,
-                      const double *xyz, const vsm_adjust_params *params);
-// the rows by frame, rs_group_fill's order with the observation's index in the row
-template <class FrameOf, class PixelOf>
-inline void ba_group_fill(int32_t t0, int32_t t1, const int32_t *offsets, const uint8_t *use, FrameOf frame_of, PixelOf pixel_of, int32_t *at, BaRow *rows) {
-  for (int32_t t = t0; t < t1; t++)
-    if (!use || use[t])
-      for (int32_t i = offsets[t]; i < offsets[t + 1]; i++) {
-        BaRow &r = rows[at[frame_of(i)]++];
-        r.track = t;
-        r.obs = i;
-        pixel_of(i, &r.u, &r.v);
-      }
-}
+bool ba_params_ok(const vsm_adjust_params *params);  // the test of the parameters (the arguments: pts_check_points)
+// the rows by frame are the resection's (RsGroup, vsm_resect.h), with the observation's index in the row
+inline void row_set(BaRow &r, int32_t t, int32_t i) { r.track = t, r.obs = i; }
 // the 16 stats from the results (include/visomatch.h)
 void ba_stats(int32_t n_frames, const int32_t *fstatus, int32_t n_tracks, const int32_t *tstatus, const BaCtl &ctl, int64_t *out16);
+// the rounds' history from hist_d [rounds][3] and hist_i [rounds][4] into the seven columns a caller wants
+void ba_history(int32_t rounds, const double *hist_d, const int32_t *hist_i, double *cost_before, double *cost_after, double *lambda, int32_t *cg_iters,
+                int32_t *cg_end, int32_t *accepted, int32_t *active);
 
 // ---- device path (vsm_ba.hip) ----
 #ifdef __HIP__

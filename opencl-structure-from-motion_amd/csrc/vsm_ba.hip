@@ -10,7 +10,7 @@
 // No atomics on doubles, no cooperative launch, no graph: the stream's order is the only synchronisation between kernels.
 // Every kernel reads the control block first and returns when the call, or the round's solve, is over; the flags are
 // uniform in the grid, so all barriers stay in uniform control flow.  All indices are bounded by the counts the host packed:
-// a row's track < n_tracks and obs < n_obs by construction (ba_group_fill), an observation's frame < n_frames by the argument
+// a row's track < n_tracks and obs < n_obs by construction (rs_group_fill), an observation's frame < n_frames by the argument
 // checks.
 #include "vsm_internal.h"
 #include "vsm_ba.h"

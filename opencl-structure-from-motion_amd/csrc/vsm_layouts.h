@@ -1,6 +1,8 @@
 // The blocks of the staged calls: per stage one struct that declares every array once - its element
 // type - and places it once - its count and the spare bytes behind it -, as a pure function of the call's counts.  No HIP
-// call is made here, so tools/stage_host_check.cpp checks the offsets on the CPU.  vsm_stage.h has the arrays' views.
+// call is made here, so tools/stage_host_check.cpp checks the offsets on the CPU.  vsm_stage.h has the arrays' views.  The
+// joint adjustment's blocks also write their uploaded block (pack) and assign BaData (bind), for the device path and the host
+// view alike.
 #pragma once
 
 #include "vsm_stage.h"
@@ -84,6 +86,37 @@ struct BaBlocks : VsmBlocks {
     usum.place(work, RS_SUMS * F, 8); cnt.place(work, F, 4); ud.place(work, 36 * F, 8); uinv.place(work, 36 * F, 8); vinv.place(work, 9 * T, 8); gp.place(work, 3 * T, 8); zt.place(work, 3 * T, 8);
     ffree.place(work, F, 1); tfree.place(work, T, 1); moved.place(work, F, 1); cg.place(work, 36 * F, 8); tcost.place(work, F, 8); tbehind.place(work, F, 4);
     out_behind_in(work.at);
+  }
+  // The uploaded block written at `block` (the pinned input; the host view's buffer).  G is the grouping whose counts sized
+  // this layout (RsGroup, vsm_resect.h): it has the tracks, their use mask and the observation source, and fills the rows.
+  template <class Group>
+  void pack(uint8_t *block, const double *poses_, const uint8_t *pose_valid, const uint8_t *refine_, Group &G, const double *xyz_) const {
+    const size_t F = valid.n, T = use.n;
+    if (F > 0) memcpy(poses.in(block), poses_, F * 96);
+    vsm_mask_bytes(pose_valid, F, valid.in(block)); vsm_mask_bytes(refine_, F, refine.in(block)); vsm_mask_bytes(G.use, T, use.in(block));
+    memcpy(row_off.in(block), G.row_off.data(), (F + 1) * 4);
+    G.fill(rows.in(block));
+    offsets.in(block)[0] = 0;
+    if (T > 0) memcpy(offsets.in(block), G.offsets, (T + 1) * 4), memcpy(xyz.in(block), xyz_, T * 24);
+    for (size_t i = 0; i < obs_frames.n; i++) obs_frames.in(block)[i] = G.obs.frame_of((int32_t)i);
+  }
+  // BaData, assigned here and nowhere else: the uploaded arrays in the block at in_block, the results and the working set
+  // in the block at out_block (the device path: S.dev and S.dev + out_at; the host view: the same two places of its buffer)
+  BaData bind(uint8_t *in_block, uint8_t *out_block, double f, double cu, double cv, const vsm_adjust_params &prm) const {
+    uint8_t *const i = in_block, *const o = out_block;
+    const size_t F6 = cg.n / 6;
+    BaData d;
+    memset(&d, 0, sizeof(d));
+    d.poses = poses.in(i); d.valid = valid.in(i); d.refine = refine.in(i); d.use = use.in(i); d.row_off = row_off.in(i); d.rows = rows.in(i);
+    d.offsets = offsets.in(i); d.obs_frames = obs_frames.in(i); d.xyz_in = xyz.in(i);
+    d.state = state.in(o); d.trial_state = trial_state.in(o); d.trial_X = trial_X.in(o); d.active = active.in(o); d.lin = lin.in(o); d.usum = usum.in(o);
+    d.cnt = cnt.in(o); d.ud = ud.in(o); d.uinv = uinv.in(o); d.vinv = vinv.in(o); d.gp = gp.in(o); d.zt = zt.in(o);
+    d.ffree = ffree.in(o); d.tfree = tfree.in(o); d.moved = moved.in(o); d.tcost = tcost.in(o); d.tbehind = tbehind.in(o); d.ctl = ctl.in(o);
+    d.b = cg.in(o); d.x = d.b + F6; d.r = d.x + F6; d.z = d.r + F6; d.p = d.z + F6; d.q = d.p + F6;
+    d.fstatus = fstatus.in(o); d.factive = factive.in(o); d.tstatus = tstatus.in(o); d.out_poses = out_poses.in(o); d.out_xyz = out_xyz.in(o);
+    d.hist_d = hist_d.in(o); d.hist_i = hist_i.in(o);
+    d.f = f; d.cu = cu; d.cv = cv; d.prm = prm; d.n_frames = (int32_t)valid.n; d.n_tracks = (int32_t)use.n;
+    return d;
   }
 };
 

@@ -209,6 +209,10 @@ int64_t pts_check_args(int32_t n_frames, const double *poses, int32_t n_tracks, 
                        const vsm_triangulate_params *params);
 // its part without the parameters, which the resection and the vetting share: the frames, the offsets and the observations
 int64_t pts_check_obs(int32_t n_frames, const double *poses, int32_t n_tracks, const int32_t *offsets, const int32_t *obs_frames, const float *uv);
+// the argument checks of the general forms that take points (resection, vetting, joint adjustment) and of their host views:
+// the stage's own test of its parameters has passed, tracks come with their points, then pts_check_obs
+int64_t pts_check_points(bool params_ok, int32_t n_frames, const double *poses, int32_t n_tracks, const int32_t *offsets, const int32_t *obs_frames,
+                         const float *uv, const double *xyz);
 // rows 0..2 of Tr_cam_road (Reconstruction::setCalibration), with libm's sin and cos
 void pts_road(double cam_pitch, double cam_height, double *road12);
 // the last step, which needs libm: the angle from the ray value, status 9 where it is not above min_angle

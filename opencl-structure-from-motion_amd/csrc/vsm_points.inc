@@ -6,7 +6,8 @@
 // bytes per observation) and the flags; one copy up, one kernel, one copy back (52 bytes per track); then libm's acos on the
 // ray values, which decides status 9.  vsm_tracks_triangulate fills the same block from the handle's last track result,
 // reading every observation's pixel from the match it names.  Blocks: PtsBlocks (vsm_layouts.h); round trip, result record,
-// keep and getters' copies: vsm_stage.h.  The handle forms' prologue (TracksInput) and the pixels' gathering live here.
+// keep and getters' copies: vsm_stage.h.  The handle forms' prologue (TracksInput), their observations as a source for the
+// grouping (TracksObs) and the pixels' gathering live here.
 struct VsmPoints : VsmResult<10> {  // the staging and the last result's stats and timings (vsm_stage.h)
   std::vector<int32_t> status, type, updates;
   std::vector<double> xyz, dist, angle;
@@ -27,10 +28,8 @@ static int points_run(vsm_handle *h, double t0, int32_t n_frames, const double *
   HIPCHK(S.grow_in(L.in.at, h->stream));
   HIPCHK(S.grow_out(L.out.at, h->stream));
   // ---- pack ----
-  for (int32_t k = 0; k < n_frames; k++) {
-    pts_frame(poses + 12 * (size_t)k, f, cu, cv, L.frames.host(S) + k);
-    L.valid.host(S)[k] = (!pose_valid || pose_valid[k]) ? 1 : 0;
-  }
+  for (int32_t k = 0; k < n_frames; k++) pts_frame(poses + 12 * (size_t)k, f, cu, cv, L.frames.host(S) + k);
+  vsm_mask_bytes(pose_valid, (size_t)n_frames, L.valid.host(S));
   memcpy(L.offsets.host(S), offsets, (T + 1) * 4);
   if (flags)
     memcpy(L.flags.host(S), flags, T);
@@ -79,7 +78,35 @@ static int points_run(vsm_handle *h, double t0, int32_t n_frames, const double *
 
 static const VsmPoints *points_result(vsm_handle *h) { return (h && h->points && h->points->have) ? h->points : nullptr; }
 
-// What a handle form works on (vsm_tracks_triangulate, vsm_points_resect, vsm_points_vet, vsm_tracks_pixels).  take() tests
+// the pixel of an observation {frame, feature, pair, 2 * match + end}, read from the match it names: end 0 = previous, 1 =
+// current
+static inline void tracks_pixel(const int32_t *row, const vsm_p_match *const *lists, int32_t side, float *u, float *v) {
+  const vsm_p_match &m = lists[row[2]][row[3] >> 1];
+  if (row[3] & 1) {
+    *u = side ? m.u2c : m.u1c;
+    *v = side ? m.v2c : m.v1c;
+  } else {
+    *u = side ? m.u2p : m.u1p;
+    *v = side ? m.v2p : m.v1p;
+  }
+}
+
+// The observation source (vsm_resect.h) "the handle's track result": an observation's frame from its row, its pixel from
+// the match list the row names - read inside the grouping, for the rows alone.
+struct TracksObs {
+  const int32_t *obs;
+  const vsm_p_match *const *lists;
+  int32_t side;
+  int32_t frame_of(int32_t i) const { return obs[4 * (size_t)i]; }
+  void pixel_of(int32_t i, float *u, float *v) const { tracks_pixel(obs + 4 * (size_t)i, lists, side, u, v); }
+};
+
+// the grouping's runner of the device paths: the handle's pool
+static inline auto pool_run(vsm_handle *h) {
+  return [h](int n, const std::function<void(int)> &fn) { h->pool->run(n, fn); };
+}
+
+// What a handle form works on (vsm_tracks_triangulate, vsm_points_resect, vsm_points_vet, vsm_points_adjust, vsm_tracks_pixels).  take() tests
 // in the order the callers see: the track result and - with_points - the point result of the same tracks, else
 // VSM_ENOTREADY; then the match lists the observations name: the caller's, checked against the result's counts (VSM_EARG),
 // or - lists == NULL - those of the last vsm_pairs_run, if the tracks came from them and they still stand (VSM_ENOTREADY).
@@ -113,20 +140,18 @@ struct TracksInput {
     n_obs = (int64_t)T->obs.size() / 4;
     return VSM_OK;
   }
-};
-
-// the pixel of an observation {frame, feature, pair, 2 * match + end}, read from the match it names: end 0 = previous, 1 =
-// current
-static inline void tracks_pixel(const int32_t *row, const vsm_p_match *const *lists, int32_t side, float *u, float *v) {
-  const vsm_p_match &m = lists[row[2]][row[3] >> 1];
-  if (row[3] & 1) {
-    *u = side ? m.u2c : m.u1c;
-    *v = side ? m.v2c : m.v1c;
-  } else {
-    *u = side ? m.u2p : m.u1p;
-    *v = side ? m.v2p : m.v1p;
+  // What vsm_points_resect and vsm_points_adjust do behind take(): the tracks whose point was kept as use bytes, into the
+  // stage's own vector, and the observations as a source.
+  // (locals: the bytes stored may alias the vectors, and the loop would reload count and pointers for every track)
+  TracksObs kept_obs(std::vector<uint8_t> &use) const {
+    const int32_t n = n_tracks;
+    const int32_t *status = P->status.data();
+    use.resize((size_t)n + 1);
+    uint8_t *u = use.data();
+    for (int32_t t = 0; t < n; t++) u[t] = status[t] == 0 ? 1 : 0;
+    return TracksObs{T->obs.data(), lists, T->side};
   }
-}
+};
 
 // every observation's frame and pixel
 static void tracks_gather(vsm_handle *h, const VsmTracks &T, const vsm_p_match *const *lists, int32_t *fr, float *px) {

@@ -28,6 +28,12 @@ int64_t pts_check_obs(int32_t n_frames, const double *poses, int32_t n_tracks, c
   return n_obs;
 }
 
+int64_t pts_check_points(bool params_ok, int32_t n_frames, const double *poses, int32_t n_tracks, const int32_t *offsets, const int32_t *obs_frames,
+                         const float *uv, const double *xyz) {
+  if (!params_ok || (n_tracks > 0 && !xyz)) return -1;
+  return pts_check_obs(n_frames, poses, n_tracks, offsets, obs_frames, uv);
+}
+
 void pts_road(double cam_pitch, double cam_height, double *road) {
   for (int i = 0; i < 12; i++) road[i] = 0;
   road[0 * 4 + 0] = 1;

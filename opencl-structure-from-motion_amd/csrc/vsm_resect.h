@@ -21,6 +21,9 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <algorithm>
+#include <vector>
+
 #include "visomatch.h"
 #include "vsm_linalg.h"
 #include "vsm_points.h"
@@ -181,29 +184,90 @@ inline void rs_frame(Eval evaluate, W ab, M S, const vsm_resect_params &prm, RsR
 }
 
 // ---- host side (vsm_resect_host.cpp; no HIP) ----
-// the argument checks of vsm_resect_run / vsm_host_resect: the number of observations, or -1
-int64_t rs_check_args(int32_t n_frames, const double *poses, int32_t n_tracks, const int32_t *offsets, const int32_t *obs_frames, const float *uv,
-                      const double *xyz, const vsm_resect_params *params);
-bool rs_params_ok(const vsm_resect_params *params);  // its test of the parameters
-// The rows by frame, a stable counting sort in two passes over the tracks t0 .. t1 - 1, so that chunks of tracks can go to
-// threads: the counts per frame (added to cnt[n_frames]), then - with at[g] where the chunk's first row of frame g belongs:
-// the frame's start plus the counts of the chunks in front - the rows themselves.  frame_of(i) is observation i's frame,
-// pixel_of(i, &u, &v) its pixel: the caller's arrays, or the track result and the match lists (vsm_resect.inc).
-template <class FrameOf>
-inline void rs_group_count(int32_t t0, int32_t t1, const int32_t *offsets, const uint8_t *use, FrameOf frame_of, int32_t *cnt) {
+bool rs_params_ok(const vsm_resect_params *params);  // the test of the parameters (the arguments: pts_check_points)
+// An observation source gives frame_of(i), observation i's frame, and pixel_of(i, &u, &v), its pixel.  This one is the
+// caller's arrays; the handle's track result and match lists are the other (TracksObs, vsm_points.inc).
+struct RsObsArrays {
+  const int32_t *obs_frames;
+  const float *uv;
+  int32_t frame_of(int32_t i) const { return obs_frames[i]; }
+  void pixel_of(int32_t i, float *u, float *v) const {
+    *u = uv[2 * (size_t)i];
+    *v = uv[2 * (size_t)i + 1];
+  }
+};
+// what a row keeps of its track and observation beside the pixel (vsm_ba.h has BaRow's)
+inline void row_set(RsRow &r, int32_t t, int32_t) { r.track = t; }
+// the two passes over the tracks t0 .. t1 - 1 of one chunk: its rows per frame, added to cnt[n_frames]; then, with at[g]
+// where the chunk's first row of frame g belongs, the rows themselves (obs by value: a copy no store of the loop can alias)
+template <class Obs>
+inline void rs_group_count(int32_t t0, int32_t t1, const int32_t *offsets, const uint8_t *use, Obs obs, int32_t *cnt) {
   for (int32_t t = t0; t < t1; t++)
     if (!use || use[t])
-      for (int32_t i = offsets[t]; i < offsets[t + 1]; i++) cnt[frame_of(i)]++;
+      for (int32_t i = offsets[t]; i < offsets[t + 1]; i++) cnt[obs.frame_of(i)]++;
 }
-template <class FrameOf, class PixelOf>
-inline void rs_group_fill(int32_t t0, int32_t t1, const int32_t *offsets, const uint8_t *use, FrameOf frame_of, PixelOf pixel_of, int32_t *at, RsRow *rows) {
+template <class Obs, class Row>
+inline void rs_group_fill(int32_t t0, int32_t t1, const int32_t *offsets, const uint8_t *use, Obs obs, int32_t *at, Row *rows) {
   for (int32_t t = t0; t < t1; t++)
     if (!use || use[t])
       for (int32_t i = offsets[t]; i < offsets[t + 1]; i++) {
-        RsRow &r = rows[at[frame_of(i)]++];
-        r.track = t;
-        pixel_of(i, &r.u, &r.v);
+        Row &r = rows[at[obs.frame_of(i)]++];
+        row_set(r, t, i);
+        obs.pixel_of(i, &r.u, &r.v);
       }
+}
+// the chunks of tracks the device paths group n_obs observations in, and the host views' runner: a loop
+inline int rs_group_chunks(int64_t n_obs) { return (int)std::max<int64_t>(1, std::min<int64_t>(32, n_obs / 512)); }
+struct RsLoop {
+  template <class Fn>
+  void operator()(int n, Fn fn) const {
+    for (int c = 0; c < n; c++) fn(c);
+  }
+};
+// The rows by frame: a stable counting sort of the observations of the tracks in use (use null: all), a chunk of tracks per
+// task of run(chunks, fn).  Every chunk counts its rows per frame, the counts of the chunks in front give a chunk its place
+// in every frame - so the order is that of one chunk, ascending (track, observation) within a frame, whatever the chunk
+// count: the sort is stable -, and the chunks write their rows side by side.  Two phases, because the row count sizes the
+// block the rows go to: the constructor fills row_off[n_frames + 1] and turns `at` ([chunks][n_frames], the caller's, so
+// that a stage keeps its allocation) into the chunks' places; fill(rows) - once - writes the rows.  offsets may be null
+// without tracks.
+template <class Obs, class Run>
+struct RsGroup {
+  const size_t F;
+  const int32_t n_tracks;
+  const int32_t *const offsets;
+  const uint8_t *const use;
+  const Obs obs;
+  const int chunks;
+  Run run;
+  std::vector<int32_t> &at;
+  std::vector<int32_t> row_off;
+  RsGroup(int32_t n_frames, int32_t n_tracks_, const int32_t *offsets_, const uint8_t *use_, const Obs &obs_, int chunks_, Run run_, std::vector<int32_t> &at_)
+      : F((size_t)n_frames), n_tracks(n_tracks_), offsets(offsets_), use(use_), obs(obs_), chunks(chunks_), run(run_), at(at_), row_off(F + 1, 0) {
+    at.assign((size_t)chunks * F, 0);
+    if (n_tracks > 0 && F > 0) run(chunks, [&](int c) { rs_group_count(first_track(c), first_track(c + 1), offsets, use, obs, at.data() + (size_t)c * F); });
+    for (size_t g = 0; g < F; g++) {
+      int32_t place = row_off[g];
+      for (int c = 0; c < chunks; c++) {
+        const int32_t n = at[(size_t)c * F + g];
+        at[(size_t)c * F + g] = place;
+        place += n;
+      }
+      row_off[g + 1] = place;
+    }
+  }
+  int32_t first_track(int c) const { return (int32_t)((int64_t)n_tracks * c / chunks); }
+  int32_t rows_of(size_t g) const { return row_off[g + 1] - row_off[g]; }
+  template <class Row>
+  void fill(Row *rows) {
+    if (row_off[F] > 0) run(chunks, [&](int c) { rs_group_fill(first_track(c), first_track(c + 1), offsets, use, obs, at.data() + (size_t)c * F, rows); });
+  }
+};
+// the tree over the first n sums of the partials [RS_LANES][RS_SUMS], as a loop; the sums are partial[0 .. n - 1] afterwards
+inline void rs_host_tree(double *partial, int n) {
+  for (int s = RS_LANES / 2; s >= 1; s >>= 1)
+    for (int l = 0; l < s; l++)
+      for (int k = 0; k < n; k++) partial[(size_t)l * RS_SUMS + k] += partial[(size_t)(l + s) * RS_SUMS + k];
 }
 // libm's part: sqrt(ss / used), 0 where nothing was used
 double rs_rms(double ss, int32_t used);

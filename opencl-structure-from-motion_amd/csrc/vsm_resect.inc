@@ -5,8 +5,10 @@
 // frame with a stable counting sort on the pool - once per call, timed with the packing -, one pinned block with the poses,
 // the two masks, the row offsets, the row table (12 bytes per row) and the points (24 bytes per track); one copy up, one
 // kernel, one copy back (128 bytes per frame); then libm's sqrt on the two sums of squares.  vsm_points_resect fills the same block
-// from the handle's last track and point results, reading every observation's pixel from the match it names.  Blocks:
-// RsBlocks (vsm_layouts.h); round trip, result record, keep, getters' copies: vsm_stage.h; prologue: TracksInput (vsm_points.inc).
+// from the handle's last track and point results, reading every observation's pixel from the match it names.  Grouping and
+// the caller's arrays as observations: RsGroup, RsObsArrays (vsm_resect.h); blocks: RsBlocks (vsm_layouts.h); round trip,
+// result record, keep, mask bytes, getters' copies: vsm_stage.h; prologue and the handle's observations: TracksInput, TracksObs
+// (vsm_points.inc).
 struct VsmResect : VsmResult<7> {  // the staging and the last result's stats and timings (vsm_stage.h)
   std::vector<int32_t> status, updates, rows, used;
   std::vector<double> poses, ss_before, ss_after, rms_before, rms_after;
@@ -16,46 +18,24 @@ struct VsmResect : VsmResult<7> {  // the staging and the last result's stats an
 
 static void resect_destroy(vsm_handle *h) { vsm_result_destroy(h->resect); }
 
-// The arguments have been checked.  frame_of(i) / pixel_of(i, &u, &v): observation i's frame and pixel (vsm_resect.h).
-// The grouping runs on the handle's pool, a chunk of tracks per task: every chunk counts its rows per frame, the counts of
-// the chunks in front give a chunk its place in every frame (so the order is that of one chunk: the sort is stable), and the
-// chunks write their rows into the pinned block side by side.
-template <class FrameOf, class PixelOf>
+// The arguments have been checked.  obs: the observation source (vsm_resect.h), grouped on the handle's pool.
+template <class Obs>
 static int resect_run(vsm_handle *h, double t0, int32_t n_frames, const double *poses, const uint8_t *pose_valid, const uint8_t *refine, double f, double cu,
-                      double cv, int32_t n_tracks, const int32_t *offsets, FrameOf frame_of, PixelOf pixel_of, const double *xyz, const uint8_t *use,
-                      const vsm_resect_params &prm) {
+                      double cv, int32_t n_tracks, const int32_t *offsets, const Obs &obs, const double *xyz, const uint8_t *use, const vsm_resect_params &prm) {
   HIPCHK(hipSetDevice(h->device));
   VsmResect &R = *h->resect;
   VsmStage &S = R.st;
   const size_t F = (size_t)n_frames, T = (size_t)n_tracks;
   // ---- group: the counts first (they size the block) ----
-  const int64_t n_obs = n_tracks > 0 ? offsets[n_tracks] : 0;
-  const int chunks = (int)std::max<int64_t>(1, std::min<int64_t>(32, n_obs / 512));
-  const auto first_track = [&](int c) { return (int32_t)((int64_t)n_tracks * c / chunks); };
-  std::vector<int32_t> &cnt = R.g_count;  // [chunks][n_frames]: the counts, then the chunks' places
-  cnt.assign((size_t)chunks * F, 0);
-  std::vector<int32_t> row_off(F + 1, 0);
-  if (n_tracks > 0 && F > 0) h->pool->run(chunks, [&](int c) { rs_group_count(first_track(c), first_track(c + 1), offsets, use, frame_of, cnt.data() + (size_t)c * F); });
-  for (size_t g = 0; g < F; g++) {
-    int32_t at = row_off[g];
-    for (int c = 0; c < chunks; c++) {
-      const int32_t n = cnt[(size_t)c * F + g];
-      cnt[(size_t)c * F + g] = at;
-      at += n;
-    }
-    row_off[g + 1] = at;
-  }
-  const RsBlocks L(F, T, (size_t)row_off[F]);
+  RsGroup G(n_frames, n_tracks, offsets, use, obs, rs_group_chunks(n_tracks > 0 ? offsets[n_tracks] : 0), pool_run(h), R.g_count);
+  const RsBlocks L(F, T, (size_t)G.row_off[F]);
   HIPCHK(S.grow_in(L.in.at, h->stream));
   HIPCHK(S.grow_out(L.out.at, h->stream));
   if (F > 0) memcpy(L.poses.host(S), poses, F * 96);
-  for (size_t g = 0; g < F; g++) {
-    L.valid.host(S)[g] = (!pose_valid || pose_valid[g]) ? 1 : 0;
-    L.refine.host(S)[g] = (!refine || refine[g]) ? 1 : 0;
-  }
-  memcpy(L.row_off.host(S), row_off.data(), (F + 1) * 4);
-  if (L.rows.n > 0)
-    h->pool->run(chunks, [&](int c) { rs_group_fill(first_track(c), first_track(c + 1), offsets, use, frame_of, pixel_of, cnt.data() + (size_t)c * F, L.rows.host(S)); });
+  vsm_mask_bytes(pose_valid, F, L.valid.host(S));
+  vsm_mask_bytes(refine, F, L.refine.host(S));
+  memcpy(L.row_off.host(S), G.row_off.data(), (F + 1) * 4);
+  G.fill(L.rows.host(S));
   if (T > 0) memcpy(L.xyz.host(S), xyz, T * 24);
   // ---- from here on the call replaces the last result ----
   HIPCHK(R.replace(L, h->stream, t0));
@@ -96,7 +76,7 @@ static int resect_run(vsm_handle *h, double t0, int32_t n_frames, const double *
   R.rms_before.resize(F);
   R.rms_after.resize(F);
   for (size_t g = 0; g < F; g++) {
-    R.rows[g] = row_off[g + 1] - row_off[g];
+    R.rows[g] = G.rows_of(g);
     R.rms_before[g] = rs_rms(R.ss_before[g], o_u0[g]);
     R.rms_after[g] = rs_rms(R.ss_after[g], (o_st[g] == 0 || o_st[g] == 6) ? o_us[g] : 0);
     if (o_st[g] >= 0 && o_st[g] < 7) R.stats[o_st[g]]++;
@@ -114,16 +94,9 @@ int vsm_resect_run(vsm_handle *h, int32_t n_frames, const double *poses, const u
                    const vsm_resect_params *params) {
   if (!h) return VSM_EARG;
   const double t0 = now_us();
-  if (rs_check_args(n_frames, poses, n_tracks, offsets, obs_frames, uv, xyz, params) < 0) return VSM_EARG;
+  if (pts_check_points(rs_params_ok(params), n_frames, poses, n_tracks, offsets, obs_frames, uv, xyz) < 0) return VSM_EARG;
   if (!h->resect) h->resect = new VsmResect();
-  const int32_t zero = 0;
-  return resect_run(
-      h, t0, n_frames, poses, pose_valid, refine, f, cu, cv, n_tracks, n_tracks > 0 ? offsets : &zero, [=](int32_t i) { return obs_frames[i]; },
-      [=](int32_t i, float *u, float *v) {
-        *u = uv[2 * (size_t)i];
-        *v = uv[2 * (size_t)i + 1];
-      },
-      xyz, use, *params);
+  return resect_run(h, t0, n_frames, poses, pose_valid, refine, f, cu, cv, n_tracks, offsets, RsObsArrays{obs_frames, uv}, xyz, use, *params);
 }
 
 int vsm_points_resect(vsm_handle *h, const vsm_p_match *const *lists, const int32_t *counts, const double *poses, const uint8_t *pose_valid,
@@ -135,20 +108,8 @@ int vsm_points_resect(vsm_handle *h, const vsm_p_match *const *lists, const int3
   if (rc != VSM_OK) return rc;
   if (!rs_params_ok(params) || (in.n_frames > 0 && !poses)) return VSM_EARG;
   if (!h->resect) h->resect = new VsmResect();
-  VsmResect &R = *h->resect;
-  // (locals: the bytes stored may alias `in` and the vectors, and the loop would reload count and pointers for every track)
-  const int32_t n_tracks = in.n_tracks;
-  const int32_t *status = in.P->status.data();
-  R.g_use.resize((size_t)n_tracks + 1);
-  uint8_t *g_use = R.g_use.data();
-  for (int32_t t = 0; t < n_tracks; t++) g_use[t] = status[t] == 0 ? 1 : 0;
-  // the pixels are read from the match lists inside the grouping, for the rows alone (tracks_pixel, vsm_points.inc)
-  const int32_t *obs = in.T->obs.data();
-  const int32_t side = in.T->side;
-  const vsm_p_match *const *ls = in.lists;
-  return resect_run(
-      h, t0, in.n_frames, poses, pose_valid, refine, f, cu, cv, n_tracks, in.T->offsets.data(), [=](int32_t i) { return obs[4 * (size_t)i]; },
-      [=](int32_t i, float *u, float *v) { tracks_pixel(obs + 4 * (size_t)i, ls, side, u, v); }, in.P->xyz.data(), g_use, *params);
+  const TracksObs obs = in.kept_obs(h->resect->g_use);
+  return resect_run(h, t0, in.n_frames, poses, pose_valid, refine, f, cu, cv, in.n_tracks, in.T->offsets.data(), obs, in.P->xyz.data(), h->resect->g_use.data(), *params);
 }
 
 int32_t vsm_resect_count(vsm_handle *h) {

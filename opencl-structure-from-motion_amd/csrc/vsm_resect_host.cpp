@@ -1,4 +1,4 @@
-// Pose refinement, the host side without HIP: the argument checks, libm's sqrt and
+// Pose refinement, the host side without HIP: the parameters' test, libm's sqrt and
 // vsm_host_resect - one host thread walking the functions of vsm_resect.h, the 256 partial sums and their tree in a loop.
 // The host view is the CPU suite's subject and the device path's second opinion, never its fallback.
 #include "vsm_resect.h"
@@ -7,12 +7,6 @@
 #include <string.h>
 
 #include <vector>
-
-int64_t rs_check_args(int32_t n_frames, const double *poses, int32_t n_tracks, const int32_t *offsets, const int32_t *obs_frames, const float *uv,
-                      const double *xyz, const vsm_resect_params *params) {
-  if (!rs_params_ok(params) || (n_tracks > 0 && !xyz)) return -1;
-  return pts_check_obs(n_frames, poses, n_tracks, offsets, obs_frames, uv);
-}
 
 bool rs_params_ok(const vsm_resect_params *p) { return p && p->min_observations >= 6 && p->max_updates >= 1 && p->eps > 0 && p->eps < HUGE_VAL; }
 
@@ -38,9 +32,7 @@ void host_evaluate(const RsRow *rows, int32_t n, const double *xyz, double f, do
       acc[27] += t;
     }
   }
-  for (int s = RS_LANES / 2; s >= 1; s >>= 1)
-    for (int l = 0; l < s; l++)
-      for (int k = 0; k < RS_SUMS; k++) partial[(size_t)l * RS_SUMS + k] += partial[(size_t)(l + s) * RS_SUMS + k];
+  rs_host_tree(partial.data(), RS_SUMS);
   for (int k = 0; k < RS_SUMS; k++) sums[k] = partial[k];
   *count = used;
 }
@@ -62,19 +54,13 @@ int32_t vsm_host_resect(int32_t n_frames, const double *poses, const uint8_t *po
                         int32_t n_tracks, const int32_t *offsets, const int32_t *obs_frames, const float *uv, const double *xyz, const uint8_t *use,
                         const vsm_resect_params *params, int32_t *status, double *out_poses, int32_t *updates, int32_t *rows, int32_t *used,
                         double *ss_before, double *ss_after, double *rms_before, double *rms_after) {
-  if (rs_check_args(n_frames, poses, n_tracks, offsets, obs_frames, uv, xyz, params) < 0) return VSM_EARG;
+  if (pts_check_points(rs_params_ok(params), n_frames, poses, n_tracks, offsets, obs_frames, uv, xyz) < 0) return VSM_EARG;
   // the rows by frame, one chunk
-  const auto frame_of = [&](int32_t i) { return obs_frames[i]; };
-  const auto pixel_of = [&](int32_t i, float *u, float *v) {
-    *u = uv[2 * (size_t)i];
-    *v = uv[2 * (size_t)i + 1];
-  };
-  std::vector<int32_t> row_off((size_t)n_frames + 1, 0);
-  rs_group_count(0, n_tracks, offsets, use, frame_of, row_off.data() + 1);
-  for (int32_t g = 0; g < n_frames; g++) row_off[g + 1] += row_off[g];
+  std::vector<int32_t> at;
+  RsGroup G(n_frames, n_tracks, offsets, use, RsObsArrays{obs_frames, uv}, 1, RsLoop(), at);
+  const std::vector<int32_t> &row_off = G.row_off;
   std::vector<RsRow> table((size_t)row_off[n_frames] + 1);
-  std::vector<int32_t> at(row_off.begin(), row_off.end() - 1);
-  rs_group_fill(0, n_tracks, offsets, use, frame_of, pixel_of, at.data(), table.data());
+  G.fill(table.data());
   std::vector<double> partial;
   for (int32_t g = 0; g < n_frames; g++) {
     const RsRow *fr = table.data() + row_off[g];

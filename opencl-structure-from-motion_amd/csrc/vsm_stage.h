@@ -180,25 +180,30 @@ struct VsmArray {
     n = count;
     at = l.take(count * sizeof(E) + spare);
   }
+  E *in(uint8_t *block) const { return (E *)(block + at); }  // the array in a copy of its block that starts at `block`
 };
 // an array of the device block alone: a working set behind the uploaded block
 template <typename E>
 struct VsmDev : VsmArray<E> {
-  E *dev(const VsmStage &S) const { return (E *)(S.dev + this->at); }
+  E *dev(const VsmStage &S) const { return this->in(S.dev); }
 };
 // an uploaded array: the same offset in the pinned input
 template <typename E>
 struct VsmIn : VsmDev<E> {
-  E *host(const VsmStage &S) const { return (E *)(S.pin_in + this->at); }
+  E *host(const VsmStage &S) const { return this->in(S.pin_in); }
 };
 // an array of the block that is copied back (or of the working set placed behind it); `out_at` is its blocks' (VsmBlocks)
 template <typename E>
 struct VsmOut : VsmArray<E> {
-  E *dev(const VsmStage &S, size_t out_at) const { return (E *)(S.dev + out_at + this->at); }
-  E *host(const VsmStage &S) const { return (E *)(S.pin_out + this->at); }
+  E *dev(const VsmStage &S, size_t out_at) const { return this->in(S.dev + out_at); }
+  E *host(const VsmStage &S) const { return this->in(S.pin_out); }
   void keep(VsmKeep &K, const VsmStage &S, std::vector<E> &vec) const { K.add(vec, host(S), this->n); }
 };
 static inline hipError_t vsm_no_pre() { return hipSuccess; }
+// a mask of the ABI (null: every entry set) as the n bytes 0 or 1 the kernels read
+static inline void vsm_mask_bytes(const uint8_t *mask, size_t n, uint8_t *out) {
+  for (size_t i = 0; i < n; i++) out[i] = (!mask || mask[i]) ? 1 : 0;
+}
 
 // a stats or timings getter: the array of the stage's last result, or zeros where there is none (src null)
 template <typename T, size_t N>

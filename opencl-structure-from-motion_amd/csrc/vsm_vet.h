@@ -83,11 +83,6 @@ VSM_HD inline int32_t vet_track_status(int in_use, const VetAcc &a, int32_t min_
 // the track's length in the pruned set
 VSM_HD inline int32_t vet_kept_length(int32_t status, int32_t n_in) { return status == 0 ? n_in : 0; }
 
-// ---- host side (vsm_vet_host.cpp; no HIP) ----
-// the argument checks of vsm_vet_run / vsm_host_vet: the number of observations, or -1
-int64_t vet_check_args(int32_t n_frames, const double *poses, int32_t n_tracks, const int32_t *offsets, const int32_t *obs_frames, const float *uv,
-                       const double *xyz, const vsm_vet_params *params);
-
 // ---- device path (vsm_vet.hip) ----
 #ifdef __HIP__
 struct VsmProf;

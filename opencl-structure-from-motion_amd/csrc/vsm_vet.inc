@@ -31,10 +31,8 @@ static int vet_run(vsm_handle *h, double t0, int32_t n_frames, const double *pos
   HIPCHK(S.grow_in(L.in.at, h->stream));
   HIPCHK(S.grow_out(L.out.at, h->stream));
   // ---- pack ----
-  for (size_t g = 0; g < F; g++) {
-    pts_rigid_inverse(poses + 12 * g, L.states.host(S) + 12 * g);
-    L.valid.host(S)[g] = (!pose_valid || pose_valid[g]) ? 1 : 0;
-  }
+  for (size_t g = 0; g < F; g++) pts_rigid_inverse(poses + 12 * g, L.states.host(S) + 12 * g);
+  vsm_mask_bytes(pose_valid, F, L.valid.host(S));
   memcpy(L.offsets.host(S), offsets, (T + 1) * 4);
   if (T > 0) memcpy(L.xyz.host(S), xyz, T * 24);
   for (size_t t = 0; t < T; t++) L.use.host(S)[t] = use_of((int32_t)t) ? 1 : 0;
@@ -117,7 +115,7 @@ int vsm_vet_run(vsm_handle *h, int32_t n_frames, const double *poses, const uint
                 const int32_t *offsets, const int32_t *obs_frames, const float *uv, const double *xyz, const uint8_t *use, const vsm_vet_params *params) {
   if (!h) return VSM_EARG;
   const double t0 = now_us();
-  const int64_t n_obs = vet_check_args(n_frames, poses, n_tracks, offsets, obs_frames, uv, xyz, params);
+  const int64_t n_obs = pts_check_points(vet_params_ok(params), n_frames, poses, n_tracks, offsets, obs_frames, uv, xyz);
   if (n_obs < 0) return VSM_EARG;
   const int32_t zero = 0;
   return vet_run(h, t0, n_frames, poses, pose_valid, f, cu, cv, n_tracks, n_obs, n_tracks > 0 ? offsets : &zero, xyz, *params, ObsCopy{n_obs, obs_frames, uv},

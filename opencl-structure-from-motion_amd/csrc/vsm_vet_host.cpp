@@ -1,4 +1,4 @@
-// Vetting of observations, the host side without HIP: the argument checks and vsm_host_vet - one host thread walking the
+// Vetting of observations, the host side without HIP: the default parameters and vsm_host_vet - one host thread walking the
 // functions of vsm_vet.h, a track's 16 partial sums and their tree in a loop.  The host view is the CPU suite's subject and
 // the device path's second opinion, never its fallback.
 #include "vsm_vet.h"
@@ -6,12 +6,6 @@
 #include <string.h>
 
 #include <vector>
-
-int64_t vet_check_args(int32_t n_frames, const double *poses, int32_t n_tracks, const int32_t *offsets, const int32_t *obs_frames, const float *uv,
-                       const double *xyz, const vsm_vet_params *params) {
-  if (!vet_params_ok(params) || (n_tracks > 0 && !xyz)) return -1;
-  return pts_check_obs(n_frames, poses, n_tracks, offsets, obs_frames, uv);
-}
 
 extern "C" {
 
@@ -26,7 +20,7 @@ int32_t vsm_host_vet(int32_t n_frames, const double *poses, const uint8_t *pose_
                      const int32_t *offsets, const int32_t *obs_frames, const float *uv, const double *xyz, const uint8_t *use, const vsm_vet_params *params,
                      uint8_t *code, float *r2, int32_t *status, int32_t *n_in, int32_t *frame_lo, int32_t *frame_hi, double *ss, double *worst,
                      int32_t *frame_counts, int32_t *kept_offsets, int32_t *kept_index, int32_t *n_kept) {
-  const int64_t n_obs = vet_check_args(n_frames, poses, n_tracks, offsets, obs_frames, uv, xyz, params);
+  const int64_t n_obs = pts_check_points(vet_params_ok(params), n_frames, poses, n_tracks, offsets, obs_frames, uv, xyz);
   if (n_obs < 0) return VSM_EARG;
   const double limit = rs_limit(params->max_residual);
   std::vector<double> states((size_t)n_frames * 12 + 1);

@@ -174,6 +174,18 @@ def double_row_case():
     return Case(perturb(true, rng), tracks, pts, true_poses=true)
 
 
+def pool_chunks_case():
+    """4 frames, 520 points, every point seen by every frame: 2080 observations, which the device paths group in 4 chunks of 130
+    tracks on the handle's pool (rs_group_chunks, csrc/vsm_resect.h) where the host views take one; every fifth track unused;
+    the root frame fixed.  Not one of cases(): the restatement walks every partial sum in Python and takes too long at this
+    size, so the device is compared with the host view alone (test_resect_gpu.py, test_ba_gpu.py)."""
+    c = scene(4, 520, seed=25, seen=1.0, refine=[0, 1, 1, 1])
+    c.use = np.ones(520, np.uint8)
+    c.use[::5] = 0
+    assert len(c.obs_frames) == 2080 and len(c.offsets) == 521
+    return c
+
+
 _cases = None
 _refs = {}
 

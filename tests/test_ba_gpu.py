@@ -63,6 +63,15 @@ def test_the_schedule_does_not_show(vm, name):
     m.close()
 
 
+def test_pool_chunks_against_one_chunk(vm, matcher):
+    """the rows grouped in four chunks on the pool against the host view's one chunk: the same rows in the same places"""
+    a, kw = RC.pool_chunks_case().args()
+    kw["params"] = dict(BC.QUICK, max_rounds=2, cg_iters=5)
+    got = matcher.adjust(*a, **kw)
+    assert got.rows.tolist() == [416] * 4 and len(got.history) >= 1
+    B.assert_same(got, vm.host_adjust(*a, **kw), "four chunks on the device path against the host view")
+
+
 # ---- 2: on the handle's own track and point results ----------------------------------------------------------------------------
 
 SCENES = ["scene_type-1", "noise_half_px", "merged_tracks"]

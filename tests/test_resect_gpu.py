@@ -52,6 +52,14 @@ def test_cases(vm, matcher, name):
         assert got.timings["kernels_us"] > 0 and got.timings["group_us"] > 0
 
 
+def test_pool_chunks_against_one_chunk(vm, matcher):
+    """the rows grouped in four chunks on the pool against the host view's one chunk: the same rows in the same places"""
+    a, kw = RC.pool_chunks_case().args()
+    got = matcher.resect(*a, **kw)
+    assert got.rows.tolist() == [416] * 4 and got.status[0] == 2 and got.stats["refined"] >= 1
+    R.assert_same(got, vm.host_resect(*a, **kw), "four chunks on the device path against the host view")
+
+
 # ---- 2: on the handle's own track and point results ----------------------------------------------------------------------------
 
 SCENES = ["scene_type-1", "noise_half_px", "merged_tracks"]
