@@ -4,13 +4,18 @@ params -; reference(name) the restatement's result (tests/ba_ref.py), computed o
 GPU suite.  The scenes are the smallest at which the kernels can go wrong: frame counts 1, 2, 3, 9 (a workgroup per frame);
 rows per frame 0, 5, 6, 255 .. 257, 513 (either side of min_observations, of the 256 lanes and of their second round); track
 lengths 1, 2, 15 .. 17, 33 and track counts 1, 15 .. 17, 65, 257 (a lane per track, 256 lanes per workgroup); every status of
-a frame and of a track in one call; and one case per exit of the solve and of the call.  Rounds and iterations are kept few:
-the restatement walks 256 partial sums and their tree in plain Python for every sum."""
+a frame and of a track in one call; and one case per exit of the solve and of the call.  Then the wide ones, for what is
+dealt out over 256 lanes by the frame: frame counts 42 | 43 and 85 | 86 (6 F entries of the solve's vectors on either side of
+the 256 partial sums of a scalar product, and of their second wrap), 256 | 257 and 513 (a lane per frame: a second and a third
+trip of one workgroup's loops, a second and a third block of the flat grids), with fewer tracks than frames, and with held
+frames all along.  Rounds and iterations are kept few: the restatement walks 256 partial sums and their tree in plain Python
+for every sum.  long_case: two scenes run to the minimum, for the comparison with the dense reference of tests/ba_dense.py."""
 import numpy as np
 
 import points_cases as PC
 import resect_cases as RC
 import ba_ref as B
+import ba_dense as D
 
 QUICK = dict(min_observations=6, max_rounds=3, cg_iters=8)
 ROW_COUNTS = (0, 5, 6, 255, 256, 257, 513)
@@ -134,6 +139,43 @@ def nan_case():
     return RC.Case(poses, tracks, c.xyz, refine=root_fixed(5), pose_valid=[1, 1, 1, 0, 1], params=dict(QUICK))
 
 
+SLOW_PATH = dict(step=(0.01, 0.0, 0.002), yaw=0.0005)  # every point stays in front of every camera over hundreds of frames
+DENSE_FRAMES = (42, 43, 85, 86, 256, 257)              # 6 F = 252, 258 | 510, 516 | 1536, 1542: either side of the 256 partials' first and second wrap, and of a block of lanes
+DENSE_POINTS = 12
+BANDS = {"band_257": (257, 520, 8), "band_513": (513, 700, 10), "band_257_held": (257, 520, 8)}  # name: frames, tracks, track length
+BAND_PARAMS = dict(QUICK, max_rounds=2, cg_iters=4, cg_tol=1e-9)
+
+
+def dense_wide(n_frames):
+    """DENSE_POINTS points, each seen by every frame of a slow path: fewer tracks than frames, so the grids over both are sized
+    by the frames; all frames but the pinned root are free"""
+    return noisy_scene(n_frames, DENSE_POINTS, seed=80 + n_frames, seen=1.0, angle=2e-3, shift=0.01, point_shift=0.02, params=dict(max_rounds=2, cg_iters=3), path=SLOW_PATH)
+
+
+def band_wide(n_frames, n_points, length, seed, held=False):
+    """point i is seen by `length` consecutive frames from (i * (n_frames - length)) // (n_points - 1) on: a band along the slow
+    path, a few rows in the frames at its two ends.  held: every fifth frame is not asked for and the frames 100 and
+    n_frames - 1 have no valid pose, so held entries are passed over all along the scalar products and the last frame of the
+    last block of lanes is one of them."""
+    rng = np.random.default_rng(seed)
+    true = PC.camera_path(n_frames, **SLOW_PATH)
+    pts = RC.visible_points(n_points, rng)
+    tracks = []
+    for i, X in enumerate(pts):
+        first = (i * (n_frames - length)) // (n_points - 1)
+        tracks.append([(g,) + RC.pixel(true[g], X, (0.3 * rng.uniform(-1, 1), 0.3 * rng.uniform(-1, 1))) for g in range(first, first + length)])
+    poses = RC.perturb(true, rng, 2e-3, 0.01)
+    poses[0] = true[0]
+    refine, valid = root_fixed(n_frames), None
+    if held:
+        refine[::5] = 0
+        valid = np.ones(n_frames, np.uint8)
+        valid[[100, n_frames - 1]] = 0
+    c = RC.Case(poses, tracks, pts + rng.uniform(-1, 1, pts.shape) * 0.02, refine=refine, pose_valid=valid, params=dict(BAND_PARAMS), true_poses=true)
+    c.true_xyz = np.ascontiguousarray(pts, dtype=np.float64)
+    return c
+
+
 def with_params(c, **params):
     d = RC.Case(c.poses, [], c.xyz, use=c.use, refine=c.refine, pose_valid=c.pose_valid, params=dict(c.params, **params), true_poses=c.true_poses, f=c.f, cu=c.cu, cv=c.cv)
     d.offsets, d.obs_frames, d.uv = c.offsets, c.obs_frames, c.uv
@@ -172,6 +214,11 @@ def cases():
     c["hits_cg_iters"] = with_params(small, cg_iters=2, cg_tol=1e-8)
     c["converges"] = with_params(small, max_rounds=8, cg_iters=30, ftol=1e-3)
     c["lambda_max"] = with_params(c["no_tracks"], lambda_max=1e-1, max_rounds=5)  # (no rows: the cost is 0 and no step can lower it)
+    # the wide ones: more than 256 entries of the frames' vectors, more than 256 frames, more frames than tracks
+    for n in DENSE_FRAMES:
+        c["dense_%d" % n] = dense_wide(n)
+    for k, (name, (n_frames, n_points, length)) in enumerate(sorted(BANDS.items())):
+        c[name] = band_wide(n_frames, n_points, length, seed=90 + k, held=name.endswith("_held"))
     _cases = c
     return c
 
@@ -181,3 +228,28 @@ def reference(name):
         a, kw = cases()[name].args()
         _refs[name] = B.adjust(*a, **kw)
     return _refs[name]
+
+
+# ---- the long run: to the minimum, against the dense reference (tests/ba_dense.py) ---------------------------------------------------
+
+LONG_SCENES = {71: (6, 60), 72: (9, 120)}  # seed: frames, points - the scenes of test_ba_cpu.py's test_minimiser
+LONG = dict(min_observations=10, max_rounds=40, cg_iters=200, cg_tol=1e-12, ftol=1e-14)
+_long = {}
+
+
+def long_case(seed):
+    """-> (the case, the dense reference's minimum (poses, points) and its cost), computed once per process"""
+    if seed not in _long:
+        c = noisy_scene(*LONG_SCENES[seed], seed=seed, params=LONG)
+        _long[seed] = (c,) + D.minimise(c)
+    return _long[seed]
+
+
+def against_the_dense_reference(got, seed, what):
+    """the four comparisons of a result of long_case(seed) with ba_dense, within ba_dense.LIMITS"""
+    c, state, cost = long_case(seed)
+    assert got.frame_status.tolist() == [2] + [0] * (len(c.poses) - 1) and (got.track_status == 0).all()  # what ba_dense takes for free
+    assert got.history["active"][-1] == len(c.uv)
+    figures = D.compare((got.poses, got.xyz), c, state, cost, reported=got.cost)
+    print(what, seed, "rounds", len(got.history), "against the dense reference:", figures, "limits:", D.LIMITS)
+    D.check(figures, (what, seed))

@@ -3,7 +3,8 @@ definition restated in plain Python floats: every int equal, every double equal 
 tests/ba_cases.py.  Then what the cases are for is checked on the restatement's own results - a census of the statuses and of
 the exits of the solve and of the call, so that a case that drifts away from its exit fails here and not silently - and the
 properties of the method on the host view: the cost never rises, what is pinned keeps its bytes, the result is not above the
-planted truth, and it is strictly below what the alternation of today's two half-steps reaches in as many rounds."""
+planted truth, and it is strictly below what the alternation of today's two half-steps reaches in as many rounds.  Host view
+and restatement share one derivation; tests/ba_dense.py does not, and the host view's minimum is held against its minimum."""
 import ctypes as C
 import os
 import re
@@ -84,6 +85,36 @@ def test_row_track_and_frame_counts():
     assert not any(column(BC.reference("frames_1"), 5))  # one frame: every track has one row, nothing is free, no step is accepted
 
 
+def test_the_wide_cases_are_wide():
+    """the cases past 256 entries and past 256 frames are what they are there for: 6 F on either side of the 256 partial sums'
+    first and second wrap, F on either side of a block of 256 lanes and past two, more frames than tracks in the dense ones,
+    held entries all along the vectors in band_257_held - and every one of them looks at a scalar product more than once"""
+    assert BC.DENSE_FRAMES == (42, 43, 85, 86, 256, 257)
+    assert [6 * n > 256 for n in (42, 43)] == [False, True] and [6 * n > 512 for n in (85, 86)] == [False, True]
+    for n in BC.DENSE_FRAMES:
+        c, want = BC.cases()["dense_%d" % n], BC.reference("dense_%d" % n)
+        assert len(want.frame_status) == n > len(want.track_status) == BC.DENSE_POINTS and (want.rows == BC.DENSE_POINTS).all()
+        assert want.frame_status.tolist() == [2] + [0] * (n - 1) and (want.track_status == 0).all() and (want.active == want.rows).all()
+        assert (c.true_poses[0] == c.poses[0]).all()
+    census = {"band_257": (257, 520, [252, 0, 1, 4, 0, 0, 0, 0]), "band_513": (513, 700, [506, 0, 1, 6, 0, 0, 0, 0])}
+    for name, (n_frames, n_tracks, frames) in census.items():
+        want = BC.reference(name)
+        assert len(want.frame_status) == n_frames and len(want.track_status) == n_tracks
+        assert want.stats["frames"] == frames and (want.track_status == 0).all()
+        short = np.nonzero(want.frame_status == 3)[0]
+        assert (want.rows[short] < 6).all() and (np.minimum(short, n_frames - 1 - short) < 4).all()  # the band's two ends
+        assert column(want, 3) == [4, 4] and column(want, 4) == [3, 3] and column(want, 5) == [1, 1]
+    c, want = BC.cases()["band_257_held"], BC.reference("band_257_held")
+    status = want.frame_status
+    assert len(status) == 257 and status[100] == 1 and status[256] == 1 and (status[np.arange(0, 257, 5)[(np.arange(0, 257, 5) != 100)]] == 2).all()
+    assert want.stats["frames"][0] == (status == 0).sum() > 190 and set(status.tolist()) == {0, 1, 2, 3}
+    assert [s != 0 for s in status[[42, 43, 85, 86]]] == [False, False, True, False]  # held and free entries on either side of the wraps
+    assert want.poses[status != 0].tobytes() == c.poses[status != 0].tobytes() and (want.poses[status == 0] != c.poses[status == 0]).any(axis=1).all()
+    for name in ["dense_%d" % n for n in BC.DENSE_FRAMES] + sorted(BC.BANDS):
+        want = BC.reference(name)
+        assert max(column(want, 3)) > 1 and any(column(want, 5)), (name, want.history)
+
+
 def test_held_sides():
     c, want = BC.cases()["points_only"], BC.reference("points_only")
     assert (want.frame_status == 2).all() and want.poses.tobytes() == c.poses.tobytes() and (want.track_status == 0).all()
@@ -151,6 +182,20 @@ def test_minimiser(vm, seed, frames, points):
     print("minimiser:", seed, "start", got.history["cost_before"][0], "result", got.cost, "planted", truth, "rounds", len(got.history))
     assert got.cost <= truth, (got.cost, truth)
     assert got.cost < 1e-2 * got.history["cost_before"][0]
+
+
+@pytest.mark.parametrize("seed", sorted(BC.LONG_SCENES))
+def test_against_the_dense_reference(vm, seed):
+    """test_minimiser's scenes run until ftol = 1e-14 stops them, against tests/ba_dense.py - a dense Levenberg-Marquardt solve
+    in numpy with a parameterisation and derivatives of its own: the cost the library reports against the cost ba_dense finds
+    at the returned state, the cost against ba_dense's minimum, ba_dense's gradient at the returned state over that at the
+    start (stationarity of the cost itself, whatever chart the library uses), and poses and points at one scale.  The limits
+    are ba_dense.LIMITS, 100 times what ba_dense differs from itself by."""
+    c, _, _ = BC.long_case(seed)
+    a, kw = c.args()
+    got = vm.host_adjust(*a, **kw)
+    BC.against_the_dense_reference(got, seed, "host view")
+    assert got.stats["stop"] == 1 and got.stats["rounds"] < BC.LONG["max_rounds"], got.stats
 
 
 ALT_POINTS = dict(point_type=-1, max_dist=1000.0, min_angle=0.0)

@@ -3,7 +3,9 @@ points adjusted jointly by the kernels of csrc/vsm_ba.hip.  Every result is comp
 restated in plain Python floats) and with vsm_host_adjust: every int equal, every double equal by its bytes.  The cases are
 those of tests/ba_cases.py, proven on the CPU by test_ba_cpu.py; their sizes are the smallest at which the kernels can go
 wrong (row counts on either side of the 256 lanes and of their second round, track counts on either side of a workgroup of
-lanes, frame counts of 1, 2, 3 and 9, every status in one grid, every exit of the solve and of the call)."""
+lanes, frame counts of 1, 2, 3 and 9, every status in one grid, every exit of the solve and of the call; frame counts on
+either side of 256 / 6, 512 / 6 and 256, and 513, for the scalar products' partial sums and the lane-per-frame loops and grids).
+test_long_run runs two scenes to the minimum, against the host view and the dense reference of tests/ba_dense.py."""
 import numpy as np
 import pytest
 
@@ -52,7 +54,7 @@ def test_cases(vm, matcher, name):
     assert got.timings["kernels_us"] > 0 and got.timings["group_us"] > 0
 
 
-@pytest.mark.parametrize("name", ["converges", "first_step_rejected", "grid", "lambda_max"])
+@pytest.mark.parametrize("name", ["band_257_held", "converges", "dense_257", "first_step_rejected", "grid", "lambda_max"])
 def test_the_schedule_does_not_show(vm, name):
     """every launch of max_rounds rounds enqueued at once, the control block turning the launches behind the call's stop into
     no-ops, against the default, a wait per round: the same bytes"""
@@ -70,6 +72,38 @@ def test_pool_chunks_against_one_chunk(vm, matcher):
     got = matcher.adjust(*a, **kw)
     assert got.rows.tolist() == [416] * 4 and len(got.history) >= 1
     B.assert_same(got, vm.host_adjust(*a, **kw), "four chunks on the device path against the host view")
+
+
+@pytest.mark.parametrize("seed", sorted(BC.LONG_SCENES))
+def test_long_run(vm, matcher, seed):
+    """to the minimum: some twenty rounds, rejected ones between accepted ones, lambda up and down, thirty and more iterations
+    of the solve in a round - too long for the restatement.  The device equals the host view, byte for byte, and meets
+    tests/ba_dense.py, the dense reference with its own derivatives, within the limits the host view is held to."""
+    c, _, _ = BC.long_case(seed)
+    a, kw = c.args()
+    want = vm.host_adjust(*a, **kw)
+    got = matcher.adjust(*a, **kw)
+    B.assert_same(got, want, (seed, "device against the host view"))
+    accepted, iters = got.history["accepted"].tolist(), got.history["cg_iters"].tolist()
+    print("long run:", seed, "accepted", accepted, "cg_iters", iters, "lambda", got.history["lambda"].tolist())
+    assert got.stats["stop"] == 1 and any(a == 0 and 1 in accepted[k:] for k, a in enumerate(accepted)), accepted
+    assert max(iters) > 20
+    BC.against_the_dense_reference(got, seed, "device")
+
+
+def test_long_run_on_the_fixed_schedule(vm):
+    """every launch of twelve rounds of up to 64 iterations enqueued at once; the run needs eight rounds and 42 iterations"""
+    c, _, _ = BC.long_case(72)
+    a, kw = c.args()
+    kw["params"] = dict(BC.LONG, max_rounds=12, cg_iters=64)
+    want = vm.host_adjust(*a, **kw)
+    assert want.stats["stop"] == 1 and len(want.history) < 12 and 20 < max(want.history["cg_iters"]) < 64
+    m = vm.Matcher()
+    m.set_option("adjust_fixed", 1)
+    got = m.adjust(*a, **kw)
+    m.close()
+    B.assert_same(got, want, "fixed schedule against the host view")
+    BC.against_the_dense_reference(got, 72, "device, fixed schedule")
 
 
 # ---- 2: on the handle's own track and point results ----------------------------------------------------------------------------
