@@ -69,6 +69,12 @@ def have_ref_refine():
     return have_ref() and hasattr(ref_lib(), "ref_matcher_refine")
 
 
+def have_ref_reconstruction():
+    """the compiled reference is there, with the Reconstruction class in it and the harness's two entries on top of it (a
+    _ref from before them still serves every other test)"""
+    return have_ref() and hasattr(ref_lib(), "ref_recon_tracks") and hasattr(ref_lib(), "ref_recon_sequence")
+
+
 _p_u8 = C.POINTER(C.c_uint8)
 _p_i16 = C.POINTER(C.c_int16)
 _p_i32 = C.POINTER(C.c_int32)
@@ -226,6 +232,12 @@ def ref_lib():
         L.ref_matrix_det.argtypes = [_p_f64, C.c_int32]
         L.ref_matrix_det.restype = C.c_double
         L.ref_mono_fundamental.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, _p_i32, C.c_int32, _p_f64]
+        if hasattr(L, "ref_recon_tracks"):      # a _ref built from an earlier harness lacks both: have_ref_reconstruction()
+            L.ref_recon_tracks.argtypes = ([C.c_double] * 3 + [C.c_int32, _p_f64, C.c_int32, _p_i32, _p_f32, _p_i32, C.c_int32, C.c_int32,
+                                                               C.c_double, C.c_double, _p_i32, _p_f32, _p_f32, _p_i32, _p_f64, _p_f64, _p_f32])
+        if hasattr(L, "ref_recon_sequence"):
+            L.ref_recon_sequence.argtypes = ([C.c_double] * 3 + [C.c_int32, C.c_void_p, _p_i32, _p_f64, C.c_int32, C.c_int32, C.c_double,
+                                                                 C.c_double, _p_i32, _p_f32, C.c_int32, _p_i32, _p_f64, _p_i32, _p_i32, C.c_int32])
         _ref = L
     return _ref
 
@@ -652,6 +664,82 @@ def ref_svd(A):
 def ref_det(A):
     A = np.ascontiguousarray(A, dtype=np.float64)
     return float(ref_lib().ref_matrix_det(A.ctypes.data_as(_p_f64), A.shape[0]))
+
+
+RECON_DEFAULTS = dict(point_type=1, min_track_length=2, max_dist=30.0, min_angle=2.0)  # viso/reconstruction.h:62
+
+
+class ReconTracks:
+    """what ref_recon_tracks reports per track: stage (the status numbering of include/visomatch.h), xyz and xyz0 (float32
+    [T, 3]: the point at that stage, and as initPoint gave it), type, dist, angle, probe (float32 [T, 3]: pointType's x1c.z,
+    x2c.z and x2r.y)"""
+
+
+def _recon_params(kw):
+    p = dict(RECON_DEFAULTS)
+    p.update(kw)
+    return int(p["point_type"]), int(p["min_track_length"]), float(p["max_dist"]), float(p["min_angle"])
+
+
+def _f32(a):
+    return a.ctypes.data_as(_p_f32)
+
+
+def _f64(a):
+    return a.ctypes.data_as(_p_f64)
+
+
+def ref_recon_tracks(f, cu, cv, fwd, offsets, uv, first_state, **params):
+    """The reference's Reconstruction on tracks of the caller's (oracle/ref_harness.cpp, ref_recon_tracks): fwd [S, 4, 4] the
+    frame states, offsets [T + 1], uv [n_obs, 2] float32 pixels, first_state [T] the state of every track's first pixel (pixel
+    i goes with state first + i).  params: point_type, min_track_length, max_dist, min_angle."""
+    fwd = np.ascontiguousarray(fwd, dtype=np.float64).reshape(-1, 16)
+    off = np.ascontiguousarray(offsets, dtype=np.int32)
+    px = np.ascontiguousarray(uv, dtype=np.float32).reshape(-1, 2)
+    first = np.ascontiguousarray(first_state, dtype=np.int32)
+    T = len(off) - 1
+    assert T >= 0 and len(first) == T and (T == 0 or (off[0] == 0 and off[-1] == len(px)))
+    r = ReconTracks()
+    r.stage, r.type = np.zeros(T, np.int32), np.zeros(T, np.int32)
+    r.xyz, r.xyz0, r.probe = np.zeros((T, 3), np.float32), np.zeros((T, 3), np.float32), np.zeros((T, 3), np.float32)
+    r.dist, r.angle = np.zeros(T, np.float64), np.zeros(T, np.float64)
+    pt, ml, md, ma = _recon_params(params)
+    rc = ref_lib().ref_recon_tracks(float(f), float(cu), float(cv), len(fwd), _f64(fwd), T, _i32(off), _f32(px), _i32(first), pt, ml, md, ma,
+                                    _i32(r.stage), _f32(r.xyz), _f32(r.xyz0), _i32(r.type), _f64(r.dist), _f64(r.angle), _f32(r.probe))
+    if rc != 0:
+        raise ValueError("ref_recon_tracks: a track without pixels or a state outside the states given")
+    return r
+
+
+def ref_recon_sequence(f, cu, cv, lists, Tr, **params):
+    """The reference's Reconstruction::update over the match lists `lists` with their 4x4 Tr, and one more update with an
+    empty list, which finishes every track (its Tr: one more entry of Tr, or the identity).  Returns one dict per update (len(lists) + 1 of them): points
+    (float32 [n, 3], those the update appended, as they stood after it), fwd (float64 [frames, 4, 4], the deque's states front
+    to back after it), live (int32 [tracks, 2]: pixels and last_idx of every track alive after it, in the list's order)."""
+    ls = [np.ascontiguousarray(l, dtype=MATCH_DTYPE) for l in lists] + [np.zeros(0, MATCH_DTYPE)]
+    U = len(ls)
+    tr = np.asarray(Tr, dtype=np.float64).reshape(-1, 16)
+    if len(tr) == U - 1:
+        tr = np.concatenate([tr, np.eye(4).reshape(1, 16)])
+    assert len(tr) == U
+    tr = np.ascontiguousarray(tr)
+    counts = np.array([len(l) for l in ls], dtype=np.int32)
+    m = np.ascontiguousarray(np.concatenate(ls))
+    cap = int(counts.sum()) + 1  # every point comes from a track, every track from a match
+    n_points, n_frames, n_live = np.zeros(U, np.int32), np.zeros(U, np.int32), np.zeros(U, np.int32)
+    points, fwd, live = np.zeros((cap, 3), np.float32), np.zeros((U, U, 16), np.float64), np.zeros((cap, 2), np.int32)
+    pt, ml, md, ma = _recon_params(params)
+    rc = ref_lib().ref_recon_sequence(float(f), float(cu), float(cv), U, m.ctypes.data, _i32(counts), _f64(tr), pt, ml, md, ma, _i32(n_points),
+                                      _f32(points), cap, _i32(n_frames), _f64(fwd), _i32(n_live), _i32(live), cap)
+    if rc < 0:
+        raise ValueError("ref_recon_sequence: a negative feature index")
+    out, p0, l0 = [], 0, 0
+    for k in range(U):
+        out.append(dict(points=points[p0:p0 + n_points[k]].copy(), fwd=fwd[k, :n_frames[k]].reshape(-1, 4, 4).copy(),
+                        live=live[l0:l0 + n_live[k]].copy()))
+        p0 += int(n_points[k])
+        l0 += int(n_live[k])
+    return out
 
 
 class VoMonoParams(C.Structure):

@@ -22,6 +22,8 @@
 #include <string.h>
 #include <math.h>
 #include <vector>
+#include <deque>
+#include <list>
 #include <array>
 #include <iostream>
 #include <algorithm>
@@ -33,6 +35,7 @@
 #include "matcher.h"
 #include "viso_stereo.h"
 #include "viso_mono.h"
+#include "reconstruction.h"
 #undef private
 #undef protected
 #include "filter.h"
@@ -548,6 +551,168 @@ void ref_mono_fundamental(void *h, const void *m, int32_t n, const int32_t *acti
   vo->fundamentalMatrix(v, act, F);
   for (int i = 0; i < 3; i++)
     for (int j = 0; j < 3; j++) F9[i * 3 + j] = F.val[i][j];
+}
+
+}  // extern "C"
+
+// ---- Reconstruction (viso/reconstruction.{h,cpp}) ------------------------------------------------------------------
+namespace {
+Matrix mat44(const double *a) {
+  Matrix M(4, 4);
+  for (int i = 0; i < 4; i++)
+    for (int j = 0; j < 4; j++) M.val[i][j] = a[i * 4 + j];
+  return M;
+}
+// A Reconstruction whose `frames` deque holds the states 0 .. last, each made the way update() makes one
+// (reconstruction.cpp:60-69): inv = Matrix::inv(fwd), proj = K * inv.getMat(0,0,2,3), frames_ago by position from the back.
+Reconstruction *recon_with_states(double f, double cu, double cv, const double *fwd, int32_t last) {
+  Reconstruction *r = new Reconstruction();
+  r->setCalibration(f, cu, cv);
+  for (int32_t s = 0; s <= last; s++) {
+    Matrix F = mat44(fwd + 16 * s);
+    Matrix I = Matrix::inv(F);
+    r->frames.push_back(Reconstruction::frame_state_t(F, I, r->K * I.getMat(0, 0, 2, 3)));
+    r->frames.back().frames_ago = (unsigned)(last - s);
+  }
+  return r;
+}
+}  // namespace
+
+extern "C" {
+
+// The per-track driver: the class's own initPoint, pointType, refinePoint, pointDistance and rayAngle on tracks of the
+// caller's, in the order and with the gating of update() (reconstruction.cpp:121-139).  fwd: n_states 4x4 matrices; track t
+// has the pixels offsets[t] .. offsets[t + 1] - 1 of uv (u, v floats), its first_frame is state first_state[t] and its
+// last_frame the state n - 1 further on, which is the back of the deque as in update() (the deque then holds the states
+// 0 .. last).  stage, in the numbering of include/visomatch.h (vsm_triangulate_run): 3 too short, 4 initPoint failed,
+// 5 pointType below point_type, 6 / 7 refinePoint returned false - the class does not say why, so the driver calls
+// updatePoint once more at the point refinePoint left: 7 where that does not fail (the loop then used its 22 updates, since
+// a failed update leaves the point alone and would fail again), 6 where it fails (the loop stopped on a failed update, or it
+// used its 22 updates and the next would have failed), 8 not below max_dist, 9 not above min_angle, 0 kept.  xyz: the point as it stood then (zeros for 3, 4), xyz0: what initPoint
+// gave; type (-2 where not reached), dist, angle (0 where not reached); probe[t] = {x1c.z, x2c.z, x2r.y} of pointType's
+// affineTransform calls on xyz0 (zeros for 3, 4).  Returns 0, or -1 before anything is written where a track has no pixel
+// or names a state outside 0 .. n_states - 1.
+int32_t ref_recon_tracks(double f, double cu, double cv, int32_t n_states, const double *fwd, int32_t n_tracks,
+                         const int32_t *offsets, const float *uv, const int32_t *first_state, int32_t point_type,
+                         int32_t min_track_length, double max_dist, double min_angle, int32_t *stage, float *xyz, float *xyz0,
+                         int32_t *type, double *dist, double *angle, float *probe) {
+  for (int32_t t = 0; t < n_tracks; t++) {
+    const int32_t n = offsets[t + 1] - offsets[t];
+    if (n < 1 || first_state[t] < 0 || first_state[t] + n - 1 >= n_states) return -1;
+  }
+  std::vector<Reconstruction *> by_last((size_t)std::max(n_states, 0), (Reconstruction *)0);
+  for (int32_t t = 0; t < n_tracks; t++) {
+    const int32_t n = offsets[t + 1] - offsets[t], first = first_state[t], last = first + n - 1;
+    stage[t] = 0;
+    type[t] = -2;
+    dist[t] = angle[t] = 0;
+    for (int i = 0; i < 3; i++) xyz[t * 3 + i] = xyz0[t * 3 + i] = probe[t * 3 + i] = 0;
+    if (!by_last[last]) by_last[last] = recon_with_states(f, cu, cv, fwd, last);
+    Reconstruction *r = by_last[last];
+    Reconstruction::track tr;
+    for (int32_t i = offsets[t]; i < offsets[t + 1]; i++) tr.pixels.push_back(Reconstruction::point2d(uv[2 * i], uv[2 * i + 1]));
+    tr.first_frame = &r->frames[first];
+    tr.last_frame = &r->frames.back();
+    tr.last_idx = 0;
+    tr.refreshed = false;
+    if (n < min_track_length) {
+      stage[t] = 3;
+      continue;
+    }
+    Point3d p(0, 0, 0);
+    if (!r->initPoint(tr, p)) {
+      stage[t] = 4;
+      continue;
+    }
+    const Point3d p0 = p;
+    const Point3d x1c = affineTransform(tr.first_frame->inv, p0), x2c = affineTransform(tr.last_frame->inv, p0);
+    const Point3d x2r = affineTransform(r->Tr_cam_road, x2c);
+    probe[t * 3 + 0] = x1c.z;
+    probe[t * 3 + 1] = x2c.z;
+    probe[t * 3 + 2] = x2r.y;
+    xyz0[t * 3 + 0] = p0.x;
+    xyz0[t * 3 + 1] = p0.y;
+    xyz0[t * 3 + 2] = p0.z;
+    type[t] = r->pointType(tr, p);
+    if (type[t] >= point_type) {
+      if (r->refinePoint(tr, p)) {
+        dist[t] = r->pointDistance(tr, p);
+        if (dist[t] < max_dist) {
+          angle[t] = r->rayAngle(tr, p);
+          if (!(angle[t] > min_angle)) stage[t] = 9;
+        } else {
+          stage[t] = 8;
+        }
+      } else {
+        // refinePoint has freed its work arrays; updatePoint needs them
+        Point3d q = p;
+        const FLOAT step = 1, eps = 1e-5;
+        r->J = new FLOAT[6 * n];
+        r->p_observe = new FLOAT[2 * n];
+        r->p_predict = new FLOAT[2 * n];
+        stage[t] = r->updatePoint(tr, q, step, eps) == Reconstruction::FAILED ? 6 : 7;
+        delete[] r->J;
+        delete[] r->p_observe;
+        delete[] r->p_predict;
+      }
+    } else {
+      stage[t] = 5;
+    }
+    xyz[t * 3 + 0] = p.x;
+    xyz[t * 3 + 1] = p.y;
+    xyz[t * 3 + 2] = p.z;
+  }
+  for (size_t i = 0; i < by_last.size(); i++) delete by_last[i];
+  return 0;
+}
+
+// The real Reconstruction::update over a sequence: update k = 0 .. n_updates - 1 gets the counts[k] matches that follow
+// those of update k - 1 in `matches` (p_match records) and Tr[k] (4x4) as its rev_Tr; the caller ends the sequence with an
+// empty list, which finishes every track still alive.  After update k: n_points[k] points were appended by it - copied
+// here, before the next update transforms them, one after the other into points (x, y, z floats); the deque holds
+// n_frames[k] states, their fwd matrices front to back in fwd[(k * n_updates + i) * 16 ..]; n_live[k] tracks are alive,
+// {pixels, last_idx} each, one after the other in live, in the order of the class's list.  Returns the number of points,
+// or -1 with nothing run where a match has a negative i1p / i1c, or with the outputs incomplete where a capacity is short.
+int32_t ref_recon_sequence(double f, double cu, double cv, int32_t n_updates, const void *matches, const int32_t *counts,
+                           const double *Tr, int32_t point_type, int32_t min_track_length, double max_dist, double min_angle,
+                           int32_t *n_points, float *points, int32_t cap_points, int32_t *n_frames, double *fwd,
+                           int32_t *n_live, int32_t *live, int32_t cap_live) {
+  const Matcher::p_match *m = (const Matcher::p_match *)matches;
+  int64_t total = 0;
+  for (int32_t k = 0; k < n_updates; k++) {
+    if (counts[k] < 0) return -1;
+    total += counts[k];
+  }
+  for (int64_t i = 0; i < total; i++)
+    if (m[i].i1p < 0 || m[i].i1c < 0) return -1;
+  Reconstruction r;
+  r.setCalibration(f, cu, cv);
+  int32_t np = 0, nl = 0;
+  for (int32_t k = 0; k < n_updates; k++) {
+    std::vector<Matcher::p_match> v(m, m + counts[k]);
+    m += counts[k];
+    const size_t before = r.points.size();
+    r.update(v, mat44(Tr + 16 * k), point_type, min_track_length, max_dist, min_angle);
+    n_points[k] = (int32_t)(r.points.size() - before);
+    if (np + n_points[k] > cap_points) return -1;
+    for (size_t i = before; i < r.points.size(); i++, np++) {
+      points[np * 3 + 0] = r.points[i].x;
+      points[np * 3 + 1] = r.points[i].y;
+      points[np * 3 + 2] = r.points[i].z;
+    }
+    n_frames[k] = (int32_t)r.frames.size();
+    if (n_frames[k] > n_updates) return -1;
+    for (int32_t i = 0; i < n_frames[k]; i++)
+      for (int a = 0; a < 4; a++)
+        for (int b = 0; b < 4; b++) fwd[((size_t)(k * n_updates + i)) * 16 + a * 4 + b] = r.frames[i].fwd.val[a][b];
+    n_live[k] = (int32_t)r.tracks.size();
+    if (nl + n_live[k] > cap_live) return -1;
+    for (std::list<Reconstruction::track>::iterator it = r.tracks.begin(); it != r.tracks.end(); ++it, nl++) {
+      live[nl * 2 + 0] = (int32_t)it->pixels.size();
+      live[nl * 2 + 1] = it->last_idx;
+    }
+  }
+  return np;
 }
 
 }  // extern "C"
