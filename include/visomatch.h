@@ -674,6 +674,26 @@ int32_t vsm_debug_predicates(const uint32_t *quads, int32_t n, int32_t *out);
  * argument, or cap < n + 1). */
 int32_t vsm_debug_seq_plan(int32_t n_frames, int32_t pool_threads, int32_t host_in, int32_t seq_chunk, int32_t seq_first_chunk,
                            const char *plan, int32_t *chunk, int32_t *starts, int32_t cap);
+/* Test hooks of the matcher's device blocks (pure arithmetic, no GPU, no handle): where every array lies.
+ * vsm_debug_ctx_layout: the working set of nframes frame slots (two images each) and npairs frame pairs for frames of
+ * w x h pixels under *p, with the dense sets' head records (option match_heads) or without.  Returns what making that
+ * working set would: VSM_OK, VSM_EDIMS (a side of 16384 pixels or more, no pixel at the matching resolution) or VSM_EARG
+ * (match_binsize outside 1..32768 or more than 2^22 bins, nms_n outside 1..31; also a NULL or negative argument here).
+ * With VSM_OK scalars[8] = bytes of the device arena, bytes of the host-mapped result block, bytes from one pair's arrays
+ * to the next pair's, elements per plane of the filter responses, floats of a pair's prior boxes, capacity of the sparse
+ * and of the dense feature set, queries per pair; *n_rows = the number of arrays, and, if cap >= *n_rows, per array in
+ * the order they are placed rows[5] = block (0 the arena, 1 the host-mapped block), image or pair (-1: one per block),
+ * feature set (-1: none), byte offset in its block, bytes asked for, and its name in names[16] (as in csrc/vsm_ctx.h; at
+ * full resolution imgm is img: it has a row with img's offset and bytes).
+ * vsm_debug_dc2_layout: the same for the bank of a Delaunay chain with npairs lists of up to list_cap matches (the look-ahead
+ * call rounds that to 1024 before it gets here), with the host's vertex sort (keys and tie patches in host-mapped memory)
+ * or without; scalars[6] = bytes of the device block, of the host-mapped block, from one pair's device arrays to the next
+ * pair's, ints of a pair's tie patches, bytes from one pair's host keys to the next pair's, and the same for the patches.
+ * VSM_OK, or VSM_EARG for a NULL or negative argument. */
+int32_t vsm_debug_ctx_layout(const vsm_params *p, int32_t w, int32_t h, int32_t nframes, int32_t npairs, int32_t heads, int64_t *scalars,
+                             int64_t *rows, char *names, int32_t cap, int32_t *n_rows);
+int32_t vsm_debug_dc2_layout(int32_t npairs, int32_t list_cap, int32_t host_ties, int64_t *scalars, int64_t *rows, char *names, int32_t cap,
+                             int32_t *n_rows);
 /* Test hook of the batched forms' per-chunk job table (pure arithmetic, no GPU): a look-ahead call of matching method
  * `method` (0 flow, 1 stereo, 2 quad) over frames of `sides` images (1 or 2), cut into n_chunks chunks that start at
  * starts[0 .. n_chunks - 1] and end at starts[n_chunks] = the number of frames, with `banks` frame banks of `chunk` frames

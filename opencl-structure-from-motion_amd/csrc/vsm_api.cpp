@@ -28,6 +28,7 @@
 #include "vsm_internal.h"
 #include "vsm_jobs.h"
 #include "vsm_stage.h"
+#include "vsm_ctx.h"
 #include "vsm_layouts.h"
 #include "vsm_tracks.h"
 #include "vsm_points.h"
@@ -46,7 +47,6 @@
     }                                                                                             \
   } while (0)
 
-static inline int32_t bpl16(int32_t w) { return w + 15 - (w - 1) % 16; }  // viso/matcher.cpp:160
 // CPUs this process may actually use: the cgroup CPU quota (containers), else the hardware
 // thread count.  Spinning more threads than the quota only gets the whole process throttled.
 static int cpu_budget() {
@@ -77,32 +77,21 @@ static inline double now_us() {
 // ---------------------------------------------------------------------------------------
 // device working set
 // ---------------------------------------------------------------------------------------
-struct VsmCtx {
+// (the dimensions and capacities are its VsmGeom, the tables and host views that the layout binds its VsmCtxViews: vsm_ctx.h)
+struct VsmCtx : VsmGeom, VsmCtxViews {
   bool ready = false;
   bool has_heads = false;  // the dense sets carry head records (option match_heads at the time the context was made)
-  VsmDims dims{};
   int nframes = 0, npairs = 0;
   uint8_t *arena = nullptr;
   size_t arena_bytes = 0;
-  std::vector<VsmImage> h_imgs;  // image id = frame_slot*2 + side
-  VsmImage *d_imgs = nullptr;
-  std::vector<VsmPair> h_pairs;
-  VsmPair *d_pairs = nullptr;
-  VsmJob *d_jobs = nullptr;
-  int16_t *f1 = nullptr, *f2 = nullptr;  // transient filter responses of one feature launch
-  size_t f_stride = 0;
-  int32_t cap_set[2] = {0, 0};
-  size_t ranges_stride = 0;  // floats per pair
-  size_t pair_stride = 0;    // bytes from one pair's buffers (raw, lists, keys ...) to the next pair's
-  float *d_ranges = nullptr;
-  // pinned host memory.  hm_* is host-mapped: kernels write feature counts and exported match
-  // lists straight into it, so results need a stream sync but no D2H copy.
+  size_t pair_stride = 0;  // bytes from one pair's buffers (raw, lists, keys ...) to the next pair's
+  // pinned host memory; hm_block is host-mapped (the hm_* views)
   uint8_t *hm_block = nullptr;
-  int32_t *hm_counts = nullptr;  // [nframes*2 images][2 sets]
-  int32_t *hm_lcount = nullptr;  // [npairs][2]
-  std::vector<vsm_p_match *> hm_list1, hm_list2;  // host views, per pair
   float *h_ranges = nullptr;     // pinned [npairs][ranges_stride]
   VsmJob *h_jobs = nullptr;      // pinned [npairs]
+  // the context is made for frames of this size and holds this many frame slots and pairs (what else a call compares - its
+  // chunk size, the head records - stands at the call)
+  bool holds(int32_t w, int32_t h, int frames, int pairs) const { return ready && dims.w == w && dims.h == h && nframes == frames && npairs == pairs; }
 };
 
 // ---------------------------------------------------------------------------------------
@@ -227,194 +216,34 @@ static void ctx_destroy(VsmCtx &c) {
   c = VsmCtx();
 }
 
-static int nms_cells(int32_t len, int32_t n) {  // loop count of "for (i=n+margin; i<len-n-margin; i+=n+1)"
-  int32_t span = len - 2 * n - 2 * VSM_MARGIN;
-  return span > 0 ? (span + n) / (n + 1) : 0;
-}
-
 // One arena per context, zero-filled once, so row padding stays 0.
 static int ctx_create(VsmCtx &c, const vsm_params &p, int32_t w, int32_t hh, int nframes, int npairs, hipStream_t stream, bool heads) {
   ctx_destroy(c);
+  VsmGeom g;
+  const int rc = vsm_ctx_geometry(p, w, hh, g);
+  if (rc != VSM_OK) return rc;
+  const VsmCtxLayout L(g, p, nframes, npairs, heads);
+  static_cast<VsmGeom &>(c) = g;
   c.has_heads = heads;
-  VsmDims &d = c.dims;
-  d.w = w;
-  d.h = hh;
-  d.bpl = bpl16(w);
-  d.scale = p.half_resolution ? 2 : 1;
-  d.mw = p.half_resolution ? w / 2 : w;
-  d.mh = p.half_resolution ? hh / 2 : hh;
-  d.mbpl = p.half_resolution ? bpl16(d.mw) : d.bpl;
-  if (d.mw <= 0 || d.mh <= 0 || d.w >= 16384 || d.h >= 16384) return VSM_EDIMS;  // 14-bit coordinates
-  d.ub = (int32_t)ceilf((float)w / (float)p.match_binsize);
-  d.vb = (int32_t)ceilf((float)hh / (float)p.match_binsize);
-  const int nb = 4 * d.ub * d.vb;
-  if (p.match_binsize < 1 || p.match_binsize > 32768 || nb > (1 << 22)) {
-    fprintf(stderr, "visomatch: match_binsize %d is not usable (%d bins)\n", p.match_binsize, nb);
-    return VSM_EARG;
-  }
-  if (p.nms_n < 1 || p.nms_n > 31) {
-    fprintf(stderr, "visomatch: nms_n %d outside the supported range 1..31\n", p.nms_n);
-    return VSM_EARG;
-  }
-  int32_t ns = p.nms_n * 3;  // viso/matcher.cpp:685-687
-  if (ns > 10) ns = p.nms_n > 10 ? p.nms_n : 10;
-  const int32_t nn[2] = {ns, p.nms_n};
-  int32_t ncu[2], ncv[2];
-  for (int k = 0; k < 2; k++) {
-    ncu[k] = nms_cells(d.mw, nn[k]);
-    ncv[k] = nms_cells(d.mh, nn[k]);
-    c.cap_set[k] = 4 * ncu[k] * ncv[k];
-    if (c.cap_set[k] < 4) c.cap_set[k] = 4;
-  }
   c.nframes = nframes;
   c.npairs = npairs;
-  const int nimg = nframes * 2;
-  const size_t full = al256((size_t)d.bpl * d.h + 64), mres = al256((size_t)d.mbpl * d.mh + 64);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = off;
-    off += al256(bytes);
-    return o;
-  };
-  struct SetOff {
-    size_t feat, count, cand, cell_off, bin_start, bin_cnt, binid, s_idx, s_uv, s_desc, s_rank, tmp, heads;
-  };
-  struct ImgOff {
-    size_t img, imgm, du, dv, duvt;
-    SetOff set[2];
-  };
-  std::vector<ImgOff> io(nimg);
-  for (int i = 0; i < nimg; i++) {
-    io[i].img = take(full);
-    io[i].imgm = p.half_resolution ? take(mres) : io[i].img;
-    io[i].du = take(mres);
-    io[i].dv = take(mres);
-    io[i].duvt = p.half_resolution ? take((size_t)d.bpl * ((d.h + 7) & ~7) * 2 + 256) : 0;  // (+ one tile row of slack: windows load the tile to their right)
-    for (int k = 0; k < 2; k++) {
-      const size_t cap = c.cap_set[k];
-      io[i].set[k].feat = take(cap * 48);
-      io[i].set[k].count = take(4);
-      io[i].set[k].cand = take((size_t)(ncu[k] * ncv[k] + 1) * 16);
-      io[i].set[k].cell_off = take((size_t)(ncu[k] * ncv[k] + 2) * 4);
-      io[i].set[k].bin_start = take((size_t)(nb * VSM_VSUB + 1) * 4);
-      io[i].set[k].bin_cnt = take((size_t)(nb * VSM_VSUB + 1) * 4);
-      io[i].set[k].s_rank = take(cap * 4);
-      io[i].set[k].binid = take(cap * 4);
-      io[i].set[k].s_idx = take(cap * 4);
-      io[i].set[k].s_uv = take(cap * 8);
-      io[i].set[k].s_desc = take(cap * 32);
-      io[i].set[k].tmp = take(cap * 4);
-      io[i].set[k].heads = k == 1 && heads ? take((size_t)nb * VSM_VSUB * 64) : 0;
-    }
-  }
-  c.f_stride = mres;  // int16 elements per image plane
-  const size_t o_f1 = take(c.f_stride * 2 * nimg), o_f2 = take(c.f_stride * 2 * nimg);
-  const size_t qcap = (size_t)(c.cap_set[0] > c.cap_set[1] ? c.cap_set[0] : c.cap_set[1]);
-  c.ranges_stride = (size_t)d.ub * d.vb * 16;
-  struct PairOff {
-    size_t raw, flag, bc, l1, l2, cnt, pf, k1, k2;
-  };
-  std::vector<PairOff> po(npairs);
-  for (int j = 0; j < npairs; j++) {
-    po[j].raw = take(qcap * 48);
-    po[j].flag = take(qcap * 4);
-    po[j].bc = take((qcap / 256 + 2) * 4);
-    po[j].l1 = take((size_t)c.cap_set[0] * 48);
-    po[j].l2 = take(qcap * 48);
-    po[j].cnt = take(16);
-    po[j].pf = p.refinement == 2 ? take(qcap * 3 * 12 * 4) : 0;  // (per-frame ring: one pair; look-ahead banks: every pair)
-    // the chains' keys beside the lists they index (every pair takes the same room: one stride from pair to pair, pair_stride)
-    po[j].k1 = take((size_t)c.cap_set[0] * 8);
-    po[j].k2 = take(qcap * 8);
-  }
-  c.pair_stride = npairs > 0 ? (off - po[0].raw) / npairs : 0;
-  const size_t o_rng = take(c.ranges_stride * 4 * npairs);
-  const size_t o_imgs = take((size_t)nimg * sizeof(VsmImage));
-  const size_t o_pairs = take((size_t)npairs * sizeof(VsmPair));
-  const size_t o_jobs = take((size_t)npairs * sizeof(VsmJob));
-  c.arena_bytes = off;
+  c.pair_stride = L.pair_stride;
+  c.arena_bytes = L.arena.at;
   HIPCHK(vsm_dev_alloc((void **)&c.arena, c.arena_bytes));
   HIPCHK(hipMemsetAsync(c.arena, 0, c.arena_bytes, stream));
   // host-mapped result block: [image counts][list counts][list1, list2 per pair]
-  const size_t l1 = al256((size_t)c.cap_set[0] * 48), l2 = al256(qcap * 48);
-  const size_t hc = al256((size_t)nimg * 2 * 4), hl = al256((size_t)npairs * 2 * 4);
-  const size_t hm_bytes = hc + hl + (l1 + l2) * npairs;
-  HIPCHK(hipHostMalloc((void **)&c.hm_block, hm_bytes, hipHostMallocMapped));
-  memset(c.hm_block, 0, hc + hl);
+  HIPCHK(hipHostMalloc((void **)&c.hm_block, L.hm.at, hipHostMallocMapped));
+  memset(c.hm_block, 0, L.hm_zeroed);
   uint8_t *dblock = nullptr;
   HIPCHK(hipHostGetDevicePointer((void **)&dblock, c.hm_block, 0));
-  c.hm_counts = (int32_t *)c.hm_block;
-  c.hm_lcount = (int32_t *)(c.hm_block + hc);
   HIPCHK(hipHostMalloc((void **)&c.h_ranges, c.ranges_stride * 4 * npairs, hipHostMallocDefault));
   HIPCHK(hipHostMalloc((void **)&c.h_jobs, sizeof(VsmJob) * npairs, hipHostMallocDefault));
-  uint8_t *b = c.arena;
-  c.h_imgs.resize(nimg);
-  for (int i = 0; i < nimg; i++) {
-    VsmImage &im = c.h_imgs[i];
-    im.img = b + io[i].img;
-    im.imgm = b + io[i].imgm;
-    im.du = b + io[i].du;
-    im.dv = b + io[i].dv;
-    im.du_full = p.half_resolution ? nullptr : im.du;
-    im.dv_full = p.half_resolution ? nullptr : im.dv;
-    im.duv_tiled = p.half_resolution ? b + io[i].duvt : nullptr;
-    for (int k = 0; k < 2; k++) {
-      VsmSet &s = im.set[k];
-      s.feat = (int32_t *)(b + io[i].set[k].feat);
-      s.count = (int32_t *)(b + io[i].set[k].count);
-      s.count_host = (int32_t *)dblock + (i * 2 + k);
-      s.cand = (int32_t *)(b + io[i].set[k].cand);
-      s.cell_off = (int32_t *)(b + io[i].set[k].cell_off);
-      s.bin_start = (int32_t *)(b + io[i].set[k].bin_start);
-      s.bin_cnt = (int32_t *)(b + io[i].set[k].bin_cnt);
-      s.binid = (int32_t *)(b + io[i].set[k].binid);
-      s.s_rank = (int32_t *)(b + io[i].set[k].s_rank);
-      s.s_idx = (int32_t *)(b + io[i].set[k].s_idx);
-      s.s_uv = (uint32_t *)(b + io[i].set[k].s_uv);
-      s.s_desc = (uint4 *)(b + io[i].set[k].s_desc);
-      s.tmp = (int32_t *)(b + io[i].set[k].tmp);
-      s.heads = k == 1 && heads ? (uint4 *)(b + io[i].set[k].heads) : nullptr;
-      s.cap = c.cap_set[k];
-      s.nms_n = nn[k];
-      s.ncu = ncu[k];
-      s.ncv = ncv[k];
-    }
-  }
-  c.f1 = (int16_t *)(b + o_f1);
-  c.f2 = (int16_t *)(b + o_f2);
-  c.d_ranges = (float *)(b + o_rng);
-  c.h_pairs.resize(npairs);
-  c.hm_list1.resize(npairs);
-  c.hm_list2.resize(npairs);
-  for (int j = 0; j < npairs; j++) {
-    VsmPair &pr = c.h_pairs[j];
-    pr.raw = (vsm_p_match *)(b + po[j].raw);
-    pr.flag = (int32_t *)(b + po[j].flag);
-    pr.blockcnt = (int32_t *)(b + po[j].bc);
-    pr.list1 = (vsm_p_match *)(b + po[j].l1);
-    pr.list2 = (vsm_p_match *)(b + po[j].l2);
-    pr.count = (int32_t *)(b + po[j].cnt);
-    pr.ranges = c.d_ranges + (size_t)j * c.ranges_stride;
-    pr.pf = po[j].pf ? (int32_t *)(b + po[j].pf) : nullptr;
-    pr.keys[0] = (uint64_t *)(b + po[j].k1);
-    pr.keys[1] = (uint64_t *)(b + po[j].k2);
-    pr.key_cap[0] = c.cap_set[0];
-    pr.key_cap[1] = (int32_t)qcap;
-    const size_t lo = hc + hl + (l1 + l2) * j;
-    c.hm_list1[j] = (vsm_p_match *)(c.hm_block + lo);
-    c.hm_list2[j] = (vsm_p_match *)(c.hm_block + lo + l1);
-    pr.hlist1 = (vsm_p_match *)(dblock + lo);
-    pr.hlist2 = (vsm_p_match *)(dblock + lo + l1);
-    pr.hcount = (int32_t *)(dblock + hc) + 2 * j;
-  }
-  c.d_imgs = (VsmImage *)(b + o_imgs);
-  c.d_pairs = (VsmPair *)(b + o_pairs);
-  c.d_jobs = (VsmJob *)(b + o_jobs);
+  L.bind(c.arena, c.hm_block, dblock, c);
   {
     // (the tables cross by the copy kernel out of a page-locked twin, like every other host-to-device transfer of the path: a
     // runtime copy of more than 16 KB out of pageable memory that finds the DMA engine busy goes through a shader copy on a
     // hardware queue the runtime creates for it and keeps - DESIGN.md section 6)
-    const size_t bi = (size_t)nimg * sizeof(VsmImage), bp = (size_t)npairs * sizeof(VsmPair);
+    const size_t bi = c.h_imgs.size() * sizeof(VsmImage), bp = c.h_pairs.size() * sizeof(VsmPair);
     uint8_t *twin = nullptr;
     HIPCHK(hipHostMalloc((void **)&twin, al256(bi) + al256(bp), hipHostMallocDefault));
     memcpy(twin, c.h_imgs.data(), bi);
@@ -826,7 +655,7 @@ static int push_common(vsm_handle *h, const uint8_t *I1, const uint8_t *I2, int3
   }
   HIPCHK(hipSetDevice(h->device));
   VsmCtx &c = h->ring;
-  if (!c.ready || w != c.dims.w || hh != c.dims.h) {
+  if (!c.holds(w, hh, 2, 1)) {
     // a change of image size restarts the ring buffer (the reference would match across sizes)
     (void)hipStreamSynchronize(h->stream);
     reset_ring_state(h);

@@ -275,7 +275,47 @@ static void debug_job_row(int32_t *o, const VsmJob &jb, int valid, int32_t last)
   o[6] = last;
 }
 
+// the rows of vsm_debug_ctx_layout / vsm_debug_dc2_layout: block 0's arrays, then block 1's
+static int32_t debug_layout_rows(const VsmPlacer *const blocks[2], int64_t *rows, char *names, int32_t cap) {
+  const size_t n = blocks[0]->rows.size() + blocks[1]->rows.size();
+  if (n > (size_t)cap || !rows || !names) return (int32_t)n;
+  for (int b = 0; b < 2; b++)
+    for (const VsmPlacer::Row &r : blocks[b]->rows) {
+      const int64_t row[5] = {b, r.index, r.set, (int64_t)r.at, (int64_t)r.bytes};
+      memcpy(rows, row, sizeof(row));
+      strncpy(names, r.name, 16);
+      rows += 5, names += 16;
+    }
+  return (int32_t)n;
+}
+
 extern "C" {
+
+// ---- debug entries of the device blocks' layouts (vsm_ctx.h, vsm_layouts.h; include/visomatch.h) ----
+int32_t vsm_debug_ctx_layout(const vsm_params *p, int32_t w, int32_t hh, int32_t nframes, int32_t npairs, int32_t heads, int64_t *scalars,
+                             int64_t *rows, char *names, int32_t cap, int32_t *n_rows) {
+  if (!p || nframes < 0 || npairs < 0 || !scalars || !n_rows) return VSM_EARG;
+  VsmGeom g;
+  const int rc = vsm_ctx_geometry(*p, w, hh, g);
+  if (rc != VSM_OK) return rc;
+  const VsmCtxLayout L(g, *p, nframes, npairs, heads != 0);
+  const int64_t s[8] = {(int64_t)L.arena.at, (int64_t)L.hm.at, (int64_t)L.pair_stride, (int64_t)g.f_stride, (int64_t)g.ranges_stride, g.cap_set[0], g.cap_set[1], (int64_t)g.qcap};
+  memcpy(scalars, s, sizeof(s));
+  const VsmPlacer *const blocks[2] = {&L.arena, &L.hm};
+  *n_rows = debug_layout_rows(blocks, rows, names, cap);
+  return VSM_OK;
+}
+
+int32_t vsm_debug_dc2_layout(int32_t npairs, int32_t list_cap, int32_t host_ties, int64_t *scalars, int64_t *rows, char *names, int32_t cap,
+                             int32_t *n_rows) {
+  if (npairs < 0 || list_cap < 0 || !scalars || !n_rows) return VSM_EARG;
+  const Dc2Layout L(npairs, list_cap, host_ties != 0);
+  const int64_t s[6] = {(int64_t)L.dev.at, (int64_t)L.host.at, (int64_t)L.pair_stride, L.ties_stride, (int64_t)L.keys_pitch, (int64_t)L.ties_pitch};
+  memcpy(scalars, s, sizeof(s));
+  const VsmPlacer *const blocks[2] = {&L.dev, &L.host};
+  *n_rows = debug_layout_rows(blocks, rows, names, cap);
+  return VSM_OK;
+}
 
 // ---- debug entries of the batched forms' arithmetic (vsm_jobs.h; include/visomatch.h) ----
 int32_t vsm_debug_seq_plan(int32_t n_frames, int32_t pool_threads, int32_t host_in, int32_t seq_chunk, int32_t seq_first_chunk, const char *plan,
@@ -498,7 +538,7 @@ int32_t vsm_host_outliers_and_prior_threads(const vsm_params *p, const vsm_p_mat
 int32_t vsm_debug_dc2(const vsm_params *p, const vsm_p_match *list, int32_t n, int32_t method, int32_t gpu_ties, int32_t copies,
                       vsm_p_match *out, int32_t cap, float *ranges, int32_t w, int32_t hh, double *kernel_us) {
   if (copies < 1) copies = 1;
-  const int ub = (int)ceilf((float)w / (float)p->match_binsize), vb = (int)ceilf((float)hh / (float)p->match_binsize);
+  const int ub = (int)vsm_bins_along(w, p->match_binsize), vb = (int)vsm_bins_along(hh, p->match_binsize);
   if (ranges && ub * vb > 1024) return -2;
   Dc2Bank B;
   if (!B.reserve(copies, std::max(n, 64), true)) return -1;

@@ -2,9 +2,11 @@
 // type - and places it once - its count and the spare bytes behind it -, as a pure function of the call's counts.  No HIP
 // call is made here, so tools/stage_host_check.cpp checks the offsets on the CPU.  vsm_stage.h has the arrays' views.  The
 // joint adjustment's blocks also write their uploaded block (pack) and assign BaData (bind), for the device path and the host
-// view alike.
+// view alike.  Last comes the bank of a Delaunay chain of the look-ahead forms (Dc2Layout), stated the same way; a context's
+// blocks are vsm_ctx.h.
 #pragma once
 
+#include "vsm_dc_gpu.h"
 #include "vsm_stage.h"
 #include "vsm_tracks.h"
 #include "vsm_points.h"
@@ -141,5 +143,52 @@ struct TrkBlocks : VsmBlocks {
   void results(size_t n_tracks, size_t n_obs) {
     out = VsmLayout();
     counters.place(out, 4, 0); offsets.place(out, n_tracks + 1, 0); obs.place(out, 4 * n_obs, 0); track_of_match.place(out, n_edges, 0); flags.place(out, n_tracks, 0);
+  }
+};
+
+// one pair's device arrays of a chain's bank
+struct Dc2PairPtr {
+  uint64_t *keys_in, *key_sorted, *key;
+  uint32_t *kd, *pt;
+  int32_t *id, *tri, *mn, *support, *remap, *out_count;
+  VsmDcHull *hulls;
+};
+// The blocks of a Delaunay chain's bank (Dc2Bank) of npairs lists of up to cap matches: the device block - per pair the
+// chain's arrays, then the job table and the tie verdicts of k_dc2_ties [npairs][VSM_DC_TIE_OUT_INTS] - and the host-mapped
+// block - error words, list lengths and, with host_ties, per pair the keys the pool sorts and the patches it answers with.
+// The CPU suite pins it through vsm_debug_dc2_layout (tests/test_ctx_layout_cpu.py), tools/ctx_host_check.cpp checks bind().
+struct Dc2Layout {
+  struct Pair {
+    VsmArray<uint64_t> keys_in, key_sorted, key;
+    VsmArray<uint32_t> kd, pt;
+    VsmArray<int32_t> id, support, remap, tri, mn;
+    VsmArray<VsmDcHull> hulls;
+  };
+  std::vector<Pair> pair;
+  VsmArray<VsmDc2Job> jobs;
+  VsmArray<int32_t> ties, h_error, h_n;
+  VsmArray<uint8_t> h_keys, h_ties;  // [npairs] rows of keys_pitch / ties_pitch bytes
+  VsmPlacer dev, host;               // dev.at / host.at: the blocks' sizes
+  const int ties_stride;             // ints of a pair's patches: the count, then (carried, right) pairs
+  const size_t keys_pitch, ties_pitch;
+  size_t pair_stride = 0;  // bytes from one pair's device arrays to the next pair's
+
+  Dc2Layout(int npairs, int cap, bool host_ties)
+      : pair((size_t)npairs), ties_stride(cap + 2), keys_pitch(al256((size_t)cap * 8)), ties_pitch(al256((size_t)ties_stride * 4)) {
+    const size_t c = (size_t)cap;
+    for (int i = 0; i < npairs; i++) {
+      Pair &q = pair[i];
+      dev.put(q.keys_in, "keys_in", i, -1, c); dev.put(q.key_sorted, "key_sorted", i, -1, c); dev.put(q.key, "key", i, -1, c); dev.put(q.kd, "kd", i, -1, c * VSM_DC_KD_SCRATCH);
+      dev.put(q.pt, "pt", i, -1, c); dev.put(q.id, "id", i, -1, c); dev.put(q.support, "support", i, -1, c); dev.put(q.remap, "remap", i, -1, c); dev.put(q.tri, "tri", i, -1, c * 16);
+      dev.put(q.mn, "mn", i, -1, 16); dev.put(q.hulls, "hulls", i, -1, (size_t)2 << VSM_DC2_MAX_DEPTH);
+      pair_stride = dev.at - q.keys_in.at;
+    }
+    dev.put(jobs, "jobs", -1, -1, (size_t)npairs); dev.put(ties, "ties", -1, -1, (size_t)npairs * VSM_DC_TIE_OUT_INTS);
+    host.put(h_error, "h_error", -1, -1, 16); host.put(h_n, "h_n", -1, -1, (size_t)npairs);
+    if (host_ties) host.put(h_keys, "h_keys", -1, -1, keys_pitch * npairs), host.put(h_ties, "h_ties", -1, -1, ties_pitch * npairs);
+  }
+  Dc2PairPtr bind(uint8_t *b, int i) const {  // (out_count lies in the pair's mn)
+    const Pair &q = pair[i];
+    return {q.keys_in.in(b), q.key_sorted.in(b), q.key.in(b), q.kd.in(b), q.pt.in(b), q.id.in(b), q.tri.in(b), q.mn.in(b), q.support.in(b), q.remap.in(b), q.mn.in(b) + 4, q.hulls.in(b)};
   }
 };

@@ -82,14 +82,14 @@ int vsm_multi_process(vsm_multi *m, const uint8_t *left, const uint8_t *right, i
   const vsm_params &p = h->param;
   const int K = m->K, method = 2;
   VsmCtx &c = h->seq;
-  if (!c.ready || c.dims.w != w || c.dims.h != hh || c.npairs != K || c.nframes != 2 * K) {
+  if (!c.holds(w, hh, 2 * K, K)) {
     (void)hipStreamSynchronize(h->stream);
     const int rc = ctx_create(c, p, w, hh, 2 * K, K, h->stream, h->sw.match_heads != 0);
     if (rc != VSM_OK) return rc;
     h->seq_chunk = K;
     m->step = 0;
     for (auto &s : m->seq) s.have_prev = false;
-    if (!m->st.arena.alloc(al256((size_t)c.cap_set[1] * sizeof(vsm_p_match)), (size_t)K)) {
+    if (!m->st.arena.alloc(c.list_slot_bytes(), (size_t)K)) {
       c.ready = false;  // (the next call sets the context up again instead of running with half of it)
       return VSM_EHIP;
     }

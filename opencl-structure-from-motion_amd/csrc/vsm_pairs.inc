@@ -154,8 +154,7 @@ int vsm_pairs_run(vsm_handle *h, const uint8_t *left, const uint8_t *right, int6
   const int sides = right ? 2 : 1;
   PairsRingSave save;  // (armed by the first fallback; puts the caller's ring back however the call is left)
   // the statistics bins of k_dc2_prior live in LDS: a binning beyond 1024 bins goes pair by pair
-  if (p.match_binsize >= 1 &&
-      (size_t)ceilf((float)w / (float)p.match_binsize) * (size_t)ceilf((float)hh / (float)p.match_binsize) > 1024) {
+  if (vsm_match_bins(p, w, hh) > 1024) {
     const int rc = pairs_fallback(h, P, save, left, right, frame_stride, on_device, w, hh, bpl, method, pairs, 0, n_pairs, Tr, Tr_valid);
     P.timings[3] = now_us() - t0;
     P.done = rc == VSM_OK;
@@ -164,12 +163,12 @@ int vsm_pairs_run(vsm_handle *h, const uint8_t *left, const uint8_t *right, int6
   const int C = seq2_plan(n_pairs, h->pool->size(), false, h->sw.pairs_chunk, 0, nullptr).C;
   const int slots = (sides * n_frames + 1) / 2;  // (a context holds two images per frame slot)
   VsmCtx &c = P.ctx;
-  if (!c.ready || c.dims.w != w || c.dims.h != hh || c.nframes != slots || c.npairs != C || c.has_heads != (h->sw.match_heads != 0)) {
+  if (!c.holds(w, hh, slots, C) || c.has_heads != (h->sw.match_heads != 0)) {
     (void)hipStreamSynchronize(h->stream);
     const int rc = ctx_create(c, p, w, hh, slots, C, h->stream, h->sw.match_heads != 0);
     if (rc != VSM_OK) return rc;
     P.chunk = C;
-    if (!P.st.arena.alloc(al256((size_t)c.cap_set[1] * sizeof(vsm_p_match)), (size_t)C)) {
+    if (!P.st.arena.alloc(c.list_slot_bytes(), (size_t)C)) {
       c.ready = false;  // (the next call sets the context up again instead of running with half of it)
       return VSM_EHIP;
     }

@@ -420,7 +420,7 @@ static int sequence_run_v1(vsm_handle *h, const uint8_t *left, const uint8_t *ri
   int C = h->sw.seq_chunk > 0 ? h->sw.seq_chunk : 50;
   if (C > n_frames) C = n_frames;
   VsmCtx &c = h->seq;
-  if (!c.ready || c.dims.w != w || c.dims.h != hh || h->seq_chunk != C || c.npairs != 2 * C || c.nframes != 3 * C) {
+  if (!c.holds(w, hh, 3 * C, 2 * C) || h->seq_chunk != C) {
     (void)hipStreamSynchronize(h->stream);
     int rc = ctx_create(c, p, w, hh, 3 * C, 2 * C, h->stream, h->sw.match_heads != 0);  // three banks of frames, two of pairs
     if (rc != VSM_OK) return rc;

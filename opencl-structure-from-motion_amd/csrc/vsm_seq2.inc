@@ -28,13 +28,9 @@ struct Dc2Bank {
   uint64_t *h_keys = nullptr;                      // host views of the host-mapped block
   int32_t *h_n = nullptr, *h_ties = nullptr, *h_error = nullptr;
   int ties_stride = 0;
-  size_t pair_stride = 0;  // bytes from one pair's device arrays to the next pair's
-  struct PairPtr {
-    uint64_t *keys_in, *key_sorted, *key;
-    uint32_t *kd, *pt;
-    int32_t *id, *tri, *mn, *support, *remap, *out_count;
-    VsmDcHull *hulls;
-  };
+  size_t pair_stride = 0;                 // bytes from one pair's device arrays to the next pair's
+  size_t keys_pitch = 0, ties_pitch = 0;  // bytes from one pair's host keys / tie patches to the next pair's
+  using PairPtr = Dc2PairPtr;
   std::vector<PairPtr> pp;
   void release() {
     if (d_block) vsm_dev_free(d_block);
@@ -42,7 +38,6 @@ struct Dc2Bank {
     if (h_jobs) (void)hipHostFree(h_jobs);
     *this = Dc2Bank();
   }
-  static size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
   bool reserve(int pairs, int want_cap, bool with_host_ties) {
     if (pairs <= npairs && want_cap <= cap && (!with_host_ties || host_ties)) return true;
     const int ncap = std::max(((want_cap + 1023) / 1024) * 1024, cap), np = std::max(pairs, npairs);
@@ -51,55 +46,23 @@ struct Dc2Bank {
     npairs = np;
     cap = ncap;
     host_ties = ht;
-    const size_t c = (size_t)cap;
-    const size_t per = al(c * 8) * 3 + al(c * 4 * VSM_DC_KD_SCRATCH) + al(c * 4) * 4 + al(c * 64) + al(64) +
-                       al(sizeof(VsmDcHull) * (2u << VSM_DC2_MAX_DEPTH));
-    pair_stride = per;
-    const size_t d_bytes = per * npairs + al(sizeof(VsmDc2Job) * npairs) + al((size_t)npairs * VSM_DC_TIE_OUT_INTS * 4);
-    ties_stride = cap + 2;
-    const size_t h_bytes = al(64) + (ht ? (al(c * 8) + al((size_t)ties_stride * 4)) * npairs : 0) + al((size_t)npairs * 4);
-    if (vsm_dev_alloc((void **)&d_block, d_bytes) != hipSuccess || hipHostMalloc((void **)&h_block, h_bytes, hipHostMallocMapped) != hipSuccess ||
+    const Dc2Layout L(npairs, cap, ht);  // (vsm_layouts.h)
+    pair_stride = L.pair_stride, ties_stride = L.ties_stride, keys_pitch = L.keys_pitch, ties_pitch = L.ties_pitch;
+    if (vsm_dev_alloc((void **)&d_block, L.dev.at) != hipSuccess || hipHostMalloc((void **)&h_block, L.host.at, hipHostMallocMapped) != hipSuccess ||
         hipHostGetDevicePointer((void **)&h_block_dev, h_block, 0) != hipSuccess ||
         hipHostMalloc((void **)&h_jobs, sizeof(VsmDc2Job) * npairs, hipHostMallocDefault) != hipSuccess) {
       release();
       return false;
     }
-    memset(h_block, 0, h_bytes);
+    memset(h_block, 0, L.host.at);
     pp.resize(npairs);
     n_src.assign(npairs, nullptr);
-    uint8_t *b = d_block;
-    auto take = [&](size_t bytes) {
-      uint8_t *r = b;
-      b += al(bytes);
-      return r;
-    };
-    for (int i = 0; i < npairs; i++) {
-      PairPtr &q = pp[i];
-      q.keys_in = (uint64_t *)take(c * 8);
-      q.key_sorted = (uint64_t *)take(c * 8);
-      q.key = (uint64_t *)take(c * 8);
-      q.kd = (uint32_t *)take(c * 4 * VSM_DC_KD_SCRATCH);
-      q.pt = (uint32_t *)take(c * 4);
-      q.id = (int32_t *)take(c * 4);
-      q.support = (int32_t *)take(c * 4);
-      q.remap = (int32_t *)take(c * 4);
-      q.tri = (int32_t *)take(c * 64);
-      q.mn = (int32_t *)take(64);
-      q.out_count = q.mn + 4;
-      q.hulls = (VsmDcHull *)take(sizeof(VsmDcHull) * (2u << VSM_DC2_MAX_DEPTH));
-    }
-    d_jobs = (VsmDc2Job *)take(sizeof(VsmDc2Job) * npairs);
-    d_ties = (int32_t *)take((size_t)npairs * VSM_DC_TIE_OUT_INTS * 4);
-    size_t ho = 0;
-    h_error = (int32_t *)(h_block + ho);
-    ho += al(64);
-    h_n = (int32_t *)(h_block + ho);
-    ho += al((size_t)npairs * 4);
-    if (ht) {
-      h_keys = (uint64_t *)(h_block + ho);
-      ho += al(c * 8) * npairs;
-      h_ties = (int32_t *)(h_block + ho);
-    }
+    for (int i = 0; i < npairs; i++) pp[i] = L.bind(d_block, i);
+    d_jobs = L.jobs.in(d_block);
+    d_ties = L.ties.in(d_block);
+    h_error = L.h_error.in(h_block);
+    h_n = L.h_n.in(h_block);
+    if (ht) h_keys = (uint64_t *)L.h_keys.in(h_block), h_ties = (int32_t *)L.h_ties.in(h_block);
     return true;
   }
   // list length of job i as the host sees it: the word k_dc2_keys writes (min(count, cap)), or - jobs whose keys the
@@ -108,8 +71,8 @@ struct Dc2Bank {
   // device side declines a list beyond cap (k_dc2_prepare) whoever made its keys.
   std::vector<const int32_t *> n_src;  // per job; set by every fill_job
   int32_t list_n(int i) const { return n_src[i] ? *n_src[i] : h_n[i]; }
-  uint64_t *host_keys(int i) const { return (uint64_t *)((uint8_t *)h_keys + al((size_t)cap * 8) * i); }
-  int32_t *host_ties_of(int i) const { return (int32_t *)((uint8_t *)h_ties + al((size_t)ties_stride * 4) * i); }
+  uint64_t *host_keys(int i) const { return (uint64_t *)((uint8_t *)h_keys + keys_pitch * i); }
+  int32_t *host_ties_of(int i) const { return (int32_t *)((uint8_t *)h_ties + ties_pitch * i); }
   // a pool task: Triangle's vertex sort of list i from its keys in host-mapped memory - the number of (carried, right) index
   // patches and the patches into host_ties_of(i); none for a list the chain leaves alone or declines.  (sort_ties works on a
   // copy of its own: one pass over the keys, then cache-resident work)
@@ -763,7 +726,7 @@ struct Seq2Call {
 
   // set-up, in three steps that return VSM_OK, an error or VSM_SEQ2_DECLINED: the context and the streams ...
   int setup_streams() {
-    if (!c.ready || c.dims.w != w || c.dims.h != hh || h->seq_chunk != C || c.npairs != kPairBanks * C || c.nframes != kFrameBanks * C) {
+    if (!c.holds(w, hh, kFrameBanks * C, kPairBanks * C) || h->seq_chunk != C) {
       (void)hipStreamSynchronize(h->stream);
       int rc = ctx_create(c, p, w, hh, kFrameBanks * C, kPairBanks * C, h->stream, h->sw.match_heads != 0);
       if (rc != VSM_OK) return rc;
@@ -801,7 +764,7 @@ struct Seq2Call {
   int setup_results() {
     // result arena: one slot of `slot` matches per frame (no list is longer than its query count, which the host only
     // learns chunk by chunk: the dense feature capacity bounds it)
-    slot = ((size_t)c.cap_set[1] * sizeof(vsm_p_match) + 255) & ~(size_t)255;
+    slot = c.list_slot_bytes();
     if (S.res_bytes < slot * n_frames || S.res_frames < n_frames) {
       if (S.res) (void)hipHostFree(S.res);
       if (S.res_cnt) (void)hipHostFree(S.res_cnt);
@@ -1081,7 +1044,7 @@ struct Seq2Call {
         if (ties1_host) {
           hipStream_t ks = host_in ? c1 : S.ns;
           if (ks != c1) HIPCHK(hipStreamWaitEvent(ks, q.ev_p1, 0));
-          HIPCHK(hipMemcpy2DAsync(B.host_keys(0), Dc2Bank::al((size_t)B.cap * 8), c.h_pairs[first_pair].keys[0], c.pair_stride,
+          HIPCHK(hipMemcpy2DAsync(B.host_keys(0), B.keys_pitch, c.h_pairs[first_pair].keys[0], c.pair_stride,
                                   (size_t)std::min(std::max(q.max_nq[0], 1), B.cap) * 8, (size_t)n, hipMemcpyDeviceToHost, ks));
           HIPCHK(hipEventRecord(ev_keys, ks));
         } else {
@@ -1513,7 +1476,7 @@ struct Seq2Call {
         for (int pc = 0; pc < pieces; pc++) {
           const int r0 = ch->gpu_sorts + (int)((int64_t)lists * pc / pieces), r1 = ch->gpu_sorts + (int)((int64_t)lists * (pc + 1) / pieces);
           if (r1 > r0 && keys_dma)
-            HIPCHK(hipMemcpy2DAsync(B.host_keys(r0), Dc2Bank::al((size_t)B.cap * 8), fused ? c.h_pairs[first_pair + r0].keys[1] : B.pp[r0].keys_in,
+            HIPCHK(hipMemcpy2DAsync(B.host_keys(r0), B.keys_pitch, fused ? c.h_pairs[first_pair + r0].keys[1] : B.pp[r0].keys_in,
                                     fused ? c.pair_stride : B.pair_stride,
                                     (size_t)std::min(std::max(q.max_nq[1], 1), B.cap) * 8, (size_t)(r1 - r0), hipMemcpyDeviceToHost, ks));
           hipEvent_t ev = S.get_event();

@@ -182,6 +182,17 @@ struct VsmArray {
   }
   E *in(uint8_t *block) const { return (E *)(block + at); }  // the array in a copy of its block that starts at `block`
 };
+// A block being laid out: VsmLayout's offsets and, for the layout hooks, a row per array - its name, its image or pair (-1:
+// one per block), its feature set (-1: none), where it lies and the bytes asked for.
+struct VsmPlacer : VsmLayout {
+  struct Row { const char *name; int32_t index, set; size_t at, bytes; };
+  std::vector<Row> rows;
+  template <typename E>
+  void put(VsmArray<E> &a, const char *name, int index, int set, size_t count, size_t spare = 0) {
+    a.place(*this, count, spare);
+    rows.push_back({name, index, set, a.at, count * sizeof(E) + spare});
+  }
+};
 // an array of the device block alone: a working set behind the uploaded block
 template <typename E>
 struct VsmDev : VsmArray<E> {

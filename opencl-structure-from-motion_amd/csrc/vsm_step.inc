@@ -84,7 +84,7 @@ static int vsm_step_run(vsm_handle *h, VsmCtx &c, VsmStep &S, int reserve, int n
       B.fill_job(i, c.h_pairs[i].list1, c.h_pairs[i].count, false, nullptr, nullptr, c.h_pairs[i].ranges, nullptr, false, fused_keys ? c.h_pairs[i].keys[0] : nullptr, c.hm_lcount + 2 * i);
     if (fused_keys) {  // the chain's job table first, the keys from the compaction - also into host-mapped memory (see above)
       VSM_CHK(vsm_upload(h->stream, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * n));
-      const VsmKeyOut ko = {B.dev_of(B.host_keys(0)), Dc2Bank::al((size_t)B.cap * 8), B.cap};
+      const VsmKeyOut ko = {B.dev_of(B.host_keys(0)), B.keys_pitch, B.cap};
       vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, n, c.dims, cfg, max_nq[0], 0, nullptr, &ko);
     } else {
       vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, n, c.dims, cfg, max_nq[0]);
@@ -109,7 +109,7 @@ static int vsm_step_run(vsm_handle *h, VsmCtx &c, VsmStep &S, int reserve, int n
                fused_keys ? c.h_pairs[i].keys[1] : nullptr, c.hm_lcount + 2 * i + 1);
   if (fused_keys) {
     VSM_CHK(vsm_upload(h->stream, B.d_jobs, B.h_jobs, sizeof(VsmDc2Job) * n));
-    const VsmKeyOut ko = {B.dev_of(B.host_keys(0)), Dc2Bank::al((size_t)B.cap * 8), B.cap};
+    const VsmKeyOut ko = {B.dev_of(B.host_keys(0)), B.keys_pitch, B.cap};
     vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, n, c.dims, cfg, max_nq[1], 0, nullptr, &ko);
   } else {
     vsm_launch_match(h->stream, h->prof, c.d_imgs, d_pairs, d_jobs, dummy, n, c.dims, cfg, max_nq[1]);

@@ -37,7 +37,7 @@ EXPORTS = ["vsm_default_params", "vsm_create", "vsm_destroy", "vsm_set_intrinsic
            "vsm_num_features", "vsm_get_features", "vsm_set_stage_capture", "vsm_stage_size", "vsm_stage_get",
            "vsm_num_ranges", "vsm_get_ranges", "vsm_get_gradients", "vsm_get_filter_responses", "vsm_get_counters",
            "vsm_get_timings", "vsm_set_profiling", "vsm_num_kernels", "vsm_kernel_name", "vsm_get_kernel_stats",
-           "vsm_host_delaunay", "vsm_host_delaunay_split", "vsm_debug_delaunay_gpu", "vsm_debug_dc_bench", "vsm_host_ties", "vsm_debug_ties_gpu", "vsm_host_outliers_and_prior", "vsm_host_outliers_and_prior_threads", "vsm_debug_dc2", "vsm_debug_dc2_band_factor", "vsm_debug_predicates", "vsm_debug_seq_plan", "vsm_debug_chunk_jobs", "vsm_debug_pair_jobs", "vsm_debug_refine", "vsm_debug_refine_check", "vsm_debug_parabolic_apply", "vsm_host_parabolic_fits", "vsm_debug_compact_keys", "vsm_local_cpus", "vsm_forkjoin_cpus", "vsm_device_pool_stats", "vsm_device_pool_trim", "vsm_sequence_run", "vsm_sequence_num_matches", "vsm_sequence_get_matches",
+           "vsm_host_delaunay", "vsm_host_delaunay_split", "vsm_debug_delaunay_gpu", "vsm_debug_dc_bench", "vsm_host_ties", "vsm_debug_ties_gpu", "vsm_host_outliers_and_prior", "vsm_host_outliers_and_prior_threads", "vsm_debug_dc2", "vsm_debug_dc2_band_factor", "vsm_debug_predicates", "vsm_debug_ctx_layout", "vsm_debug_dc2_layout", "vsm_debug_seq_plan", "vsm_debug_chunk_jobs", "vsm_debug_pair_jobs", "vsm_debug_refine", "vsm_debug_refine_check", "vsm_debug_parabolic_apply", "vsm_host_parabolic_fits", "vsm_debug_compact_keys", "vsm_local_cpus", "vsm_forkjoin_cpus", "vsm_device_pool_stats", "vsm_device_pool_trim", "vsm_sequence_run", "vsm_sequence_num_matches", "vsm_sequence_get_matches",
            "vsm_sequence_get_timings", "vsm_sequence_path", "vsm_pairs_run", "vsm_pairs_num_matches", "vsm_pairs_get_matches", "vsm_pairs_get_timings",
            "vsm_tracks_run", "vsm_pairs_tracks", "vsm_tracks_count", "vsm_tracks_num_obs", "vsm_tracks_get", "vsm_tracks_of_matches",
            "vsm_tracks_get_stats", "vsm_tracks_get_timings", "vsm_host_tracks",
@@ -202,6 +202,8 @@ def lib():
         L.vsm_debug_dc2.argtypes = [C.POINTER(VsmParams), vp, i32, i32, i32, i32, vp, i32, vp, i32, i32, vp]
         L.vsm_debug_dc2_band_factor.argtypes = [i32]
         L.vsm_debug_predicates.argtypes = [vp, i32, vp]
+        L.vsm_debug_ctx_layout.argtypes = [C.POINTER(VsmParams), i32, i32, i32, i32, i32, vp, vp, vp, i32, vp]
+        L.vsm_debug_dc2_layout.argtypes = [i32, i32, i32, vp, vp, vp, i32, vp]
         L.vsm_debug_seq_plan.argtypes = [i32, i32, i32, i32, i32, C.c_char_p, vp, vp, i32]
         L.vsm_debug_chunk_jobs.restype = i32
         L.vsm_debug_chunk_jobs.argtypes = [i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp]
@@ -585,6 +587,29 @@ def device_predicates(quads):
     if lib().vsm_debug_predicates(packed.ctypes.data_as(C.c_void_p), len(q), out.ctypes.data_as(C.c_void_p)) != 0:
         raise VisoMatchError("vsm_debug_predicates: HIP error")
     return out
+
+
+def _layout(call, n_scalars):
+    """a layout hook's answer: (return code, scalars, [(name, block, index, set, offset, bytes) per array, as placed])"""
+    scalars, n = np.zeros(n_scalars, dtype=np.int64), C.c_int32(0)
+    rc = call(scalars.ctypes.data_as(C.c_void_p), None, None, 0, C.addressof(n))
+    rows, names = np.zeros((n.value, 5), dtype=np.int64), np.zeros(n.value, dtype="S16")
+    if rc == 0:
+        rc = call(scalars.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p), names.ctypes.data_as(C.c_void_p), n.value, C.addressof(n))
+    return rc, scalars.tolist(), [(nm.decode(),) + tuple(r) for nm, r in zip(names.tolist(), rows.tolist())]
+
+
+def ctx_layout(params, w, h, nframes, npairs, heads=False):
+    """test hook (no GPU): the device arena (block 0) and the host-mapped result block (block 1) of a working set of nframes
+    frame slots and npairs pairs - (return code, [arena bytes, host-mapped bytes, pair_stride, f_stride, ranges_stride,
+    cap_set[0], cap_set[1], qcap], rows); with a code other than 0 the rest is empty"""
+    return _layout(lambda *a: lib().vsm_debug_ctx_layout(C.byref(params), w, h, nframes, npairs, int(bool(heads)), *a), 8)
+
+
+def dc2_layout(npairs, cap, host_ties):
+    """test hook (no GPU): the device block (0) and the host-mapped block (1) of a Delaunay chain's bank - (return code,
+    [device bytes, host-mapped bytes, pair_stride, ties_stride, host keys' pitch, tie patches' pitch], rows)"""
+    return _layout(lambda *a: lib().vsm_debug_dc2_layout(npairs, cap, int(bool(host_ties)), *a), 6)
 
 
 def seq_plan(n_frames, pool_threads, host_in=False, seq_chunk=0, seq_first_chunk=0, plan=None):
