@@ -516,6 +516,96 @@ int32_t vsm_host_adjust(int32_t n_frames, const double *poses, const uint8_t *po
                         const uint8_t *use, const vsm_adjust_params *params, int32_t *frame_status, double *out_poses, int32_t *rows,
                         int32_t *active, int32_t *track_status, double *out_xyz, double *cost_before, double *cost_after, double *lambda,
                         int32_t *cg_iters, int32_t *cg_end, int32_t *accepted, int32_t *round_active, int32_t *n_rounds, int64_t *stats16);
+/* ---- location of frames without a pose against the points ----
+ * The call that gives a frame a pose: every stage behind the motions takes pose_valid and has a status of its own for a frame
+ * without one, this one estimates the pose of every asked-for frame from its observations of known 3-D points alone -
+ * RANSAC over a linear six-point resection, inliers counted by the resection's row test, the winner handed to the
+ * resection's update loop.  No counterpart in the reference.  csrc/vsm_locate.h is the one statement of the arithmetic (every
+ * product, every sum and its order); what follows is the contract.
+ * Input: what vsm_resect_run takes without poses and pose_valid - n_frames; locate, a byte per frame (NULL: all frames); f, cu,
+ * cv; the tracks (offsets[T + 1], obs_frames, uv); xyz[T][3]; use[T] bytes (NULL: all).
+ * A frame's ROWS are the resection's rows in the resection's grouping and order.  A row is ELIGIBLE if u, v and the three
+ * coordinates of its point are finite; E is the frame's number of eligible rows, and position q in [0, E) names the q-th
+ * eligible row in row order.
+ * Sampling (host): every located frame owns a minstd state (x <- 16807 x mod 2^31 - 1) that starts at seed mod 2^31 - 1, or
+ * at 1 where that is 0.  Hypothesis k = 0, 1, .. draws six distinct positions in [0, E) the way the egomotion's
+ * getRandomSample draws: a partial Fisher-Yates on the identity deck of E cards, draw i (i = 0..5) uniform in [i, E - 1] by
+ * std::uniform_int_distribution's rejection on the engine, the deck put back after each hypothesis.  No process-wide sampler is
+ * read, so frame order, chunking and thread count cannot matter.
+ * Fit, per (frame, hypothesis), from the six sampled rows i = 0..5 in sample order:
+ *  1. x = (u - cu) / f, y = (v - cv) / f, in double.
+ *  2. m = (((((X0 + X1) + X2) + X3) + X4) + X5) / 6 per coordinate; s = the largest |coordinate - m| over the eighteen.  The
+ *     hypothesis is INVALID if s is not above zero or not below infinity (six identical points; an overflowed mean).  X' = (X - m) / s.
+ *  3. The 12 x 12 matrix A, zero but for: row 2i = [X' 1, 0 0 0 0, -x X' -x], row 2i + 1 = [0 0 0 0, X' 1, -y X' -y].
+ *  4. Its singular value decomposition by Matrix::svd's arithmetic (vsm_la::svd_nr), which leaves the singular values in
+ *     decreasing order, equal ones in the order the routine's shell sort leaves them; p = column 11 of V, the right singular
+ *     vector of the smallest singular value - picked exactly as the fundamental-matrix fit picks its ninth column.
+ *  5. M = the left 3 x 3 block of p read as 3 x 4 (M[i][j] = p[4 i + j]); M = U diag(w) V^T by the same routine; R0 = U V^T
+ *     (every entry summed over k ascending from the k = 0 product); d = det R0 by cofactors along row 0; sigma = 1 if d > 0,
+ *     else -1; R = sigma R0; lambda = sigma (3 / ((w0 + w1) + w2)).
+ *  6. tw[i] = (lambda p[4 i + 3]) s - ((R[i][0] m0 + R[i][1] m1) + R[i][2] m2).
+ * The state [R | tw] is world to camera, as the resection's.  The hypothesis is VALID if its twelve numbers are finite and
+ * all six sampled rows have zc > min_depth at it; an invalid hypothesis counts 0.
+ * Count: the number of the frame's eligible rows that the resection would use at [R | tw] with max_residual =
+ * inlier_threshold and min_depth (zc > min_depth and ru^2 + rv^2 < inlier_threshold^2).
+ * Winner: the first hypothesis with strictly more inliers than all before it (none if every count is 0).
+ * Refinement: the winner's state becomes the LINEAR POSE by the rigid inverse, as the resection forms poses, and is handed to
+ * the resection exactly as a caller would hand it: refine = this frame alone, max_residual = inlier_threshold,
+ * min_observations = min_inliers, max_updates, eps and min_depth as given.  So the located poses equal vsm_host_resect's
+ * from the linear poses byte for byte.
+ * Per frame, the first status that applies wins:
+ *   1  not asked for (locate == 0)
+ *   2  E < min_inliers
+ *   3  no valid hypothesis
+ *   4  the winner counts fewer than min_inliers (or every count is 0)
+ *   5  the resection ended in its status 4 or 5: the pose is the linear one
+ *   6  not converged after max_updates updates: the estimate as it stands
+ *   0  located
+ * Results per frame: status; pose[12], camera to world, zeros for 1..4; linear_pose[12], zeros where there is no winner;
+ * best, the winner's index or -1; inliers, the winner's count; rows; eligible = E (0 for status 1); updates, used, ss_after as
+ * the resection reports them (0 for 1..4); rms_after, libm's sqrt(ss_after / used) applied by the host (status 0, 6; else 0).
+ * Known limit: the linear six-point fit is degenerate for coplanar points (the matrix then has a null space of four
+ * dimensions, and the vector the decomposition returns is an arbitrary member of it): a planar scene ends in status 3 or 4. */
+typedef struct vsm_locate_params {
+  int32_t ransac_iters;     /* 200; at least 1 */
+  double inlier_threshold;  /* 2.0 pixels; positive and finite */
+  int32_t min_inliers;      /* 10; at least 6 */
+  double min_depth;         /* 1e-10 */
+  uint32_t seed;            /* 71 */
+  int32_t max_updates;      /* 20; at least 1 */
+  double eps;               /* 1e-8; positive and finite */
+} vsm_locate_params;
+void vsm_locate_default_params(vsm_locate_params *p);
+/* The general form, on the caller's arrays.  Runs on the handle's device and stream: the host groups the rows by frame as the
+ * resection does, finds the eligible rows and draws the samples on the pool (timed with the packing), one copy up (per frame
+ * 16 bytes, per row 12, per track 24, per (located frame, hypothesis) 24, per tile of 256 rows 8), the kernels - a 16-lane
+ * group per (frame, hypothesis) for the fit, (tiles of 256 rows) x (runs of 16 hypotheses) for the counts, a workgroup per
+ * frame for the winner, the resection's kernel on the device-resident linear poses -, one copy back (236 bytes per frame),
+ * one wait.  It has no CPU path.  VSM_EARG, nothing enqueued and the last result kept: what vsm_resect_run rejects for
+ * these arrays, params NULL, ransac_iters < 1, inlier_threshold not positive or not finite, min_inliers < 6, max_updates < 1,
+ * eps not positive or not finite.  VSM_EHIP after a HIP error.  Nothing else of the handle is touched. */
+int vsm_locate_run(vsm_handle *h, int32_t n_frames, const uint8_t *locate, double f, double cu, double cv, int32_t n_tracks, const int32_t *offsets,
+                   const int32_t *obs_frames, const float *uv, const double *xyz, const uint8_t *use, const vsm_locate_params *params);
+/* The same on the handle's last track and point results, found exactly as vsm_points_resect finds them (lists, counts: as
+ * there); VSM_ENOTREADY and VSM_EARG as there, with params as above.  Both results stay as they are. */
+int vsm_points_locate(vsm_handle *h, const vsm_p_match *const *lists, const int32_t *counts, const uint8_t *locate, double f, double cu, double cv,
+                      const vsm_locate_params *params);
+/* the handle's last location result: the number of frames; the arrays (any may be NULL; returns the number of frames):
+ * status[F], poses[F][12], linear_poses[F][12], best[F], inliers[F], rows[F], eligible[F], updates[F], used[F], ss_after[F],
+ * rms_after[F] */
+int32_t vsm_locate_count(vsm_handle *h);
+int32_t vsm_locate_get(vsm_handle *h, int32_t *status, double *poses, double *linear_poses, int32_t *best, int32_t *inliers, int32_t *rows,
+                       int32_t *eligible, int32_t *updates, int32_t *used, double *ss_after, double *rms_after);
+/* frames per status value 0..6 */
+void vsm_locate_get_stats(vsm_handle *h, int64_t *out7);
+/* wall-clock split of the last call, microseconds: {gather + grouping + sampling + packing, upload, kernels, download + host part} */
+void vsm_locate_get_timings(vsm_handle *h, double *out4);
+/* The same definition on one host thread: no GPU, no handle (the CPU suite's subject, the device path's second opinion and the
+ * benchmark's baseline - not a fallback).  Returns n_frames, or VSM_EARG with the output arrays untouched.  Outputs may be NULL. */
+int32_t vsm_host_locate(int32_t n_frames, const uint8_t *locate, double f, double cu, double cv, int32_t n_tracks, const int32_t *offsets,
+                        const int32_t *obs_frames, const float *uv, const double *xyz, const uint8_t *use, const vsm_locate_params *params,
+                        int32_t *status, double *poses, double *linear_poses, int32_t *best, int32_t *inliers, int32_t *rows, int32_t *eligible,
+                        int32_t *updates, int32_t *used, double *ss_after, double *rms_after);
 /* Measurement / test switches of a handle.  They are read from the environment once, by vsm_create (VSM_SEQ_V2,
  * VSM_SEQ_CHUNK, VSM_SEQ_DC_STREAMS, VSM_SEQ_SERIAL, VSM_SEQ_GPU_SORTS, VSM_SEQ_EARLY_EXPORT, VSM_FUSED_KEYS); this call changes one
  * afterwards: name = the variable's name without the VSM_ prefix, in lower case ("seq_serial", "seq_chunk", ...).

@@ -33,6 +33,7 @@
 #include "vsm_tracks.h"
 #include "vsm_points.h"
 #include "vsm_resect.h"
+#include "vsm_locate.h"
 #include "vsm_ba.h"
 #include "vsm_vet.h"
 #include "vsm_motions.h"
@@ -425,6 +426,7 @@ struct vsm_handle {
   struct VsmResect *resect = nullptr;  // pose refinement against the points (vsm_resect.inc): staging, device block, last result
   struct VsmVet *vet = nullptr;        // vetting of observations (vsm_vet.inc): staging, device block, last result
   struct VsmAdjust *adjust = nullptr;  // joint adjustment of poses and points (vsm_ba.inc): staging, device block, last result
+  struct VsmLocate *locate = nullptr;  // location of frames against the points (vsm_locate.inc): staging, device block, last result
   struct VsmMotions *motions = nullptr;  // monocular pair motions (vsm_motions_api.inc): staging, device block, last result
   struct VsmTracks *tracks = nullptr;  // feature tracks from pair match lists (vsm_tracks.inc): staging, device block, last result
 
@@ -461,6 +463,7 @@ static void points_destroy(vsm_handle *h);  // vsm_points.inc
 static void resect_destroy(vsm_handle *h);  // vsm_resect.inc
 static void vet_destroy(vsm_handle *h);     // vsm_vet.inc
 static void adjust_destroy(vsm_handle *h);  // vsm_ba.inc
+static void locate_destroy(vsm_handle *h);  // vsm_locate.inc
 static void motions_destroy(vsm_handle *h);  // vsm_motions_api.inc
 
 extern "C" {
@@ -557,6 +560,7 @@ void vsm_destroy(vsm_handle *h) {
   resect_destroy(h);
   vet_destroy(h);
   adjust_destroy(h);
+  locate_destroy(h);
   motions_destroy(h);
   ctx_destroy(h->ring);
   ctx_destroy(h->seq);
@@ -1049,6 +1053,7 @@ static int seq_ingest_host_frames(vsm_handle *h, VsmCtx &c, int first_img, const
 #include "vsm_resect.inc"
 #include "vsm_vet.inc"
 #include "vsm_ba.inc"
+#include "vsm_locate.inc"
 #include "vsm_motions_api.inc"
 extern "C" {
 
@@ -1265,7 +1270,7 @@ static const char *kKernelNames[VSM_K_COUNT] = {
     "k_trk_init", "k_trk_hook", "k_trk_flatten", "k_trk_keep", "k_trk_scan_reduce", "k_trk_scan_top", "k_trk_scan_apply", "k_trk_match_tracks", "k_trk_fill",
     "k_trk_order_wave", "k_trk_order_block", "k_pts_triangulate", "k_rs_resect", "k_vet_obs", "k_vet_emit",
     "k_ba_init", "k_ba_linearise", "k_ba_tracks", "k_ba_frames<rhs>", "k_ba_cg_init", "k_ba_op_tracks", "k_ba_frames<op>", "k_ba_cg_step", "k_ba_back",
-    "k_ba_trial_cost", "k_ba_decide", "k_ba_commit", "k_ba_finish"};
+    "k_ba_trial_cost", "k_ba_decide", "k_ba_commit", "k_ba_finish", "k_locate_fit", "k_locate_count", "k_locate_winner"};
 
 void vsm_set_profiling(vsm_handle *h, int on) {
   h->prof.on = on != 0;

@@ -335,23 +335,6 @@ void pose_matrix(const double *tr, double *T) {  // transformationVectorToMatrix
 void vsm_sampler_lock() { g_sampler.mu.lock(); }
 void vsm_sampler_unlock() { g_sampler.mu.unlock(); }
 uint32_t vsm_sampler_between(uint32_t lo, uint32_t hi) { return g_sampler.between(lo, hi); }
-VsmDrawPlan vsm_sampler_plan(uint32_t lo, uint32_t hi) {
-  VsmDrawPlan p;
-  const uint64_t engine_span = 2147483645ull, want = (uint64_t)hi - lo;
-  p.lo = lo;
-  if (engine_span > want) {
-    const uint64_t cells = want + 1;
-    p.per_cell = engine_span / cells;
-    p.reject_from = cells * p.per_cell;
-    p.magic = p.per_cell > 1 ? UINT64_MAX / p.per_cell + 1 : 0;
-    if (p.per_cell == 1) p.per_cell = 0;  // division by one: nothing to do
-  } else {
-    p.per_cell = 0;
-    p.reject_from = UINT64_MAX;
-    p.magic = 0;
-  }
-  return p;
-}
 uint32_t vsm_sampler_draw(const VsmDrawPlan &p) { return g_sampler.between(p); }
 void vsm_pose_matrix(const double *tr6, double *T16) { pose_matrix(tr6, T16); }
 

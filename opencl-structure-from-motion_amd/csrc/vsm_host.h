@@ -95,7 +95,25 @@ struct VsmDrawPlan {  // a (lo, hi) range with the divisions of the distribution
   uint64_t per_cell, reject_from, magic;
   uint32_t lo;
 };
-VsmDrawPlan vsm_sampler_plan(uint32_t lo, uint32_t hi);
+// (inline: a pure function, which the host views that own their engine - the batched mono estimate, the location - take without
+// the process-wide sampler's unit)
+inline VsmDrawPlan vsm_sampler_plan(uint32_t lo, uint32_t hi) {
+  VsmDrawPlan p;
+  const uint64_t engine_span = 2147483645ull, want = (uint64_t)hi - lo;
+  p.lo = lo;
+  if (engine_span > want) {
+    const uint64_t cells = want + 1;
+    p.per_cell = engine_span / cells;
+    p.reject_from = cells * p.per_cell;
+    p.magic = p.per_cell > 1 ? UINT64_MAX / p.per_cell + 1 : 0;
+    if (p.per_cell == 1) p.per_cell = 0;  // division by one: nothing to do
+  } else {
+    p.per_cell = 0;
+    p.reject_from = UINT64_MAX;
+    p.magic = 0;
+  }
+  return p;
+}
 uint32_t vsm_sampler_draw(const VsmDrawPlan &p);          // call with the lock held
 // the same draw from an engine state of the caller's own (seed 71 = a fresh process of the reference): what the process-wide
 // sampler runs on its state, and what every pair of a batched mono estimate (vsm_motions.inc) runs on its own

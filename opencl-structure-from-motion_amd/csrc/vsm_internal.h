@@ -120,6 +120,8 @@ enum VsmKernelId {
   // joint adjustment of poses and points (vsm_ba.hip)
   VSM_K_BA_INIT, VSM_K_BA_LINEARISE, VSM_K_BA_TRACKS, VSM_K_BA_RHS, VSM_K_BA_CG_INIT, VSM_K_BA_OP_TRACKS, VSM_K_BA_OP_FRAMES, VSM_K_BA_CG_STEP, VSM_K_BA_BACK,
   VSM_K_BA_TRIAL_COST, VSM_K_BA_DECIDE, VSM_K_BA_COMMIT, VSM_K_BA_FINISH,
+  // location of frames against the points (vsm_locate.hip; the refinement is VSM_K_RS_RESECT)
+  VSM_K_LC_FIT, VSM_K_LC_COUNT, VSM_K_LC_WINNER,
   VSM_K_COUNT
 };
 struct VsmProf {

@@ -13,6 +13,7 @@
 #include "vsm_resect.h"
 #include "vsm_vet.h"
 #include "vsm_ba.h"
+#include "vsm_locate.h"
 
 // vsm_points.inc: F frames, T tracks, N observations
 struct PtsBlocks : VsmBlocks {
@@ -119,6 +120,29 @@ struct BaBlocks : VsmBlocks {
     d.hist_d = hist_d.in(o); d.hist_i = hist_i.in(o);
     d.f = f; d.cu = cu; d.cv = cv; d.prm = prm; d.n_frames = (int32_t)valid.n; d.n_tracks = (int32_t)use.n;
     return d;
+  }
+};
+
+// vsm_locate.inc: F frames, T tracks, R rows, J jobs (frames with hypotheses, at the most), K hypotheses per job, NT tiles of
+// 256 rows (at the most); the hypotheses' states, validity and counts and the refinement's mask lie behind the results and
+// are not copied back.  The resection's kernel refines in place: its inputs are lin_poses and lin_valid, its results rs_*.
+struct LcBlocks : VsmBlocks {
+  VsmIn<int32_t> row_off, frame_job, job_frame, job_E, picks;
+  VsmIn<RsRow> rows;
+  VsmIn<double> xyz;
+  VsmIn<LcTile> tiles;
+  VsmOut<int32_t> verdict, best, inliers, rs_status, rs_updates, rs_used_before, rs_used, counts;
+  VsmOut<double> lin_poses, rs_poses, rs_ss_before, rs_ss_after, states;
+  VsmOut<uint8_t> hvalid, lin_valid;
+  LcBlocks(size_t F, size_t T, size_t R, size_t J, size_t K, size_t NT) {
+    row_off.place(in, F + 1, 0); frame_job.place(in, F, 4); job_frame.place(in, J, 4); job_E.place(in, J, 4); rows.place(in, R, 4); xyz.place(in, 3 * T, 8);
+    tiles.place(in, NT, 8); picks.place(in, J * K * LC_SAMPLE, 4);
+    verdict.place(out, F, 4); best.place(out, F, 4); inliers.place(out, F, 4); lin_poses.place(out, 12 * F, 8); rs_status.place(out, F, 4);
+    rs_updates.place(out, F, 4); rs_used_before.place(out, F, 4); rs_used.place(out, F, 4); rs_poses.place(out, 12 * F, 8); rs_ss_before.place(out, F, 8);
+    rs_ss_after.place(out, F, 8);
+    VsmLayout work = out;
+    states.place(work, J * K * 12, 8); counts.place(work, J * K, 4); hvalid.place(work, J * K, 1); lin_valid.place(work, F, 1);
+    out_behind_in(work.at);
   }
 };
 

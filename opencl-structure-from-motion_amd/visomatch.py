@@ -48,7 +48,9 @@ EXPORTS = ["vsm_default_params", "vsm_create", "vsm_destroy", "vsm_set_intrinsic
            "vsm_vet_default_params", "vsm_vet_run", "vsm_points_vet", "vsm_vet_count", "vsm_vet_get_obs", "vsm_vet_get_tracks", "vsm_vet_get_frames",
            "vsm_vet_get_kept", "vsm_vet_get_stats", "vsm_vet_get_timings", "vsm_host_vet", "vsm_tracks_pixels",
            "vsm_adjust_default_params", "vsm_adjust_run", "vsm_points_adjust", "vsm_adjust_count", "vsm_adjust_get_frames", "vsm_adjust_get_tracks",
-           "vsm_adjust_get_history", "vsm_adjust_get_stats", "vsm_adjust_get_timings", "vsm_host_adjust", "vsm_set_option", "vsm_version", "vsm_host_register", "vsm_host_unregister",
+           "vsm_adjust_get_history", "vsm_adjust_get_stats", "vsm_adjust_get_timings", "vsm_host_adjust",
+           "vsm_locate_default_params", "vsm_locate_run", "vsm_points_locate", "vsm_locate_count", "vsm_locate_get", "vsm_locate_get_stats",
+           "vsm_locate_get_timings", "vsm_host_locate", "vsm_set_option", "vsm_version", "vsm_host_register", "vsm_host_unregister",
            "vsm_multi_create", "vsm_multi_destroy", "vsm_multi_process", "vsm_multi_num_sequences", "vsm_multi_get_motion",
            "vsm_multi_motion_valid", "vsm_multi_num_matches", "vsm_multi_get_matches", "vsm_multi_num_inliers", "vsm_multi_get_inliers",
            "vsm_multi_get_timings",
@@ -103,6 +105,11 @@ class VsmAdjustParams(C.Structure):
     _fields_ = [("min_observations", C.c_int32), ("min_track_observations", C.c_int32), ("max_rounds", C.c_int32), ("cg_iters", C.c_int32),
                 ("lambda0", C.c_double), ("lambda_min", C.c_double), ("lambda_max", C.c_double), ("cg_tol", C.c_double), ("ftol", C.c_double),
                 ("max_residual", C.c_double), ("min_depth", C.c_double)]
+
+
+class VsmLocateParams(C.Structure):
+    _fields_ = [("ransac_iters", C.c_int32), ("inlier_threshold", C.c_double), ("min_inliers", C.c_int32), ("min_depth", C.c_double), ("seed", C.c_uint32),
+                ("max_updates", C.c_int32), ("eps", C.c_double)]
 
 
 def host_register(arr):
@@ -271,6 +278,18 @@ def lib():
         L.vsm_host_adjust.argtypes = [i32, vp, vp, vp, f64, f64, f64, i32, vp, vp, vp, vp, vp, C.POINTER(VsmAdjustParams)] + [vp] * 15
         L.vsm_host_resect.restype = i32
         L.vsm_host_resect.argtypes = [i32, vp, vp, vp, f64, f64, f64, i32, vp, vp, vp, vp, vp, C.POINTER(VsmResectParams)] + [vp] * 9
+        L.vsm_locate_default_params.argtypes = [C.POINTER(VsmLocateParams)]
+        L.vsm_locate_default_params.restype = None
+        L.vsm_locate_run.argtypes = [vp, i32, vp, f64, f64, f64, i32, vp, vp, vp, vp, vp, C.POINTER(VsmLocateParams)]
+        L.vsm_points_locate.argtypes = [vp, vp, vp, vp, f64, f64, f64, C.POINTER(VsmLocateParams)]
+        L.vsm_locate_count.argtypes = [vp]
+        L.vsm_locate_get.argtypes = [vp] + [vp] * 11
+        L.vsm_locate_get_stats.argtypes = [vp, vp]
+        L.vsm_locate_get_stats.restype = None
+        L.vsm_locate_get_timings.argtypes = [vp, vp]
+        L.vsm_locate_get_timings.restype = None
+        L.vsm_host_locate.restype = i32
+        L.vsm_host_locate.argtypes = [i32, vp, f64, f64, f64, i32, vp, vp, vp, vp, vp, C.POINTER(VsmLocateParams)] + [vp] * 11
         L.vsm_vet_default_params.argtypes = [C.POINTER(VsmVetParams)]
         L.vsm_vet_default_params.restype = None
         L.vsm_vet_run.argtypes = [vp, i32, vp, vp, f64, f64, f64, i32, vp, vp, vp, vp, vp, C.POINTER(VsmVetParams)]
@@ -1068,6 +1087,65 @@ def host_adjust(poses, f, cu, cv, offsets, obs_frames, uv, xyz, use=None, refine
     return Adjustment(*fa, *ta, _adjust_history(ha, n.value), dict(zip(ADJUST_STATS, stats.tolist())))
 
 
+LOCATE_STATUS = ("located", "not_asked", "too_few_eligible", "no_valid_hypothesis", "too_few_inliers", "linear_only", "not_converged")
+LOCATE_TIMINGS = ("group_sample_us", "upload_us", "kernels_us", "download_host_us")
+LOCATE_ARRAYS = ("status", "poses", "linear_poses", "best", "inliers", "rows", "eligible", "updates", "used", "ss_after", "rms_after")
+
+
+class Location:
+    """located frames (include/visomatch.h, vsm_locate_run): per frame status [F] int32 (0 = located, LOCATE_STATUS names the
+    values), poses and linear_poses [F, 12] float64 camera to world (zeros where there is none), best (the winning hypothesis or
+    -1), inliers (its count), rows, eligible, updates, used [F] int32, ss_after, rms_after [F] float64; stats: frames per status
+    name, timings: dict (both empty for the host view)."""
+
+    def __init__(self, status, poses, linear_poses, best, inliers, rows, eligible, updates, used, ss_after, rms_after, stats=None, timings=None):
+        self.status, self.poses, self.linear_poses, self.best, self.inliers = status, poses, linear_poses, best, inliers
+        self.rows, self.eligible, self.updates, self.used, self.ss_after, self.rms_after = rows, eligible, updates, used, ss_after, rms_after
+        self.stats, self.timings = stats or {}, timings or {}
+
+    def __len__(self):
+        return len(self.status)
+
+    def located(self):
+        """the frames that have a refined pose: status 0, or 6 (the estimate as it stands after max_updates)"""
+        return (self.status == 0) | (self.status == 6)
+
+
+def locate_params(**kw):
+    """vsm_locate_default_params with fields overridden by keyword"""
+    return _default_params(VsmLocateParams, "vsm_locate_default_params", kw)
+
+
+def _locate_arrays(F):
+    return (np.zeros(F, np.int32), np.zeros((F, 12), np.float64), np.zeros((F, 12), np.float64), np.zeros(F, np.int32), np.zeros(F, np.int32),
+            np.zeros(F, np.int32), np.zeros(F, np.int32), np.zeros(F, np.int32), np.zeros(F, np.int32), np.zeros(F, np.float64), np.zeros(F, np.float64))
+
+
+def _locate_inputs(n_frames, locate, offsets, obs_frames, uv, xyz, use):
+    F = int(n_frames)
+    lo = _mask(locate, max(F, 0))
+    off = np.ascontiguousarray(offsets, dtype=np.int32)
+    fr = np.ascontiguousarray(obs_frames, dtype=np.int32)
+    px = np.ascontiguousarray(np.asarray(uv, dtype=np.float32).reshape(-1, 2))
+    pt = None if xyz is None else np.ascontiguousarray(np.asarray(xyz, dtype=np.float64).reshape(-1, 3))
+    us = None if use is None else np.ascontiguousarray(use, dtype=np.uint8)
+    assert pt is None or len(pt) >= len(off) - 1
+    assert us is None or len(us) >= len(off) - 1
+    return F, lo, off, fr, px, pt, us
+
+
+def host_locate(n_frames, f, cu, cv, offsets, obs_frames, uv, xyz, use=None, locate=None, params=None, n_tracks=None):
+    """vsm_host_locate: every asked-for frame located against the points on one host thread - no GPU.  The tracks and xyz as for
+    host_resect; locate [F]: a mask (None: all frames); params: a dict of vsm_locate_params fields or the struct; n_tracks:
+    override len(offsets) - 1 (argument tests).  Returns a Location object; raises VisoMatchError on VSM_EARG."""
+    F, lo, off, fr, px, pt, us = _locate_inputs(n_frames, locate, offsets, obs_frames, uv, xyz, use)
+    out = _locate_arrays(max(F, 0))
+    got = _check(lib().vsm_host_locate(F, _ptr(lo), float(f), float(cu), float(cv), _n_tracks(off, n_tracks), _ptr(off), _ptr(fr), _ptr(px), _ptr(pt), _ptr(us),
+                                       _params_ref(VsmLocateParams, locate_params, params), *[_ptr(a) for a in out]), "vsm_host_locate")
+    assert got == F
+    return Location(*out)
+
+
 _NO_PARAMS = object()  # params=_NO_PARAMS: a NULL params pointer (argument tests)
 
 
@@ -1600,6 +1678,31 @@ class Matcher:
         rc = lib().vsm_points_adjust(self.h, ptrs, _ptr(cnt), _ptr(po), _ptr(pv), _ptr(rf), float(f), float(cu), float(cv),
                                      _params_ref(VsmAdjustParams, adjust_params, params))
         return self._adjust_result(rc, "vsm_points_adjust")
+
+    # --- frames without a pose located against the points ------------------------------------------
+    def _locate_result(self, rc, what):
+        L = lib()
+        _check(rc, what)
+        out = _locate_arrays(L.vsm_locate_count(self.h))
+        L.vsm_locate_get(self.h, *[_ptr(a) for a in out])
+        return Location(*out, *_stage_dicts(self.h, L.vsm_locate_get_stats, LOCATE_STATUS, L.vsm_locate_get_timings, LOCATE_TIMINGS))
+
+    def locate(self, n_frames, f, cu, cv, offsets, obs_frames, uv, xyz, use=None, locate=None, params=None, n_tracks=None):
+        """vsm_locate_run: every asked-for frame's pose from its observations of the points alone, on the device - RANSAC over a
+        linear six-point resection, the winner refined by the resection.  The tracks and xyz as for resect; locate [F]: a mask
+        (None: all frames); params: a dict of vsm_locate_params fields or the struct.  Returns a Location object."""
+        F, lo, off, fr, px, pt, us = _locate_inputs(n_frames, locate, offsets, obs_frames, uv, xyz, use)
+        rc = lib().vsm_locate_run(self.h, F, _ptr(lo), float(f), float(cu), float(cv), _n_tracks(off, n_tracks), _ptr(off), _ptr(fr), _ptr(px), _ptr(pt), _ptr(us),
+                                  _params_ref(VsmLocateParams, locate_params, params))
+        return self._locate_result(rc, "vsm_locate_run")
+
+    def locate_points(self, f, cu, cv, locate=None, lists=None, params=None, counts=None):
+        """vsm_points_locate: the same on the handle's last track and point results (the kept points; lists as for
+        track_points)."""
+        lo = None if locate is None else _mask(locate, len(locate) if self._track_frames is None else self._track_frames)
+        ls, ptrs, cnt = _optional_lists(lists, counts)
+        rc = lib().vsm_points_locate(self.h, ptrs, _ptr(cnt), _ptr(lo), float(f), float(cu), float(cv), _params_ref(VsmLocateParams, locate_params, params))
+        return self._locate_result(rc, "vsm_points_locate")
 
     def track_pixels(self, lists=None, counts=None):
         """vsm_tracks_pixels: (obs_frames [n_obs] int32, uv [n_obs, 2] float32) of the handle's last track result, the pixels

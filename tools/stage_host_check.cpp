@@ -140,6 +140,38 @@ static void check_adjust(size_t F, size_t T, size_t R, size_t N, size_t M) {
   CHECK(sizeof(BaRow) == 16 && sizeof(BaCtl) == 80 && L.lin.n == 26 * N && L.cg.n == 36 * F && L.hist_d.n == 3 * M && L.ctl.n == 1);
 }
 
+// F frames, T tracks, R rows, J jobs, K hypotheses per job, NT tiles
+static void check_locate(size_t F, size_t T, size_t R, size_t J, size_t K, size_t NT) {
+  const LcBlocks L(F, T, R, J, K, NT);
+  VsmLayout in, out;
+  SAME(L.row_off, in, (F + 1) * 4);
+  SAME(L.frame_job, in, F * 4 + 4);
+  SAME(L.job_frame, in, J * 4 + 4);
+  SAME(L.job_E, in, J * 4 + 4);
+  SAME(L.rows, in, R * sizeof(RsRow) + 4);
+  SAME(L.xyz, in, T * 24 + 8);
+  SAME(L.tiles, in, NT * 8 + 8);
+  SAME(L.picks, in, J * K * 24 + 4);
+  SAME(L.verdict, out, F * 4 + 4);
+  SAME(L.best, out, F * 4 + 4);
+  SAME(L.inliers, out, F * 4 + 4);
+  SAME(L.lin_poses, out, F * 96 + 8);
+  SAME(L.rs_status, out, F * 4 + 4);
+  SAME(L.rs_updates, out, F * 4 + 4);
+  SAME(L.rs_used_before, out, F * 4 + 4);
+  SAME(L.rs_used, out, F * 4 + 4);
+  SAME(L.rs_poses, out, F * 96 + 8);
+  SAME(L.rs_ss_before, out, F * 8 + 8);
+  SAME(L.rs_ss_after, out, F * 8 + 8);
+  VsmLayout work = out;  // behind the results, not copied back
+  SAME(L.states, work, J * K * 96 + 8);
+  SAME(L.counts, work, J * K * 4 + 4);
+  SAME(L.hvalid, work, J * K + 1);
+  SAME(L.lin_valid, work, F + 1);
+  CHECK(L.in.at == in.at && L.out.at == out.at && L.out_at == al256(in.at) && L.dev_bytes == al256(in.at) + work.at);
+  CHECK(sizeof(LcTile) == 8 && L.picks.n == 6 * J * K && L.states.n == 12 * J * K && L.lin_poses.n == 12 * F && L.tiles.n == NT);
+}
+
 // P pairs, F frames, E matches; then N nodes; then the totals the device reports
 static void check_tracks(size_t P, size_t F, size_t E, size_t N, size_t n_tracks, size_t n_obs) {
   TrkBlocks L(P, F, E);
@@ -375,7 +407,10 @@ int main() {
           for (size_t n : counts) check_adjust(a, b, c, c + n, n + 1);
           for (size_t n : counts) check_bind(a, b, c, c + n, n + 1);
           for (size_t n : counts) check_tracks(a, b, c, n, std::min(n, b), n);
+          for (size_t n : counts) check_locate(a, b, c, std::min(a, n), n + 1, c / 256 + n);
         }
+    check_locate(5, 257, big, 5, 200, big / 256 + 5);
+    check_locate(1 << 20, 257, 5, 1 << 20, 4096, 5);  // the hypotheses' states pass 2^38 bytes
     check_points(5, 257, big);
     check_resect(5, 257, big);
     check_vet(5, 257, big);
