@@ -838,6 +838,50 @@ int32_t vsm_host_parabolic_fits(const int32_t *records, int32_t n, float *uv, in
 int32_t vsm_debug_compact_keys(int32_t method, int32_t pass, int32_t P, const int32_t *n_query, const int32_t *const *flag,
                                const vsm_p_match *const *raw, const int32_t *key_cap, int32_t old_keys, vsm_p_match *const *list_out,
                                int32_t *count_out, uint64_t *const *keys_out);
+/* Test hooks of the location's stages (vsm_locate_run above has the definition): the host view's stages alone, and the three
+ * kernels k_locate_fit, k_locate_count and k_locate_winner one by one.  The hooks take rows without tracks: row r of a frame
+ * has the pixel rows_uv[r] and the point rows_xyz[r].  VSM_OK, VSM_EARG (nothing is touched, the device included), or
+ * VSM_EHIP from a device hook.
+ * Host side, one frame, no GPU:
+ *   sample: picks[K][6] = the positions hypothesis 0 .. K - 1 of a frame with E eligible rows draws (6 <= E, 1 <= K).
+ *   fit:    states[K][12] and valid[K] of the hypotheses picks[K][6] (row indices in [0, n_rows), eligible rows the caller's
+ *           business).  states[k] is written whenever step 2 accepts the sample - also for a hypothesis that is invalid
+ *           because its state is not finite or a sampled point is not in front - and is UNSPECIFIED (left as it was) where
+ *           step 2 refuses it: an overflowed mean, or six identical points whose mean in doubles is the point again (where
+ *           the sum of six x, rounded step by step, over 6 is an ulp off x, s is that ulp, the sample goes on and its state is
+ *           arbitrary).
+ *   count:  counts[k] = the eligible rows among the n_rows that vote for states[k]; 0 where valid[k] is 0.
+ * Device side, each ONE launch of one kernel with the call's launch geometry, on allocations of the hook's own: n_frames
+ * frames of rows (row_off[n_frames + 1], rows_uv[R][2], rows_xyz[R][3]) and n_jobs jobs, job j on frame job_frame[j] with
+ * job_E[j] eligible rows (0: a job without hypotheses), K hypotheses each; at most 2^22 (job, hypothesis) pairs.
+ *   fit:    picks[n_jobs][K][6], row indices in the job's frame.  states[n_jobs][K][12] and hvalid[n_jobs][K] go up as the
+ *           caller filled them and come back, so what the kernel leaves alone - a job with job_E = 0, the state of a
+ *           refused sample - is found again.
+ *   count:  states and hvalid given; the tiles are built as the call builds them.  The kernel only ADDS to counts: whoever
+ *           launches it clears them first, as vsm_locate_run does before its launches.  The hook clears once and launches
+ *           `launches` (1 or 2) times: with 2 every count comes back doubled.
+ *   winner: frame_job[n_frames] (-1: not a job), job_E[n_jobs], counts, hvalid and states given, min_inliers; per frame
+ *           verdict (-1 no job or job_E = 0, else 3 / 4 / 0), best, inliers, lin_poses[12] and lin_valid.
+ * vsm_debug_locate_hypotheses: the tables of the handle's last vsm_locate_run / vsm_points_locate as the call left them, at
+ * the call's own launch geometry - n_jobs and n_hyps; picks[n_jobs][K][6] from the pinned block that went up (row indices in
+ * the frame), states, hvalid and counts from the device block behind the results.  Any array may be NULL (a first call for
+ * the sizes).  The jobs are the asked-for frames with at least min_inliers rows, in frame order; a job with fewer than
+ * min_inliers eligible rows has no hypotheses and its entries are unspecified.  VSM_ENOTREADY: the handle holds no location. */
+int32_t vsm_host_locate_sample(uint32_t seed, int32_t E, int32_t K, int32_t *picks);
+int32_t vsm_host_locate_fit(double f, double cu, double cv, double min_depth, int32_t n_rows, const float *rows_uv, const double *rows_xyz,
+                            const int32_t *picks, int32_t K, double *states, uint8_t *valid);
+int32_t vsm_host_locate_count(double f, double cu, double cv, int32_t n_rows, const float *rows_uv, const double *rows_xyz, const double *states,
+                              const uint8_t *valid, int32_t K, double inlier_threshold, double min_depth, int32_t *counts);
+int32_t vsm_debug_locate_fit(double f, double cu, double cv, double min_depth, int32_t n_frames, const int32_t *row_off, const float *rows_uv,
+                             const double *rows_xyz, int32_t n_jobs, const int32_t *job_frame, const int32_t *job_E, const int32_t *picks, int32_t K,
+                             double *states, uint8_t *hvalid);
+int32_t vsm_debug_locate_count(double f, double cu, double cv, int32_t n_frames, const int32_t *row_off, const float *rows_uv, const double *rows_xyz,
+                               int32_t n_jobs, const int32_t *job_frame, const int32_t *job_E, int32_t K, const double *states, const uint8_t *hvalid,
+                               double inlier_threshold, double min_depth, int32_t launches, int32_t *counts);
+int32_t vsm_debug_locate_winner(int32_t n_frames, const int32_t *frame_job, int32_t n_jobs, const int32_t *job_E, int32_t K, int32_t min_inliers,
+                                const int32_t *counts, const uint8_t *hvalid, const double *states, int32_t *verdict, int32_t *best, int32_t *inliers,
+                                double *lin_poses, uint8_t *lin_valid);
+int32_t vsm_debug_locate_hypotheses(vsm_handle *h, int32_t *picks, double *states, uint8_t *hvalid, int32_t *counts, int32_t *n_jobs, int32_t *n_hyps);
 
 /* ---- stereo visual odometry on top of the matcher ----
  * class VisualOdometryStereo, viso/viso_stereo.h:28-88 + viso/viso.h:28-131: process() =

@@ -12,7 +12,15 @@
 //   k_locate_winner  one block per frame: the maximum of (count << 32 | ~k) - the largest count at the smallest k -, whether
 //                    any hypothesis was valid, the verdict, and the winner's state inverted to a pose where the resection's
 //                    kernel reads it.
-// No floating-point atomic; the counts are integer sums, which have no order.
+// No floating-point atomic; the counts are integer sums, which have no order.  k_locate_count only adds: whoever launches it
+// clears the counts first (vsm_locate.inc before the call's launches, vsm_debug_locate_count before its own).
+// Behind the kernels: the three launches, stated once, and the test hooks that run one of them alone (include/visomatch.h).
+#include <stdio.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
 #include "vsm_internal.h"
 #include "vsm_locate.h"
 #include "vsm_svd_coop.h"
@@ -152,22 +160,222 @@ __global__ void __launch_bounds__(256) k_locate_winner(LcDevice d) {
 
 }  // namespace
 
+// the three launches: their geometry is stated here once, for the call and for the test hooks below
+static void launch_fit(hipStream_t s, const LcDevice &d) {
+  const size_t total = (size_t)d.n_jobs * d.prm.ransac_iters;
+  hipLaunchKernelGGL(k_locate_fit, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, s, d);
+}
+static void launch_count(hipStream_t s, const LcDevice &d) {
+  const int K = d.prm.ransac_iters;
+  const int hyps = std::max(16, (K + 65534) / 65535);
+  hipLaunchKernelGGL(k_locate_count, dim3((unsigned)d.n_tiles, (unsigned)((K + hyps - 1) / hyps)), dim3(256), 0, s, d, hyps);
+}
+static void launch_winner(hipStream_t s, const LcDevice &d) { hipLaunchKernelGGL(k_locate_winner, dim3((unsigned)d.n_frames), dim3(256), 0, s, d); }
+
 void vsm_locate_launch(hipStream_t s, VsmProf &pf, const LcDevice &d) {
   if (d.n_frames <= 0) return;
-  const int K = d.prm.ransac_iters;
-  const size_t total = (size_t)d.n_jobs * K;
-  if (total > 0) {
+  if ((size_t)d.n_jobs * d.prm.ransac_iters > 0) {
     pf.begin(VSM_K_LC_FIT, s);
-    hipLaunchKernelGGL(k_locate_fit, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, s, d);
+    launch_fit(s, d);
     pf.end(s);
   }
   if (d.n_tiles > 0) {
-    const int hyps = std::max(16, (K + 65534) / 65535);
     pf.begin(VSM_K_LC_COUNT, s);
-    hipLaunchKernelGGL(k_locate_count, dim3((unsigned)d.n_tiles, (unsigned)((K + hyps - 1) / hyps)), dim3(256), 0, s, d, hyps);
+    launch_count(s, d);
     pf.end(s);
   }
   pf.begin(VSM_K_LC_WINNER, s);
-  hipLaunchKernelGGL(k_locate_winner, dim3((unsigned)d.n_frames), dim3(256), 0, s, d);
+  launch_winner(s, d);
   pf.end(s);
 }
+
+// ---- test hooks (include/visomatch.h, the debug section): ONE kernel each on plain device allocations, through the launch
+// functions above and an LcDevice filled by hand.  Every argument is checked before the device is touched: a pick, a job's
+// frame or a frame's job outside its table would be a read out of bounds on the device.
+#define HIPCHK(expr)                                                                                                           \
+  do {                                                                                                                         \
+    const hipError_t e_ = (expr);                                                                                              \
+    if (e_ != hipSuccess) {                                                                                                    \
+      fprintf(stderr, "visomatch: HIP error %s at %s:%d (%s)\n", hipGetErrorString(e_), __FILE__, __LINE__, #expr);            \
+      (void)hipGetLastError();                                                                                                 \
+      return VSM_EHIP;                                                                                                         \
+    }                                                                                                                          \
+  } while (0)
+
+namespace {
+
+enum { LC_DEBUG_MAX_HYPOTHESES = 1 << 22 };  // jobs x hypotheses of one hook call
+
+// a device array of n elements that goes when the hook returns, whichever way
+template <typename T>
+struct LcDebugDev {
+  T *p = nullptr;
+  size_t n = 0;
+  LcDebugDev() = default;
+  LcDebugDev(const LcDebugDev &) = delete;
+  LcDebugDev &operator=(const LcDebugDev &) = delete;
+  ~LcDebugDev() {
+    if (p) (void)hipFree(p);
+  }
+  // the allocation, and the caller's content where there is some
+  hipError_t put(const T *src, size_t count) {
+    n = count;
+    const hipError_t e = hipMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T));
+    if (e != hipSuccess || !src || n == 0) return e;
+    return hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice);
+  }
+  hipError_t get(T *dst) const { return n ? hipMemcpy(dst, p, n * sizeof(T), hipMemcpyDeviceToHost) : hipSuccess; }
+};
+
+// frames of rows as the hooks take them: row_off[F + 1], pixels [R][2] and a point per row [R][3]
+bool debug_frames_ok(int32_t n_frames, const int32_t *row_off, const float *rows_uv, const double *rows_xyz) {
+  if (n_frames < 1 || !row_off || row_off[0] != 0) return false;
+  for (int32_t g = 0; g < n_frames; g++)
+    if (row_off[g + 1] < row_off[g]) return false;
+  return row_off[n_frames] == 0 || (rows_uv && rows_xyz);
+}
+// the job tables: every job a frame of the call, job_E between 0 and the frame's rows
+bool debug_jobs_ok(int32_t n_frames, const int32_t *row_off, int32_t n_jobs, const int32_t *job_frame, const int32_t *job_E, int32_t K) {
+  if (n_jobs < 1 || K < 1 || !job_frame || !job_E || (int64_t)n_jobs * K > LC_DEBUG_MAX_HYPOTHESES) return false;
+  for (int32_t j = 0; j < n_jobs; j++) {
+    if (job_frame[j] < 0 || job_frame[j] >= n_frames) return false;
+    if (job_E[j] < 0 || job_E[j] > row_off[job_frame[j] + 1] - row_off[job_frame[j]]) return false;
+  }
+  return true;
+}
+
+// the frames on the device: row r is {track r, u, v}, its point xyz[r]
+struct LcDebugFrames {
+  LcDebugDev<int32_t> row_off, job_frame, job_E;
+  LcDebugDev<RsRow> rows;
+  LcDebugDev<double> xyz;
+  hipError_t put(int32_t n_frames, const int32_t *off, const float *uv, const double *pts, int32_t n_jobs, const int32_t *jf, const int32_t *je, LcDevice &d) {
+    const size_t R = (size_t)off[n_frames];
+    std::vector<RsRow> table(R + 1);
+    for (size_t r = 0; r < R; r++) table[r] = {(int32_t)r, uv[2 * r], uv[2 * r + 1]};
+    hipError_t e = row_off.put(off, (size_t)n_frames + 1);
+    if (e == hipSuccess) e = rows.put(table.data(), R);
+    if (e == hipSuccess) e = xyz.put(pts, 3 * R);
+    if (e == hipSuccess) e = job_frame.put(jf, (size_t)n_jobs);
+    if (e == hipSuccess) e = job_E.put(je, (size_t)n_jobs);
+    d.row_off = row_off.p, d.rows = rows.p, d.xyz = xyz.p, d.job_frame = job_frame.p, d.job_E = job_E.p;
+    d.n_frames = n_frames, d.n_jobs = n_jobs;
+    return e;
+  }
+};
+
+}  // namespace
+
+extern "C" {
+
+int32_t vsm_debug_locate_fit(double f, double cu, double cv, double min_depth, int32_t n_frames, const int32_t *row_off, const float *rows_uv,
+                             const double *rows_xyz, int32_t n_jobs, const int32_t *job_frame, const int32_t *job_E, const int32_t *picks, int32_t K,
+                             double *states, uint8_t *hvalid) {
+  if (!debug_frames_ok(n_frames, row_off, rows_uv, rows_xyz) || !debug_jobs_ok(n_frames, row_off, n_jobs, job_frame, job_E, K) || !picks || !states || !hvalid)
+    return VSM_EARG;
+  for (int32_t j = 0; j < n_jobs; j++) {
+    const int32_t n = row_off[job_frame[j] + 1] - row_off[job_frame[j]];
+    for (size_t i = (size_t)j * K * LC_SAMPLE; job_E[j] && i < ((size_t)j + 1) * K * LC_SAMPLE; i++)
+      if (picks[i] < 0 || picks[i] >= n) return VSM_EARG;
+  }
+  const size_t JK = (size_t)n_jobs * K;
+  LcDevice d;
+  memset(&d, 0, sizeof(d));
+  LcDebugFrames frames;
+  LcDebugDev<int32_t> d_picks;
+  LcDebugDev<double> d_states;
+  LcDebugDev<uint8_t> d_hvalid;
+  HIPCHK(frames.put(n_frames, row_off, rows_uv, rows_xyz, n_jobs, job_frame, job_E, d));
+  HIPCHK(d_picks.put(picks, JK * LC_SAMPLE));
+  HIPCHK(d_states.put(states, JK * 12));  // (the caller's content: what the kernel leaves alone comes back as it was)
+  HIPCHK(d_hvalid.put(hvalid, JK));
+  d.picks = d_picks.p, d.states = d_states.p, d.hvalid = d_hvalid.p;
+  d.f = f, d.cu = cu, d.cv = cv;
+  d.prm.ransac_iters = K;
+  d.prm.min_depth = min_depth;
+  launch_fit(nullptr, d);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(d_states.get(states));
+  HIPCHK(d_hvalid.get(hvalid));
+  return VSM_OK;
+}
+
+int32_t vsm_debug_locate_count(double f, double cu, double cv, int32_t n_frames, const int32_t *row_off, const float *rows_uv, const double *rows_xyz,
+                               int32_t n_jobs, const int32_t *job_frame, const int32_t *job_E, int32_t K, const double *states, const uint8_t *hvalid,
+                               double inlier_threshold, double min_depth, int32_t launches, int32_t *counts) {
+  if (!debug_frames_ok(n_frames, row_off, rows_uv, rows_xyz) || !debug_jobs_ok(n_frames, row_off, n_jobs, job_frame, job_E, K) || !states || !hvalid ||
+      !counts || !(inlier_threshold > 0) || launches < 1 || launches > 2)
+    return VSM_EARG;
+  const size_t JK = (size_t)n_jobs * K;
+  std::vector<LcTile> tiles;  // as the call builds them: every 256 rows of every job with hypotheses
+  for (int32_t j = 0; j < n_jobs; j++)
+    if (job_E[j])
+      for (int32_t off = 0; off < row_off[job_frame[j] + 1] - row_off[job_frame[j]]; off += 256) tiles.push_back({j, off});
+  LcDevice d;
+  memset(&d, 0, sizeof(d));
+  LcDebugFrames frames;
+  LcDebugDev<LcTile> d_tiles;
+  LcDebugDev<double> d_states;
+  LcDebugDev<uint8_t> d_hvalid;
+  LcDebugDev<int32_t> d_counts;
+  HIPCHK(frames.put(n_frames, row_off, rows_uv, rows_xyz, n_jobs, job_frame, job_E, d));
+  HIPCHK(d_tiles.put(tiles.data(), tiles.size()));
+  HIPCHK(d_states.put(states, JK * 12));
+  HIPCHK(d_hvalid.put(hvalid, JK));
+  HIPCHK(d_counts.put(nullptr, JK));
+  HIPCHK(hipMemset(d_counts.p, 0, JK * 4));  // the caller of the kernel clears, once: the kernel only adds
+  d.tiles = d_tiles.p, d.states = d_states.p, d.hvalid = d_hvalid.p, d.counts = d_counts.p;
+  d.n_tiles = (int32_t)tiles.size();
+  d.f = f, d.cu = cu, d.cv = cv;
+  d.prm.ransac_iters = K;
+  d.prm.inlier_threshold = inlier_threshold;
+  d.prm.min_depth = min_depth;
+  for (int32_t l = 0; l < launches && d.n_tiles > 0; l++) launch_count(nullptr, d);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(d_counts.get(counts));
+  return VSM_OK;
+}
+
+int32_t vsm_debug_locate_winner(int32_t n_frames, const int32_t *frame_job, int32_t n_jobs, const int32_t *job_E, int32_t K, int32_t min_inliers,
+                                const int32_t *counts, const uint8_t *hvalid, const double *states, int32_t *verdict, int32_t *best, int32_t *inliers,
+                                double *lin_poses, uint8_t *lin_valid) {
+  if (n_frames < 1 || n_jobs < 1 || K < 1 || (int64_t)n_jobs * K > LC_DEBUG_MAX_HYPOTHESES || !frame_job || !job_E || !counts || !hvalid || !states ||
+      !verdict || !best || !inliers || !lin_poses || !lin_valid)
+    return VSM_EARG;
+  for (int32_t g = 0; g < n_frames; g++)
+    if (frame_job[g] < -1 || frame_job[g] >= n_jobs) return VSM_EARG;
+  const size_t JK = (size_t)n_jobs * K, F = (size_t)n_frames;
+  LcDevice d;
+  memset(&d, 0, sizeof(d));
+  LcDebugDev<int32_t> d_frame_job, d_job_E, d_counts, d_verdict, d_best, d_inliers;
+  LcDebugDev<uint8_t> d_hvalid, d_lin_valid;
+  LcDebugDev<double> d_states, d_lin;
+  HIPCHK(d_frame_job.put(frame_job, F));
+  HIPCHK(d_job_E.put(job_E, (size_t)n_jobs));
+  HIPCHK(d_counts.put(counts, JK));
+  HIPCHK(d_hvalid.put(hvalid, JK));
+  HIPCHK(d_states.put(states, JK * 12));
+  HIPCHK(d_verdict.put(verdict, F));  // (the caller's content: the kernel writes every frame's entry)
+  HIPCHK(d_best.put(best, F));
+  HIPCHK(d_inliers.put(inliers, F));
+  HIPCHK(d_lin.put(lin_poses, 12 * F));
+  HIPCHK(d_lin_valid.put(lin_valid, F));
+  d.frame_job = d_frame_job.p, d.job_E = d_job_E.p, d.counts = d_counts.p, d.hvalid = d_hvalid.p, d.states = d_states.p;
+  d.verdict = d_verdict.p, d.best = d_best.p, d.inliers = d_inliers.p, d.lin_poses = d_lin.p, d.lin_valid = d_lin_valid.p;
+  d.n_frames = n_frames, d.n_jobs = n_jobs;
+  d.prm.ransac_iters = K;
+  d.prm.min_inliers = min_inliers;
+  launch_winner(nullptr, d);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(d_verdict.get(verdict));
+  HIPCHK(d_best.get(best));
+  HIPCHK(d_inliers.get(inliers));
+  HIPCHK(d_lin.get(lin_poses));
+  HIPCHK(d_lin_valid.get(lin_valid));
+  return VSM_OK;
+}
+
+}  // extern "C"

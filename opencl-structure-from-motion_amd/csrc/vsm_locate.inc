@@ -14,6 +14,7 @@ struct VsmLocate : VsmResult<7> {  // the staging and the last result's stats an
   std::vector<int32_t> g_count;  // the grouping's counts per (chunk of tracks, frame)
   std::vector<uint8_t> g_use;    // vsm_points_locate: the tracks whose point was kept
   std::vector<int32_t> verdict, rs_status;  // what the device said, before the host's status
+  size_t shape[6] = {};  // the last call's blocks: LcBlocks' F, T, R, J, K, NT (vsm_debug_locate_hypotheses finds the tables by them)
 };
 
 static void locate_destroy(vsm_handle *h) { vsm_result_destroy(h->locate); }
@@ -146,6 +147,8 @@ static int locate_run(vsm_handle *h, double t0, int32_t n_frames, const uint8_t 
     R.rms_after[g] = rs_rms(R.ss_after[g], (st == 0 || st == 6) ? R.used[g] : 0);
     R.stats[st]++;
   }
+  const size_t shape[6] = {F, T, (size_t)G.row_off[F], J, K, tiles_bound};
+  memcpy(R.shape, shape, sizeof(shape));
   R.close();
   return VSM_OK;
 }
@@ -196,6 +199,26 @@ int32_t vsm_locate_get(vsm_handle *h, int32_t *status, double *poses, double *li
   vsm_copy_wanted(R->ss_after, ss_after);
   vsm_copy_wanted(R->rms_after, rms_after);
   return (int32_t)R->status.size();
+}
+// test hook: every hypothesis of the last call - the samples from the pinned block that went up, the states, their validity
+// and the counts from the device block, where they lie behind the results and are never copied back by the call
+int32_t vsm_debug_locate_hypotheses(vsm_handle *h, int32_t *picks, double *states, uint8_t *hvalid, int32_t *counts, int32_t *n_jobs, int32_t *n_hyps) {
+  const VsmLocate *R = locate_result(h);
+  if (!R) return h ? VSM_ENOTREADY : VSM_EARG;
+  if (!n_jobs || !n_hyps) return VSM_EARG;
+  const size_t *sh = R->shape, JK = sh[3] * sh[4];
+  *n_jobs = (int32_t)sh[3];
+  *n_hyps = (int32_t)sh[4];
+  if (JK == 0 || sh[0] == 0) return VSM_OK;  // (a call without frames had no round trip)
+  const LcBlocks L(sh[0], sh[1], sh[2], sh[3], sh[4], sh[5]);
+  const VsmStage &S = R->st;
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (picks) memcpy(picks, L.picks.host(S), JK * LC_SAMPLE * 4);
+  if (states) HIPCHK(hipMemcpy(states, L.states.dev(S, L.out_at), JK * 96, hipMemcpyDeviceToHost));
+  if (hvalid) HIPCHK(hipMemcpy(hvalid, L.hvalid.dev(S, L.out_at), JK, hipMemcpyDeviceToHost));
+  if (counts) HIPCHK(hipMemcpy(counts, L.counts.dev(S, L.out_at), JK * 4, hipMemcpyDeviceToHost));
+  return VSM_OK;
 }
 void vsm_locate_get_stats(vsm_handle *h, int64_t *out7) { vsm_result_get(locate_result(h), &VsmLocate::stats, out7); }
 void vsm_locate_get_timings(vsm_handle *h, double *out4) { vsm_result_get(locate_result(h), &VsmLocate::timings, out4); }

@@ -60,12 +60,14 @@ void lc_sample(uint32_t seed, const int32_t *elig, int32_t E, int32_t K, int32_t
 
 namespace {
 
-// one hypothesis on the host: the state and whether it is valid
-bool host_fit(const RsRow *rows, const int32_t *pick, const double *xyz, double f, double cu, double cv, double min_depth, double *S) {
+// one hypothesis on the host: LC_UNFIT, the sample is refused and S untouched; else S is written, and the hypothesis is
+// LC_VALID or LC_INVALID (a state that is not finite, a sampled point not in front)
+enum { LC_UNFIT = 0, LC_INVALID = 1, LC_VALID = 2 };
+int host_fit(const RsRow *rows, const int32_t *pick, const double *xyz, double f, double cu, double cv, double min_depth, double *S) {
   double P[3 * LC_SAMPLE], m[3], s;
   for (int i = 0; i < LC_SAMPLE; i++)
     for (int c = 0; c < 3; c++) P[3 * i + c] = xyz[3 * (size_t)rows[pick[i]].track + c];
-  if (!lc_condition(P, m, &s)) return false;
+  if (!lc_condition(P, m, &s)) return LC_UNFIT;
   double A[LC_GROUP_DOUBLES], col[LC_N];
   for (int i = 0; i < LC_SAMPLE; i++) lc_rows(A + LC_U, i, rows[pick[i]].u, rows[pick[i]].v, P + 3 * i, m, s, f, cu, cv);
   vsm_la::svd_nr(A + LC_U, LC_N, LC_N, LC_N, A + LC_W, A + LC_V, A + LC_RV, col);
@@ -73,10 +75,27 @@ bool host_fit(const RsRow *rows, const int32_t *pick, const double *xyz, double 
   for (int i = 0; i < LC_N; i++) p[i] = A[LC_V + i * LC_N + (LC_N - 1)];
   for (int i = 0; i < 9; i++) U3[i] = p[4 * (i / 3) + i % 3];
   vsm_la::svd_nr(U3, 3, 3, 3, w3, V3, rv3, col3);
-  if (!lc_state(p, U3, w3, V3, m, s, S)) return false;
-  for (int i = 0; i < LC_SAMPLE; i++)
-    if (!lc_in_front(S, P + 3 * i, min_depth)) return false;
-  return true;
+  bool ok = lc_state(p, U3, w3, V3, m, s, S);
+  for (int i = 0; i < LC_SAMPLE; i++) ok = ok && lc_in_front(S, P + 3 * i, min_depth);
+  return ok ? LC_VALID : LC_INVALID;
+}
+
+// a row's vote among the frame's eligible rows elig[0 .. E) at the state S
+int32_t host_count(const RsRow *rows, const int32_t *elig, int32_t E, const double *xyz, const double *S, double f, double cu, double cv, double min_depth,
+                   double limit) {
+  int32_t count = 0;
+  for (int32_t q = 0; q < E; q++) {
+    const RsRow &r = rows[elig[q]];
+    if (lc_inlier(S, xyz + 3 * (size_t)r.track, r.u, r.v, f, cu, cv, min_depth, limit)) count++;
+  }
+  return count;
+}
+
+// the rows of the single-frame entries - pixels rows_uv[n][2], a point per row rows_xyz[n][3] - as a frame's row table
+std::vector<RsRow> rows_of_arrays(int32_t n, const float *uv) {
+  std::vector<RsRow> rows((size_t)n + 1);
+  for (int32_t i = 0; i < n; i++) rows[i] = {i, uv[2 * (size_t)i], uv[2 * (size_t)i + 1]};
+  return rows;
 }
 
 }  // namespace
@@ -123,13 +142,9 @@ int32_t vsm_host_locate(int32_t n_frames, const uint8_t *locate, double f, doubl
     double Sbest[12];
     for (int32_t k = 0; k < K; k++) {
       double S[12];
-      if (!host_fit(fr, &picks[(size_t)k * LC_SAMPLE], xyz, f, cu, cv, prm.min_depth, S)) continue;
+      if (host_fit(fr, &picks[(size_t)k * LC_SAMPLE], xyz, f, cu, cv, prm.min_depth, S) != LC_VALID) continue;
       any_valid = true;
-      int32_t count = 0;
-      for (int32_t q = 0; q < E[g]; q++) {
-        const RsRow &r = fr[elig[q]];
-        if (lc_inlier(S, xyz + 3 * (size_t)r.track, r.u, r.v, f, cu, cv, prm.min_depth, limit)) count++;
-      }
+      const int32_t count = host_count(fr, elig.data(), E[g], xyz, S, f, cu, cv, prm.min_depth, limit);
       if (count > win_count[g]) {
         win_count[g] = count;
         win[g] = k;
@@ -169,6 +184,42 @@ int32_t vsm_host_locate(int32_t n_frames, const uint8_t *locate, double f, doubl
     if (rms_after) rms_after[g] = rs_rms(r_ss[g], st == 0 || st == 6 ? r_used[g] : 0);
   }
   return n_frames;
+}
+
+// ---- the stages alone (include/visomatch.h, the debug section): what the loop above runs, on one frame of the caller ----
+int32_t vsm_host_locate_sample(uint32_t seed, int32_t E, int32_t K, int32_t *picks) {
+  if (E < LC_SAMPLE || K < 1 || !picks) return VSM_EARG;
+  std::vector<int32_t> elig((size_t)E), deck;
+  for (int32_t i = 0; i < E; i++) elig[i] = i;
+  lc_sample(seed, elig.data(), E, K, picks, deck);
+  return VSM_OK;
+}
+
+int32_t vsm_host_locate_fit(double f, double cu, double cv, double min_depth, int32_t n_rows, const float *rows_uv, const double *rows_xyz, const int32_t *picks,
+                            int32_t K, double *states, uint8_t *valid) {
+  if (n_rows < 1 || K < 1 || !rows_uv || !rows_xyz || !picks || !states || !valid) return VSM_EARG;
+  for (size_t i = 0; i < (size_t)K * LC_SAMPLE; i++)
+    if (picks[i] < 0 || picks[i] >= n_rows) return VSM_EARG;
+  const std::vector<RsRow> rows = rows_of_arrays(n_rows, rows_uv);
+  for (int32_t k = 0; k < K; k++) {
+    double S[12];
+    const int fit = host_fit(rows.data(), picks + (size_t)k * LC_SAMPLE, rows_xyz, f, cu, cv, min_depth, S);
+    if (fit != LC_UNFIT) memcpy(states + 12 * (size_t)k, S, sizeof(S));
+    valid[k] = fit == LC_VALID ? 1 : 0;
+  }
+  return VSM_OK;
+}
+
+int32_t vsm_host_locate_count(double f, double cu, double cv, int32_t n_rows, const float *rows_uv, const double *rows_xyz, const double *states,
+                              const uint8_t *valid, int32_t K, double inlier_threshold, double min_depth, int32_t *counts) {
+  if (n_rows < 0 || K < 1 || (n_rows > 0 && (!rows_uv || !rows_xyz)) || !states || !valid || !counts || !(inlier_threshold > 0)) return VSM_EARG;
+  const std::vector<RsRow> rows = rows_of_arrays(n_rows, rows_uv);
+  std::vector<int32_t> elig;
+  lc_eligible_rows(rows.data(), n_rows, rows_xyz, elig);
+  const double limit = rs_limit(inlier_threshold);
+  for (int32_t k = 0; k < K; k++)
+    counts[k] = valid[k] ? host_count(rows.data(), elig.data(), (int32_t)elig.size(), rows_xyz, states + 12 * (size_t)k, f, cu, cv, min_depth, limit) : 0;
+  return VSM_OK;
 }
 
 }  // extern "C"

@@ -50,7 +50,8 @@ EXPORTS = ["vsm_default_params", "vsm_create", "vsm_destroy", "vsm_set_intrinsic
            "vsm_adjust_default_params", "vsm_adjust_run", "vsm_points_adjust", "vsm_adjust_count", "vsm_adjust_get_frames", "vsm_adjust_get_tracks",
            "vsm_adjust_get_history", "vsm_adjust_get_stats", "vsm_adjust_get_timings", "vsm_host_adjust",
            "vsm_locate_default_params", "vsm_locate_run", "vsm_points_locate", "vsm_locate_count", "vsm_locate_get", "vsm_locate_get_stats",
-           "vsm_locate_get_timings", "vsm_host_locate", "vsm_set_option", "vsm_version", "vsm_host_register", "vsm_host_unregister",
+           "vsm_locate_get_timings", "vsm_host_locate", "vsm_host_locate_sample", "vsm_host_locate_fit", "vsm_host_locate_count",
+           "vsm_debug_locate_fit", "vsm_debug_locate_count", "vsm_debug_locate_winner", "vsm_debug_locate_hypotheses", "vsm_set_option", "vsm_version", "vsm_host_register", "vsm_host_unregister",
            "vsm_multi_create", "vsm_multi_destroy", "vsm_multi_process", "vsm_multi_num_sequences", "vsm_multi_get_motion",
            "vsm_multi_motion_valid", "vsm_multi_num_matches", "vsm_multi_get_matches", "vsm_multi_num_inliers", "vsm_multi_get_inliers",
            "vsm_multi_get_timings",
@@ -290,6 +291,16 @@ def lib():
         L.vsm_locate_get_timings.restype = None
         L.vsm_host_locate.restype = i32
         L.vsm_host_locate.argtypes = [i32, vp, f64, f64, f64, i32, vp, vp, vp, vp, vp, C.POINTER(VsmLocateParams)] + [vp] * 11
+        L.vsm_host_locate_sample.argtypes = [C.c_uint32, i32, i32, vp]
+        L.vsm_host_locate_fit.argtypes = [f64, f64, f64, f64, i32, vp, vp, vp, i32, vp, vp]
+        L.vsm_host_locate_count.argtypes = [f64, f64, f64, i32, vp, vp, vp, vp, i32, f64, f64, vp]
+        L.vsm_debug_locate_fit.argtypes = [f64, f64, f64, f64, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp]
+        L.vsm_debug_locate_count.argtypes = [f64, f64, f64, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp, f64, f64, i32, vp]
+        L.vsm_debug_locate_winner.argtypes = [i32, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.vsm_debug_locate_hypotheses.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+        for fn in (L.vsm_host_locate_sample, L.vsm_host_locate_fit, L.vsm_host_locate_count, L.vsm_debug_locate_fit, L.vsm_debug_locate_count,
+                   L.vsm_debug_locate_winner, L.vsm_debug_locate_hypotheses):
+            fn.restype = i32
         L.vsm_vet_default_params.argtypes = [C.POINTER(VsmVetParams)]
         L.vsm_vet_default_params.restype = None
         L.vsm_vet_run.argtypes = [vp, i32, vp, vp, f64, f64, f64, i32, vp, vp, vp, vp, vp, C.POINTER(VsmVetParams)]
@@ -1146,6 +1157,101 @@ def host_locate(n_frames, f, cu, cv, offsets, obs_frames, uv, xyz, use=None, loc
     return Location(*out)
 
 
+# ---- test hooks of the location's stages (include/visomatch.h, the debug section): rows without tracks, row r of a frame has
+# the pixel uv[r] and the point xyz[r] ----
+
+def _locate_rows(uv, xyz):
+    px = np.ascontiguousarray(np.asarray(uv, dtype=np.float32).reshape(-1, 2))
+    pt = np.ascontiguousarray(np.asarray(xyz, dtype=np.float64).reshape(-1, 3))
+    assert len(px) == len(pt)
+    return px, pt
+
+
+def _locate_tables(states, valid, K):
+    st = np.ascontiguousarray(states, dtype=np.float64).reshape(-1, K, 12)
+    va = np.ascontiguousarray(valid, dtype=np.uint8).reshape(-1, K)
+    assert len(st) == len(va)
+    return st, va
+
+
+def host_locate_sample(seed, E, K):
+    """vsm_host_locate_sample: picks [K, 6], the positions in [0, E) the K hypotheses of a frame with E eligible rows draw"""
+    picks = np.zeros((max(int(K), 0), 6), np.int32)
+    _check(lib().vsm_host_locate_sample(int(seed), int(E), int(K), _ptr(picks)), "vsm_host_locate_sample")
+    return picks
+
+
+def host_locate_fit(f, cu, cv, uv, xyz, picks, min_depth=1e-10, fill=0.0):
+    """vsm_host_locate_fit on one frame of rows: picks [K, 6] -> (states [K, 12], valid [K]); a state the fit leaves unwritten
+    stays `fill`"""
+    px, pt = _locate_rows(uv, xyz)
+    pk = np.ascontiguousarray(picks, dtype=np.int32).reshape(-1, 6)
+    states, valid = np.full((len(pk), 12), fill, np.float64), np.zeros(len(pk), np.uint8)
+    _check(lib().vsm_host_locate_fit(float(f), float(cu), float(cv), float(min_depth), len(px), _ptr(px), _ptr(pt), _ptr(pk), len(pk), _ptr(states), _ptr(valid)),
+           "vsm_host_locate_fit")
+    return states, valid
+
+
+def host_locate_count(f, cu, cv, uv, xyz, states, valid, inlier_threshold=2.0, min_depth=1e-10):
+    """vsm_host_locate_count on one frame of rows: states [K, 12], valid [K] -> counts [K]"""
+    px, pt = _locate_rows(uv, xyz)
+    va = np.ascontiguousarray(valid, dtype=np.uint8).ravel()
+    st, va = _locate_tables(states, va, len(va))
+    counts = np.zeros(len(va[0]), np.int32)
+    _check(lib().vsm_host_locate_count(float(f), float(cu), float(cv), len(px), _ptr(px), _ptr(pt), _ptr(st), _ptr(va), len(counts), float(inlier_threshold),
+                                       float(min_depth), _ptr(counts)), "vsm_host_locate_count")
+    return counts
+
+
+def _locate_frames(row_off, uv, xyz, job_frame, job_E):
+    off = np.ascontiguousarray(row_off, dtype=np.int32)
+    px, pt = _locate_rows(uv, xyz)
+    jf, je = np.ascontiguousarray(job_frame, dtype=np.int32), np.ascontiguousarray(job_E, dtype=np.int32)
+    assert len(jf) == len(je) and (len(off) == 0 or len(px) >= off[-1])
+    return off, px, pt, jf, je
+
+
+def device_locate_fit(f, cu, cv, row_off, uv, xyz, job_frame, job_E, picks, states, hvalid, min_depth=1e-10):
+    """test hook: k_locate_fit alone, one launch.  Frames of rows (row_off [F + 1], uv [R, 2], xyz [R, 3]), jobs (job_frame,
+    job_E [J]), picks [J, K, 6]; states [J, K, 12] and hvalid [J, K] go up as given and come back as new arrays"""
+    off, px, pt, jf, je = _locate_frames(row_off, uv, xyz, job_frame, job_E)
+    pk = np.ascontiguousarray(picks, dtype=np.int32)
+    K = pk.shape[1] if pk.ndim == 3 else 0
+    st, va = _locate_tables(np.array(states, dtype=np.float64), np.array(hvalid, dtype=np.uint8), max(K, 1))
+    _check(lib().vsm_debug_locate_fit(float(f), float(cu), float(cv), float(min_depth), len(off) - 1, _ptr(off), _ptr(px), _ptr(pt), len(jf), _ptr(jf), _ptr(je),
+                                      _ptr(pk), K, _ptr(st), _ptr(va)), "vsm_debug_locate_fit")
+    return st, va
+
+
+def device_locate_count(f, cu, cv, row_off, uv, xyz, job_frame, job_E, states, hvalid, inlier_threshold=2.0, min_depth=1e-10, launches=1):
+    """test hook: k_locate_count alone on states [J, K, 12] and hvalid [J, K]; the counts are cleared once, then the kernel is
+    launched `launches` times -> counts [J, K]"""
+    off, px, pt, jf, je = _locate_frames(row_off, uv, xyz, job_frame, job_E)
+    va = np.ascontiguousarray(hvalid, dtype=np.uint8)
+    K = va.shape[1] if va.ndim == 2 else 0
+    st, va = _locate_tables(states, va, max(K, 1))
+    counts = np.zeros(va.shape, np.int32)
+    _check(lib().vsm_debug_locate_count(float(f), float(cu), float(cv), len(off) - 1, _ptr(off), _ptr(px), _ptr(pt), len(jf), _ptr(jf), _ptr(je), K, _ptr(st),
+                                        _ptr(va), float(inlier_threshold), float(min_depth), int(launches), _ptr(counts)), "vsm_debug_locate_count")
+    return counts
+
+
+def device_locate_winner(frame_job, job_E, counts, hvalid, states, min_inliers, fill=77):
+    """test hook: k_locate_winner alone on counts, hvalid [J, K] and states [J, K, 12] -> (verdict, best, inliers [F], lin_poses
+    [F, 12], lin_valid [F]); the outputs go up filled with `fill`"""
+    fj, je = np.ascontiguousarray(frame_job, dtype=np.int32), np.ascontiguousarray(job_E, dtype=np.int32)
+    cn = np.ascontiguousarray(counts, dtype=np.int32)
+    K = cn.shape[1] if cn.ndim == 2 else 0
+    st, va = _locate_tables(states, hvalid, max(K, 1))
+    assert cn.shape == va.shape and len(cn) == len(je)
+    F = len(fj)
+    verdict, best, inliers = (np.full(F, fill, np.int32) for _ in range(3))
+    lin, lin_valid = np.full((F, 12), float(fill), np.float64), np.full(F, fill, np.uint8)
+    _check(lib().vsm_debug_locate_winner(F, _ptr(fj), len(je), _ptr(je), K, int(min_inliers), _ptr(cn), _ptr(va), _ptr(st), _ptr(verdict), _ptr(best),
+                                         _ptr(inliers), _ptr(lin), _ptr(lin_valid)), "vsm_debug_locate_winner")
+    return verdict, best, inliers, lin, lin_valid
+
+
 _NO_PARAMS = object()  # params=_NO_PARAMS: a NULL params pointer (argument tests)
 
 
@@ -1686,6 +1792,17 @@ class Matcher:
         out = _locate_arrays(L.vsm_locate_count(self.h))
         L.vsm_locate_get(self.h, *[_ptr(a) for a in out])
         return Location(*out, *_stage_dicts(self.h, L.vsm_locate_get_stats, LOCATE_STATUS, L.vsm_locate_get_timings, LOCATE_TIMINGS))
+
+    def locate_hypotheses(self):
+        """test hook (vsm_debug_locate_hypotheses): every hypothesis of the last location as the call left it ->
+        (picks [J, K, 6], states [J, K, 12], hvalid [J, K], counts [J, K])"""
+        J, K = C.c_int32(0), C.c_int32(0)
+        sizes = (C.cast(C.byref(J), C.c_void_p), C.cast(C.byref(K), C.c_void_p))
+        _check(lib().vsm_debug_locate_hypotheses(self.h, None, None, None, None, *sizes), "vsm_debug_locate_hypotheses")
+        j, k = J.value, K.value
+        picks, states, hvalid, counts = np.zeros((j, k, 6), np.int32), np.zeros((j, k, 12), np.float64), np.zeros((j, k), np.uint8), np.zeros((j, k), np.int32)
+        _check(lib().vsm_debug_locate_hypotheses(self.h, _ptr(picks), _ptr(states), _ptr(hvalid), _ptr(counts), *sizes), "vsm_debug_locate_hypotheses")
+        return picks, states, hvalid, counts
 
     def locate(self, n_frames, f, cu, cv, offsets, obs_frames, uv, xyz, use=None, locate=None, params=None, n_tracks=None):
         """vsm_locate_run: every asked-for frame's pose from its observations of the points alone, on the device - RANSAC over a

@@ -7,7 +7,7 @@ Row counts: rows_family (and rows_family_6 with min_inliers = 6) has frames with
 257 and 513 eligible rows - either side of min_inliers, of a 16-lane group, of the count kernel's tile of 256 rows and of its
 second and third tile.  Hypothesis counts: iters_1, 15, 16, 17, 33, 200 on three frames - either side of a group run of 16 and
 of a fit block of 16 groups, so that with K = 15, 17 and 33 a fit block is shared by two frames.  Shapes: 1, 2 and 9 frames, and
-257 frames of 10 to 12 rows."""
+257 frames of 10 to 12 rows.  outliers_tiles: a late winner on frames of 255, 257 and 513 rows."""
 import numpy as np
 
 import points_cases as PC
@@ -203,6 +203,76 @@ def outliers_case():
     return Case(n, tracks, pts, true_poses=true, clean=clean)
 
 
+TILE_ROWS = (255, 257, 513)
+
+
+def outliers_tiles_case():
+    """30 % planted outliers as in outliers_case on frames of 255, 257 and 513 rows, 33 hypotheses: the winner comes late, and the
+    counts of every hypothesis differ from tile to tile and from wave to wave of the count kernel"""
+    rng = np.random.default_rng(45)
+    true = PC.camera_path(len(TILE_ROWS))
+    pts = volume(max(TILE_ROWS), rng)
+    tracks, clean = [], []
+    for i, X in enumerate(pts):
+        t = []
+        for g, n in enumerate(TILE_ROWS):
+            if i >= n:
+                continue
+            bad = rng.uniform() < 0.3
+            a, r = rng.uniform(0, 2 * np.pi), rng.uniform(50, 120)
+            t.append((g,) + RC.pixel(true[g], X, (r * np.cos(a), r * np.sin(a)) if bad else (0.0, 0.0)))
+            clean.append(not bad)
+        tracks.append(t)
+    return Case(len(TILE_ROWS), tracks, pts, true_poses=true, clean=clean, params=dict(ransac_iters=33))
+
+
+def frame_rows(c, g):
+    """frame g's rows in the call's order - ascending (track, observation) - as (uv [n, 2] float32, xyz [n, 3]), a point per row"""
+    use = np.ones(len(c.offsets) - 1, bool) if c.use is None else c.use.astype(bool)
+    track = np.repeat(np.arange(len(c.offsets) - 1), np.diff(c.offsets))
+    at = np.nonzero((c.obs_frames == g) & use[track])[0]
+    return np.ascontiguousarray(c.uv[at]), np.ascontiguousarray(c.xyz[track[at]])
+
+
+def degenerate_rows():
+    """a frame of rows for the degenerate samples and the picks that make them: (uv, xyz, {name: pick})"""
+    c = cases()["rows_family"]
+    g = ROW_COUNTS.index(17)
+    uv, xyz = frame_rows(c, g)
+    uv, xyz = [tuple(x) for x in uv.tolist()], [tuple(x) for x in xyz.tolist()]
+    pose = c.true_poses[g]
+    def add(X):
+        xyz.append(tuple(float(x) for x in X))
+        uv.append(RC.pixel(pose, np.asarray(X, dtype=np.float64)))
+        return len(xyz) - 1
+
+    picks = {"ordinary": [0, 1, 2, 3, 4, 5], "one_row_six_times": [3] * 6, "two_rows_three_times": [2, 9, 2, 9, 2, 9]}
+    picks["one_point_six_rows"] = [add((0.5, -0.25, 9.0)) for _ in range(6)]
+    picks["coplanar"] = [add((x, y, 12.0 + 0.3 * x - 0.2 * y)) for x, y in ((-2, -1), (1.5, -0.8), (0.3, 0.9), (-1.1, 0.4), (2.2, 0.1), (-0.4, -0.6))]
+    picks["collinear"] = [add((0.2 * t - 1.0, 0.1 * t, 8.0 + 0.5 * t)) for t in range(6)]
+    far = len(xyz)
+    xyz.append((1e200, -1e200, 1e200))
+    uv.append((600.0, 200.0))
+    picks["huge"] = [0, 1, 2, 3, 4, far]
+    big = len(xyz)
+    xyz.extend([(1.7e308, 1.7e308, 1.7e308), (1.7e308, -1.7e308, 1.7e308), (-1.7e308, 1.7e308, -1.7e308)])
+    uv.extend([(600.0, 200.0)] * 3)
+    picks["overflow"] = [big, big, big + 1, big + 2, 0, 1]
+    behind = add((0.3, -0.2, -6.0))
+    picks["one_behind"] = [0, 1, 2, 3, 4, behind]
+    return np.array(uv, np.float32), np.array(xyz, np.float64), picks
+
+
+def host_hypotheses(vm, c, g, p, fill=0.0):
+    """frame g's rows and every hypothesis of it through the host entries: (uv, xyz, picks as row indices, states, valid, counts)"""
+    uv, xyz = frame_rows(c, g)
+    elig = np.nonzero(np.isfinite(uv).all(axis=1) & np.isfinite(xyz).all(axis=1))[0]
+    picks = elig[vm.host_locate_sample(p.seed, len(elig), p.ransac_iters)].astype(np.int32)
+    states, valid = vm.host_locate_fit(c.f, c.cu, c.cv, uv, xyz, picks, p.min_depth, fill=fill)
+    counts = vm.host_locate_count(c.f, c.cu, c.cv, uv, xyz, states, valid, p.inlier_threshold, p.min_depth)
+    return uv, xyz, picks, states, valid, counts
+
+
 _cases = None
 _host = {}
 
@@ -229,6 +299,7 @@ def cases():
     c["planar"] = planar_case()
     c["huge"] = huge_case()
     c["outliers"] = outliers_case()
+    c["outliers_tiles"] = outliers_tiles_case()
     c["seed_0"] = scene(2, 30, seed=44, params=dict(seed=0))
     c["no_tracks"] = Case(3, [], np.zeros((0, 3)))
     c["no_frames"] = Case(0, [], np.zeros((0, 3)))

@@ -1,5 +1,6 @@
 """CPU suite: vsm_host_locate - the location's host view, one thread walking csrc/vsm_locate.h - on the cases of
-tests/locate_cases.py.  The call has no counterpart to compare with, so it is pinned from four sides: against the two stages whose
+tests/locate_cases.py.  The call as a whole has no counterpart to compare with (its stages have one: tests/locate_ref.py,
+test_locate_kernels_cpu.py), so it is pinned from four sides: against the two stages whose
 arithmetic it shares (the located poses are host_resect's from the linear poses, byte for byte; the winner's count is host_vet's
 inlier count at the linear pose), against the truth the scenes were made from, against itself under a change of frame order and
 of the frames in the call, and by what the cases are for - every status in one call, the row and hypothesis counts, the hard
@@ -234,15 +235,28 @@ def test_determinism(vm, name):
         assert (np.delete(one.status, g) == 1).all()
 
 
-def test_planted_outliers(vm):
-    """30 % of the pixels displaced by 50 px and more: every frame is located, and the inliers at the located poses are exactly
-    the clean observations"""
-    c, r = LC.cases()["outliers"], LC.host("outliers")
+def planted_outliers(vm, name):
+    c, r = LC.cases()[name], LC.host(name)
     assert 0.25 < 1 - c.clean.mean() < 0.35
     assert (r.status == 0).all()
     v = vm.host_vet(r.poses, *c.tracks_args(), params=vet_params(vm, c))
     assert (v.code == 0).tolist() == c.clean.tolist()
     assert r.used.tolist() == np.bincount(c.obs_frames[c.clean], minlength=c.n_frames).tolist() == r.inliers.tolist()
+    return r
+
+
+def test_planted_outliers(vm):
+    """30 % of the pixels displaced by 50 px and more: every frame is located, and the inliers at the located poses are exactly
+    the clean observations"""
+    planted_outliers(vm, "outliers")
+
+
+def test_planted_outliers_across_tiles(vm):
+    """the same on frames of 255, 257 and 513 rows with 33 hypotheses: the winner is not the first hypothesis, so what the
+    hypotheses behind it hold and count decides the result, on either side of the count kernel's tile and in its third"""
+    r = planted_outliers(vm, "outliers_tiles")
+    assert r.rows.tolist() == list(LC.TILE_ROWS) and (r.best > 0).any()
+    print("outliers_tiles: best", r.best.tolist(), "inliers", r.inliers.tolist())
 
 
 def test_pose_against_truth(vm):

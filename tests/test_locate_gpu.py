@@ -4,7 +4,9 @@ tiles of 256 rows by runs of 16 hypotheses for the counts, a workgroup per frame
 refinement.  Every result is compared with vsm_host_locate: every int equal, every double equal by its bytes.  The cases are those
 of tests/locate_cases.py, proven on the CPU by test_locate_cpu.py; their sizes are the smallest at which the kernels can go
 wrong: row counts on either side of a group, of a tile of 256 and of its second and third, hypothesis counts on either side of a
-run of 16 and of a fit block (which two frames then share), frame counts of 1, 2, 9 and 257, every status in one grid."""
+run of 16 and of a fit block (which two frames then share), frame counts of 1, 2, 9 and 257, every status in one grid.  A call
+returns each frame's winner alone, and in the clean scenes that is hypothesis 0: what the other hypotheses hold and count is
+checked in test_locate_kernels_gpu.py, kernel by kernel and on these calls' own tables."""
 import numpy as np
 import pytest
 

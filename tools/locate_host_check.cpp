@@ -2,8 +2,9 @@
 // on scenes generated here - frames of 0 to 513 rows of clean pixels, a frame with 30 % planted outliers, NaN and infinite
 // pixels and points, points behind the camera, a point at 1e200, twelve copies of one point, a plane, frames not asked for,
 // hypothesis counts of 1, 17 and 200, argument errors and empty inputs - against (a) what the scenes are built to give: the
-// status, the counts, the pose within the pixels' rounding of the truth, and (b) vsm_host_resect from the linear poses, byte for byte.  Meant to
-// be built with the sanitizers, e.g.
+// status, the counts, the pose within the pixels' rounding of the truth, and (b) vsm_host_resect from the linear poses, byte for
+// byte; and the stages' own entries (vsm_host_locate_sample / _fit / _count), put together again, against the host view's
+// winner.  Meant to be built with the sanitizers, e.g.
 //   c++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude \
 //       -Iopencl-structure-from-motion_amd/csrc tools/locate_host_check.cpp opencl-structure-from-motion_amd/csrc/vsm_locate_host.cpp \
 //       opencl-structure-from-motion_amd/csrc/vsm_resect_host.cpp opencl-structure-from-motion_amd/csrc/vsm_points_host.cpp -o locate_host_check
@@ -219,6 +220,57 @@ int main() {
     CHECK(vsm_host_locate(2, nullptr, 1, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &prm, none.status.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                           nullptr, nullptr, nullptr, nullptr) == 2);
     CHECK(none.status[0] == 2 && none.status[1] == 2);
+  }
+  {  // the stages alone (vsm_host_locate_sample / _fit / _count) put together again give the host view's winner
+    Scene s;
+    s.camera(1);
+    std::vector<float> uv;
+    std::vector<double> xyz;
+    int clean = 0;
+    for (int i = 0; i < 300; i++) {
+      s.random_point();
+      const bool bad = i % 10 < 3;
+      s.see(0, bad ? 70.f : 0.f, bad ? -55.f : 0.f);
+      clean += !bad;
+    }
+    s.xyz[3 * 7] = NAN;  // a row that is not eligible
+    uv = s.uv;
+    xyz = s.xyz;  // a point per row: the tracks have one observation each
+    vsm_locate_params p = prm;
+    p.ransac_iters = 33;
+    Result r(1);
+    CHECK(run(s, nullptr, p, r) == 1 && r.status[0] == 0 && r.eligible[0] == 299);
+    const int32_t K = p.ransac_iters, E = r.eligible[0];
+    std::vector<int32_t> picks((size_t)K * 6), counts((size_t)K, -1);
+    CHECK(vsm_host_locate_sample(p.seed, E, K, picks.data()) == VSM_OK);
+    for (int32_t &q : picks) {
+      CHECK(q >= 0 && q < E);
+      if (q >= 7) q++;  // position among the eligible rows -> row
+    }
+    std::vector<double> states((size_t)K * 12, -7.5);
+    std::vector<uint8_t> valid((size_t)K, 9);
+    CHECK(vsm_host_locate_fit(s.f, s.cu, s.cv, p.min_depth, 300, uv.data(), xyz.data(), picks.data(), K, states.data(), valid.data()) == VSM_OK);
+    CHECK(vsm_host_locate_count(s.f, s.cu, s.cv, 300, uv.data(), xyz.data(), states.data(), valid.data(), K, p.inlier_threshold, p.min_depth, counts.data()) == VSM_OK);
+    int32_t best = -1, top = 0;
+    for (int32_t k = 0; k < K; k++) {
+      CHECK(valid[k] <= 1 && counts[k] >= 0 && (valid[k] || counts[k] == 0));
+      if (counts[k] > top) top = counts[k], best = k;
+    }
+    CHECK(best == r.best[0] && top == r.inliers[0] && top == clean - 1);
+    double lin[12];
+    pts_rigid_inverse(&states[12 * (size_t)best], lin);
+    CHECK(memcmp(lin, &r.lin[0], sizeof(lin)) == 0);
+    // a refused sample leaves its state alone; arguments
+    const int32_t same[6] = {4, 4, 4, 4, 4, 4};
+    double one[12];
+    for (double &x : one) x = -7.5;
+    uint8_t ok = 9;
+    xyz[12] = 0.5, xyz[13] = -0.25, xyz[14] = 9.0;
+    CHECK(vsm_host_locate_fit(s.f, s.cu, s.cv, p.min_depth, 300, uv.data(), xyz.data(), same, 1, one, &ok) == VSM_OK && ok == 0 && one[0] == -7.5 && one[11] == -7.5);
+    const int32_t out_of_range[6] = {0, 1, 2, 3, 4, 300};
+    CHECK(vsm_host_locate_fit(s.f, s.cu, s.cv, p.min_depth, 300, uv.data(), xyz.data(), out_of_range, 1, one, &ok) == VSM_EARG);
+    CHECK(vsm_host_locate_sample(p.seed, 5, 1, picks.data()) == VSM_EARG && vsm_host_locate_sample(p.seed, 6, 0, picks.data()) == VSM_EARG);
+    CHECK(vsm_host_locate_count(s.f, s.cu, s.cv, 300, uv.data(), xyz.data(), states.data(), valid.data(), K, 0.0, p.min_depth, counts.data()) == VSM_EARG);
   }
   if (fails) return 1;
   printf("ok\n");
