@@ -606,6 +606,94 @@ int32_t vsm_host_locate(int32_t n_frames, const uint8_t *locate, double f, doubl
                         const int32_t *obs_frames, const float *uv, const double *xyz, const uint8_t *use, const vsm_locate_params *params,
                         int32_t *status, double *poses, double *linear_poses, int32_t *best, int32_t *inliers, int32_t *rows, int32_t *eligible,
                         int32_t *updates, int32_t *used, double *ss_after, double *rms_after);
+/* ---- re-observation: new observations of the points, found by projection ----
+ * Every stage behind the matcher consumes observations and the vetting removes them; this one adds them.  A point in use is
+ * projected into every searched frame with a pose that does not observe it yet; among that frame's features near the
+ * projection, the one whose descriptor is nearest the track's becomes a new observation.  No counterpart in the reference,
+ * whose Reconstruction links consecutive frames only; the cost is the matcher's (Matcher::findMatch, viso/matcher.cpp:892-963):
+ * the sum of absolute differences of the 32 descriptor bytes between features of one class.  csrc/vsm_reobserve.h is the one
+ * statement of the arithmetic; what follows is the contract.
+ * Input: as vsm_vet_run takes it - n_frames poses (camera to world, 12 doubles each), pose_valid (NULL: all valid), f, cu,
+ * cv, the tracks' offsets[T + 1] and obs_frames, xyz[T][3], use[T] bytes (NULL: all) - and search, a byte per frame (NULL:
+ * all): only frames with a non-zero byte are searched; the image's width and height, 1..16383; obs_feat[n_obs], the feature
+ * index of each observation within its frame (column 1 of vsm_tracks_get's obs); ref_obs[T], the observation whose feature
+ * lends the track its class and descriptor, an index into the track, 0 <= ref_obs[t] < length (NULL: the middle one,
+ * (length - 1) / 2); and the features: feat_offsets[F + 1] and feat[n_feat][12], int32 records {u, v, 0, class, d1..d8}
+ * exactly as vsm_get_features hands them out - image pixels, class 0..3, the 32 descriptor bytes in d1..d8.  A track without
+ * observations has no reference: it counts as not in use.
+ * Feature k of frame g is OCCUPIED if any observation of any track, in use or not, names (g, k); an occupied feature is never
+ * found.  A CANDIDATE is a pair (t, g) with use[t] != 0, search[g] != 0, a valid pose of g, g not a frame of track t, and, with
+ * [Rw | tw] the rigid inverse of the pose as the resection forms it and Xc = Rw X + tw: zc > min_depth, and pu = f xc / zc + cu,
+ * pv = f yc / zc + cv with 0 <= pu <= width - 1 and 0 <= pv <= height - 1 (NaN fails by the comparison).  The candidates are
+ * listed in ascending (t, g).  A candidate's WINDOW is the set of features k of frame g that are not occupied, have the
+ * class of the track's reference feature, and satisfy u_k - pu <= radius, pu - u_k <= radius and the same in v, in double.
+ * The COST of k is the sum over the 32 descriptor bytes of |a - b|, 0..8160.  best is the smallest (cost, k) - the lowest
+ * index wins a tie -, second the smallest cost among the window's other features (-1: none), n_window the window's size.
+ * The candidate's CODE, the first that applies:
+ *   1  the window is empty (feature, cost and second are -1)
+ *   2  max_cost > 0 and best cost > max_cost
+ *   3  ratio_den > 0, there is a second, and not best * ratio_den < second * ratio_num (in 64-bit integers)
+ *   4  lost: among the candidates that come this far naming the same (g, k), the smallest (cost, candidate index) keeps the
+ *      feature; the others do not fall back to their second
+ *   0  accepted
+ * Results: per candidate seven int32 {track, frame, feature, cost, second, n_window, code} and the doubles (pu, pv); per
+ * track the number accepted; per frame {candidates, accepted}. */
+typedef struct vsm_reobserve_params {
+  double radius;      /* 4.0 pixels: half the side of the window, finite and not negative */
+  double min_depth;   /* 1e-10 */
+  int32_t max_cost;   /* 0 = no cap */
+  int32_t ratio_num;  /* 0 / 0 = no ratio test; else best / second has to be below ratio_num / ratio_den */
+  int32_t ratio_den;
+} vsm_reobserve_params;
+void vsm_reobserve_default_params(vsm_reobserve_params *p);
+/* The general form, on the caller's arrays.  Runs on the handle's device and stream: one copy up (110 bytes per frame, 8 per
+ * observation, 33 per track, 48 per feature), the kernels - the occupied features, a counting sort of the free ones by
+ * (frame, class, bin), a 16-lane group per track for the projections, the tracks' multi-level scan over the tracks' counts -,
+ * the call's one wait in the middle for the number of candidates, which sizes their block (44 bytes each), then the list,
+ * a 16-lane group per candidate for the search, a lane per candidate for the verdict, one copy back.  It has no CPU path.
+ * VSM_EARG, nothing enqueued and the last result kept: what vsm_vet_run rejects for the shared arrays, params NULL, radius not
+ * finite or negative, min_depth NaN, max_cost < 0, a negative ratio term or ratio_den > 0 with ratio_num <= 0, width or
+ * height outside 1..16383, feat_offsets not starting at 0 or decreasing, an obs_feat or ref_obs out of range, a class
+ * outside 0..3, a feature pixel outside the image, and more than 2^31 - 1 pairs of a track in use and a searched frame with
+ * a pose (search fewer frames per call).  VSM_EHIP after a HIP error, a block the device cannot hold included (nothing
+ * further is launched; there is then no result).  Nothing else of the handle is touched. */
+int vsm_reobserve_run(vsm_handle *h, int32_t n_frames, const double *poses, const uint8_t *pose_valid, const uint8_t *search, double f, double cu, double cv,
+                      int32_t width, int32_t height, int32_t n_tracks, const int32_t *offsets, const int32_t *obs_frames, const int32_t *obs_feat, const double *xyz,
+                      const uint8_t *use, const int32_t *ref_obs, const int32_t *feat_offsets, const int32_t *feat, const vsm_reobserve_params *params);
+/* The same on the handle's own results: the tracks of the last vsm_pairs_tracks with side 0, xyz and use (status 0) from the
+ * last point result, ref_obs NULL, and the features where the last vsm_pairs_run left them - set 1 of the left image of every
+ * frame, resident in HBM: nothing is uploaded for them; width and height are that run's.  VSM_ENOTREADY: no such pairs run,
+ * track result or point result, tracks not from those pairs or of side 1, lists replaced since, or a run that took the
+ * whole-call per-frame path (more than 1024 statistics bins), which leaves no resident features.  VSM_EARG for params and a
+ * NULL poses.  The lists and the other stages' results stay as they are. */
+int vsm_points_reobserve(vsm_handle *h, const double *poses, const uint8_t *pose_valid, const uint8_t *search, double f, double cu, double cv,
+                         const vsm_reobserve_params *params);
+/* the handle's last re-observation result (zeros / nothing written without one); any output may be NULL.
+ * count: the candidates, the accepted among them.  get: cand[n_cand][7], uv[n_cand][2]; returns n_cand.  get_tracks:
+ * accepted[T]; returns T.  get_frames: counts[F][2]; returns F. */
+void vsm_reobserve_count(vsm_handle *h, int32_t *n_cand, int32_t *n_accepted);
+int32_t vsm_reobserve_get(vsm_handle *h, int32_t *cand7, double *uv);
+int32_t vsm_reobserve_get_tracks(vsm_handle *h, int32_t *accepted);
+int32_t vsm_reobserve_get_frames(vsm_handle *h, int32_t *counts2);
+/* pairs (t, g) of tracks in use per reason they are no candidates, the first that applies - search[g] == 0, no valid pose, g
+ * already a frame of the track, behind the camera, outside the image -, then candidates per code 0..4 */
+void vsm_reobserve_get_stats(vsm_handle *h, int64_t *out10);
+/* wall-clock split of the last call, microseconds: {gather / packing, upload, kernels with the one wait for the number of
+ * candidates, download + host part} */
+void vsm_reobserve_get_timings(vsm_handle *h, double *out4);
+/* The same definition on one host thread: no GPU, no handle (the CPU suite's subject and the device path's second opinion -
+ * not a fallback).  cand[cap][7] and cand_uv[cap][2] take the first cap candidates; track_accepted[T], frame_counts[F][2],
+ * stats10 as above.  Returns the number of candidates (call with cap 0 to size the arrays), or VSM_EARG with the outputs
+ * untouched.  Outputs may be NULL. */
+int32_t vsm_host_reobserve(int32_t n_frames, const double *poses, const uint8_t *pose_valid, const uint8_t *search, double f, double cu, double cv, int32_t width,
+                           int32_t height, int32_t n_tracks, const int32_t *offsets, const int32_t *obs_frames, const int32_t *obs_feat, const double *xyz,
+                           const uint8_t *use, const int32_t *ref_obs, const int32_t *feat_offsets, const int32_t *feat, const vsm_reobserve_params *params,
+                           int32_t cap, int32_t *cand, double *cand_uv, int32_t *track_accepted, int32_t *frame_counts, int64_t *stats10);
+/* The feature records of a frame of the last vsm_pairs_run, in vsm_get_features' layout: side 0 = left, 1 = right; set 0 =
+ * sparse, 1 = dense (the set the match lists' indices count in).  num: the number of records; get: up to cap of them into
+ * out[cap][12], returns how many.  0 where there is no such run, frame, side or set, or the run left no resident features. */
+int32_t vsm_pairs_num_features(vsm_handle *h, int32_t frame, int32_t side, int32_t set);
+int32_t vsm_pairs_get_features(vsm_handle *h, int32_t frame, int32_t side, int32_t set, int32_t *out, int32_t cap);
 /* Measurement / test switches of a handle.  They are read from the environment once, by vsm_create (VSM_SEQ_V2,
  * VSM_SEQ_CHUNK, VSM_SEQ_DC_STREAMS, VSM_SEQ_SERIAL, VSM_SEQ_GPU_SORTS, VSM_SEQ_EARLY_EXPORT, VSM_FUSED_KEYS); this call changes one
  * afterwards: name = the variable's name without the VSM_ prefix, in lower case ("seq_serial", "seq_chunk", ...).

@@ -427,6 +427,7 @@ struct vsm_handle {
   struct VsmVet *vet = nullptr;        // vetting of observations (vsm_vet.inc): staging, device block, last result
   struct VsmAdjust *adjust = nullptr;  // joint adjustment of poses and points (vsm_ba.inc): staging, device block, last result
   struct VsmLocate *locate = nullptr;  // location of frames against the points (vsm_locate.inc): staging, device block, last result
+  struct VsmReobserve *reobserve = nullptr;  // re-observation of the points (vsm_reobserve.inc): staging, device blocks, last result
   struct VsmMotions *motions = nullptr;  // monocular pair motions (vsm_motions_api.inc): staging, device block, last result
   struct VsmTracks *tracks = nullptr;  // feature tracks from pair match lists (vsm_tracks.inc): staging, device block, last result
 
@@ -464,6 +465,7 @@ static void resect_destroy(vsm_handle *h);  // vsm_resect.inc
 static void vet_destroy(vsm_handle *h);     // vsm_vet.inc
 static void adjust_destroy(vsm_handle *h);  // vsm_ba.inc
 static void locate_destroy(vsm_handle *h);  // vsm_locate.inc
+static void reobserve_destroy(vsm_handle *h);  // vsm_reobserve.inc
 static void motions_destroy(vsm_handle *h);  // vsm_motions_api.inc
 
 extern "C" {
@@ -561,6 +563,7 @@ void vsm_destroy(vsm_handle *h) {
   vet_destroy(h);
   adjust_destroy(h);
   locate_destroy(h);
+  reobserve_destroy(h);
   motions_destroy(h);
   ctx_destroy(h->ring);
   ctx_destroy(h->seq);
@@ -1054,6 +1057,7 @@ static int seq_ingest_host_frames(vsm_handle *h, VsmCtx &c, int first_img, const
 #include "vsm_vet.inc"
 #include "vsm_ba.inc"
 #include "vsm_locate.inc"
+#include "vsm_reobserve.inc"
 #include "vsm_motions_api.inc"
 extern "C" {
 
@@ -1270,7 +1274,8 @@ static const char *kKernelNames[VSM_K_COUNT] = {
     "k_trk_init", "k_trk_hook", "k_trk_flatten", "k_trk_keep", "k_trk_scan_reduce", "k_trk_scan_top", "k_trk_scan_apply", "k_trk_match_tracks", "k_trk_fill",
     "k_trk_order_wave", "k_trk_order_block", "k_pts_triangulate", "k_rs_resect", "k_vet_obs", "k_vet_emit",
     "k_ba_init", "k_ba_linearise", "k_ba_tracks", "k_ba_frames<rhs>", "k_ba_cg_init", "k_ba_op_tracks", "k_ba_frames<op>", "k_ba_cg_step", "k_ba_back",
-    "k_ba_trial_cost", "k_ba_decide", "k_ba_commit", "k_ba_finish", "k_locate_fit", "k_locate_count", "k_locate_winner"};
+    "k_ba_trial_cost", "k_ba_decide", "k_ba_commit", "k_ba_finish", "k_locate_fit", "k_locate_count", "k_locate_winner",
+    "k_ro_occupy", "k_ro_bin_count", "k_ro_scatter", "k_ro_project<count>", "k_ro_project<list>", "k_ro_search", "k_ro_verdict"};
 
 void vsm_set_profiling(vsm_handle *h, int on) {
   h->prof.on = on != 0;

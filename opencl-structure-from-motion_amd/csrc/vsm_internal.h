@@ -122,6 +122,8 @@ enum VsmKernelId {
   VSM_K_BA_TRIAL_COST, VSM_K_BA_DECIDE, VSM_K_BA_COMMIT, VSM_K_BA_FINISH,
   // location of frames against the points (vsm_locate.hip; the refinement is VSM_K_RS_RESECT)
   VSM_K_LC_FIT, VSM_K_LC_COUNT, VSM_K_LC_WINNER,
+  // re-observation of the points by projection (vsm_reobserve.hip; its two scans are VSM_K_TRK_SCAN_*)
+  VSM_K_RO_OCCUPY, VSM_K_RO_BIN_COUNT, VSM_K_RO_SCATTER, VSM_K_RO_COUNT, VSM_K_RO_LIST, VSM_K_RO_SEARCH, VSM_K_RO_VERDICT,
   VSM_K_COUNT
 };
 struct VsmProf {

@@ -14,6 +14,7 @@
 #include "vsm_vet.h"
 #include "vsm_ba.h"
 #include "vsm_locate.h"
+#include "vsm_reobserve.h"
 
 // vsm_points.inc: F frames, T tracks, N observations
 struct PtsBlocks : VsmBlocks {
@@ -143,6 +144,40 @@ struct LcBlocks : VsmBlocks {
     VsmLayout work = out;
     states.place(work, J * K * 12, 8); counts.place(work, J * K, 4); hvalid.place(work, J * K, 1); lin_valid.place(work, F, 1);
     out_behind_in(work.at);
+  }
+};
+
+// vsm_reobserve.inc: F frames, T tracks, N observations, NF features of which NU are uploaded (the general form: all; the
+// handle form: none, they are resident), B bins per frame.  The results here are those sized before the launch; the working
+// set lies behind them and is not copied back - first what starts at zero (the occupied bytes, the bins), then the rest.
+// The candidates have a block of their own (RoCandBlocks), sized once their number is back.
+struct RoBlocks : VsmBlocks {
+  VsmIn<double> states, xyz;
+  VsmIn<uint8_t> valid, search, use;
+  VsmIn<int32_t> offsets, obs_frames, obs_feat, ref_obs, feat_offsets, feat;
+  VsmIn<const int32_t *> frame_feat;
+  VsmOut<int32_t> track_accepted, frame_counts, totals, bins, bins_part, bins_total, sorted, scan, scan_part;
+  VsmOut<unsigned long long> stats, claim;
+  VsmOut<uint8_t> occupied;
+  size_t zero_bytes = 0;  // from `occupied` on
+  RoBlocks(size_t F, size_t T, size_t N, size_t NF, size_t NU, size_t B) {
+    states.place(in, 12 * F, 8); valid.place(in, F, 1); search.place(in, F, 1); offsets.place(in, T + 1, 0); obs_frames.place(in, N, 4); obs_feat.place(in, N, 4);
+    xyz.place(in, 3 * T, 8); use.place(in, T, 1); ref_obs.place(in, T, 4); feat_offsets.place(in, F + 1, 0); frame_feat.place(in, F, 8); feat.place(in, RO_FEAT_INTS * NU, 16);
+    track_accepted.place(out, T, 4); frame_counts.place(out, 2 * F, 4); stats.place(out, RO_STATS, 0); totals.place(out, 2, 0);
+    VsmLayout work = out;
+    occupied.place(work, NF, 1); bins.place(work, 2 * F * B, 8);
+    zero_bytes = work.at - occupied.at;
+    bins_part.place(work, 2 * trk_scan_part_items((int64_t)(F * B)), 8); bins_total.place(work, 2, 0); claim.place(work, NF, 8); sorted.place(work, RO_FEAT_INTS * NF, 16);
+    scan.place(work, 2 * T, 8); scan_part.place(work, 2 * trk_scan_part_items((int64_t)T), 8);
+    out_behind_in(work.at);
+  }
+};
+struct RoCandBlocks : VsmBlocks {
+  VsmOut<int32_t> cand;
+  VsmOut<double> uv;
+  explicit RoCandBlocks(size_t n) {
+    cand.place(out, RO_CAND_INTS * n, 4); uv.place(out, 2 * n, 8);
+    out_behind_in(out.at);  // (in is empty: the block is the results)
   }
 };
 

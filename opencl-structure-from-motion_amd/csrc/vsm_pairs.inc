@@ -16,6 +16,8 @@ struct VsmPairs {
   std::vector<int32_t> pair_list;  // ... its pairs, frame count and method, for vsm_pairs_tracks; done: it ran to its end
   int32_t n_frames = 0, method = -1;
   bool done = false;
+  int32_t sides = 1;      // images per frame of the last call
+  bool resident = false;  // ... and whether its frames' feature records stand in ctx (not after the whole-call fallback)
   double timings[4] = {0, 0, 0, 0};  // image side, first passes + chains, second passes + chains, total; us
 };
 
@@ -150,8 +152,10 @@ int vsm_pairs_run(vsm_handle *h, const uint8_t *left, const uint8_t *right, int6
   P.n_frames = n_frames;
   P.method = method;
   P.done = false;
+  P.resident = false;
   memset(P.timings, 0, sizeof(P.timings));
   const int sides = right ? 2 : 1;
+  P.sides = sides;
   PairsRingSave save;  // (armed by the first fallback; puts the caller's ring back however the call is left)
   // the statistics bins of k_dc2_prior live in LDS: a binning beyond 1024 bins goes pair by pair
   if (vsm_match_bins(p, w, hh) > 1024) {
@@ -197,6 +201,7 @@ int vsm_pairs_run(vsm_handle *h, const uint8_t *left, const uint8_t *right, int6
   VSM_CHK(hipEventRecord(P.st.ev_feat, h->stream));
   VSM_CHK(hipEventSynchronize(P.st.ev_feat));  // every image's feature counts are in host-mapped memory
   VSM_CHK(hipGetLastError());
+  P.resident = true;
   P.timings[0] = now_us() - t0;
   // ---- the pairs, C at a time: the step a vsm_multi_process call runs for its K sequences (vsm_step.inc) ----
   std::vector<char> valid((size_t)C, 0);

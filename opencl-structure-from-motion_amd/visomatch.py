@@ -51,7 +51,10 @@ EXPORTS = ["vsm_default_params", "vsm_create", "vsm_destroy", "vsm_set_intrinsic
            "vsm_adjust_get_history", "vsm_adjust_get_stats", "vsm_adjust_get_timings", "vsm_host_adjust",
            "vsm_locate_default_params", "vsm_locate_run", "vsm_points_locate", "vsm_locate_count", "vsm_locate_get", "vsm_locate_get_stats",
            "vsm_locate_get_timings", "vsm_host_locate", "vsm_host_locate_sample", "vsm_host_locate_fit", "vsm_host_locate_count",
-           "vsm_debug_locate_fit", "vsm_debug_locate_count", "vsm_debug_locate_winner", "vsm_debug_locate_hypotheses", "vsm_set_option", "vsm_version", "vsm_host_register", "vsm_host_unregister",
+           "vsm_debug_locate_fit", "vsm_debug_locate_count", "vsm_debug_locate_winner", "vsm_debug_locate_hypotheses",
+           "vsm_reobserve_default_params", "vsm_reobserve_run", "vsm_points_reobserve", "vsm_reobserve_count", "vsm_reobserve_get", "vsm_reobserve_get_tracks",
+           "vsm_reobserve_get_frames", "vsm_reobserve_get_stats", "vsm_reobserve_get_timings", "vsm_host_reobserve", "vsm_pairs_num_features",
+           "vsm_pairs_get_features", "vsm_set_option", "vsm_version", "vsm_host_register", "vsm_host_unregister",
            "vsm_multi_create", "vsm_multi_destroy", "vsm_multi_process", "vsm_multi_num_sequences", "vsm_multi_get_motion",
            "vsm_multi_motion_valid", "vsm_multi_num_matches", "vsm_multi_get_matches", "vsm_multi_num_inliers", "vsm_multi_get_inliers",
            "vsm_multi_get_timings",
@@ -111,6 +114,10 @@ class VsmAdjustParams(C.Structure):
 class VsmLocateParams(C.Structure):
     _fields_ = [("ransac_iters", C.c_int32), ("inlier_threshold", C.c_double), ("min_inliers", C.c_int32), ("min_depth", C.c_double), ("seed", C.c_uint32),
                 ("max_updates", C.c_int32), ("eps", C.c_double)]
+
+
+class VsmReobserveParams(C.Structure):
+    _fields_ = [("radius", C.c_double), ("min_depth", C.c_double), ("max_cost", C.c_int32), ("ratio_num", C.c_int32), ("ratio_den", C.c_int32)]
 
 
 def host_register(arr):
@@ -300,6 +307,26 @@ def lib():
         L.vsm_debug_locate_hypotheses.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         for fn in (L.vsm_host_locate_sample, L.vsm_host_locate_fit, L.vsm_host_locate_count, L.vsm_debug_locate_fit, L.vsm_debug_locate_count,
                    L.vsm_debug_locate_winner, L.vsm_debug_locate_hypotheses):
+            fn.restype = i32
+        rop = C.POINTER(VsmReobserveParams)
+        L.vsm_reobserve_default_params.argtypes = [rop]
+        L.vsm_reobserve_default_params.restype = None
+        L.vsm_reobserve_run.argtypes = [vp, i32, vp, vp, vp, f64, f64, f64, i32, i32, i32] + [vp] * 8 + [rop]
+        L.vsm_points_reobserve.argtypes = [vp, vp, vp, vp, f64, f64, f64, rop]
+        L.vsm_reobserve_count.argtypes = [vp, vp, vp]
+        L.vsm_reobserve_count.restype = None
+        L.vsm_reobserve_get.argtypes = [vp, vp, vp]
+        L.vsm_reobserve_get_tracks.argtypes = [vp, vp]
+        L.vsm_reobserve_get_frames.argtypes = [vp, vp]
+        L.vsm_reobserve_get_stats.argtypes = [vp, vp]
+        L.vsm_reobserve_get_stats.restype = None
+        L.vsm_reobserve_get_timings.argtypes = [vp, vp]
+        L.vsm_reobserve_get_timings.restype = None
+        L.vsm_host_reobserve.argtypes = [i32, vp, vp, vp, f64, f64, f64, i32, i32, i32] + [vp] * 8 + [rop, i32] + [vp] * 5
+        L.vsm_pairs_num_features.argtypes = [vp, i32, i32, i32]
+        L.vsm_pairs_get_features.argtypes = [vp, i32, i32, i32, vp, i32]
+        for fn in (L.vsm_reobserve_get, L.vsm_reobserve_get_tracks, L.vsm_reobserve_get_frames, L.vsm_host_reobserve, L.vsm_pairs_num_features,
+                   L.vsm_pairs_get_features):
             fn.restype = i32
         L.vsm_vet_default_params.argtypes = [C.POINTER(VsmVetParams)]
         L.vsm_vet_default_params.restype = None
@@ -1252,6 +1279,104 @@ def device_locate_winner(frame_job, job_E, counts, hvalid, states, min_inliers, 
     return verdict, best, inliers, lin, lin_valid
 
 
+REOBSERVE_REASONS = ("not_searched", "no_pose", "observed", "behind", "outside")
+REOBSERVE_CODES = ("accepted", "empty_window", "over_max_cost", "ambiguous", "lost")
+REOBSERVE_STATS = tuple("pairs_" + r for r in REOBSERVE_REASONS) + tuple("cand_" + c for c in REOBSERVE_CODES)
+REOBSERVE_TIMINGS = ("gather_us", "upload_us", "kernels_us", "download_host_us")
+REOBSERVE_ARRAYS = ("cand", "uv", "track_accepted", "frame_counts")
+
+
+class Reobservation:
+    """new observations found by projection (include/visomatch.h, vsm_reobserve_run): per candidate cand [n_cand, 7] int32
+    {track, frame, feature, cost, second, n_window, code} (code 0 = accepted, REOBSERVE_CODES names the values) and uv [n_cand, 2]
+    float64, the projection; track_accepted [T] int32; frame_counts [F, 2] int32 (candidates, accepted); stats: pairs per reason
+    and candidates per code by name, timings: dict (empty for the host view).  pixels [n_cand, 2] float32, filled in by the
+    binding from the records the call searched: the integer pixel of an accepted candidate's feature (zeros elsewhere)."""
+
+    def __init__(self, cand, uv, track_accepted, frame_counts, stats=None, timings=None, pixels=None):
+        self.cand, self.uv, self.track_accepted, self.frame_counts = cand, uv, track_accepted, frame_counts
+        self.stats, self.timings = stats or {}, timings or {}
+        self.pixels = np.zeros((len(cand), 2), np.float32) if pixels is None else pixels
+
+    def _take_pixels(self, records_of):
+        """records_of(g): frame g's feature records [n, 12]"""
+        acc = self.accepted()
+        for g in np.unique(self.cand[acc, 1]).tolist():
+            i = acc[self.cand[acc, 1] == g]
+            self.pixels[i] = np.asarray(records_of(g)).reshape(-1, 12)[self.cand[i, 2], :2].astype(np.float32)
+        return self
+
+    def __len__(self):
+        return len(self.cand)
+
+    @property
+    def code(self):
+        return self.cand[:, 6]
+
+    def accepted(self):
+        """the indices of the accepted candidates, ascending"""
+        return np.nonzero(self.cand[:, 6] == 0)[0]
+
+    def extend(self, offsets, obs_frames, uv, obs_feat):
+        """the track set with the accepted observations merged in by ascending frame (a new one behind the old ones of its
+        frame: there are none), over the same T tracks: (offsets, obs_frames, uv, obs_feat).  A new observation's pixel is its
+        feature's integer pixel as float32.  The counterpart of Vetting.prune: the arrays feed triangulate, resect, vet,
+        adjust and the next reobserve as they are."""
+        off = np.asarray(offsets, dtype=np.int32)
+        fr, ft = np.asarray(obs_frames, dtype=np.int32), np.asarray(obs_feat, dtype=np.int32)
+        px = np.asarray(uv, dtype=np.float32).reshape(-1, 2)
+        T = max(len(off) - 1, 0)
+        assert len(fr) == len(ft) == len(px) == (off[-1] if T else 0) and len(self.track_accepted) == T
+        acc = self.accepted()
+        new = self.cand[acc]
+        track = np.concatenate([np.repeat(np.arange(T, dtype=np.int64), np.diff(off)), new[:, 0].astype(np.int64)])
+        frames = np.concatenate([fr, new[:, 1]]).astype(np.int32)
+        feats = np.concatenate([ft, new[:, 2]]).astype(np.int32)
+        pixels = np.concatenate([px, self.pixels[acc]])
+        order = np.lexsort((np.arange(len(track)), frames, track))  # by (track, frame), the old observations first
+        out_off = np.zeros(T + 1, np.int32)
+        out_off[1:] = np.cumsum(np.diff(off) + self.track_accepted)
+        return out_off, np.ascontiguousarray(frames[order]), np.ascontiguousarray(pixels[order]), np.ascontiguousarray(feats[order])
+
+
+def reobserve_params(**kw):
+    """vsm_reobserve_default_params with fields overridden by keyword"""
+    return _default_params(VsmReobserveParams, "vsm_reobserve_default_params", kw)
+
+
+def _reobserve_inputs(poses, pose_valid, search, offsets, obs_frames, obs_feat, xyz, use, ref_obs, feat_offsets, feat):
+    po, pv = _pose_inputs(poses, pose_valid)
+    se = _mask(search, len(po))
+    off = np.ascontiguousarray(offsets, dtype=np.int32)
+    fr, ft = np.ascontiguousarray(obs_frames, dtype=np.int32), np.ascontiguousarray(obs_feat, dtype=np.int32)
+    assert len(fr) == len(ft)
+    pt = None if xyz is None else np.ascontiguousarray(np.asarray(xyz, dtype=np.float64).reshape(-1, 3))
+    us = None if use is None else np.ascontiguousarray(use, dtype=np.uint8)
+    ro = None if ref_obs is None else np.ascontiguousarray(ref_obs, dtype=np.int32)
+    assert all(a is None or len(a) >= len(off) - 1 for a in (pt, us, ro))
+    fo = None if feat_offsets is None else np.ascontiguousarray(feat_offsets, dtype=np.int32)
+    fe = None if feat is None else np.ascontiguousarray(np.asarray(feat, dtype=np.int32).reshape(-1, 12))
+    assert fo is None or len(fo) == len(po) + 1
+    return po, pv, se, off, fr, ft, pt, us, ro, fo, fe
+
+
+def host_reobserve(poses, f, cu, cv, width, height, offsets, obs_frames, obs_feat, xyz, feat_offsets, feat, use=None, ref_obs=None, search=None, pose_valid=None,
+                   params=None, n_tracks=None):
+    """vsm_host_reobserve: the re-observation on one host thread - no GPU.  n_tracks: override len(offsets) - 1 (argument
+    tests).  Returns a Reobservation object; raises VisoMatchError on VSM_EARG."""
+    po, pv, se, off, fr, ft, pt, us, ro, fo, fe = _reobserve_inputs(poses, pose_valid, search, offsets, obs_frames, obs_feat, xyz, use, ref_obs, feat_offsets, feat)
+    T = _n_tracks(off, n_tracks)
+    prm = _params_ref(VsmReobserveParams, reobserve_params, params)
+    head = (len(po), _ptr(po), _ptr(pv), _ptr(se), float(f), float(cu), float(cv), int(width), int(height), T, _ptr(off), _ptr(fr), _ptr(ft), _ptr(pt), _ptr(us),
+            _ptr(ro), _ptr(fo), _ptr(fe), prm)
+    n = _check(lib().vsm_host_reobserve(*head, 0, None, None, None, None, None), "vsm_host_reobserve")
+    cand, uv = np.zeros((n, 7), np.int32), np.zeros((n, 2), np.float64)
+    acc, fc, stats = np.zeros(max(T, 0), np.int32), np.zeros((len(po), 2), np.int32), np.zeros(10, np.int64)
+    got = _check(lib().vsm_host_reobserve(*head, n, _ptr(cand), _ptr(uv), _ptr(acc), _ptr(fc), _ptr(stats)), "vsm_host_reobserve")
+    assert got == n
+    return Reobservation(cand, uv, acc, fc, dict(zip(REOBSERVE_STATS, stats.tolist())))._take_pixels(lambda g: fe[fo[g]:fo[g + 1]])
+
+
 _NO_PARAMS = object()  # params=_NO_PARAMS: a NULL params pointer (argument tests)
 
 
@@ -1820,6 +1945,53 @@ class Matcher:
         ls, ptrs, cnt = _optional_lists(lists, counts)
         rc = lib().vsm_points_locate(self.h, ptrs, _ptr(cnt), _ptr(lo), float(f), float(cu), float(cv), _params_ref(VsmLocateParams, locate_params, params))
         return self._locate_result(rc, "vsm_points_locate")
+
+    # --- new observations of the points, found by projection ---------------------------------------
+    def _reobserve_result(self, rc, what, records_of=None):
+        L = lib()
+        _check(rc, what)
+        n, acc = C.c_int32(0), C.c_int32(0)
+        L.vsm_reobserve_count(self.h, C.byref(n), C.byref(acc))
+        out = (np.zeros((n.value, 7), np.int32), np.zeros((n.value, 2), np.float64), np.zeros(L.vsm_reobserve_get_tracks(self.h, None), np.int32),
+               np.zeros((L.vsm_reobserve_get_frames(self.h, None), 2), np.int32))
+        L.vsm_reobserve_get(self.h, _ptr(out[0]), _ptr(out[1]))
+        L.vsm_reobserve_get_tracks(self.h, _ptr(out[2]))
+        L.vsm_reobserve_get_frames(self.h, _ptr(out[3]))
+        res = Reobservation(*out, *_stage_dicts(self.h, L.vsm_reobserve_get_stats, REOBSERVE_STATS, L.vsm_reobserve_get_timings, REOBSERVE_TIMINGS))
+        assert acc.value == res.stats.get("cand_accepted", 0)
+        return res._take_pixels(records_of or self.pair_features)
+
+    def reobserve(self, poses, f, cu, cv, width, height, offsets, obs_frames, obs_feat, xyz, feat_offsets, feat, use=None, ref_obs=None, search=None,
+                  pose_valid=None, params=None, n_tracks=None):
+        """vsm_reobserve_run: every point in use projected into every searched frame with a pose that does not observe it yet,
+        and the frame's free features near the projection searched for the track's descriptor, on the device.  poses, the
+        tracks, xyz, use as for vet; obs_feat [n_obs]: each observation's feature index in its frame; feat_offsets [F + 1], feat
+        [n_feat, 12]: the frames' feature records; search [F], ref_obs [T]: None for all / the middle observation; params: a dict
+        of vsm_reobserve_params fields or the struct.  Returns a Reobservation object."""
+        po, pv, se, off, fr, ft, pt, us, ro, fo, fe = _reobserve_inputs(poses, pose_valid, search, offsets, obs_frames, obs_feat, xyz, use, ref_obs, feat_offsets, feat)
+        T = _n_tracks(off, n_tracks)
+        rc = lib().vsm_reobserve_run(self.h, len(po), _ptr(po), _ptr(pv), _ptr(se), float(f), float(cu), float(cv), int(width), int(height), T, _ptr(off), _ptr(fr),
+                                     _ptr(ft), _ptr(pt), _ptr(us), _ptr(ro), _ptr(fo), _ptr(fe), _params_ref(VsmReobserveParams, reobserve_params, params))
+        return self._reobserve_result(rc, "vsm_reobserve_run", lambda g: fe[fo[g]:fo[g + 1]])
+
+    def reobserve_points(self, poses, f, cu, cv, search=None, pose_valid=None, params=None):
+        """vsm_points_reobserve: the same on the handle's last track and point results (pair_tracks with side 0; the kept points)
+        and the features the last match_pairs call left resident in HBM"""
+        po, pv = _pose_inputs(poses, pose_valid, self._track_frames)
+        se = _mask(search, len(po))
+        rc = lib().vsm_points_reobserve(self.h, _ptr(po), _ptr(pv), _ptr(se), float(f), float(cu), float(cv),
+                                        _params_ref(VsmReobserveParams, reobserve_params, params))
+        return self._reobserve_result(rc, "vsm_points_reobserve")
+
+    def pair_features(self, frame, side=0, set=1):
+        """vsm_pairs_get_features: the feature records [n, 12] int32 of a frame of the last match_pairs call (set 1: the set the
+        match lists' indices count in)"""
+        L = lib()
+        n = L.vsm_pairs_num_features(self.h, int(frame), int(side), int(set))
+        a = np.zeros((n, 12), np.int32)
+        if n:
+            assert L.vsm_pairs_get_features(self.h, int(frame), int(side), int(set), _ptr(a), n) == n
+        return a
 
     def track_pixels(self, lists=None, counts=None):
         """vsm_tracks_pixels: (obs_frames [n_obs] int32, uv [n_obs, 2] float32) of the handle's last track result, the pixels
