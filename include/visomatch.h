@@ -694,6 +694,85 @@ int32_t vsm_host_reobserve(int32_t n_frames, const double *poses, const uint8_t 
  * out[cap][12], returns how many.  0 where there is no such run, frame, side or set, or the run left no resident features. */
 int32_t vsm_pairs_num_features(vsm_handle *h, int32_t frame, int32_t side, int32_t set);
 int32_t vsm_pairs_get_features(vsm_handle *h, int32_t frame, int32_t side, int32_t set, int32_t *out, int32_t cap);
+/* ---- fusion: duplicate tracks of one 3-D point joined ----
+ * The tracks are connected components of the match graph: where one match is missed a point's track ends, and the point
+ * comes back later as a second track with a second point.  The re-observation cannot repair that - the feature it would find
+ * is occupied, by the duplicate.  This stage searches exactly those features and joins the two tracks.  No counterpart in
+ * the reference.  csrc/vsm_fuse.h states what is new in the arithmetic; projection, window, cost, best and second are the
+ * re-observation's, above.
+ * Input: exactly what vsm_reobserve_run takes, with the same meanings.  A track without observations is not in use.
+ * OWNER(g, k) is the smallest index of a track in use that has an observation (g, k); undefined where there is none.
+ * A CANDIDATE is a pair (a, g) as for the re-observation, with the same reasons 0..4 for the pairs that are none.  Its WINDOW
+ * is the set of features k of frame g with owner(g, k) defined, the class of a's reference feature, and inside the square of
+ * half-side radius around the projection: the complement of the re-observation's window among the features that tracks in
+ * use own.  best, second and n_window are as there.  A PROPOSAL is a candidate with a non-empty window; it names
+ * b = owner(g, best).  The proposals are listed in ascending (a, g) and numbered in that order.  A proposal's CODE, the first
+ * that applies:
+ *   2  max_cost > 0 and best cost > max_cost
+ *   3  the ratio test fails, as for the re-observation
+ *   4  conflict: some frame occurs among the observations of both a and b - the merged track would see one frame twice
+ *   5  outbid: among a's proposals that come this far another has the smaller (cost, proposal index); that one is a's choice,
+ *      and partner(a) is its b
+ *   6  one-sided: partner(b) is not a
+ *   0  fused
+ * Code 1, an empty window, is counted in the stats only.  The FUSIONS are the pairs {a, b} with partner(a) = b and
+ * partner(b) = a: a matching, so no track is in two of them.  The smaller index survives, the larger is absorbed.  A point
+ * in three fragments therefore needs two calls: the first joins two of them, the second the third - re-triangulate between.
+ * The MERGED TRACK SET covers the same T tracks: a survivor's observations are its own followed by the absorbed track's,
+ * stably sorted by frame; an absorbed track is empty; every other track is as it was.  offsets_after[T + 1] and
+ * obs_src[n_obs] describe it: obs_src[i] is the input index of observation i of the merged set, a permutation.  xyz is not
+ * touched: the caller triangulates the merged set again.
+ * Results: per proposal eight int32 {a, g, feature, cost, second, n_window, code, b} and the doubles (pu, pv); per track
+ * partner (-1: none) and fused_into (the survivor of an absorbed track, else -1); the merged set; per frame {candidates,
+ * proposals}; stats. */
+typedef struct vsm_fuse_params {
+  double radius;      /* 4.0 pixels: half the side of the window, finite and not negative */
+  double min_depth;   /* 1e-10 */
+  int32_t max_cost;   /* 0 = no cap */
+  int32_t ratio_num;  /* 0 / 0 = no ratio test; else best / second has to be below ratio_num / ratio_den */
+  int32_t ratio_den;
+} vsm_fuse_params;
+void vsm_fuse_default_params(vsm_fuse_params *p);
+/* The general form, on the caller's arrays.  Runs on the handle's device and stream: one copy up (as vsm_reobserve_run's),
+ * the kernels - the owners by a 32-bit atomic minimum, a counting sort of the owned features by (frame, class, bin), a 16-lane
+ * group per track that projects and searches and counts, the scan over the tracks' proposals -, the first wait, for the
+ * number of proposals, which sizes their block (48 bytes each), then the list - the proposals the counting pass kept in places
+ * per track (48 bytes per pair of a track in use and a searched frame with a pose, device only) moved to their prefix, or,
+ * where those places would exceed 2 GiB, the same walk again (handle option "fuse_compact": 1 / 0 force either; the bytes are
+ * the same) -, the conflict test, a 64-bit atomic minimum per track for its choice, the verdicts, a scan over the new lengths
+ * and a merge per survivor, one copy back, the second wait: two waits, because the proposals' block cannot be sized before
+ * their number is known.  The candidates are never listed and never copied: only the proposals reach the host.  It has no
+ * CPU path.  VSM_EARG, VSM_EHIP: exactly as vsm_reobserve_run; VSM_EARG leaves the last result in place.  Nothing else of the
+ * handle is touched. */
+int vsm_fuse_run(vsm_handle *h, int32_t n_frames, const double *poses, const uint8_t *pose_valid, const uint8_t *search, double f, double cu, double cv,
+                 int32_t width, int32_t height, int32_t n_tracks, const int32_t *offsets, const int32_t *obs_frames, const int32_t *obs_feat, const double *xyz,
+                 const uint8_t *use, const int32_t *ref_obs, const int32_t *feat_offsets, const int32_t *feat, const vsm_fuse_params *params);
+/* The same on the handle's own results, as vsm_points_reobserve takes them: the tracks of the last vsm_pairs_tracks with side
+ * 0, xyz and use from the last point result, the features resident in HBM.  VSM_ENOTREADY in the same states. */
+int vsm_points_fuse(vsm_handle *h, const double *poses, const uint8_t *pose_valid, const uint8_t *search, double f, double cu, double cv,
+                    const vsm_fuse_params *params);
+/* the handle's last fusion result (zeros / nothing written without one); any output may be NULL.  count: the proposals, the
+ * fusions.  get: prop[n_prop][8], uv[n_prop][2]; returns n_prop.  get_tracks: partner[T], fused_into[T]; returns T.
+ * get_merged: offsets_after[T + 1], obs_src[n_obs]; returns n_obs.  get_frames: counts[F][2]; returns F. */
+void vsm_fuse_count(vsm_handle *h, int32_t *n_prop, int32_t *n_fusions);
+int32_t vsm_fuse_get(vsm_handle *h, int32_t *prop8, double *uv);
+int32_t vsm_fuse_get_tracks(vsm_handle *h, int32_t *partner, int32_t *fused_into);
+int32_t vsm_fuse_get_merged(vsm_handle *h, int32_t *offsets_after, int32_t *obs_src);
+int32_t vsm_fuse_get_frames(vsm_handle *h, int32_t *counts2);
+/* pairs per reason 0..4 as vsm_reobserve_get_stats, candidates per code 0..6 (code 1: empty windows), the number of fusions */
+void vsm_fuse_get_stats(vsm_handle *h, int64_t *out13);
+/* wall-clock split of the last call, microseconds: {gather / packing, upload, kernels with the wait for the number of
+ * proposals, download + host part} */
+void vsm_fuse_get_timings(vsm_handle *h, double *out4);
+/* The same definition on one host thread: no GPU, no handle (not a fallback).  prop[cap][8] and prop_uv[cap][2] take the
+ * first cap proposals; partner[T], fused_into[T], offsets_after[T + 1], obs_src[n_obs], frame_counts[F][2], stats13 as above.
+ * Returns the number of proposals (call with cap 0 to size the arrays), or VSM_EARG with the outputs untouched.  Outputs may
+ * be NULL. */
+int32_t vsm_host_fuse(int32_t n_frames, const double *poses, const uint8_t *pose_valid, const uint8_t *search, double f, double cu, double cv, int32_t width,
+                      int32_t height, int32_t n_tracks, const int32_t *offsets, const int32_t *obs_frames, const int32_t *obs_feat, const double *xyz,
+                      const uint8_t *use, const int32_t *ref_obs, const int32_t *feat_offsets, const int32_t *feat, const vsm_fuse_params *params, int32_t cap,
+                      int32_t *prop, double *prop_uv, int32_t *partner, int32_t *fused_into, int32_t *offsets_after, int32_t *obs_src, int32_t *frame_counts,
+                      int64_t *stats13);
 /* Measurement / test switches of a handle.  They are read from the environment once, by vsm_create (VSM_SEQ_V2,
  * VSM_SEQ_CHUNK, VSM_SEQ_DC_STREAMS, VSM_SEQ_SERIAL, VSM_SEQ_GPU_SORTS, VSM_SEQ_EARLY_EXPORT, VSM_FUSED_KEYS); this call changes one
  * afterwards: name = the variable's name without the VSM_ prefix, in lower case ("seq_serial", "seq_chunk", ...).

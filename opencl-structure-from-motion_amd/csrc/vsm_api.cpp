@@ -302,6 +302,7 @@ struct VsmSwitches {
   int fused_keys = 1;        // VSM_FUSED_KEYS: the batched forms' compactions write the Delaunay chains' keys with the lists and the chains' job tables are uploaded ahead of the
                              // matching launch (1), or every chain starts with
                              // its job table's upload and k_dc2_keys behind the compaction (0); refinement = 2 always takes 0
+  int fuse_compact = -1;     // vsm_fuse_run / vsm_points_fuse: the search once, its proposals kept in places per track and compacted behind the scan (1), the search twice, counting and then listing (0), or the first where the places fit FU_PLACES_MAX (-1; profiles/README.md)
   int adjust_fixed = 0;      // vsm_adjust_run / vsm_points_adjust: every launch of max_rounds rounds enqueued at once (1) or a wait per round on the control block (0; profiles/README.md)
   int filter_planes = 0;     // vsm_push_back keeps f1 / f2 in HBM for vsm_get_filter_responses (the fused tiles write them on the side)
   static int env_int(const char *name, int dflt) {
@@ -356,6 +357,7 @@ struct VsmSwitches {
     else if (!strcmp(name, "pairs_chunk")) pairs_chunk = std::max(0, v);
     else if (!strcmp(name, "motions_chunk")) motions_chunk = std::max(0, v);
     else if (!strcmp(name, "adjust_fixed")) adjust_fixed = v != 0;
+    else if (!strcmp(name, "fuse_compact")) fuse_compact = v;
     else return false;
     return true;
   }
@@ -428,6 +430,7 @@ struct vsm_handle {
   struct VsmAdjust *adjust = nullptr;  // joint adjustment of poses and points (vsm_ba.inc): staging, device block, last result
   struct VsmLocate *locate = nullptr;  // location of frames against the points (vsm_locate.inc): staging, device block, last result
   struct VsmReobserve *reobserve = nullptr;  // re-observation of the points (vsm_reobserve.inc): staging, device blocks, last result
+  struct VsmFuse *fuse = nullptr;            // fusion of duplicate tracks (vsm_fuse.inc): staging, device blocks, last result
   struct VsmMotions *motions = nullptr;  // monocular pair motions (vsm_motions_api.inc): staging, device block, last result
   struct VsmTracks *tracks = nullptr;  // feature tracks from pair match lists (vsm_tracks.inc): staging, device block, last result
 
@@ -466,6 +469,7 @@ static void vet_destroy(vsm_handle *h);     // vsm_vet.inc
 static void adjust_destroy(vsm_handle *h);  // vsm_ba.inc
 static void locate_destroy(vsm_handle *h);  // vsm_locate.inc
 static void reobserve_destroy(vsm_handle *h);  // vsm_reobserve.inc
+static void fuse_destroy(vsm_handle *h);       // vsm_fuse.inc
 static void motions_destroy(vsm_handle *h);  // vsm_motions_api.inc
 
 extern "C" {
@@ -564,6 +568,7 @@ void vsm_destroy(vsm_handle *h) {
   adjust_destroy(h);
   locate_destroy(h);
   reobserve_destroy(h);
+  fuse_destroy(h);
   motions_destroy(h);
   ctx_destroy(h->ring);
   ctx_destroy(h->seq);
@@ -1058,6 +1063,7 @@ static int seq_ingest_host_frames(vsm_handle *h, VsmCtx &c, int first_img, const
 #include "vsm_ba.inc"
 #include "vsm_locate.inc"
 #include "vsm_reobserve.inc"
+#include "vsm_fuse.inc"
 #include "vsm_motions_api.inc"
 extern "C" {
 
@@ -1275,7 +1281,8 @@ static const char *kKernelNames[VSM_K_COUNT] = {
     "k_trk_order_wave", "k_trk_order_block", "k_pts_triangulate", "k_rs_resect", "k_vet_obs", "k_vet_emit",
     "k_ba_init", "k_ba_linearise", "k_ba_tracks", "k_ba_frames<rhs>", "k_ba_cg_init", "k_ba_op_tracks", "k_ba_frames<op>", "k_ba_cg_step", "k_ba_back",
     "k_ba_trial_cost", "k_ba_decide", "k_ba_commit", "k_ba_finish", "k_locate_fit", "k_locate_count", "k_locate_winner",
-    "k_ro_occupy", "k_ro_bin_count", "k_ro_scatter", "k_ro_project<count>", "k_ro_project<list>", "k_ro_search", "k_ro_verdict"};
+    "k_ro_occupy", "k_ro_bin_count", "k_ro_scatter", "k_ro_project<count>", "k_ro_project<list>", "k_ro_search", "k_ro_verdict",
+    "k_fu_owner", "k_fu_bin_count", "k_fu_scatter", "k_fu_search<count>", "k_fu_search<list>", "k_fu_conflict", "k_fu_verdict", "k_fu_lengths", "k_fu_merge", "k_fu_compact"};
 
 void vsm_set_profiling(vsm_handle *h, int on) {
   h->prof.on = on != 0;

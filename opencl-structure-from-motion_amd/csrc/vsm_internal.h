@@ -124,6 +124,8 @@ enum VsmKernelId {
   VSM_K_LC_FIT, VSM_K_LC_COUNT, VSM_K_LC_WINNER,
   // re-observation of the points by projection (vsm_reobserve.hip; its two scans are VSM_K_TRK_SCAN_*)
   VSM_K_RO_OCCUPY, VSM_K_RO_BIN_COUNT, VSM_K_RO_SCATTER, VSM_K_RO_COUNT, VSM_K_RO_LIST, VSM_K_RO_SEARCH, VSM_K_RO_VERDICT,
+  // fusion of duplicate tracks (vsm_fuse.hip; its three scans are VSM_K_TRK_SCAN_*)
+  VSM_K_FU_OWNER, VSM_K_FU_BIN_COUNT, VSM_K_FU_SCATTER, VSM_K_FU_COUNT, VSM_K_FU_LIST, VSM_K_FU_CONFLICT, VSM_K_FU_VERDICT, VSM_K_FU_LENGTHS, VSM_K_FU_MERGE, VSM_K_FU_COMPACT,
   VSM_K_COUNT
 };
 struct VsmProf {

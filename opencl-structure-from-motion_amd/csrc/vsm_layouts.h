@@ -15,6 +15,7 @@
 #include "vsm_ba.h"
 #include "vsm_locate.h"
 #include "vsm_reobserve.h"
+#include "vsm_fuse.h"
 
 // vsm_points.inc: F frames, T tracks, N observations
 struct PtsBlocks : VsmBlocks {
@@ -177,6 +178,49 @@ struct RoCandBlocks : VsmBlocks {
   VsmOut<double> uv;
   explicit RoCandBlocks(size_t n) {
     cand.place(out, RO_CAND_INTS * n, 4); uv.place(out, 2 * n, 8);
+    out_behind_in(out.at);  // (in is empty: the block is the results)
+  }
+};
+
+// vsm_fuse.inc: the counts of RoBlocks.  The results sized before the launch - the tracks' partners, the merged set, the
+// frames' counts, the stats - are copied back; the working set lies behind them - first what starts at zero (the bins), then
+// the rest.  The proposals have a block of their own (FuPropBlocks), sized once their number is back.
+struct FuBlocks : VsmBlocks {
+  VsmIn<double> states, xyz;
+  VsmIn<uint8_t> valid, search, use;
+  VsmIn<int32_t> offsets, obs_frames, obs_feat, ref_obs, use_rank, feat_offsets, feat;
+  VsmIn<const int32_t *> frame_feat;
+  VsmOut<int32_t> partner, fused_into, offsets_after, obs_src, frame_counts, totals, bins, bins_part, bins_total, sorted, scan, scan_part;
+  VsmOut<unsigned long long> stats, choice;
+  VsmOut<uint32_t> owner;
+  size_t ones_bytes = 0;  // from `partner` on: what starts at all bits set (no partner, no survivor)
+  FuBlocks(size_t F, size_t T, size_t N, size_t NF, size_t NU, size_t B) {
+    states.place(in, 12 * F, 8); valid.place(in, F, 1); search.place(in, F, 1); offsets.place(in, T + 1, 0); obs_frames.place(in, N, 4); obs_feat.place(in, N, 4);
+    xyz.place(in, 3 * T, 8); use.place(in, T, 1); ref_obs.place(in, T, 4); use_rank.place(in, T, 4); feat_offsets.place(in, F + 1, 0); frame_feat.place(in, F, 8);
+    feat.place(in, RO_FEAT_INTS * NU, 16);
+    partner.place(out, T, 4); fused_into.place(out, T, 4);
+    ones_bytes = out.at;
+    offsets_after.place(out, T + 1, 0); obs_src.place(out, N, 4); frame_counts.place(out, 2 * F, 4); stats.place(out, FU_STATS, 0); totals.place(out, 2, 0);
+    VsmLayout work = out;
+    bins.place(work, 2 * F * B, 8); bins_part.place(work, 2 * trk_scan_part_items((int64_t)(F * B)), 8); bins_total.place(work, 2, 0); owner.place(work, NF, 4);
+    choice.place(work, T, 8); sorted.place(work, RO_FEAT_INTS * NF, 16); scan.place(work, 2 * T, 8); scan_part.place(work, 2 * trk_scan_part_items((int64_t)T), 8);
+    out_behind_in(work.at);
+  }
+};
+// the compacting form's places: U tracks in use, S frames searched with a pose
+struct FuSlotBlocks : VsmBlocks {
+  VsmOut<int32_t> slots;
+  VsmOut<double> uv;
+  FuSlotBlocks(size_t U, size_t S) {
+    slots.place(out, FU_PROP_INTS * U * S, 4); uv.place(out, 2 * U * S, 8);
+    out_behind_in(out.at);
+  }
+};
+struct FuPropBlocks : VsmBlocks {
+  VsmOut<int32_t> prop;
+  VsmOut<double> uv;
+  explicit FuPropBlocks(size_t n) {
+    prop.place(out, FU_PROP_INTS * n, 4); uv.place(out, 2 * n, 8);
     out_behind_in(out.at);  // (in is empty: the block is the results)
   }
 };

@@ -54,7 +54,9 @@ EXPORTS = ["vsm_default_params", "vsm_create", "vsm_destroy", "vsm_set_intrinsic
            "vsm_debug_locate_fit", "vsm_debug_locate_count", "vsm_debug_locate_winner", "vsm_debug_locate_hypotheses",
            "vsm_reobserve_default_params", "vsm_reobserve_run", "vsm_points_reobserve", "vsm_reobserve_count", "vsm_reobserve_get", "vsm_reobserve_get_tracks",
            "vsm_reobserve_get_frames", "vsm_reobserve_get_stats", "vsm_reobserve_get_timings", "vsm_host_reobserve", "vsm_pairs_num_features",
-           "vsm_pairs_get_features", "vsm_set_option", "vsm_version", "vsm_host_register", "vsm_host_unregister",
+           "vsm_pairs_get_features",
+           "vsm_fuse_default_params", "vsm_fuse_run", "vsm_points_fuse", "vsm_fuse_count", "vsm_fuse_get", "vsm_fuse_get_tracks", "vsm_fuse_get_merged",
+           "vsm_fuse_get_frames", "vsm_fuse_get_stats", "vsm_fuse_get_timings", "vsm_host_fuse", "vsm_set_option", "vsm_version", "vsm_host_register", "vsm_host_unregister",
            "vsm_multi_create", "vsm_multi_destroy", "vsm_multi_process", "vsm_multi_num_sequences", "vsm_multi_get_motion",
            "vsm_multi_motion_valid", "vsm_multi_num_matches", "vsm_multi_get_matches", "vsm_multi_num_inliers", "vsm_multi_get_inliers",
            "vsm_multi_get_timings",
@@ -117,6 +119,10 @@ class VsmLocateParams(C.Structure):
 
 
 class VsmReobserveParams(C.Structure):
+    _fields_ = [("radius", C.c_double), ("min_depth", C.c_double), ("max_cost", C.c_int32), ("ratio_num", C.c_int32), ("ratio_den", C.c_int32)]
+
+
+class VsmFuseParams(C.Structure):
     _fields_ = [("radius", C.c_double), ("min_depth", C.c_double), ("max_cost", C.c_int32), ("ratio_num", C.c_int32), ("ratio_den", C.c_int32)]
 
 
@@ -327,6 +333,24 @@ def lib():
         L.vsm_pairs_get_features.argtypes = [vp, i32, i32, i32, vp, i32]
         for fn in (L.vsm_reobserve_get, L.vsm_reobserve_get_tracks, L.vsm_reobserve_get_frames, L.vsm_host_reobserve, L.vsm_pairs_num_features,
                    L.vsm_pairs_get_features):
+            fn.restype = i32
+        fup = C.POINTER(VsmFuseParams)
+        L.vsm_fuse_default_params.argtypes = [fup]
+        L.vsm_fuse_default_params.restype = None
+        L.vsm_fuse_run.argtypes = [vp, i32, vp, vp, vp, f64, f64, f64, i32, i32, i32] + [vp] * 8 + [fup]
+        L.vsm_points_fuse.argtypes = [vp, vp, vp, vp, f64, f64, f64, fup]
+        L.vsm_fuse_count.argtypes = [vp, vp, vp]
+        L.vsm_fuse_count.restype = None
+        L.vsm_fuse_get.argtypes = [vp, vp, vp]
+        L.vsm_fuse_get_tracks.argtypes = [vp, vp, vp]
+        L.vsm_fuse_get_merged.argtypes = [vp, vp, vp]
+        L.vsm_fuse_get_frames.argtypes = [vp, vp]
+        L.vsm_fuse_get_stats.argtypes = [vp, vp]
+        L.vsm_fuse_get_stats.restype = None
+        L.vsm_fuse_get_timings.argtypes = [vp, vp]
+        L.vsm_fuse_get_timings.restype = None
+        L.vsm_host_fuse.argtypes = [i32, vp, vp, vp, f64, f64, f64, i32, i32, i32] + [vp] * 8 + [fup, i32] + [vp] * 8
+        for fn in (L.vsm_fuse_get, L.vsm_fuse_get_tracks, L.vsm_fuse_get_merged, L.vsm_fuse_get_frames, L.vsm_host_fuse):
             fn.restype = i32
         L.vsm_vet_default_params.argtypes = [C.POINTER(VsmVetParams)]
         L.vsm_vet_default_params.restype = None
@@ -1377,6 +1401,71 @@ def host_reobserve(poses, f, cu, cv, width, height, offsets, obs_frames, obs_fea
     return Reobservation(cand, uv, acc, fc, dict(zip(REOBSERVE_STATS, stats.tolist())))._take_pixels(lambda g: fe[fo[g]:fo[g + 1]])
 
 
+FUSE_CODES = ("fused", "empty_window", "over_max_cost", "ambiguous", "conflict", "outbid", "one_sided")
+FUSE_STATS = tuple("pairs_" + r for r in REOBSERVE_REASONS) + tuple("cand_" + c for c in FUSE_CODES) + ("fusions",)
+FUSE_TIMINGS = REOBSERVE_TIMINGS
+FUSE_ARRAYS = ("prop", "uv", "partner", "fused_into", "offsets_after", "obs_src", "frame_counts")
+
+
+class Fusion:
+    """duplicate tracks joined (include/visomatch.h, vsm_fuse_run): per proposal prop [n_prop, 8] int32 {a, frame, feature, cost,
+    second, n_window, code, b} (code 0 = fused, FUSE_CODES names the values) and uv [n_prop, 2] float64, the projection;
+    partner [T] and fused_into [T] int32 (-1: none); the merged track set offsets_after [T + 1] and obs_src [n_obs] int32;
+    frame_counts [F, 2] int32 (candidates, proposals); stats by name, timings: dict (empty for the host view)."""
+
+    def __init__(self, prop, uv, partner, fused_into, offsets_after, obs_src, frame_counts, stats=None, timings=None):
+        self.prop, self.uv, self.partner, self.fused_into = prop, uv, partner, fused_into
+        self.offsets_after, self.obs_src, self.frame_counts = offsets_after, obs_src, frame_counts
+        self.stats, self.timings = stats or {}, timings or {}
+
+    def __len__(self):
+        return len(self.prop)
+
+    @property
+    def code(self):
+        return self.prop[:, 6]
+
+    def fused(self):
+        """the fusions [n, 2] int32: (survivor, absorbed), by ascending absorbed track"""
+        gone = np.nonzero(self.fused_into >= 0)[0].astype(np.int32)
+        return np.stack([self.fused_into[gone], gone], axis=1).astype(np.int32).reshape(-1, 2)
+
+    def merge(self, obs_frames, uv, obs_feat):
+        """the merged track set over the same T tracks: (offsets_after, obs_frames, uv, obs_feat), the observations gathered
+        through obs_src - a survivor's own and the absorbed track's by ascending frame, an absorbed track empty.  The
+        counterpart of Vetting.prune and Reobservation.extend: the arrays feed triangulate, adjust, vet, reobserve and the
+        next fuse as they are (the points of the survivors want a new triangulation)."""
+        fr, ft = np.asarray(obs_frames, dtype=np.int32), np.asarray(obs_feat, dtype=np.int32)
+        px = np.asarray(uv, dtype=np.float32).reshape(-1, 2)
+        assert len(fr) == len(ft) == len(px) == len(self.obs_src)
+        src = self.obs_src
+        return self.offsets_after.copy(), np.ascontiguousarray(fr[src]), np.ascontiguousarray(px[src]), np.ascontiguousarray(ft[src])
+
+
+def fuse_params(**kw):
+    """vsm_fuse_default_params with fields overridden by keyword"""
+    return _default_params(VsmFuseParams, "vsm_fuse_default_params", kw)
+
+
+def host_fuse(poses, f, cu, cv, width, height, offsets, obs_frames, obs_feat, xyz, feat_offsets, feat, use=None, ref_obs=None, search=None, pose_valid=None,
+              params=None, n_tracks=None):
+    """vsm_host_fuse: the fusion on one host thread - no GPU.  Arguments as host_reobserve.  Returns a Fusion object; raises
+    VisoMatchError on VSM_EARG."""
+    po, pv, se, off, fr, ft, pt, us, ro, fo, fe = _reobserve_inputs(poses, pose_valid, search, offsets, obs_frames, obs_feat, xyz, use, ref_obs, feat_offsets, feat)
+    T = _n_tracks(off, n_tracks)
+    prm = _params_ref(VsmFuseParams, fuse_params, params)
+    head = (len(po), _ptr(po), _ptr(pv), _ptr(se), float(f), float(cu), float(cv), int(width), int(height), T, _ptr(off), _ptr(fr), _ptr(ft), _ptr(pt), _ptr(us),
+            _ptr(ro), _ptr(fo), _ptr(fe), prm)
+    n = _check(lib().vsm_host_fuse(*head, 0, None, None, None, None, None, None, None, None), "vsm_host_fuse")
+    T = max(T, 0)
+    out = (np.zeros((n, 8), np.int32), np.zeros((n, 2), np.float64), np.zeros(T, np.int32), np.zeros(T, np.int32), np.zeros(T + 1, np.int32),
+           np.zeros(len(fr), np.int32), np.zeros((len(po), 2), np.int32))
+    stats = np.zeros(len(FUSE_STATS), np.int64)
+    got = _check(lib().vsm_host_fuse(*head, n, *[_ptr(o) for o in out], _ptr(stats)), "vsm_host_fuse")
+    assert got == n
+    return Fusion(*out, dict(zip(FUSE_STATS, stats.tolist())))
+
+
 _NO_PARAMS = object()  # params=_NO_PARAMS: a NULL params pointer (argument tests)
 
 
@@ -1982,6 +2071,43 @@ class Matcher:
         rc = lib().vsm_points_reobserve(self.h, _ptr(po), _ptr(pv), _ptr(se), float(f), float(cu), float(cv),
                                         _params_ref(VsmReobserveParams, reobserve_params, params))
         return self._reobserve_result(rc, "vsm_points_reobserve")
+
+    # --- duplicate tracks of one point, joined ---------------------------------------------------------
+    def _fuse_result(self, rc, what):
+        L = lib()
+        _check(rc, what)
+        n, nf = C.c_int32(0), C.c_int32(0)
+        L.vsm_fuse_count(self.h, C.byref(n), C.byref(nf))
+        T = L.vsm_fuse_get_tracks(self.h, None, None)
+        out = (np.zeros((n.value, 8), np.int32), np.zeros((n.value, 2), np.float64), np.zeros(T, np.int32), np.zeros(T, np.int32), np.zeros(T + 1, np.int32),
+               np.zeros(L.vsm_fuse_get_merged(self.h, None, None), np.int32), np.zeros((L.vsm_fuse_get_frames(self.h, None), 2), np.int32))
+        L.vsm_fuse_get(self.h, _ptr(out[0]), _ptr(out[1]))
+        L.vsm_fuse_get_tracks(self.h, _ptr(out[2]), _ptr(out[3]))
+        L.vsm_fuse_get_merged(self.h, _ptr(out[4]), _ptr(out[5]))
+        L.vsm_fuse_get_frames(self.h, _ptr(out[6]))
+        res = Fusion(*out, *_stage_dicts(self.h, L.vsm_fuse_get_stats, FUSE_STATS, L.vsm_fuse_get_timings, FUSE_TIMINGS))
+        assert nf.value == res.stats.get("fusions", 0) == len(res.fused())
+        return res
+
+    def fuse(self, poses, f, cu, cv, width, height, offsets, obs_frames, obs_feat, xyz, feat_offsets, feat, use=None, ref_obs=None, search=None, pose_valid=None,
+             params=None, n_tracks=None):
+        """vsm_fuse_run: every point in use projected into every searched frame with a pose that does not observe it yet, the
+        features that tracks in use own near the projection searched for the track's descriptor, and the tracks that choose
+        each other fused, on the device.  Arguments as reobserve; params: a dict of vsm_fuse_params fields or the struct.
+        Returns a Fusion object."""
+        po, pv, se, off, fr, ft, pt, us, ro, fo, fe = _reobserve_inputs(poses, pose_valid, search, offsets, obs_frames, obs_feat, xyz, use, ref_obs, feat_offsets, feat)
+        T = _n_tracks(off, n_tracks)
+        rc = lib().vsm_fuse_run(self.h, len(po), _ptr(po), _ptr(pv), _ptr(se), float(f), float(cu), float(cv), int(width), int(height), T, _ptr(off), _ptr(fr),
+                                _ptr(ft), _ptr(pt), _ptr(us), _ptr(ro), _ptr(fo), _ptr(fe), _params_ref(VsmFuseParams, fuse_params, params))
+        return self._fuse_result(rc, "vsm_fuse_run")
+
+    def fuse_points(self, poses, f, cu, cv, search=None, pose_valid=None, params=None):
+        """vsm_points_fuse: the same on the handle's last track and point results (pair_tracks with side 0; the kept points)
+        and the features the last match_pairs call left resident in HBM"""
+        po, pv = _pose_inputs(poses, pose_valid, self._track_frames)
+        se = _mask(search, len(po))
+        rc = lib().vsm_points_fuse(self.h, _ptr(po), _ptr(pv), _ptr(se), float(f), float(cu), float(cv), _params_ref(VsmFuseParams, fuse_params, params))
+        return self._fuse_result(rc, "vsm_points_fuse")
 
     def pair_features(self, frame, side=0, set=1):
         """vsm_pairs_get_features: the feature records [n, 12] int32 of a frame of the last match_pairs call (set 1: the set the
